@@ -70,51 +70,52 @@ def test_bench_one_proof_sharded_two_ranks_one_gpu_gloo():
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_one_gpu_gloo():
-    """The driver's N = 8 launch of bench.py (BASELINE configs[2]: independent proofs, one replica per rank) with the eight ranks
-    sharing GPU 0 over gloo: one JSON line from rank 0 with n_gpus = 8, the whole-job rate, one host-CPU figure per rank, and the
-    hashing mode batch.configure_host chose from the CPUs each rank can count on (fewer than six per rank: the shared eight-lane
-    service).  The rate itself means nothing here (eight ranks on one chip); the contract and the control flow are under test."""
+def test_bench_four_ranks_one_gpu_gloo():
+    """A multi-rank launch of bench.py (BASELINE configs[2]: independent proofs, one replica per rank) with four ranks
+    sharing GPU 0 over gloo (at most six processes may hold one GPU; the driver's N = 8 runs one rank per GPU): one JSON line
+    from rank 0 with n_gpus = 4, the whole-job rate, one host-CPU figure per rank, and the hashing mode batch.configure_host
+    chose from the CPUs each rank can count on (fewer than six per rank: the shared service).  The rate itself means nothing
+    here (four ranks on one chip); the contract and the control flow are under test."""
     env = _clean_env(ZKFHE_BENCH_BACKEND="gloo", ZKFHE_TABLE_GB="1")
     env.pop("ZKFHE_HASH_MODE", None)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "8", "--warmup", "1", "--streams", "4",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "8", "--warmup", "1", "--streams", "4",
            "--no-cpu-baseline", "--steady-seconds", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["steps"] == 8 and d["scaling"] == "weak" and d["config"]["mode"] == "batch"
-    assert abs(d["value"] - 8 * 8 / (d["ms_per_step"] * 8 / 1e3)) / d["value"] < 1e-6          # 64 proofs of the job over the slowest rank's time
-    assert len(d["config"]["host_cpu_ms_per_proof_by_rank"]) == 8 and all(v > 0 for v in d["config"]["host_cpu_ms_per_proof_by_rank"])
+    assert d["n_gpus"] == 4 and d["steps"] == 8 and d["scaling"] == "weak" and d["config"]["mode"] == "batch"
+    assert abs(d["value"] - 4 * 8 / (d["ms_per_step"] * 8 / 1e3)) / d["value"] < 1e-6          # 32 proofs of the job over the slowest rank's time
+    assert len(d["config"]["host_cpu_ms_per_proof_by_rank"]) == 4 and all(v > 0 for v in d["config"]["host_cpu_ms_per_proof_by_rank"])
     host = d["config"]["host"]
-    assert host["cpus_per_rank"] == host["usable_cpus"] / 8
+    assert host["cpus_per_rank"] == host["usable_cpus"] / 4
     assert host["hash_mode"] == ("shared" if host["cpus_per_rank"] < 6 else "latency")
     assert d["config"]["verified"] is True and d["vs_baseline"] is None
 
 
 @pytest.mark.gpu
-def test_bench_one_k19_proof_sharded_over_eight_ranks_gloo():
-    """bench.py --gpus 8 --mode one-proof-sharded --config k19: BASELINE configs[4] as the driver would launch it on an 8-GPU node
-    (there: one rank per GPU, RCCL), here with the eight ranks on GPU 0 over gloo -- control flow, the JSON contract (strong
-    scaling: value = proofs of the JOB per second) and a verified k = 19 proof made by eight ranks.  The rate means nothing here."""
+def test_bench_one_k19_proof_sharded_over_four_ranks_gloo():
+    """bench.py --mode one-proof-sharded --config k19: BASELINE configs[4] as the driver would launch it on a multi-GPU node
+    (there: one rank per GPU, RCCL), here with four ranks on GPU 0 over gloo (at most six processes may hold one GPU) -- control
+    flow, the JSON contract (strong scaling: value = proofs of the JOB per second) and a verified k = 19 proof made by four ranks.  The rate means nothing here."""
     env = _clean_env(ZKFHE_BENCH_BACKEND="gloo", ZKFHE_TABLE_GB="1")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
            "--steady-seconds", "0", "--mode", "one-proof-sharded", "--config", "k19", "--transcript", "blake2b"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=2400)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["mode"] == "one-proof-sharded" and d["config"]["verified"] is True
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["config"]["mode"] == "one-proof-sharded" and d["config"]["verified"] is True
     assert d["metric"] == "BFV proofs/sec (k=19)" and "k=19, N=16384" in d["config"]["workload"]
     assert abs(d["value"] - 1 / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-6            # one proof of the JOB per step
-    assert len(d["config"]["host_cpu_ms_per_proof_by_rank"]) == 8
-    assert d["config"]["sharded_proof_identical_on_all_ranks"] is True                   # all eight ranks ended with the same bytes
-    # ... and they are the SINGLE-GPU proof of the same input and seed, made here after the ranks have given the device back (eight
-    # k = 19 keys and workspaces next to a ninth do not fit one device): the sharded path -- an eighth of both SRS halves per rank,
+    assert len(d["config"]["host_cpu_ms_per_proof_by_rank"]) == 4
+    assert d["config"]["sharded_proof_identical_on_all_ranks"] is True                   # all four ranks ended with the same bytes
+    # ... and they are the SINGLE-GPU proof of the same input and seed, made here after the ranks have given the device back (four
+    # k = 19 keys and workspaces next to a fifth need not fit one device): the sharded path -- a quarter of both SRS halves per rank,
     # commitments by point range, quotient / evaluations / SHPLONK sums by column and index -- changes no byte
     import hashlib
     import torch  # noqa: F401
@@ -179,3 +180,23 @@ def test_bench_refuses_a_launch_that_is_not_the_n_asked_for():
                            capture_output=True, text=True, timeout=600)
         assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert "2 local ranks but 1 visible GPU" in r.stderr
+
+
+def test_dump_outputs_round_trips_exactly(tmp_path):
+    """bench.py --dump-outputs: the float32 files give back the proof bytes and every 32-byte public input word exactly."""
+    import importlib.util
+    import numpy as np
+    import zk_fhe_amd as zk
+    spec = importlib.util.spec_from_file_location("zkfhe_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(7)
+    proof = rng.bytes(1000)
+    words = [(1 << 256) - 1, 0, int.from_bytes(rng.bytes(32), "little")]
+    inst = zk.Instances(b"".join(w.to_bytes(32, "little") for w in words))
+    bench._dump_outputs(str(tmp_path / "out"), proof, inst)
+    p = np.load(tmp_path / "out" / "proof_bytes.npy")
+    i = np.load(tmp_path / "out" / "instances.npy")
+    assert p.dtype == np.float32 and i.dtype == np.float32 and i.shape == (3, 16)
+    assert p.astype(np.uint8).tobytes() == proof
+    assert [sum(int(v) << (16 * k) for k, v in enumerate(row)) for row in i] == words
