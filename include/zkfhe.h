@@ -80,6 +80,9 @@ int zkfhe_timer_stop_ms(zkfhe_ctx *ctx, float *ms);   /* waits for the stop even
 int zkfhe_prof_enable(zkfhe_ctx *ctx, int on);
 int zkfhe_prof_reset(zkfhe_ctx *ctx);
 int zkfhe_prof_read(zkfhe_ctx *ctx, int which, double *total_ms, uint64_t *launches, double *algorithmic_bytes);
+/* further slots of zkfhe_prof_read: the batch verifier's kernels (algorithmic bytes: 32 B in per point; 96 B per MSM term) */
+#define ZKFHE_PROF_G1_DECOMPRESS 3   /* k_g1_decompress */
+#define ZKFHE_PROF_MSM_SEGMENTED 4   /* k_msm_segmented */
 /* arithmetic units of the profiled launches: which = 0 -> mixed point additions (k_msm_accumulate), 1 -> butterflies (NTT tile kernel) */
 int zkfhe_prof_read_ops(zkfhe_ctx *ctx, int which, double *ops);
 
@@ -214,6 +217,24 @@ int zkfhe_g1_add(zkfhe_ctx *ctx, const zkfhe_g1_affine *a_dev, const zkfhe_g1_af
 /* out[i] = k[i] * p[i] */
 int zkfhe_g1_mul(zkfhe_ctx *ctx, const zkfhe_g1_affine *p_dev, const zkfhe_fr *k_dev,
                  zkfhe_g1_affine *out_dev, size_t n);
+/* Decompression of n 32-byte compressed G1 points (the proof byte stream's form: x little-endian, the sign and identity bits of
+ * byte 31 as ZKFHE_POINT_ENCODING selects) into Montgomery affine points, identity = (0, 0), with one status per point.  Any bytes
+ * are accepted; a point whose status is not ZKFHE_PT_OK is written as (0, 0).  The same checks, in the same order, as the host
+ * verifier's reader.  halo2curves: G1Affine::from_bytes. */
+#define ZKFHE_PT_OK 0
+#define ZKFHE_PT_X_NOT_REDUCED 1   /* x >= q */
+#define ZKFHE_PT_NOT_ON_CURVE 2    /* x^3 + 3 is not a square */
+#define ZKFHE_PT_BAD_IDENTITY 3    /* the identity bit with any other bit set */
+int zkfhe_g1_decompress(zkfhe_ctx *ctx, const uint8_t *in_dev, size_t n, zkfhe_g1_affine *out_dev, int32_t *status_dev);
+/* Many small MSMs over one array of affine points addressed by index (halo2 MSM::eval of many snarks' openings at once):
+ *   out[s] = sum over t in [seg_off[s], seg_off[s+1]) of scalars[t] * points[index[t]],  s < n_segs
+ * scalars: n_terms Montgomery Fr; seg_off: n_segs + 1 ascending offsets into [0, n_terms]; index: n_terms values < n_points.
+ * Segments may be empty (identity), repeat indices, hold zero scalars or identity points.  One workgroup per segment: meant for
+ * segments of up to a few thousand terms (the wide MSMs of the prover are zkfhe_msm_batch).  Waits for the result; a bad index
+ * or offset is ZKFHE_EINVAL (out_dev then undefined). */
+int zkfhe_msm_segmented(zkfhe_ctx *ctx, const zkfhe_g1_affine *points_dev, size_t n_points, const uint32_t *index_dev,
+                        const zkfhe_fr *scalars_dev, size_t n_terms, const uint32_t *seg_off_dev, size_t n_segs,
+                        zkfhe_g1_affine *out_dev);
 
 /* ---- BFV witness kernels -------------------------------- */
 /* Negacyclic product in R_q = Z_q[x]/(x^N+1) is NOT what the reference computes: Poly::mul
@@ -427,6 +448,23 @@ int zkfhe_bfv_verify(const uint8_t *vk_bytes, size_t vk_len, const uint8_t *inst
  * each (x.c0, x.c1, y.c0, y.c1), the layout of halo2curves' G2Affine coordinates. */
 int zkfhe_bfv_verify_g2(const uint8_t *vk_bytes, size_t vk_len, const uint8_t *instances, size_t n_instances, const uint8_t *proof, size_t proof_len,
                         const uint8_t g2[128], const uint8_t s_g2[128], int *accepted, char *err, size_t err_len);
+
+/* Batch verification (halo2 KZG AccumulatorStrategy / verify_proof over many snarks): n_proofs proofs under ONE verifying key,
+ * proof j with n_instances[j] canonical scalars at instances[j] and proof_lens[j] bytes at proofs[j].  accepted[j] and the
+ * reason written to errs + j * err_stride (err_stride bytes each; errs may be NULL) are exactly what zkfhe_bfv_verify (srs_seed,
+ * when g2 == NULL) or zkfhe_bfv_verify_g2 (g2 and s_g2 both given) answers for that proof.  Host memory only; the context's GPU
+ * decompresses every proof point (zkfhe_g1_decompress) and computes each proof's SHPLONK combination F_j (zkfhe_msm_segmented);
+ * the transcripts are replayed on host threads (the usable CPUs: affinity mask, OMP_NUM_THREADS), proofs of one BFV public key
+ * (the same pk0 | pk1, the first 2 N of 5 N + 1 instances) from one shared transcript state.  Then ONE pairing check:
+ *     e(sum_j r_j F_j, G2) e(-sum_j r_j W_j, s G2) = 1      (W_j = the proof's h2)
+ * over the proofs that got that far; if it fails, every one of them is checked on its own from its F_j and W_j.
+ * Randomisers: r_j = the low 128 bits of Blake2b-512(personalisation "zkfhe-batch-r"; vk digest | D | j as u64 LE), 1 if zero,
+ * with D = Blake2b-512("zkfhe-batch-D"; for every proof in order: u64 n_instances | instances | u64 proof_len | proof): fixed by
+ * the whole batch, so no prover can choose a proof that cancels against another's defect.  Proofs go to the GPU in chunks of
+ * 256.  Returns ZKFHE_EINVAL for n_proofs = 0 or NULL arguments; a malformed proof or vk is a rejection, not an error. */
+int zkfhe_bfv_verify_batch(zkfhe_ctx *ctx, const uint8_t *vk_bytes, size_t vk_len, size_t n_proofs, const uint8_t *const *instances,
+                           const size_t *n_instances, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *srs_seed,
+                           size_t seed_len, const uint8_t *g2, const uint8_t *s_g2, int *accepted, char *errs, size_t err_stride);
 
 /* prove (README.md:42-44): witness generation + create_proof.
  * seed: 32 bytes; every blinding scalar of the proof is derived from it (Blake2b(seed || counter)).  ZERO KNOWLEDGE RESTS

@@ -16,6 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkfhe_hip.so")
 _lib = None
 
+PROF_G1_DECOMPRESS, PROF_MSM_SEGMENTED = 3, 4   # zkfhe_prof_read slots of the batch verifier's kernels (zkfhe.h)
+
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
     "zkfhe_dev_alloc", "zkfhe_dev_free", "zkfhe_upload", "zkfhe_download", "zkfhe_copy_dev", "zkfhe_memset_dev",
@@ -34,6 +36,7 @@ EXPORTS = [
     "zkfhe_srs_create", "zkfhe_srs_from_points", "zkfhe_srs_destroy", "zkfhe_srs_save", "zkfhe_srs_drop_host_copy", "zkfhe_srs_load", "zkfhe_srs_g2", "zkfhe_srs_set_g2", "zkfhe_srs_file_g2",
     "zkfhe_chacha20_block", "zkfhe_snark_encode", "zkfhe_snark_decode", "zkfhe_bfv_keygen", "zkfhe_bfv_pk_destroy", "zkfhe_bfv_pk_release_ctx", "zkfhe_bfv_pk_info", "zkfhe_bfv_pk_prefix_cache",
     "zkfhe_bfv_pk_commitments", "zkfhe_bfv_pk_break_points", "zkfhe_bfv_pk_prehash", "zkfhe_bfv_prove", "zkfhe_bfv_pk_export_vk", "zkfhe_bfv_pk_save", "zkfhe_bfv_pk_load", "zkfhe_bfv_witness_stream", "zkfhe_lookup_permute", "zkfhe_bfv_verify", "zkfhe_bfv_verify_g2",
+    "zkfhe_g1_decompress", "zkfhe_msm_segmented", "zkfhe_bfv_verify_batch",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -359,6 +362,46 @@ class Context:
         out = dp.download(shape=p.shape)
         dp.free(), dk.free()
         return out
+
+    def g1_decompress(self, data):
+        """32-byte compressed G1 points (bytes, a multiple of 32 long) -> (points (n, 8) uint64 Montgomery affine, status (n,) int32:
+        0 ok, 1 x not reduced, 2 not on the curve, 3 non-canonical identity; a rejected point is (0, 0))"""
+        data = bytes(data)
+        if len(data) % 32:
+            raise ValueError("g1_decompress: input length is not a multiple of 32")
+        n = len(data) // 32
+        if not n:
+            return np.zeros((0, 8), dtype=np.uint64), np.zeros(0, dtype=np.int32)
+        din = self.to_device(np.frombuffer(data, dtype=np.uint8))
+        dout, dst = self.alloc(n * 64), self.alloc(n * 4)
+        self.lib.zkfhe_g1_decompress.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.zkfhe_g1_decompress(self.h, self._p(din), n, self._p(dout), self._p(dst)))
+        pts, st = dout.download(shape=(n, 8)), dst.download(dtype=np.int32)
+        din.free(), dout.free(), dst.free()
+        return pts, st
+
+    def msm_segmented(self, points, index, scalars, offsets):
+        """out[s] = sum over t in [offsets[s], offsets[s+1]) of scalars[t] * points[index[t]]: points (n, 8) uint64 Montgomery affine,
+        scalars (T, 4) uint64 Montgomery Fr, index (T,) and offsets (n_segs + 1,) integers.  Returns (n_segs, 8) affine."""
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        index = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        n_segs, T = offsets.shape[0] - 1, index.shape[0]
+        if n_segs < 1 or scalars.shape[0] != T:
+            raise ValueError("msm_segmented: need n_segs + 1 offsets and one scalar per index")
+        bufs = [self.to_device(a) if a.size else None for a in (points, index, scalars, offsets)]
+        dout = self.alloc(n_segs * 64)
+        self.lib.zkfhe_msm_segmented.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        dp = lambda b: self._p(b) if b is not None else None  # noqa: E731
+        try:
+            self._check(self.lib.zkfhe_msm_segmented(self.h, dp(bufs[0]), points.shape[0], dp(bufs[1]), dp(bufs[2]), T, dp(bufs[3]), n_segs, self._p(dout)))
+            return dout.download(shape=(n_segs, 8))
+        finally:
+            for b in bufs + [dout]:
+                if b is not None:
+                    b.free()
 
     def witness_poly_mul_u64(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.uint64)
@@ -1115,3 +1158,42 @@ def bfv_verify(vk_bytes, instances, proof, srs_seed=b"zkfhe-unsafe-srs", g2=None
     if rc != 0:
         raise ZkfheError("zkfhe_bfv_verify: bad arguments (%d)" % rc)
     return bool(ok.value), err.value.decode()
+
+
+def bfv_verify_batch(ctx, vk_bytes, items, srs_seed=b"zkfhe-unsafe-srs", g2=None, s_g2=None):
+    """Batch verifier (zkfhe_bfv_verify_batch): items = [(instances, proof), ...] under one verifying key, checked on ctx's GPU with
+    one pairing; returns [(accepted, reason), ...], for each proof exactly what bfv_verify answers.  g2 / s_g2 as bfv_verify."""
+    lib = load_library()
+    items = list(items)
+    n = len(items)
+    enc_inst = lambda v: v.raw if isinstance(v, Instances) else b"".join(int(x).to_bytes(32, "little") for x in v)  # noqa: E731
+    insts = [enc_inst(i) for i, _ in items]
+    proofs = [bytes(p) for _, p in items]
+    keep = insts + proofs   # the buffers below point into these
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    as_p = lambda b: ctypes.cast(ctypes.c_char_p(b), u8p)  # noqa: E731
+    inst_arr = (u8p * max(n, 1))(*[as_p(b) for b in insts])
+    proof_arr = (u8p * max(n, 1))(*[as_p(b) for b in proofs])
+    n_inst = (ctypes.c_size_t * max(n, 1))(*[len(b) // 32 for b in insts])
+    lens = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in proofs])
+    ok = (ctypes.c_int * max(n, 1))()
+    stride = 256
+    errs = ctypes.create_string_buffer(stride * max(n, 1))
+    if (g2 is None) != (s_g2 is None):
+        raise ValueError("bfv_verify_batch: give both g2 and s_g2, or neither")
+
+    def enc(p):
+        (x0, x1), (y0, y1) = p
+        return b"".join(int(v).to_bytes(32, "little") for v in (x0, x1, y0, y1))
+    lib.zkfhe_bfv_verify_batch.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(u8p),
+                                           ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t),
+                                           ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.c_char_p, ctypes.c_size_t]
+    seed = bytes(srs_seed) if srs_seed is not None else None
+    rc = lib.zkfhe_bfv_verify_batch(ctx.h, vk_bytes, len(vk_bytes), n, inst_arr, n_inst, proof_arr, lens, seed if g2 is None else None,
+                                    len(seed) if (g2 is None and seed) else 0, enc(g2) if g2 is not None else None,
+                                    enc(s_g2) if s_g2 is not None else None, ok, errs, stride)
+    del keep
+    if rc != 0:
+        raise ZkfheError("zkfhe_bfv_verify_batch failed (%d): %s" % (rc, lib.zkfhe_last_error(ctx.h).decode()))
+    return [(bool(ok[j]), errs.raw[j * stride:(j + 1) * stride].split(b"\0", 1)[0].decode()) for j in range(n)]

@@ -250,7 +250,7 @@ int zkfhe_prof_enable(zkfhe_ctx *ctx, int on) {
 }
 int zkfhe_prof_reset(zkfhe_ctx *ctx) {
   ZK_ENTER(ctx);
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < zkfhe_ctx::PROF_SLOTS; ++i) {
     ctx->prof_ms[i] = ctx->prof_bytes[i] = ctx->prof_ops[i] = 0;
     ctx->prof_launches[i] = 0;
   }
@@ -258,7 +258,7 @@ int zkfhe_prof_reset(zkfhe_ctx *ctx) {
 }
 int zkfhe_prof_read(zkfhe_ctx *ctx, int which, double *total_ms, uint64_t *launches, double *algorithmic_bytes) {
   ZK_ENTER(ctx);
-  ZK_ARG(ctx, which >= 0 && which < 3);
+  ZK_ARG(ctx, which >= 0 && which < zkfhe_ctx::PROF_SLOTS);
   if (total_ms) *total_ms = ctx->prof_ms[which];
   if (launches) *launches = ctx->prof_launches[which];
   if (algorithmic_bytes) *algorithmic_bytes = ctx->prof_bytes[which];
@@ -267,7 +267,7 @@ int zkfhe_prof_read(zkfhe_ctx *ctx, int which, double *total_ms, uint64_t *launc
 
 int zkfhe_prof_read_ops(zkfhe_ctx *ctx, int which, double *ops) {
   ZK_ENTER(ctx);
-  ZK_ARG(ctx, which >= 0 && which < 3 && ops != nullptr);
+  ZK_ARG(ctx, which >= 0 && which < zkfhe_ctx::PROF_SLOTS && ops != nullptr);
   *ops = ctx->prof_ops[which];
   return ZKFHE_OK;
 }

@@ -44,8 +44,10 @@ struct zkfhe_ctx {
   bool prof_on = false;
   hipEvent_t pe0 = nullptr, pe1 = nullptr;
   hipEvent_t wait_ev = nullptr;  // hipEventBlockingSync: host waits sleep instead of spinning (zk_wait)
-  double prof_ms[3] = {0, 0, 0}, prof_bytes[3] = {0, 0, 0}, prof_ops[3] = {0, 0, 0};   // [2] = k_msm_table of a call of a few columns
-  uint64_t prof_launches[3] = {0, 0, 0};
+  // [2] = k_msm_table of a call of a few columns, [3] = k_g1_decompress, [4] = k_msm_segmented (verify.hip)
+  static constexpr int PROF_SLOTS = 5;
+  double prof_ms[PROF_SLOTS] = {}, prof_bytes[PROF_SLOTS] = {}, prof_ops[PROF_SLOTS] = {};
+  uint64_t prof_launches[PROF_SLOTS] = {};
   // pinned bounce buffer for small host<->device transfers (pageable copies go through the runtime's shared staging path)
   void *bounce = nullptr;
   static constexpr size_t BOUNCE_BYTES = (size_t)1 << 20;

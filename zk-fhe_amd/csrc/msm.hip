@@ -41,6 +41,7 @@
 
 #include "ctx.hpp"
 #include "fq29.hip.hpp"
+#include "g1x29_wave.hip.hpp"
 
 using namespace zk;
 
@@ -564,30 +565,6 @@ __global__ void __launch_bounds__(256) k_msm_accumulate(const uint2 *__restrict_
   }
 }
 
-__device__ __forceinline__ G1X29 g1x_shfl_down(const G1X29 &p, int delta) {
-  G1X29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    r.x.l[i] = __shfl_down(p.x.l[i], delta);
-    r.y.l[i] = __shfl_down(p.y.l[i], delta);
-    r.zz.l[i] = __shfl_down(p.zz.l[i], delta);
-    r.zzz.l[i] = __shfl_down(p.zzz.l[i], delta);
-  }
-  return r;
-}
-
-__device__ __forceinline__ G1X29 g1x_shfl_xor(const G1X29 &p, int mask) {
-  G1X29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    r.x.l[i] = __shfl_xor(p.x.l[i], mask);
-    r.y.l[i] = __shfl_xor(p.y.l[i], mask);
-    r.zz.l[i] = __shfl_xor(p.zz.l[i], mask);
-    r.zzz.l[i] = __shfl_xor(p.zzz.l[i], mask);
-  }
-  return r;
-}
-
 // bucket sum = sum of its partials, ONE launch with three block ranges that run side by side (they used to be two
 // kernels and two loops, one after the other: 650 us of dependent chains per call):
 //   large_blocks: skewed witness columns (thousands of 0/1 cells in one bucket): one wave per bucket, 6-step tree;
@@ -863,28 +840,6 @@ __global__ void __launch_bounds__(64) k_basis_multiples(const G1Affine *__restri
     g1x_add_affine(acc, b, false);
     row[j] = g1_affine_to_29(g1x_to_affine(acc));
   }
-}
-
-// Sum of 256 XYZZ points held one per thread -> thread 0.  Across the waves first, through LDS (waves 2, 3 hand theirs to
-// waves 0, 1, then wave 1 to wave 0: three wave-wide additions), then a 6-step butterfly in wave 0 alone: 9 wave-wide
-// additions where a 256-lane butterfly issues 26.
-__device__ __forceinline__ G1X29 block_sum_256(G1X29 v, G1X *sh /* [128] */) {
-  const unsigned wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (wv >= 2) sh[threadIdx.x - 128] = g1x29_store(v);
-  __syncthreads();
-  if (wv < 2) g1x29_add(v, g1x29_load(sh[threadIdx.x]));
-  __syncthreads();
-  if (wv == 1) sh[threadIdx.x - 64] = g1x29_store(v);
-  __syncthreads();
-  if (wv == 0) {
-    g1x29_add(v, g1x29_load(sh[threadIdx.x]));
-    for (int m = 1; m < 64; m <<= 1) {
-      const G1X29 other = g1x_shfl_xor(v, m);
-      g1x29_add(v, other);
-    }
-  }
-  return v;
 }
 
 // Work item = chunk of P <= 256 consecutive points of one column.  Every column has a chunk counter; a grid of persistent
