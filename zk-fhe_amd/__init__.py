@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libzkfhe_hip.so")
 _lib = None
 
 PROF_G1_DECOMPRESS, PROF_MSM_SEGMENTED = 3, 4   # zkfhe_prof_read slots of the batch verifier's kernels (zkfhe.h)
+PROF_BFV_SAMPLE, PROF_RNS_NTT, PROF_RNS_EPILOGUE = 5, 6, 7   # ... and of the BFV encryption kernels
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -37,6 +38,7 @@ EXPORTS = [
     "zkfhe_chacha20_block", "zkfhe_snark_encode", "zkfhe_snark_decode", "zkfhe_bfv_keygen", "zkfhe_bfv_pk_destroy", "zkfhe_bfv_pk_release_ctx", "zkfhe_bfv_pk_info", "zkfhe_bfv_pk_prefix_cache",
     "zkfhe_bfv_pk_commitments", "zkfhe_bfv_pk_break_points", "zkfhe_bfv_pk_prehash", "zkfhe_bfv_prove", "zkfhe_bfv_pk_export_vk", "zkfhe_bfv_pk_save", "zkfhe_bfv_pk_load", "zkfhe_bfv_witness_stream", "zkfhe_lookup_permute", "zkfhe_bfv_verify", "zkfhe_bfv_verify_g2",
     "zkfhe_g1_decompress", "zkfhe_msm_segmented", "zkfhe_bfv_verify_batch",
+    "zkfhe_poly_mul_ternary_negacyclic", "zkfhe_bfv_error_cdt", "zkfhe_bfv_fhe_keypair", "zkfhe_bfv_encrypt", "zkfhe_bfv_decrypt", "zkfhe_bfv_prove_words",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -422,6 +424,94 @@ class Context:
         da.free(), dd.free(), dr.free()
         return d, r
 
+    # ------------------------------------------------------------------ BFV keygen / encrypt / decrypt (zkfhe.h, bfv_enc.hip)
+    # Polynomials are uint64 arrays of N residues in [0, Q), CircuitInput order (highest degree first); params = (n, q, t, b).
+
+    def poly_mul_ternary_negacyclic(self, a, s, q):
+        """zkfhe_poly_mul_ternary_negacyclic on host arrays: a of shape (N,) (shared) or (n_polys, N), s of shape (n_polys, N) with
+        coefficients in {0, 1, q - 1}; returns a * s mod (x^N + 1, q), shape (n_polys, N).  A non-ternary s raises ZkfheError."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        s = np.ascontiguousarray(s, dtype=np.uint64)
+        s2 = s.reshape(-1, s.shape[-1])
+        n_polys, n = s2.shape
+        a_count = 1 if a.ndim == 1 else a.shape[0]
+        vp = ctypes.c_void_p
+        self.lib.zkfhe_poly_mul_ternary_negacyclic.argtypes = [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64,
+                                                               vp, ctypes.POINTER(ctypes.c_int)]
+        da, ds, do = self.to_device(a), self.to_device(s2), self.alloc(s2.nbytes)
+        try:
+            bad = ctypes.c_int()
+            self._check(self.lib.zkfhe_poly_mul_ternary_negacyclic(self.h, self._p(da), a_count, self._p(ds), n_polys, n, int(q), self._p(do),
+                                                                   ctypes.byref(bad)))
+            return do.download(shape=(n_polys, n))
+        finally:
+            da.free(), ds.free(), do.free()
+
+    def bfv_fhe_keypair(self, params, seed=None):
+        """zkfhe_bfv_fhe_keypair -> (sk, pk0, pk1).  seed: 32 secret bytes (None: os.urandom)."""
+        n = int(params[0])
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the key-generation seed is 32 bytes")
+        out = [np.empty(n, dtype=np.uint64) for _ in range(3)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_fhe_keypair.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_char_p, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_fhe_keypair(self.h, ctypes.byref(prm), seed, *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_encrypt(self, params, pk0, pk1, m, seed=None, first_index=0):
+        """zkfhe_bfv_encrypt: m of shape (N,) or (n_msgs, N) -> dict u, e0, e1, c0, c1 of shape (n_msgs, N).  seed: 32 SECRET, FRESH
+        bytes (None: os.urandom); reusing a (seed, index) pair reuses u (zkfhe.h)."""
+        n = int(params[0])
+        pk0 = np.ascontiguousarray(pk0, dtype=np.uint64)
+        pk1 = np.ascontiguousarray(pk1, dtype=np.uint64)
+        m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1, n)
+        if pk0.size != n or pk1.size != n:
+            raise ValueError("pk0 / pk1 must hold N coefficients")
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the encryption seed is 32 bytes")
+        names = ("u", "e0", "e1", "c0", "c1")
+        out = {k: np.empty(m.shape, dtype=np.uint64) for k in names}
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_encrypt.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_char_p,
+                                               ctypes.c_uint64] + [u64p] * 5
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_encrypt(self.h, ctypes.byref(prm), pk0.ctypes.data_as(u64p), pk1.ctypes.data_as(u64p), m.shape[0],
+                                               m.ctypes.data_as(u64p), seed, int(first_index), *[out[k].ctypes.data_as(u64p) for k in names]))
+        return out
+
+    def bfv_decrypt(self, params, sk, c0, c1):
+        """zkfhe_bfv_decrypt: c0, c1 of shape (N,) or (n_msgs, N) -> m as residues mod Q, shape (n_msgs, N)."""
+        n = int(params[0])
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64).reshape(-1, n)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1, n)
+        if sk.size != n or c0.shape != c1.shape:
+            raise ValueError("sk must hold N coefficients and c0, c1 the same shape")
+        out = np.empty(c0.shape, dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_decrypt.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_size_t, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_decrypt(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c0.shape[0], c0.ctypes.data_as(u64p),
+                                               c1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        return out
+
+
+def bfv_error_cdt(params):
+    """zkfhe_bfv_error_cdt (host only): the 2 B thresholds of the error sampler as a uint64 array."""
+    lib = load_library()
+    lib.zkfhe_bfv_error_cdt.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    prm = BfvParamsC(*[int(x) for x in params])
+    cnt = ctypes.c_size_t()
+    rc = lib.zkfhe_bfv_error_cdt(ctypes.byref(prm), None, ctypes.byref(cnt))
+    if rc != 0:
+        raise ZkfheError("zkfhe_bfv_error_cdt failed (%d): %s" % (rc, lib.zkfhe_last_error(None).decode()))
+    out = np.empty(cnt.value, dtype=np.uint64)
+    lib.zkfhe_bfv_error_cdt(ctypes.byref(prm), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt))
+    return out
+
 
 def version():
     return load_library().zkfhe_version().decode()
@@ -555,6 +645,10 @@ def poseidon_constants():
 # ----------------------------------------------------------------------------- BFV circuit (host layer)
 class BfvParamsC(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("q", ctypes.c_uint64), ("t", ctypes.c_uint64), ("b", ctypes.c_uint64)]
+
+
+class _BfvWordsC(ctypes.Structure):
+    _fields_ = [(k, ctypes.POINTER(ctypes.c_uint64)) for k in ("pk0", "pk1", "m", "u", "e0", "e1", "c0", "c1")]
 
 
 class BfvConfigC(ctypes.Structure):
@@ -1065,6 +1159,53 @@ class BfvProvingKey:
                 break      # otherwise: the library reported the instance count it needs -- retry once with that capacity
         ctx._check(rc)
         return buf.raw[: plen.value], Instances(ibuf.raw[: 32 * ninst.value]), list(tm)
+
+    WORD_FIELDS = ("pk0", "pk1", "m", "u", "e0", "e1", "c0", "c1")
+
+    def prove_words(self, words, seed=None, ctx=None):
+        """zkfhe_bfv_prove_words: the input as machine words, `words` = a mapping of pk0, pk1, m, u, e0, e1, c0, c1 to N residues
+        each (CircuitInput order; cyclo is x^N + 1).  Same bytes as prove() on the JSON that spells the same numbers."""
+        ctx = ctx or self.ctx
+        n = int(self.params[0])
+        seed = os.urandom(32) if seed is None else seed32(seed)
+        arrs = []
+        for k in self.WORD_FIELDS:
+            a = np.ascontiguousarray(words[k], dtype=np.uint64).reshape(-1)
+            if a.size != n:
+                raise ValueError("%s must hold N = %d words" % (k, n))
+            arrs.append(a)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        w = _BfvWordsC(*[a.ctypes.data_as(u64p) for a in arrs])
+        vp = ctypes.c_void_p
+        ctx.lib.zkfhe_bfv_prove_words.argtypes = [vp, vp, vp, ctypes.POINTER(_BfvWordsC), ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t,
+                                                  ctypes.POINTER(ctypes.c_size_t), ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_float)]
+        cap = 1 << 18
+        buf = ctypes.create_string_buffer(cap)
+        plen = ctypes.c_size_t()
+        ninst = ctypes.c_size_t(5 * n + 8)
+        tm = (ctypes.c_float * 5)()
+        ibuf = ctypes.create_string_buffer(32 * ninst.value)
+        ctx._check(ctx.lib.zkfhe_bfv_prove_words(ctx.h, self.srs.h, self.h, ctypes.byref(w), seed, buf, cap, ctypes.byref(plen), ibuf,
+                                                 ctypes.byref(ninst), tm))
+        return buf.raw[: plen.value], Instances(ibuf.raw[: 32 * ninst.value]), list(tm)
+
+    def encrypt_and_prove(self, pk0, pk1, m, enc_seed=None, seed=None, first_index=0, ctx=None):
+        """Encrypt m (shape (N,) or (n_msgs, N), residues mod Q) under (pk0, pk1) on the GPU and prove each encryption.  Returns
+        (c0, c1, proofs, instances): for one message c0, c1 of shape (N,) and one proof; otherwise lists.  enc_seed (the encryption
+        randomness) and seed (the blinding of the proofs): None draws os.urandom(32); both must be secret and fresh."""
+        ctx = ctx or self.ctx
+        single = np.asarray(m).ndim == 1
+        ct = ctx.bfv_encrypt(self.params, pk0, pk1, m, seed=enc_seed, first_index=first_index)
+        proofs, insts = [], []
+        for j in range(ct["c0"].shape[0]):
+            words = {"pk0": pk0, "pk1": pk1, "m": np.asarray(m, dtype=np.uint64).reshape(-1, int(self.params[0]))[j]}
+            words.update({k: ct[k][j] for k in ("u", "e0", "e1", "c0", "c1")})
+            proof, inst, _ = self.prove_words(words, seed=None if seed is None else seed32(bytes(seed32(seed)) + j.to_bytes(8, "little")), ctx=ctx)
+            proofs.append(proof)
+            insts.append(inst)
+        if single:
+            return ct["c0"][0], ct["c1"][0], proofs[0], insts[0]
+        return ct["c0"], ct["c1"], proofs, insts
 
     def witness_stream(self, input_json_text, gamma):
         """zkfhe_bfv_witness_stream: the phase-1 gate-context cells as the GPU generates them, as an (n_cells, 4) uint64 array

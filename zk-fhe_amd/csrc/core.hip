@@ -158,6 +158,8 @@ int zkfhe_ctx_destroy(zkfhe_ctx *ctx) {
   for (int i = 0; i < 4; ++i)
     if (ctx->scratch[i]) hipFree(ctx->scratch[i]);
   if (ctx->tickets) hipFree(ctx->tickets);
+  if (ctx->bfv_tw) hipFree(ctx->bfv_tw);
+  if (ctx->bfv_work) hipFree(ctx->bfv_work);
   if (ctx->wait_ev) hipEventDestroy(ctx->wait_ev);
   hipEventDestroy(ctx->ev0);
   hipEventDestroy(ctx->ev1);

@@ -44,8 +44,9 @@ struct zkfhe_ctx {
   bool prof_on = false;
   hipEvent_t pe0 = nullptr, pe1 = nullptr;
   hipEvent_t wait_ev = nullptr;  // hipEventBlockingSync: host waits sleep instead of spinning (zk_wait)
-  // [2] = k_msm_table of a call of a few columns, [3] = k_g1_decompress, [4] = k_msm_segmented (verify.hip)
-  static constexpr int PROF_SLOTS = 5;
+  // [2] = k_msm_table of a call of a few columns, [3] = k_g1_decompress, [4] = k_msm_segmented (verify.hip),
+  // [5] = k_bfv_sample, [6] = k_rns_ntt, [7] = k_rns_epilogue (bfv_enc.hip)
+  static constexpr int PROF_SLOTS = 8;
   double prof_ms[PROF_SLOTS] = {}, prof_bytes[PROF_SLOTS] = {}, prof_ops[PROF_SLOTS] = {};
   uint64_t prof_launches[PROF_SLOTS] = {};
   // pinned bounce buffer for small host<->device transfers (pageable copies go through the runtime's shared staging path)
@@ -56,7 +57,11 @@ struct zkfhe_ctx {
   // host-side marks of the last proof made on this context, ms from its start (zkfhe_ctx_last_proof_marks): [0] the phase-0
   // commitment is back from the GPU, [1] the first challenge is squeezed (behind the public inputs' sponge), [2] the proof is done
   float proof_marks[3] = {0, 0, 0};
-  unsigned *tickets = nullptr;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
+  unsigned *tickets = nullptr;
+  // BFV encryption (bfv_enc.hip): the RNS twiddle tables (built on first use) and a grow-only work arena
+  uint32_t *bfv_tw = nullptr;
+  void *bfv_work = nullptr;
+  size_t bfv_work_sz = 0;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
 };
 
 struct zkfhe_basis {

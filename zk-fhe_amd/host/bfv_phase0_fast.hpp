@@ -134,17 +134,25 @@ inline bool phase0_force_generic() {
   return e && strcmp(e, "generic") == 0;
 }
 
-// See the header comment.  ctx must be empty and in prover mode (values only).
-inline bool bfv_phase0_fast(Context &ctx, const char *text, size_t text_len, const BfvParams &prm, std::vector<Cell> &make_public, BfvState &st,
-                            const std::function<void(const std::vector<Cell> &)> &on_public = nullptr) {
+inline bool phase0_fast_domain(const Context &ctx, const BfvParams &prm) {
+  const size_t N = prm.N;
+  const uint64_t Q = prm.Q;
+  return !(phase0_force_generic() || ctx.record_structure || !ctx.advice.empty() || N < 2 || (N & (N - 1)) || Q < 2 || (Q >> 63) || prm.T == 0);
+}
+
+// The values stage: the input as machine words (what fast_parse_input makes of the text, or the caller's words for
+// zkfhe_bfv_prove_words).  Same contract as bfv_phase0_fast; `in` is only read during the call.
+inline bool bfv_phase0_fast_values(Context &ctx, const FastInput &in, const BfvParams &prm, std::vector<Cell> &make_public, BfvState &st,
+                                   const std::function<void(const std::vector<Cell> &)> &on_public = nullptr) {
   typedef unsigned __int128 u128;
   const size_t N = prm.N;
   const uint64_t Q = prm.Q;
-  if (phase0_force_generic() || ctx.record_structure || !ctx.advice.empty() || N < 2 || (N & (N - 1)) || Q < 2 || (Q >> 63) || prm.T == 0) return false;
-  FastInput in;
-  if (!fast_parse_input(text, text_len, Q, in)) return false;
+  if (!phase0_fast_domain(ctx, prm)) return false;
   for (int k = 0; k < 8; ++k)
     if (in.a[k].size() != N) return false;
+  for (int k = 0; k < 9; ++k)   // the parser's own bound (`coeff <= modulus`): words that did not come through it are checked here
+    for (const uint64_t v : in.a[k])
+      if (v > Q) return false;
   const std::vector<uint64_t> &cy = in.a[8];
   if (cy.size() != N + 1 || cy[0] != 1 || cy[N] != 1) return false;
   for (size_t i = 1; i < N; ++i)
@@ -280,6 +288,34 @@ inline bool bfv_phase0_fast(Context &ctx, const char *text, size_t text_len, con
     for (int k = 9; k < 17; ++k) fill(k);
   }
   return true;
+}
+
+// See the header comment.  ctx must be empty and in prover mode (values only).
+inline bool bfv_phase0_fast(Context &ctx, const char *text, size_t text_len, const BfvParams &prm, std::vector<Cell> &make_public, BfvState &st,
+                            const std::function<void(const std::vector<Cell> &)> &on_public = nullptr) {
+  if (!phase0_fast_domain(ctx, prm)) return false;
+  FastInput in;
+  if (!fast_parse_input(text, text_len, prm.Q, in)) return false;
+  return bfv_phase0_fast_values(ctx, in, prm, make_public, st, on_public);
+}
+
+// The CircuitInput JSON that spells the same numbers as `in` (what the text path gets when the values stage declines words).
+inline std::string render_input_json(const FastInput &in) {
+  static const char *names[9] = {"pk0", "pk1", "m", "u", "e0", "e1", "c0", "c1", "cyclo"};
+  std::string out = "{";
+  char buf[24];
+  for (int k = 0; k < 9; ++k) {
+    out += k ? ", \"" : "\"";
+    out += names[k];
+    out += "\": [";
+    for (size_t i = 0; i < in.a[k].size(); ++i) {
+      snprintf(buf, sizeof(buf), i ? ", \"%llu\"" : "\"%llu\"", (unsigned long long)in.a[k][i]);
+      out += buf;
+    }
+    out += "]";
+  }
+  out += "}";
+  return out;
 }
 
 }  // namespace zkhost

@@ -533,7 +533,8 @@ struct Trace {
   }
 };
 
-int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const char *input_json, const uint8_t seed[32],
+// input_json: the CircuitInput text; or words (input_json == nullptr): the same numbers as machine words (zkfhe_bfv_prove_words)
+int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const char *input_json, const FastInput *words, const uint8_t seed[32],
                std::vector<uint8_t> &proof, std::vector<U256> &instances, float *timings) {
   const CircuitConfig &cfg = pk->cfg;
   const size_t n = cfg.n(), u = cfg.u(), ne = 4 * n;
@@ -605,7 +606,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     for (const Cell &c : pub) instances.push_back(c.value);
     const size_t n_key = std::min<size_t>(instances.size(), 2 * (size_t)pk->prm.N);
     Transcript::State mid;
-    if (pk->prehash.take(input_json, strlen(input_json), instances.data(), instances.size(), mid)) {
+    if (input_json && pk->prehash.take(input_json, strlen(input_json), instances.data(), instances.size(), mid)) {
       tr.restore(mid);   // announced ahead of time (zkfhe_bfv_pk_prehash): `vk digest | public inputs` are absorbed already
     } else if (!n_key || !pk->prefix.capacity()) {
       tr.common_scalars_async(instances);
@@ -620,8 +621,16 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   };
   // machine-word phase 0 (bfv_phase0_fast.hpp) for every input in its domain; anything else goes through the line-by-line
   // restatement of the reference, which also words the errors
+  // words the values stage declines are rendered as the JSON that spells them and take the text path: the same outcome as
+  // zkfhe_bfv_prove on that text by construction (the announcements of zkfhe_bfv_pk_prehash are keyed on text and serve text only)
   BfvState st;
-  if (!bfv_phase0_fast(ctx0, input_json, strlen(input_json), pk->prm, make_public, st, on_public)) {
+  std::string rendered;
+  if (words ? !bfv_phase0_fast_values(ctx0, *words, pk->prm, make_public, st, on_public)
+            : !bfv_phase0_fast(ctx0, input_json, strlen(input_json), pk->prm, make_public, st, on_public)) {
+    if (words) {
+      rendered = render_input_json(*words);
+      input_json = rendered.c_str();
+    }
     const CircuitInput in = CircuitInput::parse_json(input_json);
     trace.mark("parse_json");
     st = bfv_phase0(ctx0, in, pk->prm, make_public, on_public);
@@ -1429,6 +1438,22 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   return ZKFHE_OK;
 }
 
+int copy_proof_out(zkfhe_ctx *ctx, const std::vector<uint8_t> &proof, const std::vector<U256> &inst, uint8_t *proof_out, size_t proof_cap,
+                   size_t *proof_len, uint8_t *instances_out, size_t *n_instances) {
+  if (proof.size() > proof_cap) return zk_fail_msg(ctx, ZKFHE_EINVAL, "proof buffer too small");
+  memcpy(proof_out, proof.data(), proof.size());
+  *proof_len = proof.size();
+  if (n_instances) {
+    const size_t have = *n_instances;
+    *n_instances = inst.size();
+    if (instances_out) {
+      if (have < inst.size()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "instance buffer too small (the required count is returned in *n_instances)");
+      memcpy(instances_out, inst.data(), inst.size() * 32);
+    }
+  }
+  return ZKFHE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1441,24 +1466,39 @@ int zkfhe_bfv_prove(zkfhe_ctx *ctx, const zkfhe_srs *srs, const zkfhe_bfv_pk *pk
     pos::BulkClientScope in_flight;   // transcript.hpp bulk_ok(): the hash service is shared by the provers in flight
     std::vector<uint8_t> proof;
     std::vector<U256> inst;
-    int rc = prove_impl(ctx, srs, const_cast<zkfhe_bfv_pk *>(pk), input_json, seed, proof, inst, timings_ms);
+    int rc = prove_impl(ctx, srs, const_cast<zkfhe_bfv_pk *>(pk), input_json, nullptr, seed, proof, inst, timings_ms);
     if (rc) return rc;
-    if (proof.size() > proof_cap) return zk_fail_msg(ctx, ZKFHE_EINVAL, "proof buffer too small");
-    memcpy(proof_out, proof.data(), proof.size());
-    *proof_len = proof.size();
-    if (n_instances) {
-      const size_t have = *n_instances;
-      *n_instances = inst.size();
-      if (instances_out) {
-        if (have < inst.size()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "instance buffer too small (the required count is returned in *n_instances)");
-        memcpy(instances_out, inst.data(), inst.size() * 32);
-      }
-    }
-    return ZKFHE_OK;
+    return copy_proof_out(ctx, proof, inst, proof_out, proof_cap, proof_len, instances_out, n_instances);
   } catch (const std::exception &e) {
     return zk_fail_msg(ctx, ZKFHE_EINVAL, e.what());
   }
 }
+
+// zkfhe_bfv_prove on the input as machine words: the key's N words per polynomial, cyclo = x^N + 1.  Same proof, instances and
+// return codes as zkfhe_bfv_prove on the JSON that spells the same numbers.
+int zkfhe_bfv_prove_words(zkfhe_ctx *ctx, const zkfhe_srs *srs, const zkfhe_bfv_pk *pk, const zkfhe_bfv_words *words, const uint8_t seed[32],
+                          uint8_t *proof_out, size_t proof_cap, size_t *proof_len, uint8_t *instances_out, size_t *n_instances, float *timings_ms) {
+  ZK_ENTER(ctx);
+  ZK_ARG(ctx, srs && pk && words && seed && proof_out && proof_len);
+  const uint64_t *src[8] = {words->pk0, words->pk1, words->m, words->u, words->e0, words->e1, words->c0, words->c1};
+  for (const uint64_t *p : src) ZK_ARG(ctx, p != nullptr);
+  try {
+    pos::BulkClientScope in_flight;
+    const size_t N = pk->prm.N;
+    FastInput in;
+    for (int k = 0; k < 8; ++k) in.a[k].assign(src[k], src[k] + N);
+    in.a[8].assign(N + 1, 0);
+    in.a[8][0] = in.a[8][N] = 1;
+    std::vector<uint8_t> proof;
+    std::vector<U256> inst;
+    int rc = prove_impl(ctx, srs, const_cast<zkfhe_bfv_pk *>(pk), nullptr, &in, seed, proof, inst, timings_ms);
+    if (rc) return rc;
+    return copy_proof_out(ctx, proof, inst, proof_out, proof_cap, proof_len, instances_out, n_instances);
+  } catch (const std::exception &e) {
+    return zk_fail_msg(ctx, ZKFHE_EINVAL, e.what());
+  }
+}
+
 
 // Admission gate of the GPU-heavy middle of the proofs of this process (HeavyGate above): n > 0 = that many proofs inside at once,
 // 0 = no gate, negative = query.  Returns the previous setting.  For a service that keeps its streams full (measured: 16 streams,
