@@ -528,6 +528,47 @@ int zkfhe_bfv_decrypt(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint
 #define ZKFHE_PROF_RNS_NTT 6        /* k_rns_ntt */
 #define ZKFHE_PROF_RNS_EPILOGUE 7   /* k_rns_epilogue */
 
+/* ---- BFV evaluation on the GPU: computing on verified ciphertexts (bfv_eval.hip) ----
+ * The conventions above: host arrays, N uint64_t per polynomial in CircuitInput order, residues in [0, Q), batches n x N, the
+ * parameter checks of zkfhe_bfv_encrypt.  Plaintexts m are in [0, T/2] or [Q - T/2, Q - 1].  Every call refuses, with ZKFHE_EINVAL and
+ * a message: a ciphertext or key coefficient >= Q, a plaintext out of range, a non-ternary sk, base_bits outside [1, 32], an m_count
+ * other than 1 or n.  The output of an evaluation is NOT a fresh encryption: zkfhe_bfv_prove_words cannot prove it, and its noise
+ * grows with every operation (zkfhe_bfv_noise).  Every call waits for its result. */
+/* n pairwise a + b (subtract = 0) or a - b (subtract != 0) mod Q */
+int zkfhe_bfv_add(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0,
+                  const uint64_t *b1, int subtract, uint64_t *out0, uint64_t *out1);
+/* one ciphertext (out0, out1 of N), the sum of all n_cts mod Q: the tally.  Uploaded in chunks. */
+int zkfhe_bfv_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0,
+                  uint64_t *out1);
+/* out0 = c0 + floor(Q/T) m mod Q, out1 = c1; m_count = 1 (one plaintext for every ciphertext) or n */
+int zkfhe_bfv_add_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1, size_t m_count,
+                        const uint64_t *m, uint64_t *out0, uint64_t *out1);
+/* (c0 m, c1 m) mod (x^N + 1, Q); m_count = 1 or n */
+int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1, size_t m_count,
+                        const uint64_t *m, uint64_t *out0, uint64_t *out1);
+/* Host only: *l = ceil(bitlen(Q - 1) / w), the number of relinearization digits of width w = base_bits in [1, 32] */
+int zkfhe_bfv_relin_digits(const zkfhe_bfv_params *params, int base_bits, size_t *l);
+/* the relinearization key of sk: l pairs (rlk0, rlk1 of l x N), rlk0_i = -(a_i s + e_i) + 2^(i w) s^2 mod Q, rlk1_i = a_i, with a_i
+ * uniform from ChaCha20 domain 7 and e_i an error sample from domain 8, both with index i (the samplers of zkfhe_bfv_encrypt).  The
+ * key is public; its SEED IS SECRET like any key seed (it gives a_i and e_i, and with them s^2). */
+int zkfhe_bfv_relin_keygen(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk, const uint8_t seed[32], int base_bits,
+                           uint64_t *rlk0, uint64_t *rlk1);
+/* n ciphertext products, relinearized, defined exactly: every input coefficient lifted to its centred integer (v - Q if
+ * v > floor(Q/2)); x0 = a0 b0, x1 = a0 b1 + a1 b0, x2 = a1 b1 exactly over Z in Z[x]/(x^N + 1); c^_j = floor((2 T x_j + Q) / 2Q)
+ * mod Q; digits d_i = (c^2 >> i w) & (2^w - 1) of c^2 in [0, Q); out0 = c^0 + sum_i d_i rlk0_i, out1 = c^1 + sum_i d_i rlk1_i mod Q.
+ * rlk0, rlk1: l x N from zkfhe_bfv_relin_keygen with the same base_bits; they are transformed once per call. */
+int zkfhe_bfv_mul(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0,
+                  const uint64_t *b1, const uint64_t *rlk0, const uint64_t *rlk1, int base_bits, uint64_t *out0, uint64_t *out1);
+/* per ciphertext, max over coefficients of |[c0 + c1 s - floor(Q/T) m]_Q| (centred), m its decryption (zkfhe_bfv_decrypt): the
+ * noise that decryption tolerates while it stays below floor(Q/T) / 2 */
+int zkfhe_bfv_noise(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk, size_t n, const uint64_t *c0, const uint64_t *c1,
+                    uint64_t *noise_out);
+/* zkfhe_prof_read slots of the BFV evaluation kernels */
+#define ZKFHE_PROF_BFV_TENSOR 8            /* k_bfv_tensor */
+#define ZKFHE_PROF_BFV_RELIN 9             /* k_bfv_relin */
+#define ZKFHE_PROF_BFV_EVAL_EPILOGUE 10    /* k_eval_epilogue */
+#define ZKFHE_PROF_BFV_ELEMENTWISE 11      /* k_bfv_sum, k_bfv_add */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

@@ -18,6 +18,7 @@ _lib = None
 
 PROF_G1_DECOMPRESS, PROF_MSM_SEGMENTED = 3, 4   # zkfhe_prof_read slots of the batch verifier's kernels (zkfhe.h)
 PROF_BFV_SAMPLE, PROF_RNS_NTT, PROF_RNS_EPILOGUE = 5, 6, 7   # ... and of the BFV encryption kernels
+PROF_BFV_TENSOR, PROF_BFV_RELIN, PROF_BFV_EVAL_EPILOGUE, PROF_BFV_ELEMENTWISE = 8, 9, 10, 11   # ... and of the BFV evaluation kernels
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -39,6 +40,8 @@ EXPORTS = [
     "zkfhe_bfv_pk_commitments", "zkfhe_bfv_pk_break_points", "zkfhe_bfv_pk_prehash", "zkfhe_bfv_prove", "zkfhe_bfv_pk_export_vk", "zkfhe_bfv_pk_save", "zkfhe_bfv_pk_load", "zkfhe_bfv_witness_stream", "zkfhe_lookup_permute", "zkfhe_bfv_verify", "zkfhe_bfv_verify_g2",
     "zkfhe_g1_decompress", "zkfhe_msm_segmented", "zkfhe_bfv_verify_batch",
     "zkfhe_poly_mul_ternary_negacyclic", "zkfhe_bfv_error_cdt", "zkfhe_bfv_fhe_keypair", "zkfhe_bfv_encrypt", "zkfhe_bfv_decrypt", "zkfhe_bfv_prove_words",
+    "zkfhe_bfv_add", "zkfhe_bfv_sum", "zkfhe_bfv_add_plain", "zkfhe_bfv_mul_plain", "zkfhe_bfv_relin_digits", "zkfhe_bfv_relin_keygen",
+    "zkfhe_bfv_mul", "zkfhe_bfv_noise",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -497,6 +500,129 @@ class Context:
         self._check(self.lib.zkfhe_bfv_decrypt(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c0.shape[0], c0.ctypes.data_as(u64p),
                                                c1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
         return out
+
+    # ------------------------------------------------------------------ BFV evaluation (zkfhe.h, bfv_eval.hip)
+    # Ciphertext components are (n, N) or (N,) uint64 arrays of residues; results are (n, N) like the encrypt wrappers' (bfv_sum: (N,)).
+
+    def _eval_arrays(self, params, *arrs):
+        n = int(params[0])
+        out = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, n) for a in arrs]
+        if any(a.shape != out[0].shape for a in out):
+            raise ValueError("ciphertext components must have the same shape (n, N)")
+        return out
+
+    def _plain(self, params, m, n_cts):
+        n = int(params[0])
+        m = np.ascontiguousarray(m, dtype=np.uint64)
+        m2 = m.reshape(-1, n)
+        if m.ndim == 2 and m2.shape[0] not in (1, n_cts):
+            raise ValueError("m must be one plaintext (N,) or one per ciphertext (n, N)")
+        return m2
+
+    def bfv_add(self, params, a0, a1, b0, b1, subtract=False):
+        """zkfhe_bfv_add: (a0 + b0, a1 + b1) mod Q, or a - b with subtract=True; every input (n, N)."""
+        a0, a1, b0, b1 = self._eval_arrays(params, a0, a1, b0, b1)
+        out = [np.empty(a0.shape, dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_add.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 4 + [ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_add(self.h, ctypes.byref(prm), a0.shape[0], *[x.ctypes.data_as(u64p) for x in (a0, a1, b0, b1)],
+                                           int(bool(subtract)), *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_sum(self, params, c0, c1):
+        """zkfhe_bfv_sum: the sum of all n ciphertexts (c0, c1 of shape (n, N)) as one ciphertext (two arrays of N)."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        out = [np.empty(c0.shape[1], dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_sum.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 4
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_sum(self.h, ctypes.byref(prm), c0.shape[0], c0.ctypes.data_as(u64p), c1.ctypes.data_as(u64p),
+                                           *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def _plain_op(self, fn, params, c0, c1, m):
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        m = self._plain(params, m, c0.shape[0])
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        f = getattr(self.lib, fn)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, u64p, u64p, ctypes.c_size_t, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(f(self.h, ctypes.byref(prm), c0.shape[0], c0.ctypes.data_as(u64p), c1.ctypes.data_as(u64p), m.shape[0],
+                      m.ctypes.data_as(u64p), *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_add_plain(self, params, c0, c1, m):
+        """zkfhe_bfv_add_plain: (c0 + floor(Q/T) m, c1); m is one plaintext (N,) for every ciphertext or one per ciphertext (n, N)."""
+        return self._plain_op("zkfhe_bfv_add_plain", params, c0, c1, m)
+
+    def bfv_mul_plain(self, params, c0, c1, m):
+        """zkfhe_bfv_mul_plain: (c0 m, c1 m) mod (x^N + 1, Q); m as for bfv_add_plain."""
+        return self._plain_op("zkfhe_bfv_mul_plain", params, c0, c1, m)
+
+    def bfv_relin_keygen(self, params, sk, seed=None, base_bits=16):
+        """zkfhe_bfv_relin_keygen -> (rlk0, rlk1) of shape (l, N), l = bfv_relin_digits(params, base_bits).  seed: 32 SECRET bytes
+        (None: os.urandom); the key itself is public."""
+        n = int(params[0])
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        if sk.size != n:
+            raise ValueError("sk must hold N coefficients")
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the relinearization-key seed is 32 bytes")
+        l = bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else 0   # else the call refuses base_bits itself
+        out = [np.empty((l, n), dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_relin_keygen.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_char_p, ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_relin_keygen(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), seed, int(base_bits),
+                                                    *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_mul(self, params, a0, a1, b0, b1, rlk0, rlk1, base_bits=16):
+        """zkfhe_bfv_mul: n relinearized products a * b (every input (n, N)) under the key (rlk0, rlk1) made with base_bits."""
+        a0, a1, b0, b1 = self._eval_arrays(params, a0, a1, b0, b1)
+        n = int(params[0])
+        rlk0 = np.ascontiguousarray(rlk0, dtype=np.uint64)
+        rlk1 = np.ascontiguousarray(rlk1, dtype=np.uint64)
+        l = bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else rlk0.shape[0]   # else the call refuses base_bits
+        if rlk0.shape != (l, n) or rlk1.shape != (l, n):
+            raise ValueError("rlk0 and rlk1 must have shape (l, N) = (%d, %d) for base_bits %d" % (l, n, base_bits))
+        out = [np.empty(a0.shape, dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_mul.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 6 + [ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_mul(self.h, ctypes.byref(prm), a0.shape[0], *[x.ctypes.data_as(u64p) for x in (a0, a1, b0, b1, rlk0, rlk1)],
+                                           int(base_bits), *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_noise(self, params, sk, c0, c1):
+        """zkfhe_bfv_noise: per ciphertext, max |[c0 + c1 s - floor(Q/T) m]_Q| with m the decryption; shape (n,)."""
+        n = int(params[0])
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        if sk.size != n:
+            raise ValueError("sk must hold N coefficients")
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        out = np.empty(c0.shape[0], dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_noise.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_size_t, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_noise(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c0.shape[0], c0.ctypes.data_as(u64p),
+                                             c1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        return out
+
+
+def bfv_relin_digits(params, base_bits):
+    """zkfhe_bfv_relin_digits (host only): l = ceil(bitlen(Q - 1) / base_bits), the rows of a relinearization key."""
+    lib = load_library()
+    lib.zkfhe_bfv_relin_digits.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+    prm = BfvParamsC(*[int(x) for x in params])
+    l = ctypes.c_size_t()
+    rc = lib.zkfhe_bfv_relin_digits(ctypes.byref(prm), int(base_bits), ctypes.byref(l))
+    if rc != 0:
+        raise ZkfheError("zkfhe_bfv_relin_digits failed (%d): %s" % (rc, lib.zkfhe_last_error(None).decode()))
+    return l.value
 
 
 def bfv_error_cdt(params):

@@ -4,9 +4,10 @@
 //
 // Every product has a ternary factor, so the centred integer product c of a (coefficients below 2^64) and s in {-1, 0, 1}^N has
 // |c| < N 2^64 <= 2^79.  Three NTT primes below 2^31 (product 2^89.2 > 2 |c|) carry it exactly: per (polynomial, prime) one
-// workgroup runs the whole negacyclic transform in LDS (k_rns_ntt: N <= 2^15 words = 128 KiB), the shared operand of a batch
-// (pk0, pk1, a, or sk) is transformed once, and one fused epilogue (k_rns_epilogue) rebuilds c by Garner's CRT, reduces it mod Q,
-// adds delta m + e (or rounds to T for decryption) and writes each output coefficient once.  Q itself need not be NTT-friendly.
+// workgroup runs the whole negacyclic transform in LDS (k_rns_ntt of rns_ntt.hip.hpp: N <= 2^15 words = 128 KiB), the shared
+// operand of a batch (pk0, pk1, a, or sk) is transformed once, and one fused epilogue (k_rns_epilogue) rebuilds c by Garner's CRT,
+// reduces it mod Q, adds delta m + e (or rounds to T for decryption) and writes each output coefficient once.  Q itself need not
+// be NTT-friendly.
 //
 // Randomness (zkfhe.h): ChaCha20 keyed by the caller's 32-byte seed, state words 12..15 = {block, domain, index_lo, index_hi},
 // word w of a stream = the w-th little-endian u64 of its keystream, array position p reads word p (uniform: words 2p, 2p + 1).
@@ -14,22 +15,14 @@
 #include <cmath>
 #include <mutex>
 
-#include "ctx.hpp"
+#include "rns_ntt.hip.hpp"
+
+using namespace zkrns;
 
 namespace {
 
-constexpr int NP = 3;
-constexpr uint32_t PRIMES[NP] = {2013265921u, 469762049u, 754974721u};   // 15 2^27 + 1, 7 2^26 + 1, 45 2^24 + 1
-constexpr int LOG_NMAX = 15;
-constexpr size_t NMAX = (size_t)1 << LOG_NMAX;
-constexpr int NTT_THREADS = 1024;
+constexpr int NP = 3;   // the first three primes of rns_ntt.hip.hpp: product 2^89.2
 constexpr int MAX_CDT = 2046;   // 2 B thresholds, B < 1024
-
-// per-call constants of the three primes: p, -p^-1 mod 2^32, and N^-1 R^2 mod p (R = 2^32: the inverse transform's scale, which
-// also undoes the R^-1 of the Montgomery pointwise product)
-struct RnsConst {
-  uint32_t p[NP], pinv[NP], scale[NP];
-};
 // Garner: y1 = (r1 - r0) p0^-1 mod p1, y2 = (r2 - r0 - p0 y1) (p0 p1)^-1 mod p2, x = r0 + p0 y1 + p0 p1 y2
 struct CrtConst {
   uint64_t inv01, inv012, p0_mod_p2, p01;
@@ -48,113 +41,6 @@ struct Epi {
 struct ChaKey {
   uint32_t k[8];
 };
-
-__device__ __forceinline__ uint32_t mont_mul(uint32_t a, uint32_t b, uint32_t p, uint32_t pinv) {
-  const uint64_t x = (uint64_t)a * b;   // < p^2 < 2^62
-  const uint32_t m = (uint32_t)x * pinv;
-  const uint32_t r = (uint32_t)((x + (uint64_t)m * p) >> 32);   // < 2 p
-  return r >= p ? r - p : r;
-}
-__device__ __forceinline__ uint32_t add_p(uint32_t a, uint32_t b, uint32_t p) {
-  const uint32_t s = a + b;   // < 2^32: p < 2^31
-  return s >= p ? s - p : s;
-}
-__device__ __forceinline__ uint32_t sub_p(uint32_t a, uint32_t b, uint32_t p) { return a >= b ? a - b : a + p - b; }
-__device__ __forceinline__ uint64_t add_q(uint64_t a, uint64_t b, uint64_t q) {
-  const uint64_t s = a + b;   // < 2^64: q < 2^63
-  return s >= q ? s - q : s;
-}
-
-// (hi 2^64 + lo) mod q, q < 2^63: bit by bit, no data-dependent branch
-__device__ __forceinline__ uint64_t mod128(uint64_t hi, uint64_t lo, uint64_t q) {
-  uint64_t r = hi % q;
-#pragma unroll 8
-  for (int i = 63; i >= 0; --i) {
-    r = (r << 1) | ((lo >> i) & 1);   // < 2 q < 2^64
-    r -= r >= q ? q : 0;
-  }
-  return r;
-}
-// floor((hi 2^64 + lo) / d) for a quotient below 2^64 (hi < d), any d < 2^64
-__device__ __forceinline__ uint64_t div128(uint64_t hi, uint64_t lo, uint64_t d) {
-  uint64_t r = hi, quo = 0;
-#pragma unroll 8
-  for (int i = 63; i >= 0; --i) {
-    const uint64_t carry = r >> 63;
-    r = (r << 1) | ((lo >> i) & 1);
-    const bool take = carry || r >= d;
-    r -= take ? d : 0;
-    quo |= (uint64_t)take << i;
-  }
-  return quo;
-}
-
-// One workgroup per (polynomial, prime), blockIdx.x = poly * NP + prime.  Loads N coefficients (src is in CircuitInput order:
-// position N-1-d holds degree d) into LDS as residues -- `ternary`: {0, 1, Q-1} -> {0, 1, p-1}, anything else is flagged and read
-// as 0; otherwise the integer mod p -- and runs the merged-twist negacyclic transform (Cooley-Tukey, bit-reversed output).
-// MUL = false: the transform is stored to `out` (hat[poly][prime][N]).  MUL = true: it is multiplied by hat + poly * hat_stride,
-// transformed back (Gentleman-Sande), scaled, and the residues of the product are stored to out[poly][prime][degree].
-template <bool MUL>
-__global__ __launch_bounds__(NTT_THREADS) void k_rns_ntt(const uint64_t *__restrict__ src, int ternary, uint64_t q, int log_n,
-                                                          const uint32_t *__restrict__ tw, RnsConst rc, const uint32_t *__restrict__ hat,
-                                                          size_t hat_stride, uint32_t *__restrict__ out, int *flag) {
-  extern __shared__ uint32_t lds[];
-  const unsigned j = blockIdx.x % NP;
-  const size_t poly = blockIdx.x / NP;
-  const unsigned n = 1u << log_n, half = n >> 1, tid = threadIdx.x;
-  const uint32_t p = rc.p[j], pinv = rc.pinv[j];
-  const uint64_t *s = src + poly * n;
-  bool bad = false;
-  for (unsigned d = tid; d < n; d += NTT_THREADS) {
-    const uint64_t v = s[n - 1 - d];
-    uint32_t r;
-    if (ternary) {
-      const bool one = v == 1, minus = v == q - 1;
-      bad |= !(one || minus || v == 0);
-      r = one ? 1u : (minus ? p - 1 : 0u);
-    } else {
-      r = (uint32_t)(v % p);
-    }
-    lds[d] = r;
-  }
-  if (bad) atomicOr(flag, 1);
-  __syncthreads();
-  const uint32_t *fw = tw + (size_t)j * 2 * NMAX, *iv = fw + NMAX;   // psi^br(k), psi^-br(k) (Montgomery form); prefixes serve every N
-  for (int lm = 0; lm < log_n; ++lm) {   // m = 2^lm groups, t = n / 2m
-    const int lt = log_n - 1 - lm;
-    const unsigned t = 1u << lt;
-    for (unsigned b = tid; b < half; b += NTT_THREADS) {
-      const unsigned i = b >> lt, x = (i << (lt + 1)) + (b & (t - 1));
-      const uint32_t w = fw[(1u << lm) + i];
-      const uint32_t U = lds[x], V = mont_mul(lds[x + t], w, p, pinv);
-      lds[x] = add_p(U, V, p);
-      lds[x + t] = sub_p(U, V, p);
-    }
-    __syncthreads();
-  }
-  if (!MUL) {
-    uint32_t *o = out + (poly * NP + j) * n;
-    for (unsigned d = tid; d < n; d += NTT_THREADS) o[d] = lds[d];
-    return;
-  }
-  const uint32_t *h = hat + poly * hat_stride + (size_t)j * n;
-  for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = mont_mul(lds[d], h[d], p, pinv);
-  __syncthreads();
-  for (int lh = log_n - 1; lh >= 0; --lh) {   // h = 2^lh groups, t = n / 2h
-    const int lt = log_n - 1 - lh;
-    const unsigned t = 1u << lt;
-    for (unsigned b = tid; b < half; b += NTT_THREADS) {
-      const unsigned i = b >> lt, x = (i << (lt + 1)) + (b & (t - 1));
-      const uint32_t w = iv[(1u << lh) + i];
-      const uint32_t U = lds[x], V = lds[x + t];
-      lds[x] = add_p(U, V, p);
-      lds[x + t] = mont_mul(sub_p(U, V, p), w, p, pinv);
-    }
-    __syncthreads();
-  }
-  uint32_t *o = out + (poly * NP + j) * n;
-  for (unsigned d = tid; d < n; d += NTT_THREADS) o[d] = mont_mul(lds[d], rc.scale[j], p, pinv);
-}
 
 // One thread per output coefficient: CRT of the three residues to the centred integer, mod Q, then the mode's additions; writes
 // out[poly][N-1-d] (CircuitInput order).  m, e, c0 are read at the same position.
@@ -271,65 +157,6 @@ __global__ __launch_bounds__(256) void k_bfv_sample(ChaKey key, uint32_t domain,
 
 // ------------------------------------------------------------------------------------------------------------------ host side
 
-uint64_t pow_mod(uint64_t a, uint64_t e, uint64_t p) {
-  uint64_t r = 1;
-  for (a %= p; e; e >>= 1, a = a * a % p)
-    if (e & 1) r = r * a % p;
-  return r;
-}
-
-int bit_log2(uint64_t n) {
-  int l = 0;
-  while (((uint64_t)1 << l) < n) ++l;
-  return l;
-}
-
-// [prime][fwd | inv][NMAX]: psi^br15(k) and psi^-br15(k) in Montgomery form, psi of order 2 NMAX.  The first N entries are the
-// tables of every N <= NMAX (bit reversal in 15 bits of k < N = bit reversal in log N bits times NMAX / N).
-int rns_tables(zkfhe_ctx *ctx, const uint32_t **out) {
-  if (!ctx->bfv_tw) {
-    std::vector<uint32_t> h((size_t)NP * 2 * NMAX);
-    for (int j = 0; j < NP; ++j) {
-      const uint64_t p = PRIMES[j];
-      uint64_t psi = 0;
-      for (uint64_t g = 2; !psi; ++g) {
-        const uint64_t c = pow_mod(g, (p - 1) / (2 * NMAX), p);
-        if (pow_mod(c, NMAX, p) == p - 1) psi = c;
-      }
-      const uint64_t psi_inv = pow_mod(psi, p - 2, p), R = ((uint64_t)1 << 32) % p;
-      uint64_t f = 1, b = 1;
-      std::vector<uint64_t> pf(NMAX), pb(NMAX);
-      for (size_t e = 0; e < NMAX; ++e) pf[e] = f, pb[e] = b, f = f * psi % p, b = b * psi_inv % p;
-      for (size_t k = 0; k < NMAX; ++k) {
-        size_t r = 0;
-        for (int i = 0; i < LOG_NMAX; ++i) r |= ((k >> i) & 1) << (LOG_NMAX - 1 - i);
-        h[(size_t)j * 2 * NMAX + k] = (uint32_t)(pf[r] * R % p);
-        h[(size_t)j * 2 * NMAX + NMAX + k] = (uint32_t)(pb[r] * R % p);
-      }
-    }
-    void *d;
-    ZK_HIP(ctx, hipMalloc(&d, h.size() * 4));
-    ZK_HIP(ctx, hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    ctx->bfv_tw = (uint32_t *)d;
-  }
-  *out = ctx->bfv_tw;
-  return ZKFHE_OK;
-}
-
-RnsConst rns_const(int log_n) {
-  RnsConst c;
-  for (int j = 0; j < NP; ++j) {
-    const uint64_t p = PRIMES[j];
-    uint32_t inv = 1;   // p^-1 mod 2^32 by Newton
-    for (int i = 0; i < 5; ++i) inv *= 2 - (uint32_t)p * inv;
-    c.p[j] = (uint32_t)p;
-    c.pinv[j] = (uint32_t)(0u - inv);
-    const uint64_t n_inv = pow_mod((uint64_t)1 << log_n, p - 2, p), R2 = pow_mod(2, 64, p);
-    c.scale[j] = (uint32_t)(n_inv * R2 % p);
-  }
-  return c;
-}
-
 CrtConst crt_const() {
   const uint64_t p0 = PRIMES[0], p1 = PRIMES[1], p2 = PRIMES[2];
   CrtConst c;
@@ -359,19 +186,7 @@ int work_arena(zkfhe_ctx *ctx, size_t bytes, char **out) {
 
 int launch_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, bool ternary, uint64_t q, size_t n_polys, int log_n, const uint32_t *hat,
                size_t hat_stride, uint32_t *out, int *flag) {
-  const uint32_t *tw;
-  ZK_CK(rns_tables(ctx, &tw));
-  const int lds = 4 << log_n;
-  const void *kern = mul ? (const void *)k_rns_ntt<true> : (const void *)k_rns_ntt<false>;
-  if (lds > 64 * 1024) ZK_CK(zk_func_max_lds(ctx, kern, 4 << LOG_NMAX));
-  zk_prof_begin(ctx);
-  if (mul)
-    k_rns_ntt<true><<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(src, ternary, q, log_n, tw, rns_const(log_n), hat, hat_stride, out, flag);
-  else
-    k_rns_ntt<false><<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(src, ternary, q, log_n, tw, rns_const(log_n), nullptr, 0, out, flag);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, (double)n_polys * NP * (8.0 + (mul ? 8.0 : 4.0)) * ((size_t)1 << log_n));
-  return ZKFHE_OK;
+  return launch_rns_ntt<NP>(ctx, mul, src, ternary ? LOAD_TERNARY : LOAD_RESIDUE, q, n_polys, log_n, hat, hat_stride, out, flag);
 }
 
 int launch_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const Epi &epi, uint64_t *out) {
@@ -430,11 +245,48 @@ ChaKey cha_key(const uint8_t seed[32]) {
   return k;
 }
 
-size_t chunk_polys(uint64_t n) { return std::max<size_t>(8, ((size_t)1 << 21) / n); }
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
+
+// [prime][fwd | inv][NMAX] for all NP_MAX primes (the three-prime kernels read the first three): psi^br15(k) and psi^-br15(k) in
+// Montgomery form, psi of order 2 NMAX.  The first N entries are the tables of every N <= NMAX (bit reversal in 15 bits of k < N =
+// bit reversal in log N bits times NMAX / N).
+int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out) {
+  if (!ctx->bfv_tw) {
+    std::vector<uint32_t> h((size_t)NP_MAX * 2 * NMAX);
+    for (int j = 0; j < NP_MAX; ++j) {
+      const uint64_t p = PRIMES[j];
+      uint64_t psi = 0;
+      for (uint64_t g = 2; !psi; ++g) {
+        const uint64_t c = pow_mod(g, (p - 1) / (2 * NMAX), p);
+        if (pow_mod(c, NMAX, p) == p - 1) psi = c;
+      }
+      const uint64_t psi_inv = pow_mod(psi, p - 2, p), R = ((uint64_t)1 << 32) % p;
+      uint64_t f = 1, b = 1;
+      std::vector<uint64_t> pf(NMAX), pb(NMAX);
+      for (size_t e = 0; e < NMAX; ++e) pf[e] = f, pb[e] = b, f = f * psi % p, b = b * psi_inv % p;
+      for (size_t k = 0; k < NMAX; ++k) {
+        size_t r = 0;
+        for (int i = 0; i < LOG_NMAX; ++i) r |= ((k >> i) & 1) << (LOG_NMAX - 1 - i);
+        h[(size_t)j * 2 * NMAX + k] = (uint32_t)(pf[r] * R % p);
+        h[(size_t)j * 2 * NMAX + NMAX + k] = (uint32_t)(pb[r] * R % p);
+      }
+    }
+    void *d;
+    ZK_HIP(ctx, hipMalloc(&d, h.size() * 4));
+    ZK_HIP(ctx, hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    ctx->bfv_tw = (uint32_t *)d;
+  }
+  *out = ctx->bfv_tw;
+  return ZKFHE_OK;
+}
+
+int zk_bfv_check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm) { return check_params(ctx, prm); }
+int zk_bfv_work_arena(zkfhe_ctx *ctx, size_t bytes, char **out) { return work_arena(ctx, bytes, out); }
+void zk_bfv_error_cdt(uint64_t b, uint64_t *t) { error_cdt(b, t); }
+int zk_bfv_sample(zkfhe_ctx *ctx, const uint8_t seed[32], uint32_t domain, uint64_t index0, int kind, size_t n_polys, int log_n, uint64_t q,
+                  const uint64_t *cdt_dev, int n_cdt, uint64_t *out) {
+  return launch_sample(ctx, cha_key(seed), domain, index0, kind, n_polys, log_n, q, cdt_dev, n_cdt, out);
+}
 
 extern "C" {
 

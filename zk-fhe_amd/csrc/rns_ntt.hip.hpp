@@ -1,0 +1,220 @@
+// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip): an RNS NTT over NP primes below 2^31, one
+// workgroup per (polynomial, prime), the whole transform of N <= 2^15 words in LDS (128 KiB at N = 2^15), with 32-bit Montgomery
+// arithmetic.  Templated on the prime count: encryption uses the first three primes (product 2^89.2: a ternary factor keeps the
+// product below N 2^64), the evaluator all five (product 2^151.2: a product of two centred residues below 2^63 stays below 2^140).
+// Headroom at p < 2^31: a b + m p < 2^62 + 2^63 < 2^64 in mont_mul, and a + b < 2^32 in add_p.
+#pragma once
+#include <algorithm>
+
+#include "ctx.hpp"
+
+// defined in bfv_enc.hip, shared with bfv_eval.hip
+// the twiddle tables of every prime: [prime][fwd | inv][NMAX], psi^br15(k) and psi^-br15(k) in Montgomery form (built on first use)
+int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out);
+// the parameter check of every BFV call (zkfhe.h)
+int zk_bfv_check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm);
+// the context's grow-only BFV work arena
+int zk_bfv_work_arena(zkfhe_ctx *ctx, size_t bytes, char **out);
+// the 2 B thresholds of the error sampler
+void zk_bfv_error_cdt(uint64_t b, uint64_t *t);
+// n_polys samples of ChaCha20 stream (seed, domain, index0 + j); kind 0 ternary, 1 uniform, 2 error (cdt_dev: n_cdt thresholds)
+int zk_bfv_sample(zkfhe_ctx *ctx, const uint8_t seed[32], uint32_t domain, uint64_t index0, int kind, size_t n_polys, int log_n, uint64_t q,
+                  const uint64_t *cdt_dev, int n_cdt, uint64_t *out);
+
+namespace zkrns {
+
+constexpr int NP_MAX = 5;
+// 15 2^27 + 1, 7 2^26 + 1, 45 2^24 + 1, 32766 2^16 + 1, 32760 2^16 + 1: every one has 2^16 | p - 1 (order-2N roots up to N = 2^15)
+constexpr uint32_t PRIMES[NP_MAX] = {2013265921u, 469762049u, 754974721u, 2147352577u, 2146959361u};
+constexpr int LOG_NMAX = 15;
+constexpr size_t NMAX = (size_t)1 << LOG_NMAX;
+constexpr int NTT_THREADS = 1024;
+
+// per-call constants of the primes: p, -p^-1 mod 2^32, and N^-1 R^2 mod p (R = 2^32: the inverse transform's scale, which also
+// undoes the R^-1 of the Montgomery pointwise product)
+template <int NP>
+struct RnsConst {
+  uint32_t p[NP], pinv[NP], scale[NP];
+};
+
+// how k_rns_ntt reads a coefficient v (below 2^64) of its source: as the integer v; as a ternary {0, 1, Q-1} -> {0, 1, -1} (anything
+// else is flagged and read as 0); or centred, v - Q if v > floor(Q/2)
+enum LoadMode { LOAD_RESIDUE = 0, LOAD_TERNARY = 1, LOAD_CENTRED = 2 };
+
+__device__ __forceinline__ uint32_t mont_mul(uint32_t a, uint32_t b, uint32_t p, uint32_t pinv) {
+  const uint64_t x = (uint64_t)a * b;   // < p^2 < 2^62
+  const uint32_t m = (uint32_t)x * pinv;
+  const uint32_t r = (uint32_t)((x + (uint64_t)m * p) >> 32);   // < 2 p
+  return r >= p ? r - p : r;
+}
+__device__ __forceinline__ uint32_t add_p(uint32_t a, uint32_t b, uint32_t p) {
+  const uint32_t s = a + b;   // < 2^32: p < 2^31
+  return s >= p ? s - p : s;
+}
+__device__ __forceinline__ uint32_t sub_p(uint32_t a, uint32_t b, uint32_t p) { return a >= b ? a - b : a + p - b; }
+
+__device__ __forceinline__ uint64_t add_q(uint64_t a, uint64_t b, uint64_t q) {
+  const uint64_t s = a + b;   // < 2^64: q < 2^63
+  return s >= q ? s - q : s;
+}
+
+// (hi 2^64 + lo) mod q, q < 2^63: bit by bit, no data-dependent branch
+__device__ __forceinline__ uint64_t mod128(uint64_t hi, uint64_t lo, uint64_t q) {
+  uint64_t r = hi % q;
+#pragma unroll 8
+  for (int i = 63; i >= 0; --i) {
+    r = (r << 1) | ((lo >> i) & 1);   // < 2 q < 2^64
+    r -= r >= q ? q : 0;
+  }
+  return r;
+}
+// floor((hi 2^64 + lo) / d) for a quotient below 2^64 (hi < d), any d < 2^64
+__device__ __forceinline__ uint64_t div128(uint64_t hi, uint64_t lo, uint64_t d) {
+  uint64_t r = hi, quo = 0;
+#pragma unroll 8
+  for (int i = 63; i >= 0; --i) {
+    const uint64_t carry = r >> 63;
+    r = (r << 1) | ((lo >> i) & 1);
+    const bool take = carry || r >= d;
+    r -= take ? d : 0;
+    quo |= (uint64_t)take << i;
+  }
+  return quo;
+}
+
+// v read in `mode` as a residue mod p; `bad` collects non-ternary coefficients of LOAD_TERNARY
+__device__ __forceinline__ uint32_t rns_load(uint64_t v, int mode, uint64_t q, uint32_t p, bool &bad) {
+  if (mode == LOAD_TERNARY) {
+    const bool one = v == 1, minus = v == q - 1;
+    bad |= !(one || minus || v == 0);
+    return one ? 1u : (minus ? p - 1 : 0u);
+  }
+  if (mode == LOAD_CENTRED) {
+    const bool neg = v > q / 2;
+    const uint32_t r = (uint32_t)((neg ? q - v : v) % p);
+    return neg && r ? p - r : r;
+  }
+  return (uint32_t)(v % p);
+}
+
+// merged-twist negacyclic forward transform of lds[0, n) in place (Cooley-Tukey, bit-reversed output); fw = psi^br(k) in Montgomery
+// form.  Ends with a barrier.
+__device__ __forceinline__ void rns_forward(uint32_t *lds, const uint32_t *__restrict__ fw, int log_n, uint32_t p, uint32_t pinv) {
+  const unsigned half = (1u << log_n) >> 1, tid = threadIdx.x;
+  for (int lm = 0; lm < log_n; ++lm) {   // m = 2^lm groups, t = n / 2m
+    const int lt = log_n - 1 - lm;
+    const unsigned t = 1u << lt;
+    for (unsigned b = tid; b < half; b += NTT_THREADS) {
+      const unsigned i = b >> lt, x = (i << (lt + 1)) + (b & (t - 1));
+      const uint32_t w = fw[(1u << lm) + i];
+      const uint32_t U = lds[x], V = mont_mul(lds[x + t], w, p, pinv);
+      lds[x] = add_p(U, V, p);
+      lds[x + t] = sub_p(U, V, p);
+    }
+    __syncthreads();
+  }
+}
+
+// the inverse (Gentleman-Sande) of rns_forward without the final scale; iv = psi^-br(k) in Montgomery form.  Ends with a barrier.
+__device__ __forceinline__ void rns_inverse(uint32_t *lds, const uint32_t *__restrict__ iv, int log_n, uint32_t p, uint32_t pinv) {
+  const unsigned half = (1u << log_n) >> 1, tid = threadIdx.x;
+  for (int lh = log_n - 1; lh >= 0; --lh) {   // h = 2^lh groups, t = n / 2h
+    const int lt = log_n - 1 - lh;
+    const unsigned t = 1u << lt;
+    for (unsigned b = tid; b < half; b += NTT_THREADS) {
+      const unsigned i = b >> lt, x = (i << (lt + 1)) + (b & (t - 1));
+      const uint32_t w = iv[(1u << lh) + i];
+      const uint32_t U = lds[x], V = lds[x + t];
+      lds[x] = add_p(U, V, p);
+      lds[x + t] = mont_mul(sub_p(U, V, p), w, p, pinv);
+    }
+    __syncthreads();
+  }
+}
+
+// One workgroup per (polynomial, prime), blockIdx.x = poly * NP + prime.  Loads N coefficients (src is in CircuitInput order:
+// position N-1-d holds degree d) into LDS in `mode` and runs the forward transform.  MUL = false: the transform is stored to `out`
+// (hat[poly][prime][N]).  MUL = true: it is multiplied by hat + poly * hat_stride, transformed back, scaled, and the residues of the
+// product are stored to out[poly][prime][degree].  tw: [prime][fwd | inv][NMAX] (zk_rns_tables).
+template <int NP, bool MUL>
+__global__ __launch_bounds__(NTT_THREADS) void k_rns_ntt(const uint64_t *__restrict__ src, int mode, uint64_t q, int log_n,
+                                                          const uint32_t *__restrict__ tw, RnsConst<NP> rc, const uint32_t *__restrict__ hat,
+                                                          size_t hat_stride, uint32_t *__restrict__ out, int *flag) {
+  extern __shared__ uint32_t lds[];
+  const unsigned j = blockIdx.x % NP;
+  const size_t poly = blockIdx.x / NP;
+  const unsigned n = 1u << log_n, tid = threadIdx.x;
+  const uint32_t p = rc.p[j], pinv = rc.pinv[j];
+  const uint64_t *s = src + poly * n;
+  bool bad = false;
+  for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = rns_load(s[n - 1 - d], mode, q, p, bad);
+  if (bad) atomicOr(flag, 1);
+  __syncthreads();
+  const uint32_t *fw = tw + (size_t)j * 2 * NMAX, *iv = fw + NMAX;   // prefixes serve every N
+  rns_forward(lds, fw, log_n, p, pinv);
+  uint32_t *o = out + (poly * NP + j) * n;
+  if (!MUL) {
+    for (unsigned d = tid; d < n; d += NTT_THREADS) o[d] = lds[d];
+    return;
+  }
+  const uint32_t *h = hat + poly * hat_stride + (size_t)j * n;
+  for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = mont_mul(lds[d], h[d], p, pinv);
+  __syncthreads();
+  rns_inverse(lds, iv, log_n, p, pinv);
+  for (unsigned d = tid; d < n; d += NTT_THREADS) o[d] = mont_mul(lds[d], rc.scale[j], p, pinv);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+
+inline uint64_t pow_mod(uint64_t a, uint64_t e, uint64_t p) {
+  uint64_t r = 1;
+  for (a %= p; e; e >>= 1, a = a * a % p)
+    if (e & 1) r = r * a % p;
+  return r;
+}
+
+inline int bit_log2(uint64_t n) {
+  int l = 0;
+  while (((uint64_t)1 << l) < n) ++l;
+  return l;
+}
+
+template <int NP>
+RnsConst<NP> rns_const(int log_n) {
+  RnsConst<NP> c;
+  for (int j = 0; j < NP; ++j) {
+    const uint64_t p = PRIMES[j];
+    uint32_t inv = 1;   // p^-1 mod 2^32 by Newton
+    for (int i = 0; i < 5; ++i) inv *= 2 - (uint32_t)p * inv;
+    c.p[j] = (uint32_t)p;
+    c.pinv[j] = (uint32_t)(0u - inv);
+    const uint64_t n_inv = pow_mod((uint64_t)1 << log_n, p - 2, p), R2 = pow_mod(2, 64, p);
+    c.scale[j] = (uint32_t)(n_inv * R2 % p);
+  }
+  return c;
+}
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// polynomials per chunk of a batch: 2^21 coefficients, at least 8 polynomials
+inline size_t chunk_polys(uint64_t n) { return std::max<size_t>(8, ((size_t)1 << 21) / n); }
+
+// k_rns_ntt over n_polys polynomials with the first NP primes; mul: the MUL = true instance against hat
+template <int NP>
+int launch_rns_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, int mode, uint64_t q, size_t n_polys, int log_n, const uint32_t *hat,
+                   size_t hat_stride, uint32_t *out, int *flag) {
+  const uint32_t *tw;
+  ZK_CK(zk_rns_tables(ctx, &tw));
+  const int lds = 4 << log_n;
+  const void *kern = mul ? (const void *)k_rns_ntt<NP, true> : (const void *)k_rns_ntt<NP, false>;
+  if (lds > 64 * 1024) ZK_CK(zk_func_max_lds(ctx, kern, 4 << LOG_NMAX));
+  zk_prof_begin(ctx);
+  if (mul)
+    k_rns_ntt<NP, true><<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(src, mode, q, log_n, tw, rns_const<NP>(log_n), hat, hat_stride, out, flag);
+  else
+    k_rns_ntt<NP, false><<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(src, mode, q, log_n, tw, rns_const<NP>(log_n), nullptr, 0, out, flag);
+  ZK_LAUNCH_CHECK(ctx);
+  zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, (double)n_polys * NP * (8.0 + (mul ? 8.0 : 4.0)) * ((size_t)1 << log_n));
+  return ZKFHE_OK;
+}
+
+}  // namespace zkrns
