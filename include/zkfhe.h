@@ -569,6 +569,57 @@ int zkfhe_bfv_noise(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64
 #define ZKFHE_PROF_BFV_EVAL_EPILOGUE 10    /* k_eval_epilogue */
 #define ZKFHE_PROF_BFV_ELEMENTWISE 11      /* k_bfv_sum, k_bfv_add */
 
+/* ---- Threshold BFV on the GPU: collective keys and decryption by shares (bfv_threshold.hip) ----
+ * The multiparty BFV of Mouchet et al. (collective key generation, relinearization key generation, threshold decryption with
+ * smudging noise), so that voters encrypt to a key the committee holds jointly and only the committee together opens the tally.
+ * P parties; party i holds a ternary s_i; the collective secret s = sum_i s_i is never formed by the library.  The conventions
+ * above: host arrays, N uint64_t per polynomial in CircuitInput order, residues in [0, Q), the parameter checks of
+ * zkfhe_bfv_encrypt; every call waits for its result.  Randomness: the ChaCha20 streams and samplers of zkfhe_bfv_encrypt;
+ * domains 1 to 8 keep their meaning and the new ones are 9 to 13:
+ *   CRS a of the public key           crs_seed (public)    domain 5, index 0   uniform mod Q
+ *   s_i, e_i of a key share           party_seed (secret)  domains 4, 6, index 0   ternary, error
+ *   CRS a_j of the relin key, j < l   crs_seed             domain 7, index j   uniform mod Q
+ *   smudging noise of share j         share seed (secret)  domain 9, index first_index + j   uniform mod 2E + 1, minus E
+ *   u_i (both relin rounds)           party_seed           domain 10, index 0   ternary
+ *   e0_ij, e1_ij (round 1), e2_ij     party_seed           domains 11, 12, 13, index j   error
+ * Every call refuses, with ZKFHE_EINVAL and a message: a NULL argument, a zero n_parties, n_polys or n_cts, a coefficient >= Q in
+ * any input, a non-ternary sk_i, base_bits outside [1, 32], and 2 E + 1 > floor(Q/T).
+ * PARTY SEEDS AND SHARE SEEDS ARE SECRET, like every seed here: a party seed gives s_i.  NEVER REUSE a (share seed, index) pair on
+ * a different c1: two shares with the same noise give (c1 - c1') s_i.  The same party_seed must be used in both relinearization
+ * rounds (u_i is drawn from it twice).  The smudging bound E is the caller's choice: the library claims no statistical hiding for
+ * it, and at the k = 13 parameters (29-bit Q, T = 7) there is little room between the noise and floor(Q/T) / 2.
+ * zkfhe_bfv_noise refuses the collective s (it is not ternary): a caller who wants the noise computes it from s = sum_i s_i. */
+/* party i's key share: sk = s_i, pk0_share = -(a s_i + e_i) mod (x^N + 1, Q), pk1 = a.  With crs_seed == party_seed the output
+ * is zkfhe_bfv_fhe_keypair(party_seed) bit for bit.  The collective pk0 = zkfhe_bfv_share_aggregate of the pk0 shares. */
+int zkfhe_bfv_keygen_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint8_t crs_seed[32], const uint8_t party_seed[32],
+                           uint64_t *sk_out, uint64_t *pk0_share_out, uint64_t *pk1_out);
+/* out = sum_i shares[i] mod Q; shares: n_parties x n_polys x N, out: n_polys x N.  It forms the collective pk0 (n_polys = 1), the
+ * round-1 h0 | h1 (2 l) and the final rlk0 (l). */
+int zkfhe_bfv_share_aggregate(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_parties, size_t n_polys, const uint64_t *shares,
+                              uint64_t *out);
+/* relinearization key, round 1 of party i, l = zkfhe_bfv_relin_digits(base_bits) rows each, w = base_bits:
+ * h0_i[j] = -u_i a_j + 2^(j w) s_i + e0_ij,  h1_i[j] = s_i a_j + e1_ij  mod (x^N + 1, Q). */
+int zkfhe_bfv_relin_share1(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, const uint8_t crs_seed[32],
+                           const uint8_t party_seed[32], int base_bits, uint64_t *h0_out, uint64_t *h1_out);
+/* round 2 of party i on the round-1 aggregates h0, h1 (l x N each): r_i[j] = s_i h0[j] + (u_i - s_i) h1[j] + e2_ij, u_i drawn again
+ * from party_seed.  The collective key is rlk0 = zkfhe_bfv_share_aggregate of the r_i and rlk1 = h1; it satisfies
+ * rlk0[j] + rlk1[j] s = 2^(j w) s^2 + s e0_j + u e1_j + e2_j (e0_j, e1_j, e2_j, u the sums over the parties), so zkfhe_bfv_mul
+ * takes it unchanged with the same base_bits. */
+int zkfhe_bfv_relin_share2(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, const uint8_t party_seed[32], int base_bits,
+                           const uint64_t *h0, const uint64_t *h1, uint64_t *r_out);
+/* party i's decryption shares of n_cts ciphertexts: d_j = c1_j s_i + e_j mod Q, e_j the smudging noise of stream (seed, 9,
+ * first_index + j) with E = smudge_bound (E = 0: no noise); c1, d_out: n_cts x N. */
+int zkfhe_bfv_decrypt_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, size_t n_cts, const uint64_t *c1,
+                            const uint8_t seed[32], uint64_t first_index, uint64_t smudge_bound, uint64_t *d_out);
+/* m = the rounding of zkfhe_bfv_decrypt applied to [c0 + sum_i d_i]_Q; c0, m_out: n_cts x N, d: n_parties x n_cts x N.  With one
+ * party and E = 0 this is zkfhe_bfv_decrypt(sk) bit for bit. */
+int zkfhe_bfv_decrypt_combine(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_parties, size_t n_cts, const uint64_t *c0,
+                              const uint64_t *d, uint64_t *m_out);
+/* zkfhe_prof_read slots of the threshold kernels (algorithmic bytes: words read and written); the CRT epilogue of the share calls
+ * (k_thr_epilogue) counts in ZKFHE_PROF_RNS_EPILOGUE */
+#define ZKFHE_PROF_BFV_SHARE_SUM 12         /* k_bfv_share_sum */
+#define ZKFHE_PROF_BFV_DECRYPT_COMBINE 13   /* k_bfv_decrypt_combine */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

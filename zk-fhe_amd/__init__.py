@@ -19,6 +19,7 @@ _lib = None
 PROF_G1_DECOMPRESS, PROF_MSM_SEGMENTED = 3, 4   # zkfhe_prof_read slots of the batch verifier's kernels (zkfhe.h)
 PROF_BFV_SAMPLE, PROF_RNS_NTT, PROF_RNS_EPILOGUE = 5, 6, 7   # ... and of the BFV encryption kernels
 PROF_BFV_TENSOR, PROF_BFV_RELIN, PROF_BFV_EVAL_EPILOGUE, PROF_BFV_ELEMENTWISE = 8, 9, 10, 11   # ... and of the BFV evaluation kernels
+PROF_BFV_SHARE_SUM, PROF_BFV_DECRYPT_COMBINE = 12, 13   # ... and of the threshold kernels
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -42,6 +43,8 @@ EXPORTS = [
     "zkfhe_poly_mul_ternary_negacyclic", "zkfhe_bfv_error_cdt", "zkfhe_bfv_fhe_keypair", "zkfhe_bfv_encrypt", "zkfhe_bfv_decrypt", "zkfhe_bfv_prove_words",
     "zkfhe_bfv_add", "zkfhe_bfv_sum", "zkfhe_bfv_add_plain", "zkfhe_bfv_mul_plain", "zkfhe_bfv_relin_digits", "zkfhe_bfv_relin_keygen",
     "zkfhe_bfv_mul", "zkfhe_bfv_noise",
+    "zkfhe_bfv_keygen_share", "zkfhe_bfv_share_aggregate", "zkfhe_bfv_relin_share1", "zkfhe_bfv_relin_share2", "zkfhe_bfv_decrypt_share",
+    "zkfhe_bfv_decrypt_combine",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -610,6 +613,119 @@ class Context:
         prm = BfvParamsC(*[int(x) for x in params])
         self._check(self.lib.zkfhe_bfv_noise(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c0.shape[0], c0.ctypes.data_as(u64p),
                                              c1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        return out
+
+    # ------------------------------------------------------------------ threshold BFV (zkfhe.h, bfv_threshold.hip)
+    # Party i holds sk_i; keys and shares are uint64 arrays of residues like the calls above.  Every seed is 32 SECRET bytes
+    # (the CRS seed is public); a None share seed draws os.urandom(32).
+
+    @staticmethod
+    def _seed(seed, what, fresh=False):
+        if seed is None and not fresh:
+            raise ValueError("the %s is required" % what)
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the %s is 32 bytes" % what)
+        return seed
+
+    def _sk(self, params, sk):
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        if sk.size != int(params[0]):
+            raise ValueError("sk must hold N coefficients")
+        return sk
+
+    def bfv_keygen_share(self, params, crs_seed, party_seed):
+        """zkfhe_bfv_keygen_share -> (sk_i, pk0_share, pk1): pk0_share = -(a s_i + e_i), pk1 = a from the public crs_seed."""
+        n = int(params[0])
+        crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
+        out = [np.empty(n, dtype=np.uint64) for _ in range(3)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_keygen_share.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_char_p, ctypes.c_char_p, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_keygen_share(self.h, ctypes.byref(prm), crs_seed, party_seed, *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_share_aggregate(self, params, shares):
+        """zkfhe_bfv_share_aggregate: shares of shape (P, N) or (P, n_polys, N) -> their sum mod Q, shape (N,) or (n_polys, N)."""
+        n = int(params[0])
+        shares = np.ascontiguousarray(shares, dtype=np.uint64)
+        if shares.ndim not in (2, 3) or shares.shape[-1] != n:
+            raise ValueError("shares must have shape (P, N) or (P, n_polys, N)")
+        s3 = shares.reshape(shares.shape[0], shares.shape[1] if shares.ndim == 3 else 1, n)   # P = 0 is refused by the call
+        out = np.empty(s3.shape[1:], dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_share_aggregate.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, ctypes.c_size_t, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_share_aggregate(self.h, ctypes.byref(prm), s3.shape[0], s3.shape[1], s3.ctypes.data_as(u64p),
+                                                       out.ctypes.data_as(u64p)))
+        return out.reshape(shares.shape[1:])
+
+    def _relin_rows(self, params, base_bits):
+        return bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else 0   # else the call refuses base_bits itself
+
+    def bfv_relin_share1(self, params, sk, crs_seed, party_seed, base_bits=8):
+        """zkfhe_bfv_relin_share1 -> (h0_i, h1_i) of shape (l, N): round 1 of the collective relinearization key."""
+        n, sk = int(params[0]), self._sk(params, sk)
+        crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
+        l = self._relin_rows(params, base_bits)
+        out = [np.empty((l, n), dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_relin_share1.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_char_p, ctypes.c_char_p,
+                                                    ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_relin_share1(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), crs_seed, party_seed, int(base_bits),
+                                                    *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_relin_share2(self, params, sk, party_seed, h0, h1, base_bits=8):
+        """zkfhe_bfv_relin_share2 -> r_i of shape (l, N) from the round-1 aggregates h0, h1 (l, N); rlk0 = bfv_share_aggregate of
+        the r_i, rlk1 = h1.  party_seed must be the one of round 1."""
+        n, sk = int(params[0]), self._sk(params, sk)
+        party_seed = self._seed(party_seed, "party seed")
+        h0 = np.ascontiguousarray(h0, dtype=np.uint64)
+        h1 = np.ascontiguousarray(h1, dtype=np.uint64)
+        l = self._relin_rows(params, base_bits)
+        if l and (h0.shape != (l, n) or h1.shape != (l, n)):
+            raise ValueError("h0 and h1 must have shape (l, N) = (%d, %d) for base_bits %d" % (l, n, base_bits))
+        out = np.empty((l, n), dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_relin_share2.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_char_p, ctypes.c_int, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_relin_share2(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), party_seed, int(base_bits),
+                                                    h0.ctypes.data_as(u64p), h1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        return out
+
+    def bfv_decrypt_share(self, params, sk, c1, seed=None, first_index=0, smudge_bound=0):
+        """zkfhe_bfv_decrypt_share: c1 of shape (N,) or (n, N) -> d_j = c1_j s_i + e_j, shape (n, N); e_j uniform in
+        [-smudge_bound, smudge_bound] from (seed, 9, first_index + j).  seed: 32 SECRET bytes (None: os.urandom); never reuse a
+        (seed, index) pair on a different c1."""
+        n, sk = int(params[0]), self._sk(params, sk)
+        seed = self._seed(seed, "share seed", fresh=True)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1, n)
+        out = np.empty(c1.shape, dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_decrypt_share.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_size_t, u64p, ctypes.c_char_p,
+                                                     ctypes.c_uint64, ctypes.c_uint64, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_decrypt_share(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c1.shape[0], c1.ctypes.data_as(u64p),
+                                                     seed, int(first_index), int(smudge_bound), out.ctypes.data_as(u64p)))
+        return out
+
+    def bfv_decrypt_combine(self, params, c0, shares):
+        """zkfhe_bfv_decrypt_combine: c0 of shape (N,) or (n, N) and the parties' shares (P, n, N) (or (P, N)) -> m as residues mod Q,
+        shape (n, N): the rounding of bfv_decrypt applied to [c0 + sum_i d_i]_Q."""
+        n = int(params[0])
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64).reshape(-1, n)
+        d = np.ascontiguousarray(shares, dtype=np.uint64)
+        d = d.reshape(d.shape[0], 1, n) if d.ndim == 2 else d
+        if d.ndim != 3 or d.shape[1:] != c0.shape:
+            raise ValueError("shares must have shape (P, n, N) for c0 of shape (n, N)")
+        out = np.empty(c0.shape, dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_decrypt_combine.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, ctypes.c_size_t, u64p, u64p, u64p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(self.lib.zkfhe_bfv_decrypt_combine(self.h, ctypes.byref(prm), d.shape[0], c0.shape[0], c0.ctypes.data_as(u64p),
+                                                       d.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
         return out
 
 

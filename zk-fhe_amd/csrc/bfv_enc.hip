@@ -23,12 +23,6 @@ namespace {
 
 constexpr int NP = 3;   // the first three primes of rns_ntt.hip.hpp: product 2^89.2
 constexpr int MAX_CDT = 2046;   // 2 B thresholds, B < 1024
-// Garner: y1 = (r1 - r0) p0^-1 mod p1, y2 = (r2 - r0 - p0 y1) (p0 p1)^-1 mod p2, x = r0 + p0 y1 + p0 p1 y2
-struct CrtConst {
-  uint64_t inv01, inv012, p0_mod_p2, p01;
-  uint64_t P_lo, P_hi;   // p0 p1 p2
-};
-
 enum EpiMode { EPI_PLAIN = 0, EPI_ADD = 1, EPI_NEG_ADD = 2, EPI_DECRYPT = 3 };
 struct Epi {
   int mode;
@@ -49,19 +43,7 @@ __global__ __launch_bounds__(256) void k_rns_epilogue(const uint32_t *__restrict
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total) return;
   const size_t n = (size_t)1 << log_n, poly = g >> log_n, d = g & (n - 1), pos = poly * n + (n - 1 - d);
-  const uint64_t p0 = PRIMES[0], p1 = PRIMES[1], p2 = PRIMES[2];
-  const uint32_t *r = res + poly * NP * n + d;
-  const uint64_t r0 = r[0], r1 = r[n], r2 = r[2 * n];
-  const uint64_t y1 = (r1 + p1 - r0 % p1) % p1 * cc.inv01 % p1;
-  const uint64_t x01 = (r0 % p2 + cc.p0_mod_p2 * y1) % p2;
-  const uint64_t y2 = (r2 + p2 - x01) % p2 * cc.inv012 % p2;
-  typedef unsigned __int128 u128;
-  const u128 x = (u128)r0 + (u128)p0 * y1 + (u128)cc.p01 * y2;   // < P
-  const u128 P = ((u128)cc.P_hi << 64) | cc.P_lo;
-  const bool neg = x > (P >> 1);
-  const u128 mag = neg ? P - x : x;
-  const uint64_t rm = mod128((uint64_t)(mag >> 64), (uint64_t)mag, q);
-  uint64_t v = neg && rm ? q - rm : rm;   // c mod Q
+  uint64_t v = crt3_mod_q(res + poly * NP * n + d, n, q, cc);   // c mod Q
   if (epi.mode == EPI_ADD) {
     if (epi.m) {   // m in [0, T/2] or [Q - T/2, Q): delta |m| <= Q / 2, no reduction needed
       const uint64_t mv = epi.m[pos];
@@ -74,13 +56,7 @@ __global__ __launch_bounds__(256) void k_rns_epilogue(const uint32_t *__restrict
     v = add_q(v, epi.e[pos], q);
     v = v ? q - v : 0;
   } else if (epi.mode == EPI_DECRYPT) {
-    // round(T x / Q) mod T with x = [c0 + c1 s]_Q centred; for the residue v the quotient floor((2 T v + Q) / 2Q) differs by
-    // T at most, which the reduction mod T removes (inputs.decrypt)
-    v = add_q(v, epi.c0[pos], q);
-    const u128 num = (u128)(2 * epi.t) * v + q;   // 2 T < 2^64
-    uint64_t m = div128((uint64_t)(num >> 64), (uint64_t)num, 2 * q);   // in [0, T]
-    m = m == epi.t ? 0 : m;
-    v = m > epi.t / 2 ? q - (epi.t - m) : m;
+    v = decrypt_round(add_q(v, epi.c0[pos], q), q, epi.t);   // round(T x / Q) mod T, x = [c0 + c1 s]_Q centred
   }
   out[pos] = v;
 }
@@ -157,18 +133,6 @@ __global__ __launch_bounds__(256) void k_bfv_sample(ChaKey key, uint32_t domain,
 
 // ------------------------------------------------------------------------------------------------------------------ host side
 
-CrtConst crt_const() {
-  const uint64_t p0 = PRIMES[0], p1 = PRIMES[1], p2 = PRIMES[2];
-  CrtConst c;
-  c.inv01 = pow_mod(p0 % p1, p1 - 2, p1);
-  c.p01 = p0 * p1;
-  c.inv012 = pow_mod(c.p01 % p2, p2 - 2, p2);
-  c.p0_mod_p2 = p0 % p2;
-  const unsigned __int128 P = (unsigned __int128)c.p01 * p2;
-  c.P_lo = (uint64_t)P, c.P_hi = (uint64_t)(P >> 64);
-  return c;
-}
-
 int work_arena(zkfhe_ctx *ctx, size_t bytes, char **out) {
   if (ctx->bfv_work_sz < bytes) {
     if (ctx->bfv_work) {
@@ -192,7 +156,7 @@ int launch_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, bool ternary, uint
 int launch_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const Epi &epi, uint64_t *out) {
   const size_t total = n_polys << log_n;
   zk_prof_begin(ctx);
-  k_rns_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt_const(), epi, out);
+  k_rns_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt3_const(), epi, out);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_RNS_EPILOGUE, (double)total * (12 + 8 + (epi.m ? 8 : 0) + (epi.e || epi.c0 ? 8 : 0)));
   return ZKFHE_OK;

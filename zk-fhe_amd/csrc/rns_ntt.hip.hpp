@@ -1,14 +1,15 @@
-// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip): an RNS NTT over NP primes below 2^31, one
-// workgroup per (polynomial, prime), the whole transform of N <= 2^15 words in LDS (128 KiB at N = 2^15), with 32-bit Montgomery
-// arithmetic.  Templated on the prime count: encryption uses the first three primes (product 2^89.2: a ternary factor keeps the
-// product below N 2^64), the evaluator all five (product 2^151.2: a product of two centred residues below 2^63 stays below 2^140).
+// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip, bfv_threshold.hip): an RNS NTT over NP primes
+// below 2^31, one workgroup per (polynomial, prime), the whole transform of N <= 2^15 words in LDS (128 KiB at N = 2^15), with
+// 32-bit Montgomery arithmetic.  Templated on the prime count: encryption and the threshold calls use the first three primes
+// (product 2^89.2: a ternary factor keeps the product below N 2^64), the evaluator all five (product 2^151.2: a product of two
+// centred residues below 2^63 stays below 2^140).
 // Headroom at p < 2^31: a b + m p < 2^62 + 2^63 < 2^64 in mont_mul, and a + b < 2^32 in add_p.
 #pragma once
 #include <algorithm>
 
 #include "ctx.hpp"
 
-// defined in bfv_enc.hip, shared with bfv_eval.hip
+// defined in bfv_enc.hip, shared with bfv_eval.hip and bfv_threshold.hip
 // the twiddle tables of every prime: [prime][fwd | inv][NMAX], psi^br15(k) and psi^-br15(k) in Montgomery form (built on first use)
 int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out);
 // the parameter check of every BFV call (zkfhe.h)
@@ -80,6 +81,39 @@ __device__ __forceinline__ uint64_t div128(uint64_t hi, uint64_t lo, uint64_t d)
     quo |= (uint64_t)take << i;
   }
   return quo;
+}
+
+// Garner over the first three primes (product 2^89.2): y1 = (r1 - r0) p0^-1 mod p1, y2 = (r2 - r0 - p0 y1) (p0 p1)^-1 mod p2,
+// x = r0 + p0 y1 + p0 p1 y2
+struct CrtConst {
+  uint64_t inv01, inv012, p0_mod_p2, p01;
+  uint64_t P_lo, P_hi;   // p0 p1 p2
+};
+
+// the centred integer of the three residues r[0], r[n], r[2 n], reduced mod q
+__device__ __forceinline__ uint64_t crt3_mod_q(const uint32_t *__restrict__ r, size_t n, uint64_t q, const CrtConst &cc) {
+  const uint64_t p0 = PRIMES[0], p1 = PRIMES[1], p2 = PRIMES[2];
+  const uint64_t r0 = r[0], r1 = r[n], r2 = r[2 * n];
+  const uint64_t y1 = (r1 + p1 - r0 % p1) % p1 * cc.inv01 % p1;
+  const uint64_t x01 = (r0 % p2 + cc.p0_mod_p2 * y1) % p2;
+  const uint64_t y2 = (r2 + p2 - x01) % p2 * cc.inv012 % p2;
+  typedef unsigned __int128 u128;
+  const u128 x = (u128)r0 + (u128)p0 * y1 + (u128)cc.p01 * y2;   // < P
+  const u128 P = ((u128)cc.P_hi << 64) | cc.P_lo;
+  const bool neg = x > (P >> 1);
+  const u128 mag = neg ? P - x : x;
+  const uint64_t rm = mod128((uint64_t)(mag >> 64), (uint64_t)mag, q);
+  return neg && rm ? q - rm : rm;
+}
+
+// the decryption of the residue v = [c0 + c1 s]_Q: round(T x / Q) mod T with x = v centred, as a residue mod Q.  For the residue v
+// the quotient floor((2 T v + Q) / 2Q) differs by T at most, which the reduction mod T removes (inputs.decrypt)
+__device__ __forceinline__ uint64_t decrypt_round(uint64_t v, uint64_t q, uint64_t t) {
+  typedef unsigned __int128 u128;
+  const u128 num = (u128)(2 * t) * v + q;   // 2 T < 2^64
+  uint64_t m = div128((uint64_t)(num >> 64), (uint64_t)num, 2 * q);   // in [0, T]
+  m = m == t ? 0 : m;
+  return m > t / 2 ? q - (t - m) : m;
 }
 
 // v read in `mode` as a residue mod p; `bad` collects non-ternary coefficients of LOAD_TERNARY
@@ -191,6 +225,18 @@ RnsConst<NP> rns_const(int log_n) {
     const uint64_t n_inv = pow_mod((uint64_t)1 << log_n, p - 2, p), R2 = pow_mod(2, 64, p);
     c.scale[j] = (uint32_t)(n_inv * R2 % p);
   }
+  return c;
+}
+
+inline CrtConst crt3_const() {
+  const uint64_t p0 = PRIMES[0], p1 = PRIMES[1], p2 = PRIMES[2];
+  CrtConst c;
+  c.inv01 = pow_mod(p0 % p1, p1 - 2, p1);
+  c.p01 = p0 * p1;
+  c.inv012 = pow_mod(c.p01 % p2, p2 - 2, p2);
+  c.p0_mod_p2 = p0 % p2;
+  const unsigned __int128 P = (unsigned __int128)c.p01 * p2;
+  c.P_lo = (uint64_t)P, c.P_hi = (uint64_t)(P >> 64);
   return c;
 }
 
