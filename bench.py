@@ -7,6 +7,11 @@ A "step" = ONE complete proof of zk-fhe's BFV correct-encryption circuit at the 
 SHPLONK) through zkfhe_bfv_prove.  The proving key, SRS tables and the input texts are resident before the timed
 region (the reference's 10.2 s likewise excludes SRS / pk loading).  Inputs are seeded synthetic BFV
 encryptions of that shape.  N > 1: independent proofs, one replica per rank -- weak scaling, no data-path collective.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.  --full
+adds everything else, each outside the clock: the host verifier on the last timed proofs (every rank's; a sharded proof's bytes
+compared across ranks), the steady-state and cold-key passes, the two profiled proofs behind `roofline`, the native CPU prover
+(`cpu_baseline`) and the two rocprofv3 PMC child runs (`roofline.traffic`).  A plain run prints null for what it did not do.
 """
 import argparse
 import json
@@ -72,7 +77,7 @@ def _measure_traffic(transcript, timeout_s=300):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="zkfhe_pmc_", dir="/tmp")
         cmd = [exe, "--pmc", ctr, "--kernel-trace", "-d", d, "-o", "r", "--", sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1",
-               "--streams", "1", "--no-cpu-baseline", "--steady-seconds", "0", "--no-traffic-pass", "--transcript", transcript]
+               "--streams", "1", "--full", "--no-cpu-baseline", "--steady-seconds", "0", "--no-traffic-pass", "--transcript", transcript]
         try:
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=timeout_s)
             dbs = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
@@ -134,7 +139,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--streams", type=int, default=0, help="concurrent proofs per GPU (one HIP stream + workspace each); 0 = 16 at k13, 2 at k16, 1 at k19")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="k13", help="k13 = the headline (BASELINE configs[1]); k16 / k19 = configs[3] / [4], single GPU")
-    ap.add_argument("--steady-seconds", type=float, default=2.0, help="length of the extra, separately reported steady-state pass (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also verify the last timed proofs, run the steady-state and cold-key passes, the profiled proofs of "
+                         "`roofline`, the CPU baseline and the PMC traffic pass (a plain run prints null for these)")
+    ap.add_argument("--steady-seconds", type=float, default=2.0, help="with --full: length of the extra, separately reported steady-state pass (0 = skip)")
     ap.add_argument("--mode", choices=["batch", "one-proof-sharded"], default="batch",
                     help="batch = independent proofs, one replica per rank (weak scaling: the headline); one-proof-sharded = every proof is made by ALL ranks "
                          "(BASELINE configs[4]: commitments by point range with an RCCL all-gather of the partials, coset extension and quotient by column, "
@@ -142,8 +150,8 @@ def main():
     ap.add_argument("--announce", choices=["auto", "on", "off"], default="auto",
                     help="announce every proof's input one proof ahead (zkfhe_bfv_pk_prehash: the sponge over its 5 N + 1 public inputs runs on a host thread "
                          "while the previous proof is on the GPU) -- auto: with the Poseidon transcript and at most 8 proofs in flight; never on the driver's wave of 20")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic-pass", action="store_true", help="do not measure roofline.traffic with two child rocprofv3 --pmc passes (N = 1, k13 only; ~20 s): "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the native CPU prover")
+    ap.add_argument("--no-traffic-pass", action="store_true", help="with --full: do not measure roofline.traffic with two child rocprofv3 --pmc passes (N = 1, k13 only; ~20 s): "
                                                                    "take it from the committed pass under profiles/")
     ap.add_argument("--stagger-ms", type=float, default=None, help="start offset between the concurrent proofs of the timed wave")
     ap.add_argument("--transcript", choices=["poseidon", "blake2b"], default="poseidon",
@@ -302,19 +310,21 @@ def main():
     host["prefix_cache_hits"] = pc1["hits"] - pc0["hits"]
     host["prefix_cache_misses"] = pc1["misses"] - pc0["misses"]
     host["prefix_cache_keys"] = pc1["entries"]
-    # outside the clock: the LAST proof made inside the timed region goes through the host verifier (transcript replay, quotient
-    # identity, SHPLONK, one pairing-product check -- zkfhe_bfv_verify); its public inputs are the ones the prover returned
     v_proof, v_inst = last[si + args.steps - 1]
-    verified, why = zk.bfv_verify(pk.export_vk(), v_inst, v_proof)
-    if not verified:
-        raise SystemExit("bench: a proof of the timed region does not verify: %s" % why)
+    # --full, outside the clock: the LAST proof made inside the timed region goes through the host verifier (transcript replay,
+    # quotient identity, SHPLONK, one pairing-product check -- zkfhe_bfv_verify); its public inputs are the ones the prover returned
+    verified = None
+    if args.full:
+        verified, why = zk.bfv_verify(pk.export_vk(), v_inst, v_proof)
+        if not verified:
+            raise SystemExit("bench: a proof of the timed region does not verify: %s" % why)
     if args.dump_outputs and rank == 0:
         _dump_outputs(args.dump_outputs, v_proof, v_inst)
     si += args.steps
-    # a batch's only collective besides the clock (batch.gather_proofs: all_gather_object of <= 62 KB per proof): every rank's last
-    # timed proof goes to all ranks and rank 0 verifies each -- outside the clock, like the check above
+    # --full: a batch's only collective besides the clock (batch.gather_proofs: all_gather_object of <= 62 KB per proof): every rank's
+    # last timed proof goes to all ranks and rank 0 verifies each -- outside the clock, like the check above
     gathered = None
-    if use_dist and not sharded:
+    if args.full and use_dist and not sharded:
         everyone = batch.gather_proofs({rank: (v_proof, v_inst)}, world, rank, world)
         if rank == 0:
             for r_, (p_, i_) in enumerate(everyone):
@@ -322,11 +332,11 @@ def main():
                 if not ok_:
                     raise SystemExit("bench: rank %d's last timed proof does not verify: %s" % (r_, why_))
         gathered = len(everyone)
-    # one-proof-sharded: every rank made every proof together and must hold the same bytes
+    # --full, one-proof-sharded: every rank made every proof together and must hold the same bytes
     import hashlib
     last_sha = hashlib.sha256(v_proof).hexdigest()
     same_on_all_ranks = None
-    if sharded:
+    if args.full and sharded:
         digests = batch.gather_proofs({rank: last_sha}, world, rank, world)
         same_on_all_ranks = len(set(digests)) == 1
         if not same_on_all_ranks:
@@ -340,7 +350,7 @@ def main():
     # steady state, reported separately (never the headline): the driver's --steps may be a single wave of concurrent proofs,
     # whose rate is (proofs) / (latency of the slowest); this pass keeps every stream busy for >= steady_seconds
     steady = None
-    if args.steady_seconds > 0:
+    if args.full and args.steady_seconds > 0:
         n_more = max(4 * n_streams, int(args.steady_seconds * args.steps / dt))
         if "ZKFHE_GATE" not in os.environ and not big and not sharded and n_streams >= 8:
             zk.prover_gate(4)
@@ -355,7 +365,7 @@ def main():
     # WARM-key rate (many encryptions under a few keys: a client encrypting to a server's key).  The same K proofs again with the cache
     # off = every proof under a key never seen before (BASELINE configs[2]: 64 vectors, 64 keys): reported beside it, never the headline.
     cold = None
-    if args.transcript == "poseidon" and not sharded:
+    if args.full and args.transcript == "poseidon" and not sharded:
         zk.prover_gate(gate_timed)
         pk.prefix_cache(0)
         tc = time.perf_counter()
@@ -369,27 +379,26 @@ def main():
         except ValueError:
             pk.prefix_cache(8)
 
-    # dominant kernel timed live with HIP events on the library's stream, in a separate untimed pass: k_msm_table (the sum of
-    # table points of a commitment batch) when the SRS holds a digit-multiple table wide enough for such calls, else the
+    # --full: dominant kernel timed live with HIP events on the library's stream, in a separate untimed pass: k_msm_table (the sum
+    # of table points of a commitment batch) when the SRS holds a digit-multiple table wide enough for such calls, else the
     # bucket pipeline's k_msm_accumulate
-    table_bits, table_wide = srs.table_bits()
-    table_info = srs.table_info()   # digit widths (monomial, Lagrange), resident GB, whether the device forced a narrower table
-    table_info["budget_gb"] = float(os.environ["ZKFHE_TABLE_GB"])
-    table_info["srs_create_s"] = round(t_srs, 2)
-    msm_kernel = "k_msm_table" if table_wide else "k_msm_accumulate"
-    ctx.prof_enable(True)
-    for _ in range(2):
-        pk.prove(inputs[si % len(inputs)], seeds[si % len(seeds)])
-    msm = ctx.prof_read(0)
-    ntt = ctx.prof_read(1)
-    direct = ctx.prof_read(2)
-    ctx.prof_enable(False)
+    if args.full:
+        table_bits, table_wide = srs.table_bits()
+        table_info = srs.table_info()   # digit widths (monomial, Lagrange), resident GB, whether the device forced a narrower table
+        table_info["budget_gb"] = float(os.environ["ZKFHE_TABLE_GB"])
+        table_info["srs_create_s"] = round(t_srs, 2)
+        msm_kernel = "k_msm_table" if table_wide else "k_msm_accumulate"
+        ctx.prof_enable(True)
+        for _ in range(2):
+            pk.prove(inputs[si % len(inputs)], seeds[si % len(seeds)])
+        msm = ctx.prof_read(0)
+        ntt = ctx.prof_read(1)
+        direct = ctx.prof_read(2)
+        ctx.prof_enable(False)
 
     if rank == 0:
-        ach = msm["algorithmic_bytes"] / (msm["total_ms"] * 1e-3) / 1e9
-        ntt_ach = ntt["algorithmic_bytes"] / (ntt["total_ms"] * 1e-3) / 1e9 if ntt["launches"] else None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and not big:
+        if args.full and world == 1 and not args.no_cpu_baseline and not big:
             try:
                 # the native multithreaded CPU prover (oracle/cpu_prover.cpp: the build's own host witness generation and transcript,
                 # Pippenger / NTT / quotient loops under OpenMP) on the same workload; key and SRS from the oracle's keygen (not timed)
@@ -430,33 +439,49 @@ def main():
                        "phase_ms_last_proof": phases, "seconds_per_proof_by_threads": sweep}
             except Exception as e:  # noqa: BLE001  -- the CPU leg is a label: never lose the GPU measurement over it
                 cpu = {"value": None, "unit": "proofs/s", "cores": None, "kind": "port", "sample": "native CPU prover failed: %r" % (e,)}
-        traffic = ntt_traffic = traffic_source = None
-        measured = None
         vk_hex = "%064x" % pk.info()["vk_digest"]
-        if rank == 0 and world == 1 and not big and table_wide and not args.no_traffic_pass:
-            # VERDICT r5 "weak" 9: the counters are read in THIS run, not from a file.  The children build their own SRS tables: this
-            # process gives the device back first (160 + 160 GB of tables do not fit next to each other)
-            pk.destroy()
-            srs.destroy()
-            for c in ctxs[1:]:
-                c.close()
-            torch.cuda.empty_cache()
-            t_pm = time.perf_counter()
-            measured = _measure_traffic(args.transcript)
-            if measured:
-                traffic, ntt_traffic = measured["bytes_per_launch"], measured["ntt13"]
-                traffic_source = ("measured in this run: two child passes `rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py --steps 2 --warmup 1 --streams 1` "
-                                  "(%.0f s), per-launch average over %d launches of k_msm_table<false>; FETCH_SIZE x 1 for the scattered 64-byte table gathers + half the streamed "
-                                  "scalar bytes + WRITE_SIZE x 1 (factors: profiles/r5_pmc_calibration.md)" % (time.perf_counter() - t_pm, measured["launches"]))
-        for fn in (() if measured else ("r6_pmc_traffic.json", "r5_pmc_traffic.json", "r4_pmc_traffic.json", "r3_pmc_traffic.json")):   # HBM bytes per launch from the committed PMC passes (profiles/, rocprofv3 --pmc)
-            try:
-                pt = json.load(open(os.path.join(ROOT, "profiles", fn)))
-                traffic = pt["bytes_per_launch"] if (not big and table_wide) else None
-                ntt_traffic = pt["ntt13"] if not big else None   # the same for the 2^13 NTT tile (second kernel of every configuration)
-                traffic_source = "profiles/%s (a committed rocprofv3 --pmc pass of this command, not measured in this run)" % fn
-                break
-            except Exception:  # noqa: BLE001
-                continue
+        roofline = None
+        if args.full:
+            traffic = ntt_traffic = traffic_source = None
+            measured = None
+            if rank == 0 and world == 1 and not big and table_wide and not args.no_traffic_pass:
+                # VERDICT r5 "weak" 9: the counters are read in THIS run, not from a file.  The children build their own SRS tables: this
+                # process gives the device back first (160 + 160 GB of tables do not fit next to each other)
+                pk.destroy()
+                srs.destroy()
+                for c in ctxs[1:]:
+                    c.close()
+                torch.cuda.empty_cache()
+                t_pm = time.perf_counter()
+                measured = _measure_traffic(args.transcript)
+                if measured:
+                    traffic, ntt_traffic = measured["bytes_per_launch"], measured["ntt13"]
+                    traffic_source = ("measured in this run: two child passes `rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py --steps 2 --warmup 1 --streams 1` "
+                                      "(%.0f s), per-launch average over %d launches of k_msm_table<false>; FETCH_SIZE x 1 for the scattered 64-byte table gathers + half the streamed "
+                                      "scalar bytes + WRITE_SIZE x 1 (factors: profiles/r5_pmc_calibration.md)" % (time.perf_counter() - t_pm, measured["launches"]))
+            for fn in (() if measured else ("r6_pmc_traffic.json", "r5_pmc_traffic.json", "r4_pmc_traffic.json", "r3_pmc_traffic.json")):   # HBM bytes per launch from the committed PMC passes (profiles/, rocprofv3 --pmc)
+                try:
+                    pt = json.load(open(os.path.join(ROOT, "profiles", fn)))
+                    traffic = pt["bytes_per_launch"] if (not big and table_wide) else None
+                    ntt_traffic = pt["ntt13"] if not big else None   # the same for the 2^13 NTT tile (second kernel of every configuration)
+                    traffic_source = "profiles/%s (a committed rocprofv3 --pmc pass of this command, not measured in this run)" % fn
+                    break
+                except Exception:  # noqa: BLE001
+                    continue
+            ach = msm["algorithmic_bytes"] / (msm["total_ms"] * 1e-3) / 1e9
+            ntt_ach = ntt["algorithmic_bytes"] / (ntt["total_ms"] * 1e-3) / 1e9 if ntt["launches"] else None
+            roofline = {"bound": "hbm", "kernel": msm_kernel, "table_digit_bits": table_bits, "tables": table_info, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": msm["total_ms"] / max(1, msm["launches"]),
+                        "launches_per_proof": msm["launches"] / 2,
+                        # the bound that actually binds this kernel (SURVEY.md 8(d) "secondary, honest bound"): 256-bit modular
+                        # multiplications, 10 per mixed XYZZ addition, against the multiply-add issue bound (MODMUL_PEAK_G above)
+                        "int_alu": {"achieved": msm["ops"] * MODMUL_PER_MIXED_ADD / (msm["total_ms"] * 1e-3) / 1e9, "peak": MODMUL_PEAK_G,
+                                    "peak_kind": "multiply-add issue estimate from the builder's own probe (5.3 cycles per v_mad_u64_u32, 162 per product; "
+                                                 "a bare product loop measures 168 G/s, tools/exp/mad_rate.hip) -- NOT a published hardware bound",
+                                    "unit": "G modmul/s", "frac": msm["ops"] * MODMUL_PER_MIXED_ADD / (msm["total_ms"] * 1e-3) / 1e9 / MODMUL_PEAK_G,
+                                    "mixed_additions_per_proof": msm["ops"] / 2},
+                        "msm_few_columns": {"avg_launch_ms": direct["total_ms"] / max(1, direct["launches"]), "launches_per_proof": direct["launches"] / 2},
+                        "ntt_tile": {"kernel": "k_ntt13", "traffic": ntt_traffic, "achieved": ntt_ach, "int_alu_frac": (ntt["ops"] / (ntt["total_ms"] * 1e-3) / 1e9 / MODMUL_PEAK_G) if ntt["launches"] else None, "avg_launch_ms": ntt["total_ms"] / max(1, ntt["launches"]), "launches_per_proof": ntt["launches"] / 2}}
         out = {
             "metric": "BFV proofs/sec (k=%d)" % conf["k"], "value": jobs * args.steps / dt, "unit": "proofs/s", "n_gpus": world, "gpus_requested": args.gpus,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -468,7 +493,7 @@ def main():
                                    % (conf["k"], conf["N"], 3 if args.config == "k16" else 4),
                        "columns": {"gate0": zcfg.n_gate0, "gate1": zcfg.n_gate1, "lookup": zcfg.n_lookup, "rlc": zcfg.n_rlc},
                        "mode": args.mode if use_dist else "batch", "transcript": args.transcript, "concurrent_proofs_per_gpu": n_streams, "host_cpu_ms_per_proof": host_cpu_ms,
-                       "host_cpu_ms_per_proof_by_rank": host_cpu_by_rank, "host": host, "verified": bool(verified), "proofs_gathered_and_verified": gathered, "sharded_proof_identical_on_all_ranks": same_on_all_ranks,
+                       "host_cpu_ms_per_proof_by_rank": host_cpu_by_rank, "host": host, "verified": None if verified is None else bool(verified), "proofs_gathered_and_verified": gathered, "sharded_proof_identical_on_all_ranks": same_on_all_ranks,
                        # rank 0's last timed proof, reproducible: input = index into this configuration's input list (bench.py main), seed as given to zkfhe_bfv_prove
                        "last_timed_proof": {"sha256": last_sha, "vk_digest": vk_hex, "input_index": j_last % len(inputs), "seed": seeds[j_last % len(seeds)].decode()}, "process_group": (backend if use_dist else None),
                        "steady_state_proofs_per_s": steady, "cold_key_proofs_per_s": cold, "headline_keys": "warm: %d public keys cycled, all in the per-key transcript cache (cold_key_proofs_per_s: the same K proofs with the cache off)" % len(inputs), "admission_gate": gate_timed, "inputs_announced_one_proof_ahead": announce,
@@ -479,18 +504,7 @@ def main():
                        "vs_baseline_note": "reference README.md:58: 10.2 s per proof on an 8-core M2 -- DIFFERENT HARDWARE and a LARGER constraint system "
                                            "(axiom-eth always configures a Keccak sub-circuit whose columns this prover does not have, DESIGN.md 6.1); "
                                            "a batch rate against a single-proof latency: not a like-for-like speed-up"},
-            "roofline": {"bound": "hbm", "kernel": msm_kernel, "table_digit_bits": table_bits, "tables": table_info, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "avg_launch_ms": msm["total_ms"] / max(1, msm["launches"]),
-                         "launches_per_proof": msm["launches"] / 2,
-                         # the bound that actually binds this kernel (SURVEY.md 8(d) "secondary, honest bound"): 256-bit modular
-                         # multiplications, 10 per mixed XYZZ addition, against the multiply-add issue bound (MODMUL_PEAK_G above)
-                         "int_alu": {"achieved": msm["ops"] * MODMUL_PER_MIXED_ADD / (msm["total_ms"] * 1e-3) / 1e9, "peak": MODMUL_PEAK_G,
-                                     "peak_kind": "multiply-add issue estimate from the builder's own probe (5.3 cycles per v_mad_u64_u32, 162 per product; "
-                                                  "a bare product loop measures 168 G/s, tools/exp/mad_rate.hip) -- NOT a published hardware bound",
-                                     "unit": "G modmul/s", "frac": msm["ops"] * MODMUL_PER_MIXED_ADD / (msm["total_ms"] * 1e-3) / 1e9 / MODMUL_PEAK_G,
-                                     "mixed_additions_per_proof": msm["ops"] / 2},
-                         "msm_few_columns": {"avg_launch_ms": direct["total_ms"] / max(1, direct["launches"]), "launches_per_proof": direct["launches"] / 2},
-                         "ntt_tile": {"kernel": "k_ntt13", "traffic": ntt_traffic, "achieved": ntt_ach, "int_alu_frac": (ntt["ops"] / (ntt["total_ms"] * 1e-3) / 1e9 / MODMUL_PEAK_G) if ntt["launches"] else None, "avg_launch_ms": ntt["total_ms"] / max(1, ntt["launches"]), "launches_per_proof": ntt["launches"] / 2}},
+            "roofline": roofline,
             "cpu_baseline": cpu,
         }
         print(json.dumps(out))

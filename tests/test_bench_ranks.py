@@ -3,7 +3,8 @@ torch.distributed.run with N local ranks) and the way the task's contract words 
 --nproc-per-node N bench.py --gpus N ...`).  The ranks share GPU 0 here with the gloo backend (ZKFHE_BENCH_BACKEND=gloo; on a
 multi-GPU node the same script runs one rank per GPU over RCCL); the RCCL branch itself runs as a ONE-rank process group
 (ZKFHE_BENCH_FORCE_DIST=1).  Checks the contract of the JSON line: one line, from rank 0, n_gpus = the N asked for, the whole-job
-rate -- and that a launch whose size is not the N asked for prints no line at all."""
+rate -- and that a launch whose size is not the N asked for prints no line at all.  The runs that check proofs pass --full (a
+plain run verifies nothing); one plain single-GPU run checks what such a run leaves out."""
 import json
 import os
 import socket
@@ -35,7 +36,7 @@ def test_bench_plain_command_with_gpus_2_runs_two_ranks():
     """`python bench.py --gpus 2` with NO launcher around it must be a two-rank job (the script starts itself
     again under torch.distributed.run) and print n_gpus = 2 -- not a single-GPU line that ignores the flag."""
     env = _clean_env(ZKFHE_BENCH_BACKEND="gloo", ZKFHE_TABLE_GB="4")          # two SRS on one device: the suite's budget, not a service's table profile
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--steady-seconds", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--steady-seconds", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,7 +58,7 @@ def test_bench_one_proof_sharded_two_ranks_one_gpu_gloo():
     and the line says so: strong scaling, value = proofs of the job, not per rank; the timed proofs verify."""
     env = _clean_env(ZKFHE_BENCH_BACKEND="gloo", ZKFHE_TABLE_GB="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--steady-seconds", "0", "--mode", "one-proof-sharded", "--transcript", "blake2b"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -80,7 +81,7 @@ def test_bench_four_ranks_one_gpu_gloo():
     env.pop("ZKFHE_HASH_MODE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "8", "--warmup", "1", "--streams", "4",
-           "--no-cpu-baseline", "--steady-seconds", "0"]
+           "--full", "--no-cpu-baseline", "--steady-seconds", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -102,7 +103,7 @@ def test_bench_one_k19_proof_sharded_over_four_ranks_gloo():
     flow, the JSON contract (strong scaling: value = proofs of the JOB per second) and a verified k = 19 proof made by four ranks.  The rate means nothing here."""
     env = _clean_env(ZKFHE_BENCH_BACKEND="gloo", ZKFHE_TABLE_GB="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
            "--steady-seconds", "0", "--mode", "one-proof-sharded", "--config", "k19", "--transcript", "blake2b"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=2400)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -147,7 +148,7 @@ def test_bench_rccl_process_group_of_one_rank(mode):
     library's RCCL communicator (ncclAllGather of the partials)."""
     env = _clean_env(ZKFHE_BENCH_FORCE_DIST="1", ZKFHE_TABLE_GB="4")
     env.pop("ZKFHE_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--streams", "2", "--no-cpu-baseline", "--no-traffic-pass",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--streams", "2", "--full", "--no-cpu-baseline", "--no-traffic-pass",
            "--steady-seconds", "0", "--mode", mode]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -180,6 +181,33 @@ def test_bench_refuses_a_launch_that_is_not_the_n_asked_for():
                            capture_output=True, text=True, timeout=600)
         assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert "2 local ranks but 1 visible GPU" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_only_the_headline(tmp_path):
+    """A plain `bench.py --gpus 1` sets up, warms up, times its steps, writes --dump-outputs and prints the line: the headline
+    fields are there, and what only --full measures or checks is null (host verifier, steady-state and cold-key passes, roofline,
+    CPU baseline) -- even with --steady-seconds left at its default.  The dumped proof is the last timed one the line names."""
+    import hashlib
+    import numpy as np
+    env = _clean_env(ZKFHE_TABLE_GB="4")
+    env.pop("ZKFHE_BENCH_BACKEND", None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--streams", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "BFV proofs/sec (k=13)" and d["unit"] == "proofs/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"].startswith("u32x8")
+    assert d["value"] > 0 and abs(d["value"] - 3 / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 1e-6
+    c = d["config"]
+    assert c["verified"] is None and c["steady_state_proofs_per_s"] is None and c["cold_key_proofs_per_s"] is None
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    proof = np.load(out / "proof_bytes.npy").astype(np.uint8).tobytes()
+    assert len(proof) == c["proof_bytes"] and hashlib.sha256(proof).hexdigest() == c["last_timed_proof"]["sha256"]
+    assert np.load(out / "instances.npy").shape == (5 * 1024 + 1, 16)
 
 
 def test_dump_outputs_round_trips_exactly(tmp_path):

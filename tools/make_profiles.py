@@ -56,9 +56,9 @@ for l in lp.splitlines():
         single_avg = float(l.split()[3]) / int(l.split()[2])
 W('_a_driver_kernel_stats.md', """# @RT@ (a) -- kernel stats of the driver's command (k = 13, Poseidon transcript, one wave of 20 concurrent proofs)
 
-Command (MI355X box): `cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_a_driver -o r -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline`,
+Command (MI355X box): `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline`,
 summarised with `tools/rocpd_stats.py` (`tools/profile.sh` runs all of these profiles, `tools/make_profiles.py` writes
-these files).  The run printed %.1f proofs/s under the profiler; un-profiled `python bench.py --steps 20 --warmup 5` right after:
+these files).  The run printed %.1f proofs/s under the profiler; un-profiled `python bench.py --full --steps 20 --warmup 5` right after:
 %.1f proofs/s, steady-state pass %.1f.  With 20 proofs sharing the GPU a launch's duration includes the time its workgroups
 wait for CUs, so the averages below are NOT per-kernel costs: those are in `@RT@_b_single_proof.md`.
 
@@ -75,7 +75,7 @@ flight, the two calls of 266 and 136 columns) average %.3f ms.
 b, bs, bp = jl('b_single_bench.json'), jl('bench_single_blake2b.json'), jl('bench_single_poseidon.json')
 W('_b_single_proof.md', """# @RT@ (b) -- one proof in flight (k = 13, Blake2b transcript so that the host hash does not pace the GPU)
 
-`rocprofv3 --kernel-trace --stats -- python bench.py --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --transcript blake2b --steady-seconds 0`
+`rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 4 --warmup 1 --streams 1 --no-cpu-baseline --transcript blake2b --steady-seconds 0`
 (%.2f ms per proof under the profiler; %.2f ms un-profiled, %.1f ms with the Poseidon transcript: `@RT@_bench_lines.md`).
 
 ## Kernels of the last proof (`tools/last_proof_stats.py`)
@@ -96,7 +96,7 @@ for tag, name, cfgn in (('c_k16', 'k16', 'BASELINE configs[3]: N = 4096, Q = 2^6
            "No digit-multiple table at n = 2^19 (8-bit digits would need 137 GB per SRS half): every call takes the bucket pipeline."
     W('_%s_kernel_stats.md' % name, """# @RT@ -- %s (%s), one proof in flight, Blake2b transcript
 
-`rocprofv3 --kernel-trace --stats -- python bench.py --config %s --steps %d --warmup 1 --streams 1 --transcript blake2b --steady-seconds 0`
+`rocprofv3 --kernel-trace --stats -- python bench.py --full --config %s --steps %d --warmup 1 --streams 1 --transcript blake2b --steady-seconds 0`
 %.1f ms per proof under the profiler.  Un-profiled: `@RT@_bench_lines.md`.  %s
 
 ## Kernels of the last proof
@@ -136,7 +136,7 @@ W('_pmc.md', """# @RT@ -- PMC counters (rocprofv3, one or two counters per pass,
 
 ## HBM traffic, k = 13, one proof in flight, Poseidon transcript
 
-`rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --steady-seconds 0`,
+`rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --full --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --steady-seconds 0`,
 the same with `--pmc WRITE_SIZE`; `tools/pmc_stats.py`.  Units: KB per launch, averaged over the launches of the run.  gfx950
 factors measured on this library's own access patterns (`@CAL@`): coalesced 16 / 32-byte reads are tallied at half
 their bytes (x 2), scattered 64-byte gathers at their size (x 1), writes at their size (x 1).
@@ -158,7 +158,7 @@ writes 256 MB.  Each column is read by both of its workgroups: FETCH_SIZE shows 
 
 ## VALU instructions per proof (who uses the ALUs), k = 13, one proof in flight, Blake2b
 
-`rocprofv3 --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES --kernel-trace -- python bench.py --steps 6 --warmup 1 --streams 1 --no-cpu-baseline --transcript blake2b --steady-seconds 0`,
+`rocprofv3 --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES --kernel-trace -- python bench.py --full --steps 6 --warmup 1 --streams 1 --no-cpu-baseline --transcript blake2b --steady-seconds 0`,
 `tools/pmc_per_proof.py <db> 10` (sums over the run / 10 proofs incl. warm-up and the two profiled ones; `k_basis_multiples`,
 `k_g1_mul`, `k_basis_table` are the one-time SRS set-up and dominate the totals -- read the other rows against each other).
 
@@ -182,7 +182,7 @@ lines = ["# @RT@ -- bench lines (un-profiled, MI355X box, `tools/profile.sh` sec
          "sponge over the 5 N + 1 public inputs); `announced` = every input announced one proof ahead (`zkfhe_bfv_pk_prehash`: that sponge runs on a host thread while the previous proof is on the GPU).", "",
          "| command | proofs/s | ms per proof | in flight | steady-state pass | cold keys | first challenge ms (host wait) | announced | prefix cache hits / misses | host CPU ms / proof | dominant kernel: avg launch ms, int_alu frac |",
          "|---|---|---|---|---|---|---|---|---|---|---|"]
-for fn, cmd in (('bench_driver', "`python bench.py --steps 20 --warmup 5` (the driver's command)"), ('bench_default', '`python bench.py --no-cpu-baseline`'),
+for fn, cmd in (('bench_driver', "`python bench.py --full --steps 20 --warmup 5` (the driver's command)"), ('bench_default', '`python bench.py --full --no-cpu-baseline`'),
                 ('bench_blake2b', '`--transcript blake2b`'), ('bench_blake2b_20', '`--transcript blake2b --steps 20 --warmup 5`'),
                 ('bench_single_blake2b', '`--steps 8 --streams 1 --transcript blake2b`'), ('bench_single_poseidon', '`--steps 8 --streams 1 --announce off`'),
                 ('bench_single_poseidon_announced', '`--steps 16 --streams 1` (announced)'),
@@ -198,7 +198,7 @@ for fn, cmd in (('bench_driver', "`python bench.py --steps 20 --warmup 5` (the d
                 ('bench_k19_poseidon_s2', '`--config k19 --steps 9 --streams 2` (announced)'), ('bench_k19_poseidon_s3', '`--config k19 --steps 9 --streams 3` (announced)'),
                 ('bench_k19_poseidon_s3_plain', '`--config k19 --steps 9 --streams 3 --announce off`'),
                 ('bench_driver_shared', "`ZKFHE_HASH_MODE=shared` + the driver's command (eight-lane Poseidon service)"),
-                ('bench_default_shared', '`ZKFHE_HASH_MODE=shared python bench.py --no-cpu-baseline`'),
+                ('bench_default_shared', '`ZKFHE_HASH_MODE=shared python bench.py --full --no-cpu-baseline`'),
                 ('bench_driver_nocache', "`ZKFHE_PREFIX_CACHE=0` + the driver's command (no per-public-key transcript cache)")):
     d = jl(fn + '.json')
     if not d:
@@ -226,7 +226,7 @@ W('_microbench.md', "# @RT@ -- micro-benchmarks (`python tools/microbench.py`, M
 # ---- wave occupancy --------------------------------------------------------------------------------------------------------
 W('_wave_occupancy.md', """# @RT@ -- GPU occupancy over the driver's wave of 20 concurrent proofs (2 ms bins)
 
-`rocprofv3 --kernel-trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady-seconds 0` (`tools/profile.sh`), `tools/busy_bins.py <db> 400 2`:
+`rocprofv3 --kernel-trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady-seconds 0` (`tools/profile.sh`), `tools/busy_bins.py <db> 400 2`:
 per bin the fraction of time with at least one kernel running, the average number of kernels in flight and the kernel with the largest
 share.  The trace ends with what follows the timed region -- the cold-key pass (the same 20 proofs with the per-key transcript cache off:
 a second wave of ~100 ms) and the two profiled proofs (one in flight, ~60 ms); the timed wave is the ~100 ms block before those: a head of 14-18 ms in which the proofs' early work (phase-0 commitment, gadgets, early phase-1 commitment) shares the
