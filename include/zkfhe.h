@@ -620,6 +620,62 @@ int zkfhe_bfv_decrypt_combine(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, si
 #define ZKFHE_PROF_BFV_SHARE_SUM 12         /* k_bfv_share_sum */
 #define ZKFHE_PROF_BFV_DECRYPT_COMBINE 13   /* k_bfv_decrypt_combine */
 
+/* ---- BFV slots and rotations on the GPU (bfv_galois.hip) ----
+ * SIMD batching and Galois automorphisms.  The conventions above: host arrays, N uint64_t per polynomial in CircuitInput order,
+ * residues in [0, Q), the parameter checks of zkfhe_bfv_encrypt; every call waits for its result.  Below, coefficient i is the
+ * coefficient of x^i.
+ *   sigma_g(m)(x) = m(x^g) mod (x^N + 1), g odd, 1 <= g < 2N: coefficient i moves to k = i g mod 2N, negated (mod Q) and placed at
+ *   k - N when k >= N.
+ *   Batching: T prime, T < 2^31, 2N | T - 1 (T = 65537 for N <= 32768, 12289 for N <= 2048); then there are N slots.
+ *   zeta = r^((T - 1) / 2N) mod T, r the smallest primitive root mod T.  Slot p = row N/2 + j (row in {0, 1}, j < N/2) is the
+ *   evaluation at zeta^(e_p), e_p = (-1)^row 5^j mod 2N.  g = 5^k mod 2N rotates both rows left by k (new slot (row, j) = old slot
+ *   (row, j + k mod N/2)); g = 2N - 1 swaps the rows.
+ *   Galois key of s for g, w = base_bits, l = zkfhe_bfv_relin_digits rows: gk0_i = -(a_i s + e_i) + 2^(i w) sigma_g(s) mod Q,
+ *   gk1_i = a_i, a_i uniform from ChaCha20 domain 14 and e_i an error sample from domain 15, both with index g 64 + i (the
+ *   samplers of zkfhe_bfv_encrypt).  The key is public; its SEED IS SECRET like any key seed.
+ * Slot-encoded plaintexts are ordinary plaintexts (centred residues mod T): zkfhe_bfv_encrypt and the proof take them unchanged, and
+ * zkfhe_bfv_mul / zkfhe_bfv_mul_plain multiply them slot by slot.  Every call refuses, with ZKFHE_EINVAL and a message: a NULL
+ * argument, n = 0, g even or >= 2N, a coefficient >= Q in a ciphertext or key, a value >= T (encode), a plaintext out of range
+ * (decode), a non-ternary sk, base_bits outside [1, 32], and a T that does not batch (encode, decode and zkfhe_bfv_slot_count).
+ * Key-switch noise grows with 2^w: a narrower base costs more rows and time and adds less noise. */
+/* Host only: *slots = N, or ZKFHE_EINVAL when T is not a batching modulus */
+int zkfhe_bfv_slot_count(const zkfhe_bfv_params *params, size_t *slots);
+/* Host only: *g = 5^(steps mod N/2) mod 2N (negative steps rotate right), times 2N - 1 mod 2N if swap_rows */
+int zkfhe_bfv_galois_element(const zkfhe_bfv_params *params, int64_t steps, int swap_rows, uint64_t *g);
+/* Host only: *count = log2(N) and, if g is not NULL, the elements of zkfhe_bfv_slot_sum in order: g = 5^(2^k) mod 2N for
+ * k = 0 ... log2(N) - 2, then 2N - 1 */
+int zkfhe_bfv_slot_sum_elements(const zkfhe_bfv_params *params, uint64_t *g, size_t *count);
+/* n polynomials of N slot values in [0, T) -> the unique m of degree < N over Z_T with m(zeta^(e_p)) = values[p], centred mod T
+ * and written as residues mod Q (the representation zkfhe_bfv_decrypt returns).  One LDS NTT mod T per polynomial. */
+int zkfhe_bfv_encode_slots(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *values, uint64_t *m_out);
+/* the inverse of zkfhe_bfv_encode_slots: n plaintexts in [0, T/2] or [Q - T/2, Q - 1] -> their slot values in [0, T) */
+int zkfhe_bfv_decode_slots(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *m, uint64_t *values_out);
+/* the Galois key of sk for g (gk0, gk1 of l x N, see above) */
+int zkfhe_bfv_galois_keygen(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk, const uint8_t seed[32], uint64_t g,
+                            int base_bits, uint64_t *gk0, uint64_t *gk1);
+/* n key switches, defined exactly: c'_j = sigma_g(c_j) as residues in [0, Q); digits d_i = (c'_1 >> i w) & (2^w - 1);
+ * out0 = c'_0 + sum_i d_i gk0_i, out1 = sum_i d_i gk1_i mod (x^N + 1, Q).  The result decrypts under s to sigma_g(m); g = 1 is a
+ * plain key switch.  gk0, gk1: l x N with the same base_bits, transformed once per call. */
+int zkfhe_bfv_apply_galois(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1, uint64_t g,
+                           const uint64_t *gk0, const uint64_t *gk1, int base_bits, uint64_t *out0, uint64_t *out1);
+/* n ciphertexts, each x <- x + zkfhe_bfv_apply_galois(x, g_k) (the sum of zkfhe_bfv_add) for the log2(N) elements of
+ * zkfhe_bfv_slot_sum_elements in order, bit for bit that composition; under a batching T every slot then holds the sum of all N
+ * slots mod T.  gk0, gk1: log2(N) x l x N, the keys of those elements in the same order, all transformed once per call; the steps
+ * run on device buffers. */
+int zkfhe_bfv_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1, const uint64_t *gk0,
+                       const uint64_t *gk1, int base_bits, uint64_t *out0, uint64_t *out1);
+/* party i's share of the collective Galois key for g, in one round (the rotation-key generation of Mouchet et al.):
+ * r[j] = -(a_j s_i + e_ij) + 2^(j w) sigma_g(s_i) mod Q, a[j] = a_j; a_j from crs_seed (domain 14), e_ij from party_seed
+ * (domain 15), index g 64 + j.  The collective key is gk0 = zkfhe_bfv_share_aggregate of the r_i and gk1 = a; zkfhe_bfv_apply_galois
+ * and zkfhe_bfv_slot_sum take it unchanged.  With crs_seed == party_seed == seed, (r, a) is zkfhe_bfv_galois_keygen(seed) bit for
+ * bit.  PARTY SEEDS ARE SECRET. */
+int zkfhe_bfv_galois_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, const uint8_t crs_seed[32],
+                           const uint8_t party_seed[32], uint64_t g, int base_bits, uint64_t *r_out, uint64_t *a_out);
+/* zkfhe_prof_read slots of the slot and rotation kernels; the CRT epilogue of the key calls (k_gal_key_epilogue) counts in
+ * ZKFHE_PROF_RNS_EPILOGUE */
+#define ZKFHE_PROF_BFV_GALOIS 14     /* k_gal_switch, k_gal_epilogue */
+#define ZKFHE_PROF_BFV_SLOT_NTT 15   /* k_slot_ntt */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

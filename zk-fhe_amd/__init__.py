@@ -20,6 +20,7 @@ PROF_G1_DECOMPRESS, PROF_MSM_SEGMENTED = 3, 4   # zkfhe_prof_read slots of the b
 PROF_BFV_SAMPLE, PROF_RNS_NTT, PROF_RNS_EPILOGUE = 5, 6, 7   # ... and of the BFV encryption kernels
 PROF_BFV_TENSOR, PROF_BFV_RELIN, PROF_BFV_EVAL_EPILOGUE, PROF_BFV_ELEMENTWISE = 8, 9, 10, 11   # ... and of the BFV evaluation kernels
 PROF_BFV_SHARE_SUM, PROF_BFV_DECRYPT_COMBINE = 12, 13   # ... and of the threshold kernels
+PROF_BFV_GALOIS, PROF_BFV_SLOT_NTT = 14, 15   # ... and of the slot and rotation kernels
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -45,6 +46,8 @@ EXPORTS = [
     "zkfhe_bfv_mul", "zkfhe_bfv_noise",
     "zkfhe_bfv_keygen_share", "zkfhe_bfv_share_aggregate", "zkfhe_bfv_relin_share1", "zkfhe_bfv_relin_share2", "zkfhe_bfv_decrypt_share",
     "zkfhe_bfv_decrypt_combine",
+    "zkfhe_bfv_slot_count", "zkfhe_bfv_galois_element", "zkfhe_bfv_slot_sum_elements", "zkfhe_bfv_encode_slots", "zkfhe_bfv_decode_slots",
+    "zkfhe_bfv_galois_keygen", "zkfhe_bfv_apply_galois", "zkfhe_bfv_slot_sum", "zkfhe_bfv_galois_share",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -728,6 +731,89 @@ class Context:
                                                        d.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
         return out
 
+    # ------------------------------------------------------------------ slots and rotations (zkfhe.h, bfv_galois.hip)
+    # Slot values and plaintexts are (n, N) uint64 arrays like the calls above; a Galois key is (gk0, gk1) of shape (l, N), and
+    # bfv_slot_sum takes the keys of bfv_slot_sum_elements stacked as (log2(N), l, N).
+
+    def _slots(self, fn, params, x):
+        n = int(params[0])
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, n)
+        out = np.empty(x.shape, dtype=np.uint64)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        f = getattr(self.lib, fn)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, u64p, u64p]
+        prm = BfvParamsC(*[int(v) for v in params])
+        self._check(f(self.h, ctypes.byref(prm), x.shape[0], x.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        return out
+
+    def bfv_encode_slots(self, params, values):
+        """zkfhe_bfv_encode_slots: slot values in [0, T) of shape (N,) or (n, N) -> plaintexts (n, N), centred residues mod Q."""
+        return self._slots("zkfhe_bfv_encode_slots", params, values)
+
+    def bfv_decode_slots(self, params, m):
+        """zkfhe_bfv_decode_slots: plaintexts of shape (N,) or (n, N) -> slot values in [0, T), shape (n, N)."""
+        return self._slots("zkfhe_bfv_decode_slots", params, m)
+
+    def _galois_key(self, fn, params, sk, crs_seed, party_seed, g, base_bits):
+        n, sk = int(params[0]), self._sk(params, sk)
+        l = self._relin_rows(params, base_bits)
+        out = [np.empty((l, n), dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        f = getattr(self.lib, fn)
+        seeds = [crs_seed] if party_seed is None else [crs_seed, party_seed]
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p] + [ctypes.c_char_p] * len(seeds) + [ctypes.c_uint64, ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(v) for v in params])
+        self._check(f(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), *seeds, int(g), int(base_bits), *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_galois_keygen(self, params, sk, g, seed=None, base_bits=16):
+        """zkfhe_bfv_galois_keygen -> (gk0, gk1) of shape (l, N): the Galois key of sk for the element g.  seed: 32 SECRET bytes
+        (None: os.urandom); the key itself is public."""
+        seed = self._seed(seed, "Galois-key seed", fresh=True)
+        return self._galois_key("zkfhe_bfv_galois_keygen", params, sk, seed, None, g, base_bits)
+
+    def bfv_galois_share(self, params, sk, crs_seed, party_seed, g, base_bits=8):
+        """zkfhe_bfv_galois_share -> (r_i, a) of shape (l, N): party i's share of the collective Galois key for g; gk0 =
+        bfv_share_aggregate of the r_i, gk1 = a."""
+        crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
+        return self._galois_key("zkfhe_bfv_galois_share", params, sk, crs_seed, party_seed, g, base_bits)
+
+    def _galois_keys(self, params, gk0, gk1, base_bits, lead):
+        n = int(params[0])
+        gk0 = np.ascontiguousarray(gk0, dtype=np.uint64)
+        gk1 = np.ascontiguousarray(gk1, dtype=np.uint64)
+        l = self._relin_rows(params, base_bits) or (gk0.shape[-2] if gk0.ndim >= 2 else 0)   # else the call refuses base_bits
+        if gk0.shape != lead + (l, n) or gk1.shape != lead + (l, n):
+            raise ValueError("gk0 and gk1 must have shape %s for base_bits %d" % (lead + (l, n), base_bits))
+        return gk0, gk1
+
+    def bfv_apply_galois(self, params, c0, c1, g, gk0, gk1, base_bits=16):
+        """zkfhe_bfv_apply_galois: n ciphertexts (n, N) -> sigma_g of each, key-switched back to s with (gk0, gk1) of shape (l, N)."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        gk0, gk1 = self._galois_keys(params, gk0, gk1, base_bits, ())
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_apply_galois.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, u64p, u64p, ctypes.c_uint64,
+                                                    u64p, u64p, ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(v) for v in params])
+        self._check(self.lib.zkfhe_bfv_apply_galois(self.h, ctypes.byref(prm), c0.shape[0], c0.ctypes.data_as(u64p), c1.ctypes.data_as(u64p),
+                                                    int(g), gk0.ctypes.data_as(u64p), gk1.ctypes.data_as(u64p), int(base_bits),
+                                                    *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
+    def bfv_slot_sum(self, params, c0, c1, gk0, gk1, base_bits=16):
+        """zkfhe_bfv_slot_sum: n ciphertexts (n, N) -> every slot holds the total, with the keys of bfv_slot_sum_elements stacked
+        as gk0, gk1 of shape (log2(N), l, N)."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        gk0, gk1 = self._galois_keys(params, gk0, gk1, base_bits, (int(params[0]).bit_length() - 1,))
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkfhe_bfv_slot_sum.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 4 + [ctypes.c_int, u64p, u64p]
+        prm = BfvParamsC(*[int(v) for v in params])
+        self._check(self.lib.zkfhe_bfv_slot_sum(self.h, ctypes.byref(prm), c0.shape[0], *[x.ctypes.data_as(u64p) for x in (c0, c1, gk0, gk1)],
+                                                int(base_bits), *[o.ctypes.data_as(u64p) for o in out]))
+        return tuple(out)
+
 
 def bfv_relin_digits(params, base_bits):
     """zkfhe_bfv_relin_digits (host only): l = ceil(bitlen(Q - 1) / base_bits), the rows of a relinearization key."""
@@ -739,6 +825,49 @@ def bfv_relin_digits(params, base_bits):
     if rc != 0:
         raise ZkfheError("zkfhe_bfv_relin_digits failed (%d): %s" % (rc, lib.zkfhe_last_error(None).decode()))
     return l.value
+
+
+def _host_fail(lib, fn, rc):
+    raise ZkfheError("%s failed (%d): %s" % (fn, rc, lib.zkfhe_last_error(None).decode()))
+
+
+def bfv_slot_count(params):
+    """zkfhe_bfv_slot_count (host only): N when T is a batching modulus (prime, below 2^31, 2N | T - 1); raises otherwise."""
+    lib = load_library()
+    lib.zkfhe_bfv_slot_count.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.POINTER(ctypes.c_size_t)]
+    prm = BfvParamsC(*[int(x) for x in params])
+    slots = ctypes.c_size_t()
+    rc = lib.zkfhe_bfv_slot_count(ctypes.byref(prm), ctypes.byref(slots))
+    if rc != 0:
+        _host_fail(lib, "zkfhe_bfv_slot_count", rc)
+    return slots.value
+
+
+def bfv_galois_element(params, steps=0, swap_rows=False):
+    """zkfhe_bfv_galois_element (host only): g = 5^(steps mod N/2) mod 2N (a rotation of both rows left by steps), times 2N - 1 if
+    swap_rows."""
+    lib = load_library()
+    lib.zkfhe_bfv_galois_element.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    prm = BfvParamsC(*[int(x) for x in params])
+    g = ctypes.c_uint64()
+    rc = lib.zkfhe_bfv_galois_element(ctypes.byref(prm), int(steps), int(bool(swap_rows)), ctypes.byref(g))
+    if rc != 0:
+        _host_fail(lib, "zkfhe_bfv_galois_element", rc)
+    return g.value
+
+
+def bfv_slot_sum_elements(params):
+    """zkfhe_bfv_slot_sum_elements (host only): the log2(N) Galois elements of bfv_slot_sum in order, a list of ints."""
+    lib = load_library()
+    lib.zkfhe_bfv_slot_sum_elements.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    prm = BfvParamsC(*[int(x) for x in params])
+    cnt = ctypes.c_size_t()
+    rc = lib.zkfhe_bfv_slot_sum_elements(ctypes.byref(prm), None, ctypes.byref(cnt))
+    if rc != 0:
+        _host_fail(lib, "zkfhe_bfv_slot_sum_elements", rc)
+    out = np.empty(cnt.value, dtype=np.uint64)
+    lib.zkfhe_bfv_slot_sum_elements(ctypes.byref(prm), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt))
+    return [int(x) for x in out]
 
 
 def bfv_error_cdt(params):

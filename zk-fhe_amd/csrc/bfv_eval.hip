@@ -22,12 +22,6 @@ namespace {
 constexpr int NP = NP_MAX;
 typedef unsigned __int128 u128;
 
-// Garner over the five primes: y_k = (((r_k - y_0) p_0^-1 - y_1) p_1^-1 - ...) mod p_k, x = y_0 + p_0 (y_1 + p_1 (y_2 + ...))
-struct Crt5 {
-  uint32_t inv[NP][NP];   // inv[j][k] = p_j^-1 mod p_k for j < k
-  uint64_t P[3], H[3];    // p_0 ... p_4 and floor of its half, little-endian limbs
-};
-
 enum EvMode { EV_MODQ = 0, EV_ROUND = 1, EV_ADD = 2, EV_RLK = 3, EV_NOISE = 4 };
 struct EvEpi {
   int mode;
@@ -39,31 +33,6 @@ struct EvEpi {
 };
 
 __device__ __forceinline__ uint64_t sub_q(uint64_t a, uint64_t b, uint64_t q) { return a >= b ? a - b : a + q - b; }
-
-// the centred integer of the residues r[k n], k < NP: magnitude m (three limbs) and sign
-__device__ __forceinline__ void crt5(const uint32_t *__restrict__ r, size_t n, const Crt5 &cc, uint64_t m[3], bool &neg) {
-  uint64_t y[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const uint64_t pk = PRIMES[k];
-    uint64_t t = r[k * n];
-#pragma unroll
-    for (int j = 0; j < k; ++j) t = (t + pk - y[j] % pk) * cc.inv[j][k] % pk;   // < 2^32 * 2^31
-    y[k] = t;
-  }
-  uint64_t x0 = y[NP - 1], x1 = 0, x2 = 0;
-#pragma unroll
-  for (int k = NP - 2; k >= 0; --k) {
-    const u128 a = (u128)x0 * PRIMES[k] + y[k];
-    const u128 b = (u128)x1 * PRIMES[k] + (uint64_t)(a >> 64);
-    x0 = (uint64_t)a, x1 = (uint64_t)b, x2 = x2 * PRIMES[k] + (uint64_t)(b >> 64);
-  }
-  neg = x2 > cc.H[2] || (x2 == cc.H[2] && (x1 > cc.H[1] || (x1 == cc.H[1] && x0 > cc.H[0])));
-  const uint64_t d0 = cc.P[0] - x0, b0 = cc.P[0] < x0;
-  const uint64_t d1 = cc.P[1] - x1 - b0, b1 = cc.P[1] < x1 || (cc.P[1] - x1) < b0;
-  const uint64_t d2 = cc.P[2] - x2 - b1;
-  m[0] = neg ? d0 : x0, m[1] = neg ? d1 : x1, m[2] = neg ? d2 : x2;
-}
 
 // One thread per output coefficient of res ([poly][prime][degree], total = n_polys N): the centred integer x of its residues, then
 // EV_MODQ x mod Q; EV_ROUND floor((2 T x + Q) / 2Q) mod Q; EV_ADD x + add mod Q; EV_RLK 2^(i w) s^2 - x - e mod Q for polynomial i;
@@ -215,23 +184,6 @@ __global__ __launch_bounds__(256) void k_bfv_add(const uint64_t *__restrict__ a,
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
-
-Crt5 crt5_const() {
-  Crt5 c{};
-  for (int j = 0; j < NP; ++j)
-    for (int k = j + 1; k < NP; ++k) c.inv[j][k] = (uint32_t)pow_mod(PRIMES[j] % PRIMES[k], PRIMES[k] - 2, PRIMES[k]);
-  uint64_t P[3] = {1, 0, 0};
-  for (int k = 0; k < NP; ++k) {
-    u128 a = (u128)P[0] * PRIMES[k];
-    P[0] = (uint64_t)a;
-    a = (u128)P[1] * PRIMES[k] + (uint64_t)(a >> 64);
-    P[1] = (uint64_t)a;
-    P[2] = P[2] * PRIMES[k] + (uint64_t)(a >> 64);
-  }
-  for (int i = 0; i < 3; ++i) c.P[i] = P[i];
-  c.H[0] = P[0] >> 1 | P[1] << 63, c.H[1] = P[1] >> 1 | P[2] << 63, c.H[2] = P[2] >> 1;
-  return c;
-}
 
 int launch_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out) {
   const size_t total = n_polys << log_n;

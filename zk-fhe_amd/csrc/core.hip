@@ -160,6 +160,7 @@ int zkfhe_ctx_destroy(zkfhe_ctx *ctx) {
   if (ctx->tickets) hipFree(ctx->tickets);
   if (ctx->bfv_tw) hipFree(ctx->bfv_tw);
   if (ctx->bfv_work) hipFree(ctx->bfv_work);
+  for (auto &kv : ctx->slot_tw) hipFree(kv.second.dev);
   if (ctx->wait_ev) hipEventDestroy(ctx->wait_ev);
   hipEventDestroy(ctx->ev0);
   hipEventDestroy(ctx->ev1);

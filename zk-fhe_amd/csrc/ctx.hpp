@@ -47,8 +47,8 @@ struct zkfhe_ctx {
   // [2] = k_msm_table of a call of a few columns, [3] = k_g1_decompress, [4] = k_msm_segmented (verify.hip),
   // [5] = k_bfv_sample, [6] = k_rns_ntt, [7] = k_rns_epilogue (bfv_enc.hip), [8] = k_bfv_tensor, [9] = k_bfv_relin,
   // [10] = k_eval_epilogue, [11] = k_bfv_sum / k_bfv_add (bfv_eval.hip), [12] = k_bfv_share_sum, [13] = k_bfv_decrypt_combine
-  // (bfv_threshold.hip)
-  static constexpr int PROF_SLOTS = 14;
+  // (bfv_threshold.hip), [14] = k_gal_switch / k_gal_epilogue, [15] = k_slot_ntt (bfv_galois.hip)
+  static constexpr int PROF_SLOTS = 16;
   double prof_ms[PROF_SLOTS] = {}, prof_bytes[PROF_SLOTS] = {}, prof_ops[PROF_SLOTS] = {};
   uint64_t prof_launches[PROF_SLOTS] = {};
   // pinned bounce buffer for small host<->device transfers (pageable copies go through the runtime's shared staging path)
@@ -64,6 +64,12 @@ struct zkfhe_ctx {
   uint32_t *bfv_tw = nullptr;
   void *bfv_work = nullptr;
   size_t bfv_work_sz = 0;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
+  // slot batching (bfv_galois.hip): per (T, N), [fwd | inv | slot of NTT index][N] on the device and the constants of T
+  struct SlotTables {
+    uint32_t *dev = nullptr;
+    uint32_t pinv = 0, n_inv = 0;   // -T^-1 mod 2^32; N^-1 R mod T (R = 2^32: mont_mul by it scales by N^-1)
+  };
+  std::map<std::pair<uint64_t, uint64_t>, SlotTables> slot_tw;
 };
 
 struct zkfhe_basis {

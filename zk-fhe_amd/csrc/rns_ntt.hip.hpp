@@ -1,15 +1,15 @@
-// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip, bfv_threshold.hip): an RNS NTT over NP primes
-// below 2^31, one workgroup per (polynomial, prime), the whole transform of N <= 2^15 words in LDS (128 KiB at N = 2^15), with
-// 32-bit Montgomery arithmetic.  Templated on the prime count: encryption and the threshold calls use the first three primes
-// (product 2^89.2: a ternary factor keeps the product below N 2^64), the evaluator all five (product 2^151.2: a product of two
-// centred residues below 2^63 stays below 2^140).
+// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip, bfv_threshold.hip, bfv_galois.hip): an RNS NTT
+// over NP primes below 2^31, one workgroup per (polynomial, prime), the whole transform of N <= 2^15 words in LDS (128 KiB at
+// N = 2^15), with 32-bit Montgomery arithmetic.  Templated on the prime count: encryption and the threshold calls use the first
+// three primes (product 2^89.2: a ternary factor keeps the product below N 2^64), the evaluator all five (product 2^151.2: a
+// product of two centred residues below 2^63 stays below 2^140).
 // Headroom at p < 2^31: a b + m p < 2^62 + 2^63 < 2^64 in mont_mul, and a + b < 2^32 in add_p.
 #pragma once
 #include <algorithm>
 
 #include "ctx.hpp"
 
-// defined in bfv_enc.hip, shared with bfv_eval.hip and bfv_threshold.hip
+// defined in bfv_enc.hip, shared with bfv_eval.hip, bfv_threshold.hip and bfv_galois.hip
 // the twiddle tables of every prime: [prime][fwd | inv][NMAX], psi^br15(k) and psi^-br15(k) in Montgomery form (built on first use)
 int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out);
 // the parameter check of every BFV call (zkfhe.h)
@@ -104,6 +104,38 @@ __device__ __forceinline__ uint64_t crt3_mod_q(const uint32_t *__restrict__ r, s
   const u128 mag = neg ? P - x : x;
   const uint64_t rm = mod128((uint64_t)(mag >> 64), (uint64_t)mag, q);
   return neg && rm ? q - rm : rm;
+}
+
+// Garner over the five primes: y_k = (((r_k - y_0) p_0^-1 - y_1) p_1^-1 - ...) mod p_k, x = y_0 + p_0 (y_1 + p_1 (y_2 + ...))
+struct Crt5 {
+  uint32_t inv[NP_MAX][NP_MAX];   // inv[j][k] = p_j^-1 mod p_k for j < k
+  uint64_t P[3], H[3];            // p_0 ... p_4 and floor of its half, little-endian limbs
+};
+
+// the centred integer of the residues r[k n], k < NP_MAX: magnitude m (three limbs) and sign
+__device__ __forceinline__ void crt5(const uint32_t *__restrict__ r, size_t n, const Crt5 &cc, uint64_t m[3], bool &neg) {
+  typedef unsigned __int128 u128;
+  uint64_t y[NP_MAX];
+#pragma unroll
+  for (int k = 0; k < NP_MAX; ++k) {
+    const uint64_t pk = PRIMES[k];
+    uint64_t t = r[k * n];
+#pragma unroll
+    for (int j = 0; j < k; ++j) t = (t + pk - y[j] % pk) * cc.inv[j][k] % pk;   // < 2^32 * 2^31
+    y[k] = t;
+  }
+  uint64_t x0 = y[NP_MAX - 1], x1 = 0, x2 = 0;
+#pragma unroll
+  for (int k = NP_MAX - 2; k >= 0; --k) {
+    const u128 a = (u128)x0 * PRIMES[k] + y[k];
+    const u128 b = (u128)x1 * PRIMES[k] + (uint64_t)(a >> 64);
+    x0 = (uint64_t)a, x1 = (uint64_t)b, x2 = x2 * PRIMES[k] + (uint64_t)(b >> 64);
+  }
+  neg = x2 > cc.H[2] || (x2 == cc.H[2] && (x1 > cc.H[1] || (x1 == cc.H[1] && x0 > cc.H[0])));
+  const uint64_t d0 = cc.P[0] - x0, b0 = cc.P[0] < x0;
+  const uint64_t d1 = cc.P[1] - x1 - b0, b1 = cc.P[1] < x1 || (cc.P[1] - x1) < b0;
+  const uint64_t d2 = cc.P[2] - x2 - b1;
+  m[0] = neg ? d0 : x0, m[1] = neg ? d1 : x1, m[2] = neg ? d2 : x2;
 }
 
 // the decryption of the residue v = [c0 + c1 s]_Q: round(T x / Q) mod T with x = v centred, as a residue mod Q.  For the residue v
@@ -237,6 +269,24 @@ inline CrtConst crt3_const() {
   c.p0_mod_p2 = p0 % p2;
   const unsigned __int128 P = (unsigned __int128)c.p01 * p2;
   c.P_lo = (uint64_t)P, c.P_hi = (uint64_t)(P >> 64);
+  return c;
+}
+
+inline Crt5 crt5_const() {
+  typedef unsigned __int128 u128;
+  Crt5 c{};
+  for (int j = 0; j < NP_MAX; ++j)
+    for (int k = j + 1; k < NP_MAX; ++k) c.inv[j][k] = (uint32_t)pow_mod(PRIMES[j] % PRIMES[k], PRIMES[k] - 2, PRIMES[k]);
+  uint64_t P[3] = {1, 0, 0};
+  for (int k = 0; k < NP_MAX; ++k) {
+    u128 a = (u128)P[0] * PRIMES[k];
+    P[0] = (uint64_t)a;
+    a = (u128)P[1] * PRIMES[k] + (uint64_t)(a >> 64);
+    P[1] = (uint64_t)a;
+    P[2] = P[2] * PRIMES[k] + (uint64_t)(a >> 64);
+  }
+  for (int i = 0; i < 3; ++i) c.P[i] = P[i];
+  c.H[0] = P[0] >> 1 | P[1] << 63, c.H[1] = P[1] >> 1 | P[2] << 63, c.H[2] = P[2] >> 1;
   return c;
 }
 
