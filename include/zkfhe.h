@@ -526,7 +526,7 @@ int zkfhe_bfv_decrypt(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint
 /* zkfhe_prof_read slots of the BFV encryption kernels (algorithmic bytes: words read and written) */
 #define ZKFHE_PROF_BFV_SAMPLE 5     /* k_bfv_sample */
 #define ZKFHE_PROF_RNS_NTT 6        /* k_rns_ntt */
-#define ZKFHE_PROF_RNS_EPILOGUE 7   /* k_rns_epilogue */
+#define ZKFHE_PROF_RNS_EPILOGUE 7   /* k_rns_epilogue (every three-prime product of the BFV calls) */
 
 /* ---- BFV evaluation on the GPU: computing on verified ciphertexts (bfv_eval.hip) ----
  * The conventions above: host arrays, N uint64_t per polynomial in CircuitInput order, residues in [0, Q), batches n x N, the
@@ -565,7 +565,7 @@ int zkfhe_bfv_noise(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64
                     uint64_t *noise_out);
 /* zkfhe_prof_read slots of the BFV evaluation kernels */
 #define ZKFHE_PROF_BFV_TENSOR 8            /* k_bfv_tensor */
-#define ZKFHE_PROF_BFV_RELIN 9             /* k_bfv_relin */
+#define ZKFHE_PROF_BFV_RELIN 9             /* k_key_switch<false> (the relinearization) */
 #define ZKFHE_PROF_BFV_EVAL_EPILOGUE 10    /* k_eval_epilogue */
 #define ZKFHE_PROF_BFV_ELEMENTWISE 11      /* k_bfv_sum, k_bfv_add */
 
@@ -616,7 +616,7 @@ int zkfhe_bfv_decrypt_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, cons
 int zkfhe_bfv_decrypt_combine(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_parties, size_t n_cts, const uint64_t *c0,
                               const uint64_t *d, uint64_t *m_out);
 /* zkfhe_prof_read slots of the threshold kernels (algorithmic bytes: words read and written); the CRT epilogue of the share calls
- * (k_thr_epilogue) counts in ZKFHE_PROF_RNS_EPILOGUE */
+ * (k_rns_epilogue) counts in ZKFHE_PROF_RNS_EPILOGUE */
 #define ZKFHE_PROF_BFV_SHARE_SUM 12         /* k_bfv_share_sum */
 #define ZKFHE_PROF_BFV_DECRYPT_COMBINE 13   /* k_bfv_decrypt_combine */
 
@@ -671,9 +671,9 @@ int zkfhe_bfv_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n,
  * bit.  PARTY SEEDS ARE SECRET. */
 int zkfhe_bfv_galois_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, const uint8_t crs_seed[32],
                            const uint8_t party_seed[32], uint64_t g, int base_bits, uint64_t *r_out, uint64_t *a_out);
-/* zkfhe_prof_read slots of the slot and rotation kernels; the CRT epilogue of the key calls (k_gal_key_epilogue) counts in
+/* zkfhe_prof_read slots of the slot and rotation kernels; the CRT epilogue of the key calls (k_rns_epilogue) counts in
  * ZKFHE_PROF_RNS_EPILOGUE */
-#define ZKFHE_PROF_BFV_GALOIS 14     /* k_gal_switch, k_gal_epilogue */
+#define ZKFHE_PROF_BFV_GALOIS 14     /* k_key_switch<true>, k_eval_epilogue of the key switch */
 #define ZKFHE_PROF_BFV_SLOT_NTT 15   /* k_slot_ntt */
 
 const char *zkfhe_version(void);

@@ -436,6 +436,32 @@ class Context:
     # ------------------------------------------------------------------ BFV keygen / encrypt / decrypt (zkfhe.h, bfv_enc.hip)
     # Polynomials are uint64 arrays of N residues in [0, Q), CircuitInput order (highest degree first); params = (n, q, t, b).
 
+    def _bfv(self, fn, sig, params, *args):
+        """fn(ctx, &params, *args) for a BFV entry point; sig spells its remaining parameters, one letter each (_BFV_ARGS):
+        p a uint64 array, n size_t, s a 32-byte seed, u uint64, i int.  argtypes are assigned on every call."""
+        f = getattr(self.lib, fn)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC)] + [_BFV_ARGS[c] for c in sig]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(f(self.h, ctypes.byref(prm), *[a.ctypes.data_as(_U64P) if c == "p" else a for c, a in zip(sig, args)]))
+
+    @staticmethod
+    def _seed(seed, what, fresh=False):
+        if seed is None and not fresh:
+            raise ValueError("the %s is required" % what)
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the %s is 32 bytes" % what)
+        return seed
+
+    def _sk(self, params, sk):
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        if sk.size != int(params[0]):
+            raise ValueError("sk must hold N coefficients")
+        return sk
+
+    def _relin_rows(self, params, base_bits):
+        return bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else 0   # else the call refuses base_bits itself
+
     def poly_mul_ternary_negacyclic(self, a, s, q):
         """zkfhe_poly_mul_ternary_negacyclic on host arrays: a of shape (N,) (shared) or (n_polys, N), s of shape (n_polys, N) with
         coefficients in {0, 1, q - 1}; returns a * s mod (x^N + 1, q), shape (n_polys, N).  A non-ternary s raises ZkfheError."""
@@ -459,14 +485,9 @@ class Context:
     def bfv_fhe_keypair(self, params, seed=None):
         """zkfhe_bfv_fhe_keypair -> (sk, pk0, pk1).  seed: 32 secret bytes (None: os.urandom)."""
         n = int(params[0])
-        seed = os.urandom(32) if seed is None else bytes(seed)
-        if len(seed) != 32:
-            raise ValueError("the key-generation seed is 32 bytes")
+        seed = self._seed(seed, "key-generation seed", fresh=True)
         out = [np.empty(n, dtype=np.uint64) for _ in range(3)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_fhe_keypair.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_char_p, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_fhe_keypair(self.h, ctypes.byref(prm), seed, *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_fhe_keypair", "sppp", params, seed, *out)
         return tuple(out)
 
     def bfv_encrypt(self, params, pk0, pk1, m, seed=None, first_index=0):
@@ -478,17 +499,10 @@ class Context:
         m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1, n)
         if pk0.size != n or pk1.size != n:
             raise ValueError("pk0 / pk1 must hold N coefficients")
-        seed = os.urandom(32) if seed is None else bytes(seed)
-        if len(seed) != 32:
-            raise ValueError("the encryption seed is 32 bytes")
+        seed = self._seed(seed, "encryption seed", fresh=True)
         names = ("u", "e0", "e1", "c0", "c1")
         out = {k: np.empty(m.shape, dtype=np.uint64) for k in names}
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_encrypt.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, u64p, ctypes.c_size_t, u64p, ctypes.c_char_p,
-                                               ctypes.c_uint64] + [u64p] * 5
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_encrypt(self.h, ctypes.byref(prm), pk0.ctypes.data_as(u64p), pk1.ctypes.data_as(u64p), m.shape[0],
-                                               m.ctypes.data_as(u64p), seed, int(first_index), *[out[k].ctypes.data_as(u64p) for k in names]))
+        self._bfv("zkfhe_bfv_encrypt", "ppnpsuppppp", params, pk0, pk1, m.shape[0], m, seed, int(first_index), *[out[k] for k in names])
         return out
 
     def bfv_decrypt(self, params, sk, c0, c1):
@@ -500,11 +514,7 @@ class Context:
         if sk.size != n or c0.shape != c1.shape:
             raise ValueError("sk must hold N coefficients and c0, c1 the same shape")
         out = np.empty(c0.shape, dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_decrypt.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_size_t, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_decrypt(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c0.shape[0], c0.ctypes.data_as(u64p),
-                                               c1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        self._bfv("zkfhe_bfv_decrypt", "pnppp", params, sk, c0.shape[0], c0, c1, out)
         return out
 
     # ------------------------------------------------------------------ BFV evaluation (zkfhe.h, bfv_eval.hip)
@@ -529,34 +539,21 @@ class Context:
         """zkfhe_bfv_add: (a0 + b0, a1 + b1) mod Q, or a - b with subtract=True; every input (n, N)."""
         a0, a1, b0, b1 = self._eval_arrays(params, a0, a1, b0, b1)
         out = [np.empty(a0.shape, dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_add.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 4 + [ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_add(self.h, ctypes.byref(prm), a0.shape[0], *[x.ctypes.data_as(u64p) for x in (a0, a1, b0, b1)],
-                                           int(bool(subtract)), *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_add", "nppppipp", params, a0.shape[0], a0, a1, b0, b1, int(bool(subtract)), *out)
         return tuple(out)
 
     def bfv_sum(self, params, c0, c1):
         """zkfhe_bfv_sum: the sum of all n ciphertexts (c0, c1 of shape (n, N)) as one ciphertext (two arrays of N)."""
         c0, c1 = self._eval_arrays(params, c0, c1)
         out = [np.empty(c0.shape[1], dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_sum.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 4
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_sum(self.h, ctypes.byref(prm), c0.shape[0], c0.ctypes.data_as(u64p), c1.ctypes.data_as(u64p),
-                                           *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_sum", "npppp", params, c0.shape[0], c0, c1, *out)
         return tuple(out)
 
     def _plain_op(self, fn, params, c0, c1, m):
         c0, c1 = self._eval_arrays(params, c0, c1)
         m = self._plain(params, m, c0.shape[0])
         out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        f = getattr(self.lib, fn)
-        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, u64p, u64p, ctypes.c_size_t, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(f(self.h, ctypes.byref(prm), c0.shape[0], c0.ctypes.data_as(u64p), c1.ctypes.data_as(u64p), m.shape[0],
-                      m.ctypes.data_as(u64p), *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv(fn, "nppnppp", params, c0.shape[0], c0, c1, m.shape[0], m, *out)
         return tuple(out)
 
     def bfv_add_plain(self, params, c0, c1, m):
@@ -570,20 +567,10 @@ class Context:
     def bfv_relin_keygen(self, params, sk, seed=None, base_bits=16):
         """zkfhe_bfv_relin_keygen -> (rlk0, rlk1) of shape (l, N), l = bfv_relin_digits(params, base_bits).  seed: 32 SECRET bytes
         (None: os.urandom); the key itself is public."""
-        n = int(params[0])
-        sk = np.ascontiguousarray(sk, dtype=np.uint64)
-        if sk.size != n:
-            raise ValueError("sk must hold N coefficients")
-        seed = os.urandom(32) if seed is None else bytes(seed)
-        if len(seed) != 32:
-            raise ValueError("the relinearization-key seed is 32 bytes")
-        l = bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else 0   # else the call refuses base_bits itself
-        out = [np.empty((l, n), dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_relin_keygen.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_char_p, ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_relin_keygen(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), seed, int(base_bits),
-                                                    *[o.ctypes.data_as(u64p) for o in out]))
+        n, sk = int(params[0]), self._sk(params, sk)
+        seed = self._seed(seed, "relinearization-key seed", fresh=True)
+        out = [np.empty((self._relin_rows(params, base_bits), n), dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_relin_keygen", "psipp", params, sk, seed, int(base_bits), *out)
         return tuple(out)
 
     def bfv_mul(self, params, a0, a1, b0, b1, rlk0, rlk1, base_bits=16):
@@ -592,60 +579,31 @@ class Context:
         n = int(params[0])
         rlk0 = np.ascontiguousarray(rlk0, dtype=np.uint64)
         rlk1 = np.ascontiguousarray(rlk1, dtype=np.uint64)
-        l = bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else rlk0.shape[0]   # else the call refuses base_bits
+        l = self._relin_rows(params, base_bits) or rlk0.shape[0]   # else the call refuses base_bits
         if rlk0.shape != (l, n) or rlk1.shape != (l, n):
             raise ValueError("rlk0 and rlk1 must have shape (l, N) = (%d, %d) for base_bits %d" % (l, n, base_bits))
         out = [np.empty(a0.shape, dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_mul.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 6 + [ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_mul(self.h, ctypes.byref(prm), a0.shape[0], *[x.ctypes.data_as(u64p) for x in (a0, a1, b0, b1, rlk0, rlk1)],
-                                           int(base_bits), *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_mul", "nppppppipp", params, a0.shape[0], a0, a1, b0, b1, rlk0, rlk1, int(base_bits), *out)
         return tuple(out)
 
     def bfv_noise(self, params, sk, c0, c1):
         """zkfhe_bfv_noise: per ciphertext, max |[c0 + c1 s - floor(Q/T) m]_Q| with m the decryption; shape (n,)."""
-        n = int(params[0])
-        sk = np.ascontiguousarray(sk, dtype=np.uint64)
-        if sk.size != n:
-            raise ValueError("sk must hold N coefficients")
+        sk = self._sk(params, sk)
         c0, c1 = self._eval_arrays(params, c0, c1)
         out = np.empty(c0.shape[0], dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_noise.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_size_t, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_noise(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c0.shape[0], c0.ctypes.data_as(u64p),
-                                             c1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        self._bfv("zkfhe_bfv_noise", "pnppp", params, sk, c0.shape[0], c0, c1, out)
         return out
 
     # ------------------------------------------------------------------ threshold BFV (zkfhe.h, bfv_threshold.hip)
     # Party i holds sk_i; keys and shares are uint64 arrays of residues like the calls above.  Every seed is 32 SECRET bytes
     # (the CRS seed is public); a None share seed draws os.urandom(32).
 
-    @staticmethod
-    def _seed(seed, what, fresh=False):
-        if seed is None and not fresh:
-            raise ValueError("the %s is required" % what)
-        seed = os.urandom(32) if seed is None else bytes(seed)
-        if len(seed) != 32:
-            raise ValueError("the %s is 32 bytes" % what)
-        return seed
-
-    def _sk(self, params, sk):
-        sk = np.ascontiguousarray(sk, dtype=np.uint64)
-        if sk.size != int(params[0]):
-            raise ValueError("sk must hold N coefficients")
-        return sk
-
     def bfv_keygen_share(self, params, crs_seed, party_seed):
         """zkfhe_bfv_keygen_share -> (sk_i, pk0_share, pk1): pk0_share = -(a s_i + e_i), pk1 = a from the public crs_seed."""
         n = int(params[0])
         crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
         out = [np.empty(n, dtype=np.uint64) for _ in range(3)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_keygen_share.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_char_p, ctypes.c_char_p, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_keygen_share(self.h, ctypes.byref(prm), crs_seed, party_seed, *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_keygen_share", "ssppp", params, crs_seed, party_seed, *out)
         return tuple(out)
 
     def bfv_share_aggregate(self, params, shares):
@@ -656,28 +614,15 @@ class Context:
             raise ValueError("shares must have shape (P, N) or (P, n_polys, N)")
         s3 = shares.reshape(shares.shape[0], shares.shape[1] if shares.ndim == 3 else 1, n)   # P = 0 is refused by the call
         out = np.empty(s3.shape[1:], dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_share_aggregate.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, ctypes.c_size_t, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_share_aggregate(self.h, ctypes.byref(prm), s3.shape[0], s3.shape[1], s3.ctypes.data_as(u64p),
-                                                       out.ctypes.data_as(u64p)))
+        self._bfv("zkfhe_bfv_share_aggregate", "nnpp", params, s3.shape[0], s3.shape[1], s3, out)
         return out.reshape(shares.shape[1:])
-
-    def _relin_rows(self, params, base_bits):
-        return bfv_relin_digits(params, base_bits) if 1 <= int(base_bits) <= 32 else 0   # else the call refuses base_bits itself
 
     def bfv_relin_share1(self, params, sk, crs_seed, party_seed, base_bits=8):
         """zkfhe_bfv_relin_share1 -> (h0_i, h1_i) of shape (l, N): round 1 of the collective relinearization key."""
         n, sk = int(params[0]), self._sk(params, sk)
         crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
-        l = self._relin_rows(params, base_bits)
-        out = [np.empty((l, n), dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_relin_share1.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_char_p, ctypes.c_char_p,
-                                                    ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_relin_share1(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), crs_seed, party_seed, int(base_bits),
-                                                    *[o.ctypes.data_as(u64p) for o in out]))
+        out = [np.empty((self._relin_rows(params, base_bits), n), dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_relin_share1", "pssipp", params, sk, crs_seed, party_seed, int(base_bits), *out)
         return tuple(out)
 
     def bfv_relin_share2(self, params, sk, party_seed, h0, h1, base_bits=8):
@@ -691,11 +636,7 @@ class Context:
         if l and (h0.shape != (l, n) or h1.shape != (l, n)):
             raise ValueError("h0 and h1 must have shape (l, N) = (%d, %d) for base_bits %d" % (l, n, base_bits))
         out = np.empty((l, n), dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_relin_share2.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_char_p, ctypes.c_int, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_relin_share2(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), party_seed, int(base_bits),
-                                                    h0.ctypes.data_as(u64p), h1.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        self._bfv("zkfhe_bfv_relin_share2", "psippp", params, sk, party_seed, int(base_bits), h0, h1, out)
         return out
 
     def bfv_decrypt_share(self, params, sk, c1, seed=None, first_index=0, smudge_bound=0):
@@ -706,12 +647,7 @@ class Context:
         seed = self._seed(seed, "share seed", fresh=True)
         c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1, n)
         out = np.empty(c1.shape, dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_decrypt_share.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p, ctypes.c_size_t, u64p, ctypes.c_char_p,
-                                                     ctypes.c_uint64, ctypes.c_uint64, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_decrypt_share(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), c1.shape[0], c1.ctypes.data_as(u64p),
-                                                     seed, int(first_index), int(smudge_bound), out.ctypes.data_as(u64p)))
+        self._bfv("zkfhe_bfv_decrypt_share", "pnpsuup", params, sk, c1.shape[0], c1, seed, int(first_index), int(smudge_bound), out)
         return out
 
     def bfv_decrypt_combine(self, params, c0, shares):
@@ -724,11 +660,7 @@ class Context:
         if d.ndim != 3 or d.shape[1:] != c0.shape:
             raise ValueError("shares must have shape (P, n, N) for c0 of shape (n, N)")
         out = np.empty(c0.shape, dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_decrypt_combine.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, ctypes.c_size_t, u64p, u64p, u64p]
-        prm = BfvParamsC(*[int(x) for x in params])
-        self._check(self.lib.zkfhe_bfv_decrypt_combine(self.h, ctypes.byref(prm), d.shape[0], c0.shape[0], c0.ctypes.data_as(u64p),
-                                                       d.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        self._bfv("zkfhe_bfv_decrypt_combine", "nnppp", params, d.shape[0], c0.shape[0], c0, d, out)
         return out
 
     # ------------------------------------------------------------------ slots and rotations (zkfhe.h, bfv_galois.hip)
@@ -736,14 +668,9 @@ class Context:
     # bfv_slot_sum takes the keys of bfv_slot_sum_elements stacked as (log2(N), l, N).
 
     def _slots(self, fn, params, x):
-        n = int(params[0])
-        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, n)
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, int(params[0]))
         out = np.empty(x.shape, dtype=np.uint64)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        f = getattr(self.lib, fn)
-        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, u64p, u64p]
-        prm = BfvParamsC(*[int(v) for v in params])
-        self._check(f(self.h, ctypes.byref(prm), x.shape[0], x.ctypes.data_as(u64p), out.ctypes.data_as(u64p)))
+        self._bfv(fn, "npp", params, x.shape[0], x, out)
         return out
 
     def bfv_encode_slots(self, params, values):
@@ -754,29 +681,23 @@ class Context:
         """zkfhe_bfv_decode_slots: plaintexts of shape (N,) or (n, N) -> slot values in [0, T), shape (n, N)."""
         return self._slots("zkfhe_bfv_decode_slots", params, m)
 
-    def _galois_key(self, fn, params, sk, crs_seed, party_seed, g, base_bits):
+    def _galois_key(self, fn, params, sk, seeds, g, base_bits):
         n, sk = int(params[0]), self._sk(params, sk)
-        l = self._relin_rows(params, base_bits)
-        out = [np.empty((l, n), dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        f = getattr(self.lib, fn)
-        seeds = [crs_seed] if party_seed is None else [crs_seed, party_seed]
-        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), u64p] + [ctypes.c_char_p] * len(seeds) + [ctypes.c_uint64, ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(v) for v in params])
-        self._check(f(self.h, ctypes.byref(prm), sk.ctypes.data_as(u64p), *seeds, int(g), int(base_bits), *[o.ctypes.data_as(u64p) for o in out]))
+        out = [np.empty((self._relin_rows(params, base_bits), n), dtype=np.uint64) for _ in range(2)]
+        self._bfv(fn, "p" + "s" * len(seeds) + "uipp", params, sk, *seeds, int(g), int(base_bits), *out)
         return tuple(out)
 
     def bfv_galois_keygen(self, params, sk, g, seed=None, base_bits=16):
         """zkfhe_bfv_galois_keygen -> (gk0, gk1) of shape (l, N): the Galois key of sk for the element g.  seed: 32 SECRET bytes
         (None: os.urandom); the key itself is public."""
         seed = self._seed(seed, "Galois-key seed", fresh=True)
-        return self._galois_key("zkfhe_bfv_galois_keygen", params, sk, seed, None, g, base_bits)
+        return self._galois_key("zkfhe_bfv_galois_keygen", params, sk, [seed], g, base_bits)
 
     def bfv_galois_share(self, params, sk, crs_seed, party_seed, g, base_bits=8):
         """zkfhe_bfv_galois_share -> (r_i, a) of shape (l, N): party i's share of the collective Galois key for g; gk0 =
         bfv_share_aggregate of the r_i, gk1 = a."""
         crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
-        return self._galois_key("zkfhe_bfv_galois_share", params, sk, crs_seed, party_seed, g, base_bits)
+        return self._galois_key("zkfhe_bfv_galois_share", params, sk, [crs_seed, party_seed], g, base_bits)
 
     def _galois_keys(self, params, gk0, gk1, base_bits, lead):
         n = int(params[0])
@@ -792,13 +713,7 @@ class Context:
         c0, c1 = self._eval_arrays(params, c0, c1)
         gk0, gk1 = self._galois_keys(params, gk0, gk1, base_bits, ())
         out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_apply_galois.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, u64p, u64p, ctypes.c_uint64,
-                                                    u64p, u64p, ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(v) for v in params])
-        self._check(self.lib.zkfhe_bfv_apply_galois(self.h, ctypes.byref(prm), c0.shape[0], c0.ctypes.data_as(u64p), c1.ctypes.data_as(u64p),
-                                                    int(g), gk0.ctypes.data_as(u64p), gk1.ctypes.data_as(u64p), int(base_bits),
-                                                    *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_apply_galois", "nppuppipp", params, c0.shape[0], c0, c1, int(g), gk0, gk1, int(base_bits), *out)
         return tuple(out)
 
     def bfv_slot_sum(self, params, c0, c1, gk0, gk1, base_bits=16):
@@ -807,81 +722,66 @@ class Context:
         c0, c1 = self._eval_arrays(params, c0, c1)
         gk0, gk1 = self._galois_keys(params, gk0, gk1, base_bits, (int(params[0]).bit_length() - 1,))
         out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        self.lib.zkfhe_bfv_slot_sum.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t] + [u64p] * 4 + [ctypes.c_int, u64p, u64p]
-        prm = BfvParamsC(*[int(v) for v in params])
-        self._check(self.lib.zkfhe_bfv_slot_sum(self.h, ctypes.byref(prm), c0.shape[0], *[x.ctypes.data_as(u64p) for x in (c0, c1, gk0, gk1)],
-                                                int(base_bits), *[o.ctypes.data_as(u64p) for o in out]))
+        self._bfv("zkfhe_bfv_slot_sum", "nppppipp", params, c0.shape[0], c0, c1, gk0, gk1, int(base_bits), *out)
         return tuple(out)
+
+
+_U64P = ctypes.POINTER(ctypes.c_uint64)
+# the parameter letters of Context._bfv
+_BFV_ARGS = {"p": _U64P, "n": ctypes.c_size_t, "s": ctypes.c_char_p, "u": ctypes.c_uint64, "i": ctypes.c_int}
+
+
+def _host_bfv(fn, argtypes, params, *args):
+    """fn(&params, *args) for a host-only BFV function; raises ZkfheError with the library's message on failure"""
+    lib = load_library()
+    f = getattr(lib, fn)
+    f.argtypes = [ctypes.POINTER(BfvParamsC)] + argtypes
+    rc = f(ctypes.byref(BfvParamsC(*[int(x) for x in params])), *args)
+    if rc != 0:
+        raise ZkfheError("%s failed (%d): %s" % (fn, rc, lib.zkfhe_last_error(None).decode()))
+
+
+def _host_bfv_list(fn, params):
+    """the count-then-fill host functions: fn(&params, NULL, &count), then fn(&params, out, &count) into a uint64 array"""
+    argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    cnt = ctypes.c_size_t()
+    _host_bfv(fn, argtypes, params, None, ctypes.byref(cnt))
+    out = np.empty(cnt.value, dtype=np.uint64)
+    _host_bfv(fn, argtypes, params, out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt))
+    return out
 
 
 def bfv_relin_digits(params, base_bits):
     """zkfhe_bfv_relin_digits (host only): l = ceil(bitlen(Q - 1) / base_bits), the rows of a relinearization key."""
-    lib = load_library()
-    lib.zkfhe_bfv_relin_digits.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
-    prm = BfvParamsC(*[int(x) for x in params])
     l = ctypes.c_size_t()
-    rc = lib.zkfhe_bfv_relin_digits(ctypes.byref(prm), int(base_bits), ctypes.byref(l))
-    if rc != 0:
-        raise ZkfheError("zkfhe_bfv_relin_digits failed (%d): %s" % (rc, lib.zkfhe_last_error(None).decode()))
+    _host_bfv("zkfhe_bfv_relin_digits", [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)], params, int(base_bits), ctypes.byref(l))
     return l.value
-
-
-def _host_fail(lib, fn, rc):
-    raise ZkfheError("%s failed (%d): %s" % (fn, rc, lib.zkfhe_last_error(None).decode()))
 
 
 def bfv_slot_count(params):
     """zkfhe_bfv_slot_count (host only): N when T is a batching modulus (prime, below 2^31, 2N | T - 1); raises otherwise."""
-    lib = load_library()
-    lib.zkfhe_bfv_slot_count.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.POINTER(ctypes.c_size_t)]
-    prm = BfvParamsC(*[int(x) for x in params])
     slots = ctypes.c_size_t()
-    rc = lib.zkfhe_bfv_slot_count(ctypes.byref(prm), ctypes.byref(slots))
-    if rc != 0:
-        _host_fail(lib, "zkfhe_bfv_slot_count", rc)
+    _host_bfv("zkfhe_bfv_slot_count", [ctypes.POINTER(ctypes.c_size_t)], params, ctypes.byref(slots))
     return slots.value
 
 
 def bfv_galois_element(params, steps=0, swap_rows=False):
     """zkfhe_bfv_galois_element (host only): g = 5^(steps mod N/2) mod 2N (a rotation of both rows left by steps), times 2N - 1 if
     swap_rows."""
-    lib = load_library()
-    lib.zkfhe_bfv_galois_element.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-    prm = BfvParamsC(*[int(x) for x in params])
     g = ctypes.c_uint64()
-    rc = lib.zkfhe_bfv_galois_element(ctypes.byref(prm), int(steps), int(bool(swap_rows)), ctypes.byref(g))
-    if rc != 0:
-        _host_fail(lib, "zkfhe_bfv_galois_element", rc)
+    _host_bfv("zkfhe_bfv_galois_element", [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)], params, int(steps),
+              int(bool(swap_rows)), ctypes.byref(g))
     return g.value
 
 
 def bfv_slot_sum_elements(params):
     """zkfhe_bfv_slot_sum_elements (host only): the log2(N) Galois elements of bfv_slot_sum in order, a list of ints."""
-    lib = load_library()
-    lib.zkfhe_bfv_slot_sum_elements.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
-    prm = BfvParamsC(*[int(x) for x in params])
-    cnt = ctypes.c_size_t()
-    rc = lib.zkfhe_bfv_slot_sum_elements(ctypes.byref(prm), None, ctypes.byref(cnt))
-    if rc != 0:
-        _host_fail(lib, "zkfhe_bfv_slot_sum_elements", rc)
-    out = np.empty(cnt.value, dtype=np.uint64)
-    lib.zkfhe_bfv_slot_sum_elements(ctypes.byref(prm), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt))
-    return [int(x) for x in out]
+    return [int(x) for x in _host_bfv_list("zkfhe_bfv_slot_sum_elements", params)]
 
 
 def bfv_error_cdt(params):
     """zkfhe_bfv_error_cdt (host only): the 2 B thresholds of the error sampler as a uint64 array."""
-    lib = load_library()
-    lib.zkfhe_bfv_error_cdt.argtypes = [ctypes.POINTER(BfvParamsC), ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
-    prm = BfvParamsC(*[int(x) for x in params])
-    cnt = ctypes.c_size_t()
-    rc = lib.zkfhe_bfv_error_cdt(ctypes.byref(prm), None, ctypes.byref(cnt))
-    if rc != 0:
-        raise ZkfheError("zkfhe_bfv_error_cdt failed (%d): %s" % (rc, lib.zkfhe_last_error(None).decode()))
-    out = np.empty(cnt.value, dtype=np.uint64)
-    lib.zkfhe_bfv_error_cdt(ctypes.byref(prm), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(cnt))
-    return out
+    return _host_bfv_list("zkfhe_bfv_error_cdt", params)
 
 
 def version():

@@ -7,11 +7,14 @@
 // workgroup runs the whole negacyclic transform in LDS (k_rns_ntt of rns_ntt.hip.hpp: N <= 2^15 words = 128 KiB), the shared
 // operand of a batch (pk0, pk1, a, or sk) is transformed once, and one fused epilogue (k_rns_epilogue) rebuilds c by Garner's CRT,
 // reduces it mod Q, adds delta m + e (or rounds to T for decryption) and writes each output coefficient once.  Q itself need not
-// be NTT-friendly.
+// be NTT-friendly.  k_rns_epilogue serves every three-prime product of the BFV files (its modes: EpiMode of rns_ntt.hip.hpp).
 //
 // Randomness (zkfhe.h): ChaCha20 keyed by the caller's 32-byte seed, state words 12..15 = {block, domain, index_lo, index_hi},
 // word w of a stream = the w-th little-endian u64 of its keystream, array position p reads word p (uniform: words 2p, 2p + 1).
 // The samplers are branch-free and address nothing by a secret value (k_bfv_sample).
+//
+// Also the host helpers that rns_ntt.hip.hpp declares for every BFV file: the parameter and range checks, the error table and the
+// work arena.
 #include <cmath>
 #include <mutex>
 
@@ -23,21 +26,13 @@ namespace {
 
 constexpr int NP = 3;   // the first three primes of rns_ntt.hip.hpp: product 2^89.2
 constexpr int MAX_CDT = 2046;   // 2 B thresholds, B < 1024
-enum EpiMode { EPI_PLAIN = 0, EPI_ADD = 1, EPI_NEG_ADD = 2, EPI_DECRYPT = 3 };
-struct Epi {
-  int mode;
-  const uint64_t *m;    // EPI_ADD: delta m (may be null)
-  const uint64_t *e;    // EPI_ADD / EPI_NEG_ADD: + e
-  const uint64_t *c0;   // EPI_DECRYPT: + c0 before rounding
-  uint64_t delta, t;
-};
 
 struct ChaKey {
   uint32_t k[8];
 };
 
-// One thread per output coefficient: CRT of the three residues to the centred integer, mod Q, then the mode's additions; writes
-// out[poly][N-1-d] (CircuitInput order).  m, e, c0 are read at the same position.
+// One thread per output coefficient of res ([poly][prime][degree], total = n_polys N): CRT of the three residues to the centred
+// integer, mod Q, then the mode's additions (EpiMode); out and every addend in CircuitInput order, read and written at pos.
 __global__ __launch_bounds__(256) void k_rns_epilogue(const uint32_t *__restrict__ res, size_t total, int log_n, uint64_t q, CrtConst cc,
                                                       Epi epi, uint64_t *__restrict__ out) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -45,18 +40,21 @@ __global__ __launch_bounds__(256) void k_rns_epilogue(const uint32_t *__restrict
   const size_t n = (size_t)1 << log_n, poly = g >> log_n, d = g & (n - 1), pos = poly * n + (n - 1 - d);
   uint64_t v = crt3_mod_q(res + poly * NP * n + d, n, q, cc);   // c mod Q
   if (epi.mode == EPI_ADD) {
-    if (epi.m) {   // m in [0, T/2] or [Q - T/2, Q): delta |m| <= Q / 2, no reduction needed
-      const uint64_t mv = epi.m[pos];
-      const bool mneg = mv > q / 2;
-      const uint64_t dm = epi.delta * (mneg ? q - mv : mv);
-      v = add_q(v, mneg && dm ? q - dm : dm, q);
-    }
-    v = add_q(v, epi.e[pos], q);
+    if (epi.m) v = add_delta_m(v, epi.m[pos], epi.delta, q);
+    if (epi.a) v = sub_q(add_q(v, epi.a[pos], q), epi.b[pos], q);
+    if (epi.e) v = add_q(v, epi.e[pos], q);
   } else if (epi.mode == EPI_NEG_ADD) {
     v = add_q(v, epi.e[pos], q);
     v = v ? q - v : 0;
   } else if (epi.mode == EPI_DECRYPT) {
     v = decrypt_round(add_q(v, epi.c0[pos], q), q, epi.t);   // round(T x / Q) mod T, x = [c0 + c1 s]_Q centred
+  } else if (epi.mode == EPI_SHARE) {
+    v = sub_q(add_q(v, epi.e[pos], q), epi.bound, q);   // r <= 2E < Q
+  } else if (epi.mode == EPI_GADGET) {
+    // row j: j w <= (l - 1) w < bitlen(Q - 1), so 2^(j w) < Q
+    const uint64_t x = v ? q - v : 0, e = epi.e[pos];
+    v = epi.neg_e ? sub_q(x, e, q) : add_q(x, e, q);
+    v = add_q(v, gadget_select(auto_coeff(epi.s, (unsigned)d, epi.ginv, (unsigned)n, q), (uint64_t)1 << (poly * epi.w), q), q);
   }
   out[pos] = v;
 }
@@ -81,8 +79,6 @@ __device__ __forceinline__ void chacha20(const ChaKey &key, uint32_t w12, uint32
 #pragma unroll
   for (int i = 0; i < 16; ++i) o[i] += s[i];
 }
-
-enum SampleKind { S_TERNARY = 0, S_UNIFORM = 1, S_ERROR = 2 };
 
 // One thread per ChaCha20 block of one polynomial (8 words: 8 ternary / error samples, or 4 uniform ones).  Polynomial j of the
 // launch uses index0 + j.  Branch-free samplers: ternary ((w * 3) >> 64) - 1; uniform (x * Q) >> 128 of x = w[2p] + 2^64 w[2p+1];
@@ -133,6 +129,19 @@ __global__ __launch_bounds__(256) void k_bfv_sample(ChaKey key, uint32_t domain,
 
 // ------------------------------------------------------------------------------------------------------------------ host side
 
+bool ring_ok(uint64_t n, uint64_t q) { return n >= 8 && n <= NMAX && !(n & (n - 1)) && q >= 2 && !(q >> 63); }
+
+ChaKey cha_key(const uint8_t seed[32]) {
+  ChaKey k;
+  for (int i = 0; i < 8; ++i)
+    k.k[i] = (uint32_t)seed[4 * i] | (uint32_t)seed[4 * i + 1] << 8 | (uint32_t)seed[4 * i + 2] << 16 | (uint32_t)seed[4 * i + 3] << 24;
+  return k;
+}
+
+}  // namespace
+
+namespace zkrns {
+
 int work_arena(zkfhe_ctx *ctx, size_t bytes, char **out) {
   if (ctx->bfv_work_sz < bytes) {
     if (ctx->bfv_work) {
@@ -148,32 +157,6 @@ int work_arena(zkfhe_ctx *ctx, size_t bytes, char **out) {
   return ZKFHE_OK;
 }
 
-int launch_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, bool ternary, uint64_t q, size_t n_polys, int log_n, const uint32_t *hat,
-               size_t hat_stride, uint32_t *out, int *flag) {
-  return launch_rns_ntt<NP>(ctx, mul, src, ternary ? LOAD_TERNARY : LOAD_RESIDUE, q, n_polys, log_n, hat, hat_stride, out, flag);
-}
-
-int launch_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const Epi &epi, uint64_t *out) {
-  const size_t total = n_polys << log_n;
-  zk_prof_begin(ctx);
-  k_rns_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt3_const(), epi, out);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ZKFHE_PROF_RNS_EPILOGUE, (double)total * (12 + 8 + (epi.m ? 8 : 0) + (epi.e || epi.c0 ? 8 : 0)));
-  return ZKFHE_OK;
-}
-
-int launch_sample(zkfhe_ctx *ctx, const ChaKey &key, uint32_t domain, uint64_t index0, int kind, size_t n_polys, int log_n, uint64_t q,
-                  const uint64_t *cdt_dev, int n_cdt, uint64_t *out) {
-  const size_t n = (size_t)1 << log_n, threads = n_polys * (kind == S_UNIFORM ? n / 4 : n / 8);
-  zk_prof_begin(ctx);
-  k_bfv_sample<<<zk_blocks(threads, 256), 256, 0, ctx->stream>>>(key, domain, index0, kind, n_polys, log_n, q, cdt_dev, n_cdt, out);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ZKFHE_PROF_BFV_SAMPLE, (double)n_polys * n * 8);
-  return ZKFHE_OK;
-}
-
-bool ring_ok(uint64_t n, uint64_t q) { return n >= 8 && n <= NMAX && !(n & (n - 1)) && q >= 2 && !(q >> 63); }
-
 int check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm) {
   if (!prm) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv params: NULL");
   if (prm->n < 8 || prm->n > NMAX || (prm->n & (prm->n - 1)))
@@ -181,6 +164,32 @@ int check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm) {
   if (prm->q < 2 || (prm->q >> 63)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv params: Q must satisfy 2 <= Q < 2^63");
   if (prm->t < 2 || prm->t >= prm->q) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv params: T must satisfy 2 <= T < Q");
   if (prm->b < 1 || prm->b >= prm->q || prm->b >= 1024) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv params: B must satisfy 1 <= B < min(Q, 1024)");
+  return ZKFHE_OK;
+}
+
+int check_below_q(zkfhe_ctx *ctx, const uint64_t *v, size_t count, uint64_t q, const char *fn, const char *what, const uint64_t *v2) {
+  bool bad = false;   // without an exit per word; two arrays in one pass read faster than one after the other
+  if (v2)
+    for (size_t i = 0; i < count; ++i) bad |= (v[i] >= q) | (v2[i] >= q);
+  else
+    for (size_t i = 0; i < count; ++i) bad |= v[i] >= q;
+  if (bad) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": " + what + " coefficient is not below Q");
+  return ZKFHE_OK;
+}
+
+int check_plain(zkfhe_ctx *ctx, const uint64_t *m, size_t count, uint64_t q, uint64_t t, const char *fn, const char *what) {
+  const uint64_t half = t / 2;
+  bool bad = false;   // without a branch per word: plaintext signs are random
+  for (size_t i = 0; i < count; ++i) bad |= (m[i] > half) & ((m[i] >= q) | (m[i] < q - half));
+  if (bad) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": " + what + " coefficient is outside [0, T/2] and [Q - T/2, Q - 1]");
+  return ZKFHE_OK;
+}
+
+int relin_rows(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, int base_bits, const char *fn, int *l) {
+  if (base_bits < 1 || base_bits > 32) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": base_bits must be in [1, 32]");
+  int bits = 0;
+  while (bits < 64 && ((prm->q - 1) >> bits)) ++bits;   // bitlen(Q - 1)
+  *l = (bits + base_bits - 1) / base_bits;
   return ZKFHE_OK;
 }
 
@@ -202,14 +211,11 @@ void error_cdt(uint64_t b, uint64_t *t) {
   }
 }
 
-ChaKey cha_key(const uint8_t seed[32]) {
-  ChaKey k;
-  for (int i = 0; i < 8; ++i)
-    k.k[i] = (uint32_t)seed[4 * i] | (uint32_t)seed[4 * i + 1] << 8 | (uint32_t)seed[4 * i + 2] << 16 | (uint32_t)seed[4 * i + 3] << 24;
-  return k;
+int upload_error_cdt(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, uint64_t *cdt_d) {
+  std::vector<uint64_t> cdt(2 * prm->b);
+  error_cdt(prm->b, cdt.data());
+  return zkfhe_upload(ctx, cdt_d, cdt.data(), cdt.size() * 8);
 }
-
-}  // namespace
 
 // [prime][fwd | inv][NMAX] for all NP_MAX primes (the three-prime kernels read the first three): psi^br15(k) and psi^-br15(k) in
 // Montgomery form, psi of order 2 NMAX.  The first N entries are the tables of every N <= NMAX (bit reversal in 15 bits of k < N =
@@ -244,13 +250,28 @@ int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out) {
   return ZKFHE_OK;
 }
 
-int zk_bfv_check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm) { return check_params(ctx, prm); }
-int zk_bfv_work_arena(zkfhe_ctx *ctx, size_t bytes, char **out) { return work_arena(ctx, bytes, out); }
-void zk_bfv_error_cdt(uint64_t b, uint64_t *t) { error_cdt(b, t); }
-int zk_bfv_sample(zkfhe_ctx *ctx, const uint8_t seed[32], uint32_t domain, uint64_t index0, int kind, size_t n_polys, int log_n, uint64_t q,
-                  const uint64_t *cdt_dev, int n_cdt, uint64_t *out) {
-  return launch_sample(ctx, cha_key(seed), domain, index0, kind, n_polys, log_n, q, cdt_dev, n_cdt, out);
+
+int zk_bfv_sample(zkfhe_ctx *ctx, const uint8_t seed[32], Domain domain, uint64_t index0, SampleKind kind, size_t n_polys, int log_n,
+                  uint64_t q, const uint64_t *cdt_dev, int n_cdt, uint64_t *out) {
+  const size_t n = (size_t)1 << log_n, threads = n_polys * (kind == S_UNIFORM ? n / 4 : n / 8);
+  zk_prof_begin(ctx);
+  k_bfv_sample<<<zk_blocks(threads, 256), 256, 0, ctx->stream>>>(cha_key(seed), domain, index0, kind, n_polys, log_n, q, cdt_dev, n_cdt, out);
+  ZK_LAUNCH_CHECK(ctx);
+  zk_prof_end(ctx, ZKFHE_PROF_BFV_SAMPLE, (double)n_polys * n * 8);
+  return ZKFHE_OK;
 }
+
+int zk_bfv_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const Epi &epi, uint64_t *out) {
+  const size_t total = n_polys << log_n;
+  zk_prof_begin(ctx);
+  k_rns_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt3_const(), epi, out);
+  ZK_LAUNCH_CHECK(ctx);
+  const int addends = !!epi.m + !!epi.e + !!epi.c0 + !!epi.s;
+  zk_prof_end(ctx, ZKFHE_PROF_RNS_EPILOGUE, (double)total * (12 + 8 + 8 * addends + (epi.a ? 16 : 0)));
+  return ZKFHE_OK;
+}
+
+}  // namespace zkrns
 
 extern "C" {
 
@@ -261,20 +282,18 @@ int zkfhe_poly_mul_ternary_negacyclic(zkfhe_ctx *ctx, const uint64_t *a_dev, siz
   if (!ring_ok(n, q)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "poly_mul_ternary: N must be a power of two in [8, 32768] and 2 <= Q < 2^63");
   *not_ternary = 0;
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_polys, chunk_polys(n)), plane = (size_t)NP * n * 4;
-  char *w;
-  ZK_CK(work_arena(ctx, 256 + align256(chunk * plane) * 2, &w));
-  int *flag = (int *)w;
-  uint32_t *hat = (uint32_t *)(w + 256), *res = (uint32_t *)(w + 256 + align256(chunk * plane));
+  const size_t chunk = std::min<size_t>(n_polys, chunk_polys(n));
+  int *flag;
+  uint32_t *hat, *res;
+  ZK_CK(Arena().add(flag, 1).add(hat, chunk * NP * n).add(res, chunk * NP * n).carve(ctx));
   ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
   const bool shared = a_count == 1;
-  if (shared) ZK_CK(launch_ntt(ctx, false, a_dev, false, q, 1, log_n, nullptr, 0, hat, flag));
-  Epi epi{EPI_PLAIN, nullptr, nullptr, nullptr, 0, 0};
+  if (shared) ZK_CK(launch_rns_ntt<NP>(ctx, false, a_dev, LOAD_RESIDUE, q, 1, log_n, nullptr, 0, hat, flag));
   for (size_t lo = 0; lo < n_polys; lo += chunk) {
     const size_t c = std::min(chunk, n_polys - lo);
-    if (!shared) ZK_CK(launch_ntt(ctx, false, a_dev + lo * n, false, q, c, log_n, nullptr, 0, hat, flag));
-    ZK_CK(launch_ntt(ctx, true, s_dev + lo * n, true, q, c, log_n, hat, shared ? 0 : (size_t)NP * n, res, flag));
-    ZK_CK(launch_epilogue(ctx, res, c, log_n, q, epi, out_dev + lo * n));
+    if (!shared) ZK_CK(launch_rns_ntt<NP>(ctx, false, a_dev + lo * n, LOAD_RESIDUE, q, c, log_n, nullptr, 0, hat, flag));
+    ZK_CK(launch_rns_ntt<NP>(ctx, true, s_dev + lo * n, LOAD_TERNARY, q, c, log_n, hat, shared ? 0 : (size_t)NP * n, res, flag));
+    ZK_CK(zk_bfv_epilogue(ctx, res, c, log_n, q, Epi{}, out_dev + lo * n));
   }
   int bad = 0;
   ZK_CK(zkfhe_download(ctx, &bad, flag, 4));
@@ -293,36 +312,12 @@ int zkfhe_bfv_error_cdt(const zkfhe_bfv_params *params, uint64_t *thresholds, si
   return ZKFHE_OK;
 }
 
+// the key share of one party that is also the CRS (zkfhe.h: identical bits when crs_seed == party_seed)
 int zkfhe_bfv_fhe_keypair(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint8_t seed[32], uint64_t *sk_out, uint64_t *pk0_out,
                           uint64_t *pk1_out) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && seed && sk_out && pk0_out && pk1_out);
-  ZK_CK(check_params(ctx, params));
-  const uint64_t n = params->n, q = params->q;
-  const int log_n = bit_log2(n), n_cdt = (int)(2 * params->b);
-  std::vector<uint64_t> cdt(n_cdt);
-  error_cdt(params->b, cdt.data());
-  const size_t vec = align256(n * 8);
-  char *w;
-  ZK_CK(work_arena(ctx, 256 + 4 * vec + align256(n_cdt * 8) + 2 * align256((size_t)NP * n * 4), &w));
-  int *flag = (int *)w;
-  uint64_t *s = (uint64_t *)(w + 256), *a = (uint64_t *)((char *)s + vec), *e = (uint64_t *)((char *)a + vec), *pk0 = (uint64_t *)((char *)e + vec);
-  uint64_t *cdt_dev = (uint64_t *)((char *)pk0 + vec);
-  uint32_t *hat = (uint32_t *)((char *)cdt_dev + align256(n_cdt * 8)), *res = (uint32_t *)((char *)hat + align256((size_t)NP * n * 4));
-  ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
-  ZK_CK(zkfhe_upload(ctx, cdt_dev, cdt.data(), n_cdt * 8));
-  const ChaKey key = cha_key(seed);
-  ZK_CK(launch_sample(ctx, key, 4, 0, S_TERNARY, 1, log_n, q, nullptr, 0, s));
-  ZK_CK(launch_sample(ctx, key, 5, 0, S_UNIFORM, 1, log_n, q, nullptr, 0, a));
-  ZK_CK(launch_sample(ctx, key, 6, 0, S_ERROR, 1, log_n, q, cdt_dev, n_cdt, e));
-  ZK_CK(launch_ntt(ctx, false, a, false, q, 1, log_n, nullptr, 0, hat, flag));
-  ZK_CK(launch_ntt(ctx, true, s, true, q, 1, log_n, hat, 0, res, flag));
-  Epi epi{EPI_NEG_ADD, nullptr, e, nullptr, 0, 0};
-  ZK_CK(launch_epilogue(ctx, res, 1, log_n, q, epi, pk0));
-  ZK_CK(zkfhe_download(ctx, sk_out, s, n * 8));
-  ZK_CK(zkfhe_download(ctx, pk1_out, a, n * 8));
-  ZK_CK(zkfhe_download(ctx, pk0_out, pk0, n * 8));
-  return ZKFHE_OK;
+  return zkfhe_bfv_keygen_share(ctx, params, seed, seed, sk_out, pk0_out, pk1_out);
 }
 
 int zkfhe_bfv_encrypt(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *pk0, const uint64_t *pk1, size_t n_msgs, const uint64_t *m,
@@ -332,44 +327,33 @@ int zkfhe_bfv_encrypt(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint
   ZK_ARG(ctx, ctx && pk0 && pk1 && m && seed && u_out && e0_out && e1_out && c0_out && c1_out && n_msgs > 0);
   ZK_CK(check_params(ctx, params));
   const uint64_t n = params->n, q = params->q, t = params->t;
-  for (uint64_t i = 0; i < n; ++i)
-    if (pk0[i] >= q || pk1[i] >= q) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_encrypt: a public-key coefficient is not below Q");
-  for (size_t i = 0; i < n_msgs * n; ++i)
-    if (m[i] > t / 2 && (m[i] >= q || m[i] < q - t / 2))
-      return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_encrypt: a message coefficient is outside [0, T/2] and [Q - T/2, Q - 1]");
+  ZK_CK(check_below_q(ctx, pk0, n, q, "bfv_encrypt", "a public-key", pk1));
+  ZK_CK(check_plain(ctx, m, n_msgs * n, q, t, "bfv_encrypt", "a message"));
   const int log_n = bit_log2(n), n_cdt = (int)(2 * params->b);
-  std::vector<uint64_t> cdt(n_cdt);
-  error_cdt(params->b, cdt.data());
-  const size_t chunk = std::min<size_t>(n_msgs, chunk_polys(n)), vec = align256(n * 8), cvec = align256(chunk * n * 8), plane = (size_t)NP * n * 4;
-  char *w;
-  ZK_CK(work_arena(ctx, 256 + 2 * vec + align256(n_cdt * 8) + 2 * align256(plane) + 6 * cvec + align256(chunk * plane), &w));
-  int *flag = (int *)w;
-  char *at = w + 256;
-  auto take = [&](size_t bytes) { char *r = at; at += bytes; return r; };
-  uint64_t *pk0_d = (uint64_t *)take(vec), *pk1_d = (uint64_t *)take(vec), *cdt_dev = (uint64_t *)take(align256(n_cdt * 8));
-  uint32_t *hat0 = (uint32_t *)take(align256(plane)), *hat1 = (uint32_t *)take(align256(plane));
-  uint64_t *m_d = (uint64_t *)take(cvec), *u_d = (uint64_t *)take(cvec), *e0_d = (uint64_t *)take(cvec), *e1_d = (uint64_t *)take(cvec);
-  uint64_t *c0_d = (uint64_t *)take(cvec), *c1_d = (uint64_t *)take(cvec);
-  uint32_t *res = (uint32_t *)take(align256(chunk * plane));
+  const size_t chunk = std::min<size_t>(n_msgs, chunk_polys(n)), cw = chunk * n;
+  int *flag;
+  uint64_t *pk0_d, *pk1_d, *cdt_d, *m_d, *u_d, *e0_d, *e1_d, *c0_d, *c1_d;
+  uint32_t *hat0, *hat1, *res;
+  ZK_CK(Arena().add(flag, 1).add(pk0_d, n).add(pk1_d, n).add(cdt_d, n_cdt).add(hat0, NP * n).add(hat1, NP * n).add(m_d, cw).add(u_d, cw)
+            .add(e0_d, cw).add(e1_d, cw).add(c0_d, cw).add(c1_d, cw).add(res, cw * NP).carve(ctx));
   ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
-  ZK_CK(zkfhe_upload(ctx, cdt_dev, cdt.data(), n_cdt * 8));
+  ZK_CK(upload_error_cdt(ctx, params, cdt_d));
   ZK_CK(zkfhe_upload(ctx, pk0_d, pk0, n * 8));
   ZK_CK(zkfhe_upload(ctx, pk1_d, pk1, n * 8));
-  ZK_CK(launch_ntt(ctx, false, pk0_d, false, q, 1, log_n, nullptr, 0, hat0, flag));
-  ZK_CK(launch_ntt(ctx, false, pk1_d, false, q, 1, log_n, nullptr, 0, hat1, flag));
-  const ChaKey key = cha_key(seed);
+  ZK_CK(launch_rns_ntt<NP>(ctx, false, pk0_d, LOAD_RESIDUE, q, 1, log_n, nullptr, 0, hat0, flag));
+  ZK_CK(launch_rns_ntt<NP>(ctx, false, pk1_d, LOAD_RESIDUE, q, 1, log_n, nullptr, 0, hat1, flag));
   const uint64_t delta = q / t;
   for (size_t lo = 0; lo < n_msgs; lo += chunk) {
     const size_t c = std::min(chunk, n_msgs - lo), bytes = c * n * 8;
     const uint64_t index0 = first_index + lo;
     ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, bytes));
-    ZK_CK(launch_sample(ctx, key, 1, index0, S_TERNARY, c, log_n, q, nullptr, 0, u_d));
-    ZK_CK(launch_sample(ctx, key, 2, index0, S_ERROR, c, log_n, q, cdt_dev, n_cdt, e0_d));
-    ZK_CK(launch_sample(ctx, key, 3, index0, S_ERROR, c, log_n, q, cdt_dev, n_cdt, e1_d));
-    ZK_CK(launch_ntt(ctx, true, u_d, true, q, c, log_n, hat0, 0, res, flag));
-    ZK_CK(launch_epilogue(ctx, res, c, log_n, q, Epi{EPI_ADD, m_d, e0_d, nullptr, delta, t}, c0_d));
-    ZK_CK(launch_ntt(ctx, true, u_d, true, q, c, log_n, hat1, 0, res, flag));
-    ZK_CK(launch_epilogue(ctx, res, c, log_n, q, Epi{EPI_ADD, nullptr, e1_d, nullptr, delta, t}, c1_d));
+    ZK_CK(zk_bfv_sample(ctx, seed, DOM_ENC_U, index0, S_TERNARY, c, log_n, q, nullptr, 0, u_d));
+    ZK_CK(zk_bfv_sample(ctx, seed, DOM_ENC_E0, index0, S_ERROR, c, log_n, q, cdt_d, n_cdt, e0_d));
+    ZK_CK(zk_bfv_sample(ctx, seed, DOM_ENC_E1, index0, S_ERROR, c, log_n, q, cdt_d, n_cdt, e1_d));
+    ZK_CK(launch_rns_ntt<NP>(ctx, true, u_d, LOAD_TERNARY, q, c, log_n, hat0, 0, res, flag));
+    ZK_CK(zk_bfv_epilogue(ctx, res, c, log_n, q, Epi{.mode = EPI_ADD, .m = m_d, .e = e0_d, .delta = delta}, c0_d));
+    ZK_CK(launch_rns_ntt<NP>(ctx, true, u_d, LOAD_TERNARY, q, c, log_n, hat1, 0, res, flag));
+    ZK_CK(zk_bfv_epilogue(ctx, res, c, log_n, q, Epi{.mode = EPI_ADD, .e = e1_d}, c1_d));
     ZK_CK(zkfhe_download(ctx, u_out + lo * n, u_d, bytes));
     ZK_CK(zkfhe_download(ctx, e0_out + lo * n, e0_d, bytes));
     ZK_CK(zkfhe_download(ctx, e1_out + lo * n, e1_d, bytes));
@@ -385,29 +369,20 @@ int zkfhe_bfv_decrypt(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint
   ZK_ARG(ctx, ctx && sk && c0 && c1 && m_out && n_msgs > 0);
   ZK_CK(check_params(ctx, params));
   const uint64_t n = params->n, q = params->q;
-  for (size_t i = 0; i < n_msgs * n; ++i)
-    if (c0[i] >= q || c1[i] >= q) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_decrypt: a ciphertext coefficient is not below Q");
+  ZK_CK(check_below_q(ctx, c0, n_msgs * n, q, "bfv_decrypt", "a ciphertext", c1));
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_msgs, chunk_polys(n)), vec = align256(n * 8), cvec = align256(chunk * n * 8), plane = (size_t)NP * n * 4;
-  char *w;
-  ZK_CK(work_arena(ctx, 256 + vec + align256(plane) + 3 * cvec + align256(chunk * plane), &w));
-  int *flag = (int *)w;
-  uint64_t *sk_d = (uint64_t *)(w + 256);
-  uint32_t *hat = (uint32_t *)((char *)sk_d + vec);
-  uint64_t *c0_d = (uint64_t *)((char *)hat + align256(plane)), *c1_d = (uint64_t *)((char *)c0_d + cvec), *m_d = (uint64_t *)((char *)c1_d + cvec);
-  uint32_t *res = (uint32_t *)((char *)m_d + cvec);
-  ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
-  ZK_CK(zkfhe_upload(ctx, sk_d, sk, n * 8));
-  ZK_CK(launch_ntt(ctx, false, sk_d, true, q, 1, log_n, nullptr, 0, hat, flag));
-  int bad = 0;
-  ZK_CK(zkfhe_download(ctx, &bad, flag, 4));
-  if (bad) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_decrypt: a secret-key coefficient is not in {0, 1, Q - 1}");
+  const size_t chunk = std::min<size_t>(n_msgs, chunk_polys(n)), cw = chunk * n;
+  int *flag;
+  uint64_t *sk_d, *c0_d, *c1_d, *m_d;
+  uint32_t *hat, *res;
+  ZK_CK(Arena().add(flag, 1).add(sk_d, n).add(hat, NP * n).add(c0_d, cw).add(c1_d, cw).add(m_d, cw).add(res, cw * NP).carve(ctx));
+  ZK_CK(secret_hat<NP>(ctx, sk, n, q, sk_d, hat, flag, "bfv_decrypt"));
   for (size_t lo = 0; lo < n_msgs; lo += chunk) {
     const size_t c = std::min(chunk, n_msgs - lo), bytes = c * n * 8;
     ZK_CK(zkfhe_upload(ctx, c0_d, c0 + lo * n, bytes));
     ZK_CK(zkfhe_upload(ctx, c1_d, c1 + lo * n, bytes));
-    ZK_CK(launch_ntt(ctx, true, c1_d, false, q, c, log_n, hat, 0, res, flag));
-    ZK_CK(launch_epilogue(ctx, res, c, log_n, q, Epi{EPI_DECRYPT, nullptr, nullptr, c0_d, 0, params->t}, m_d));
+    ZK_CK(launch_rns_ntt<NP>(ctx, true, c1_d, LOAD_RESIDUE, q, c, log_n, hat, 0, res, flag));
+    ZK_CK(zk_bfv_epilogue(ctx, res, c, log_n, q, Epi{.mode = EPI_DECRYPT, .c0 = c0_d, .t = params->t}, m_d));
     ZK_CK(zkfhe_download(ctx, m_out + lo * n, m_d, bytes));
   }
   return ZKFHE_OK;

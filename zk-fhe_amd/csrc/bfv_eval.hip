@@ -7,10 +7,12 @@
 //   1. k_rns_ntt: forward transforms of a0, a1, b0, b1 (centred), one workgroup per (polynomial, prime);
 //   2. k_bfv_tensor: x0 = a0 b0, x1 = a0 b1 + a1 b0, x2 = a1 b1 pointwise, one inverse transform each;
 //   3. k_eval_epilogue (EV_ROUND): Garner into three u64 limbs, centre, c^_j = floor((2 T x_j + Q) / 2Q) mod Q;
-//   4. k_bfv_relin: per (pair, prime), every digit d_i = (c^2 >> i w) & (2^w - 1) is loaded, transformed, multiplied by the
-//      transformed rlk0_i and rlk1_i and accumulated pointwise; one inverse transform per component (sum < l N 2^w Q < 2^114);
+//   4. k_key_switch<false> (the relinearization): per (pair, prime), every digit d_i = (c^2 >> i w) & (2^w - 1) is loaded,
+//      transformed, multiplied by the transformed rlk0_i and rlk1_i and accumulated pointwise; one inverse transform per component
+//      (sum < l N 2^w Q < 2^114);
 //   5. k_eval_epilogue (EV_ADD): out_j = c^_j + sum mod Q.
 // The relinearization key is transformed once per call.  No step branches on or addresses by a coefficient's value.
+// k_eval_epilogue and k_key_switch also serve the Galois key switch of bfv_galois.hip (EV_GALOIS, k_key_switch<true>).
 #include <cstring>
 
 #include "rns_ntt.hip.hpp"
@@ -22,21 +24,8 @@ namespace {
 constexpr int NP = NP_MAX;
 typedef unsigned __int128 u128;
 
-enum EvMode { EV_MODQ = 0, EV_ROUND = 1, EV_ADD = 2, EV_RLK = 3, EV_NOISE = 4 };
-struct EvEpi {
-  int mode;
-  const uint64_t *add;   // EV_ADD: + add[pos]; EV_RLK: - e[pos]; EV_NOISE: + c0[pos]
-  const uint64_t *s2;    // EV_RLK: s^2, one polynomial
-  uint64_t t, delta;
-  int w;                 // EV_RLK: the digit width; polynomial i gets 2^(i w) s^2
-  unsigned long long *noise;   // EV_NOISE: the maximum per polynomial (zeroed before the launch)
-};
-
-__device__ __forceinline__ uint64_t sub_q(uint64_t a, uint64_t b, uint64_t q) { return a >= b ? a - b : a + q - b; }
-
 // One thread per output coefficient of res ([poly][prime][degree], total = n_polys N): the centred integer x of its residues, then
-// EV_MODQ x mod Q; EV_ROUND floor((2 T x + Q) / 2Q) mod Q; EV_ADD x + add mod Q; EV_RLK 2^(i w) s^2 - x - e mod Q for polynomial i;
-// EV_NOISE |[c0 + x - delta m]_Q| with m = the decryption of [c0 + x]_Q, maximised per polynomial.  out: CircuitInput order.
+// the mode's result (EvMode).  out: CircuitInput order.
 __global__ __launch_bounds__(256) void k_eval_epilogue(const uint32_t *__restrict__ res, size_t total, int log_n, uint64_t q, Crt5 cc,
                                                        EvEpi epi, uint64_t *__restrict__ out) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,23 +52,21 @@ __global__ __launch_bounds__(256) void k_eval_epilogue(const uint32_t *__restric
     out[pos] = neg && r ? q - r : r;
     return;
   }
-  const uint64_t rm = mod128(mod128(m[2], m[1], q), m[0], q);
-  uint64_t v = neg && rm ? q - rm : rm;   // x mod Q
+  uint64_t v = crt5_mod_q(m, neg, q);   // x mod Q
   if (epi.mode == EV_ADD) {
     v = add_q(v, epi.add[pos], q);
   } else if (epi.mode == EV_RLK) {
-    const u128 k = (u128)epi.s2[n - 1 - d] << (poly * epi.w);   // i w <= 62, s^2 < 2^63
+    const u128 k = (u128)epi.poly[n - 1 - d] << (poly * epi.w);   // i w <= 62, s^2 < 2^63
     v = sub_q(mod128((uint64_t)(k >> 64), (uint64_t)k, q), add_q(v, epi.add[pos], q), q);
   } else if (epi.mode == EV_NOISE) {
     v = add_q(v, epi.add[pos], q);   // [c0 + c1 s]_Q
-    const u128 num = (u128)(2 * epi.t) * v + q;
-    uint64_t dm = div128((uint64_t)(num >> 64), (uint64_t)num, 2 * q);   // as EPI_DECRYPT of bfv_enc.hip: in [0, T]
-    dm = dm == epi.t ? 0 : dm;
-    dm = dm > epi.t / 2 ? q - (epi.t - dm) : dm;   // m as a residue
-    const u128 prod = (u128)epi.delta * dm;
+    const u128 prod = (u128)epi.delta * decrypt_round(v, q, epi.t);   // delta m, m as a residue
     const uint64_t x = sub_q(v, mod128((uint64_t)(prod >> 64), (uint64_t)prod, q), q);
     atomicMax(epi.noise + poly, (unsigned long long)(x > q / 2 ? q - x : x));
     return;
+  } else if (epi.mode == EV_GALOIS) {
+    if (poly < epi.c) v = add_q(v, auto_coeff(epi.poly + poly * n, (unsigned)d, epi.ginv, (unsigned)n, q), q);
+    if (epi.add) v = add_q(v, epi.add[pos], q);
   }
   out[pos] = v;
 }
@@ -112,13 +99,15 @@ __global__ __launch_bounds__(NTT_THREADS) void k_bfv_tensor(const uint32_t *__re
   for (unsigned d = tid; d < n; d += NTT_THREADS) o[d] = mont_mul(lds[d], rc.scale[j], p, pinv);
 }
 
-// One workgroup per (pair, prime), blockIdx.x = k * NP + prime.  For every digit i < l, d_i = (c2 >> i w) & (2^w - 1) of pair k
-// (c2: [c][N], CircuitInput order) is loaded, transformed and multiplied by the transforms of rlk0_i and rlk1_i (rlk_hat: [2 l][NP][N],
-// the rlk0_i then the rlk1_i); the products are summed in acc[0][k][prime] and acc[1][k][prime] (each thread owns its positions),
-// which are then transformed back in place.
-__global__ __launch_bounds__(NTT_THREADS) void k_bfv_relin(const uint64_t *__restrict__ c2, int l, int w, const uint32_t *__restrict__ rlk_hat,
-                                                           size_t c, int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc,
-                                                           uint32_t *__restrict__ acc) {
+// One workgroup per (polynomial, prime), blockIdx.x = k * NP + prime: the key switch of polynomial k of src ([c][N], CircuitInput
+// order).  For every digit i < l, d_i = (v >> i w) & (2^w - 1) of v = src (GALOIS = false: the relinearization of c^2) or
+// v = sigma_g(src) (GALOIS = true, ginv = g^-1 mod 2N) is loaded, transformed and multiplied by the transforms of key0_i and key1_i
+// (key_hat: [2 l][NP][N], the key0_i then the key1_i); the products are summed in acc[0][k][prime] and acc[1][k][prime] (each
+// thread owns its positions), which are then transformed back in place.
+template <bool GALOIS>
+__global__ __launch_bounds__(NTT_THREADS) void k_key_switch(const uint64_t *__restrict__ src, int l, int w, const uint32_t *__restrict__ key_hat,
+                                                            size_t c, int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc,
+                                                            uint32_t *__restrict__ acc, unsigned ginv, uint64_t q) {
   extern __shared__ uint32_t lds[];
   const unsigned j = blockIdx.x % NP;
   const size_t k = blockIdx.x / NP;
@@ -127,13 +116,16 @@ __global__ __launch_bounds__(NTT_THREADS) void k_bfv_relin(const uint64_t *__res
   const size_t plane = (size_t)NP * n;
   const uint32_t *fw = tw + (size_t)j * 2 * NMAX, *iv = fw + NMAX;
   uint32_t *acc0 = acc + k * plane + (size_t)j * n, *acc1 = acc0 + c * plane;
-  const uint64_t *s = c2 + k * n, mask = ((uint64_t)1 << w) - 1;
+  const uint64_t *s = src + k * n, mask = ((uint64_t)1 << w) - 1;
   for (int i = 0; i < l; ++i) {
     const int shift = i * w;   // < bitlen(Q - 1) <= 63
-    for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = (uint32_t)(((s[n - 1 - d] >> shift) & mask) % p);
+    for (unsigned d = tid; d < n; d += NTT_THREADS) {
+      const uint64_t v = GALOIS ? auto_coeff(s, d, ginv, n, q) : s[n - 1 - d];
+      lds[d] = (uint32_t)(((v >> shift) & mask) % p);
+    }
     __syncthreads();
     rns_forward(lds, fw, log_n, p, pinv);
-    const uint32_t *r0 = rlk_hat + (size_t)i * plane + (size_t)j * n, *r1 = rlk_hat + (size_t)(l + i) * plane + (size_t)j * n;
+    const uint32_t *r0 = key_hat + (size_t)i * plane + (size_t)j * n, *r1 = key_hat + (size_t)(l + i) * plane + (size_t)j * n;
     for (unsigned d = tid; d < n; d += NTT_THREADS) {
       const uint32_t x = lds[d], u0 = mont_mul(x, r0[d], p, pinv), u1 = mont_mul(x, r1[d], p, pinv);
       acc0[d] = i ? add_p(acc0[d], u0, p) : u0;
@@ -176,45 +168,20 @@ __global__ __launch_bounds__(256) void k_bfv_add(const uint64_t *__restrict__ a,
     out[g] = subtract ? sub_q(v, b[g], q) : add_q(v, b[g], q);
     return;
   }
-  // m in [0, T/2] or [Q - T/2, Q): delta |m| <= Q / 2, no reduction needed (EPI_ADD of bfv_enc.hip)
-  const uint64_t mv = m[m_shared ? (g & (((size_t)1 << log_n) - 1)) : g];
-  const bool mneg = mv > q / 2;
-  const uint64_t dm = delta * (mneg ? q - mv : mv);
-  out[g] = add_q(v, mneg && dm ? q - dm : dm, q);
+  out[g] = add_delta_m(v, m[m_shared ? (g & (((size_t)1 << log_n) - 1)) : g], delta, q);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
 
-int launch_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out) {
-  const size_t total = n_polys << log_n;
-  zk_prof_begin(ctx);
-  k_eval_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt5_const(), epi, out);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ZKFHE_PROF_BFV_EVAL_EPILOGUE, (double)total * (NP * 4 + 8 + (epi.add ? 8 : 0)));
-  return ZKFHE_OK;
-}
-
 int launch_tensor(zkfhe_ctx *ctx, const uint32_t *hat, size_t c, int log_n, uint32_t *out) {
   const uint32_t *tw;
   ZK_CK(zk_rns_tables(ctx, &tw));
-  const int lds = 4 << log_n;
-  if (lds > 64 * 1024) ZK_CK(zk_func_max_lds(ctx, (const void *)k_bfv_tensor, 4 << LOG_NMAX));
+  int lds;
+  ZK_CK(ntt_lds(ctx, (const void *)k_bfv_tensor, log_n, &lds));
   zk_prof_begin(ctx);
   k_bfv_tensor<<<(unsigned)(3 * c * NP), NTT_THREADS, lds, ctx->stream>>>(hat, c, log_n, tw, rns_const<NP>(log_n), out);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_TENSOR, (double)c * NP * (16.0 + 12.0) * ((size_t)1 << log_n));
-  return ZKFHE_OK;
-}
-
-int launch_relin(zkfhe_ctx *ctx, const uint64_t *c2, int l, int w, const uint32_t *rlk_hat, size_t c, int log_n, uint32_t *acc) {
-  const uint32_t *tw;
-  ZK_CK(zk_rns_tables(ctx, &tw));
-  const int lds = 4 << log_n;
-  if (lds > 64 * 1024) ZK_CK(zk_func_max_lds(ctx, (const void *)k_bfv_relin, 4 << LOG_NMAX));
-  zk_prof_begin(ctx);
-  k_bfv_relin<<<(unsigned)(c * NP), NTT_THREADS, lds, ctx->stream>>>(c2, l, w, rlk_hat, c, log_n, tw, rns_const<NP>(log_n), acc);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ZKFHE_PROF_BFV_RELIN, (double)c * NP * (l * (8.0 + 8.0 + 16.0) + 16.0) * ((size_t)1 << log_n));
   return ZKFHE_OK;
 }
 
@@ -227,42 +194,39 @@ int launch_add(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtrac
   return ZKFHE_OK;
 }
 
-int relin_digits(uint64_t q, int w) {
-  int bits = 0;
-  while (bits < 64 && ((q - 1) >> bits)) ++bits;   // bitlen(Q - 1)
-  return (bits + w - 1) / w;
-}
-
-int check_below_q(zkfhe_ctx *ctx, const uint64_t *v, size_t count, uint64_t q, const char *what) {
-  for (size_t i = 0; i < count; ++i)
-    if (v[i] >= q) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(what) + " coefficient is not below Q");
-  return ZKFHE_OK;
-}
-
-int check_plain(zkfhe_ctx *ctx, const uint64_t *m, size_t count, uint64_t q, uint64_t t, const char *fn) {
-  for (size_t i = 0; i < count; ++i)
-    if (m[i] > t / 2 && (m[i] >= q || m[i] < q - t / 2))
-      return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": a plaintext coefficient is outside [0, T/2] and [Q - T/2, Q - 1]");
-  return ZKFHE_OK;
-}
-
-// the secret key, transformed with the five primes into hat (NP planes); refuses a non-ternary key
-int secret_hat(zkfhe_ctx *ctx, const uint64_t *sk, uint64_t n, uint64_t q, uint64_t *sk_d, uint32_t *hat, int *flag, const char *fn) {
-  ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
-  ZK_CK(zkfhe_upload(ctx, sk_d, sk, n * 8));
-  ZK_CK(launch_rns_ntt<NP>(ctx, false, sk_d, LOAD_TERNARY, q, 1, bit_log2(n), nullptr, 0, hat, flag));
-  int bad = 0;
-  ZK_CK(zkfhe_download(ctx, &bad, flag, 4));
-  if (bad) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": a secret-key coefficient is not in {0, 1, Q - 1}");
-  return ZKFHE_OK;
-}
-
-int check_base_bits(zkfhe_ctx *ctx, int base_bits, const char *fn) {
-  if (base_bits < 1 || base_bits > 32) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": base_bits must be in [1, 32]");
-  return ZKFHE_OK;
-}
-
 }  // namespace
+
+namespace zkrns {
+
+int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out) {
+  const size_t total = n_polys << log_n;
+  zk_prof_begin(ctx);
+  k_eval_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt5_const(), epi, out);
+  ZK_LAUNCH_CHECK(ctx);
+  double bytes = (double)total * (NP * 4 + 8 + (epi.add ? 8 : 0));
+  if (epi.mode == EV_GALOIS) bytes += (double)(epi.c << log_n) * 8;   // sigma_g(c0)
+  zk_prof_end(ctx, epi.mode == EV_GALOIS ? ZKFHE_PROF_BFV_GALOIS : ZKFHE_PROF_BFV_EVAL_EPILOGUE, bytes);
+  return ZKFHE_OK;
+}
+
+int zk_bfv_key_switch(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64_t q, int l, int w, const uint32_t *key_hat, size_t c,
+                      int log_n, uint32_t *acc) {
+  const uint32_t *tw;
+  ZK_CK(zk_rns_tables(ctx, &tw));
+  int lds;
+  ZK_CK(ntt_lds(ctx, ginv ? (const void *)k_key_switch<true> : (const void *)k_key_switch<false>, log_n, &lds));
+  const RnsConst<NP> rc = rns_const<NP>(log_n);
+  zk_prof_begin(ctx);
+  if (ginv)
+    k_key_switch<true><<<(unsigned)(c * NP), NTT_THREADS, lds, ctx->stream>>>(src, l, w, key_hat, c, log_n, tw, rc, acc, ginv, q);
+  else
+    k_key_switch<false><<<(unsigned)(c * NP), NTT_THREADS, lds, ctx->stream>>>(src, l, w, key_hat, c, log_n, tw, rc, acc, 0, q);
+  ZK_LAUNCH_CHECK(ctx);
+  zk_prof_end(ctx, ginv ? ZKFHE_PROF_BFV_GALOIS : ZKFHE_PROF_BFV_RELIN, (double)c * NP * (l * (8.0 + 8.0 + 16.0) + 16.0) * ((size_t)1 << log_n));
+  return ZKFHE_OK;
+}
+
+}  // namespace zkrns
 
 extern "C" {
 
@@ -270,14 +234,14 @@ int zkfhe_bfv_add(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, 
                   const uint64_t *b1, int subtract, uint64_t *out0, uint64_t *out1) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && a0 && a1 && b0 && b1 && out0 && out1 && n_cts > 0);
-  ZK_CK(zk_bfv_check_params(ctx, params));
+  ZK_CK(check_params(ctx, params));
   const uint64_t n = params->n, q = params->q;
-  for (const uint64_t *v : {a0, a1, b0, b1}) ZK_CK(check_below_q(ctx, v, n_cts * n, q, "bfv_add: a ciphertext"));
+  ZK_CK(check_below_q(ctx, a0, n_cts * n, q, "bfv_add", "a ciphertext", a1));
+  ZK_CK(check_below_q(ctx, b0, n_cts * n, q, "bfv_add", "a ciphertext", b1));
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cvec = align256(chunk * n * 8);
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, 3 * cvec, &w));
-  uint64_t *a_d = (uint64_t *)w, *b_d = (uint64_t *)(w + cvec), *o_d = (uint64_t *)(w + 2 * cvec);
+  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
+  uint64_t *a_d, *b_d, *o_d;
+  ZK_CK(Arena().add(a_d, cw).add(b_d, cw).add(o_d, cw).carve(ctx));
   for (int comp = 0; comp < 2; ++comp) {
     const uint64_t *a = comp ? a1 : a0, *b = comp ? b1 : b0;
     uint64_t *out = comp ? out1 : out0;
@@ -296,15 +260,13 @@ int zkfhe_bfv_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, 
                   uint64_t *out1) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && c0 && c1 && out0 && out1 && n_cts > 0);
-  ZK_CK(zk_bfv_check_params(ctx, params));
+  ZK_CK(check_params(ctx, params));
   const uint64_t n = params->n, q = params->q;
-  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_sum: a ciphertext"));
-  ZK_CK(check_below_q(ctx, c1, n_cts * n, q, "bfv_sum: a ciphertext"));
+  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_sum", "a ciphertext", c1));
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cvec = align256(chunk * n * 8);
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, align256(2 * n * 8) + 2 * cvec, &w));
-  uint64_t *acc = (uint64_t *)w, *src = (uint64_t *)(w + align256(2 * n * 8));
+  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n));
+  uint64_t *acc, *src;
+  ZK_CK(Arena().add(acc, 2 * n).add(src, 2 * chunk * n).carve(ctx));
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
     ZK_CK(zkfhe_upload(ctx, src, c0 + lo * n, bytes));
@@ -323,17 +285,15 @@ int zkfhe_bfv_add_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
                         const uint64_t *m, uint64_t *out0, uint64_t *out1) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && c0 && c1 && m && out0 && out1 && n_cts > 0);
-  ZK_CK(zk_bfv_check_params(ctx, params));
+  ZK_CK(check_params(ctx, params));
   if (m_count != 1 && m_count != n_cts) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_add_plain: m_count must be 1 or the ciphertext count");
   const uint64_t n = params->n, q = params->q;
-  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_add_plain: a ciphertext"));
-  ZK_CK(check_below_q(ctx, c1, n_cts * n, q, "bfv_add_plain: a ciphertext"));
+  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_add_plain", "a ciphertext", c1));
   ZK_CK(check_plain(ctx, m, m_count * n, q, params->t, "bfv_add_plain"));
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cvec = align256(chunk * n * 8);
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, 3 * cvec, &w));
-  uint64_t *c_d = (uint64_t *)w, *m_d = (uint64_t *)(w + cvec), *o_d = (uint64_t *)(w + 2 * cvec);
+  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
+  uint64_t *c_d, *m_d, *o_d;
+  ZK_CK(Arena().add(c_d, cw).add(m_d, cw).add(o_d, cw).carve(ctx));
   const bool shared = m_count == 1;
   if (shared) ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
@@ -351,25 +311,22 @@ int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
                         const uint64_t *m, uint64_t *out0, uint64_t *out1) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && c0 && c1 && m && out0 && out1 && n_cts > 0);
-  ZK_CK(zk_bfv_check_params(ctx, params));
+  ZK_CK(check_params(ctx, params));
   if (m_count != 1 && m_count != n_cts) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_mul_plain: m_count must be 1 or the ciphertext count");
   const uint64_t n = params->n, q = params->q;
-  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_mul_plain: a ciphertext"));
-  ZK_CK(check_below_q(ctx, c1, n_cts * n, q, "bfv_mul_plain: a ciphertext"));
+  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_mul_plain", "a ciphertext", c1));
   ZK_CK(check_plain(ctx, m, m_count * n, q, params->t, "bfv_mul_plain"));
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cvec = align256(chunk * n * 8), cplane = align256(chunk * NP * n * 4);
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, 256 + 3 * cvec + 2 * cplane, &w));
-  int *flag = (int *)w;
-  uint64_t *c_d = (uint64_t *)(w + 256), *m_d = (uint64_t *)((char *)c_d + cvec), *o_d = (uint64_t *)((char *)m_d + cvec);
-  uint32_t *hat = (uint32_t *)((char *)o_d + cvec), *res = (uint32_t *)((char *)hat + cplane);
+  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
+  int *flag;
+  uint64_t *c_d, *m_d, *o_d;
+  uint32_t *hat, *res;
+  ZK_CK(Arena().add(flag, 1).add(c_d, cw).add(m_d, cw).add(o_d, cw).add(hat, cw * NP).add(res, cw * NP).carve(ctx));
   const bool shared = m_count == 1;
   if (shared) {
     ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
     ZK_CK(launch_rns_ntt<NP>(ctx, false, m_d, LOAD_CENTRED, q, 1, log_n, nullptr, 0, hat, flag));
   }
-  const EvEpi epi{EV_MODQ, nullptr, nullptr, 0, 0, 0, nullptr};
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
     if (!shared) {
@@ -379,7 +336,7 @@ int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
     for (int comp = 0; comp < 2; ++comp) {
       ZK_CK(zkfhe_upload(ctx, c_d, (comp ? c1 : c0) + lo * n, bytes));
       ZK_CK(launch_rns_ntt<NP>(ctx, true, c_d, LOAD_CENTRED, q, c, log_n, hat, shared ? 0 : (size_t)NP * n, res, flag));
-      ZK_CK(launch_eval_epilogue(ctx, res, c, log_n, q, epi, o_d));
+      ZK_CK(zk_bfv_eval_epilogue(ctx, res, c, log_n, q, EvEpi{}, o_d));
       ZK_CK(zkfhe_download(ctx, (comp ? out1 : out0) + lo * n, o_d, bytes));
     }
   }
@@ -388,9 +345,10 @@ int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
 
 int zkfhe_bfv_relin_digits(const zkfhe_bfv_params *params, int base_bits, size_t *l) {
   if (!l) return zk_fail_msg(nullptr, ZKFHE_EINVAL, "bfv_relin_digits: l is NULL");
-  ZK_CK(zk_bfv_check_params(nullptr, params));
-  ZK_CK(check_base_bits(nullptr, base_bits, "bfv_relin_digits"));
-  *l = (size_t)relin_digits(params->q, base_bits);
+  ZK_CK(check_params(nullptr, params));
+  int rows = 0;
+  ZK_CK(relin_rows(nullptr, params, base_bits, "bfv_relin_digits", &rows));
+  *l = (size_t)rows;
   return ZKFHE_OK;
 }
 
@@ -398,32 +356,28 @@ int zkfhe_bfv_relin_keygen(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const
                            uint64_t *rlk0_out, uint64_t *rlk1_out) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && sk && seed && rlk0_out && rlk1_out);
-  ZK_CK(zk_bfv_check_params(ctx, params));
-  ZK_CK(check_base_bits(ctx, base_bits, "bfv_relin_keygen"));
+  ZK_CK(check_params(ctx, params));
+  int l = 0;
+  ZK_CK(relin_rows(ctx, params, base_bits, "bfv_relin_keygen", &l));
   const uint64_t n = params->n, q = params->q;
-  const int log_n = bit_log2(n), l = relin_digits(q, base_bits), n_cdt = (int)(2 * params->b);
-  std::vector<uint64_t> cdt(n_cdt);
-  zk_bfv_error_cdt(params->b, cdt.data());
-  const size_t vec = align256(n * 8), lvec = align256(l * n * 8), plane = align256((size_t)NP * n * 4);
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, 256 + 2 * vec + 3 * lvec + align256(n_cdt * 8) + plane + align256((size_t)l * NP * n * 4), &w));
-  int *flag = (int *)w;
-  char *at = w + 256;
-  auto take = [&](size_t bytes) { char *r = at; at += bytes; return r; };
-  uint64_t *s_d = (uint64_t *)take(vec), *s2_d = (uint64_t *)take(vec), *a_d = (uint64_t *)take(lvec), *e_d = (uint64_t *)take(lvec);
-  uint64_t *r0_d = (uint64_t *)take(lvec), *cdt_d = (uint64_t *)take(align256(n_cdt * 8));
-  uint32_t *hat = (uint32_t *)take(plane), *res = (uint32_t *)take(align256((size_t)l * NP * n * 4));
-  ZK_CK(secret_hat(ctx, sk, n, q, s_d, hat, flag, "bfv_relin_keygen"));
-  ZK_CK(zkfhe_upload(ctx, cdt_d, cdt.data(), n_cdt * 8));
+  const int log_n = bit_log2(n), n_cdt = (int)(2 * params->b);
+  const size_t lw = (size_t)l * n;
+  int *flag;
+  uint64_t *s_d, *s2_d, *a_d, *e_d, *r0_d, *cdt_d;
+  uint32_t *hat, *res;
+  ZK_CK(Arena().add(flag, 1).add(s_d, n).add(s2_d, n).add(a_d, lw).add(e_d, lw).add(r0_d, lw).add(cdt_d, n_cdt).add(hat, NP * n)
+            .add(res, lw * NP).carve(ctx));
+  ZK_CK(secret_hat<NP>(ctx, sk, n, q, s_d, hat, flag, "bfv_relin_keygen"));
+  ZK_CK(upload_error_cdt(ctx, params, cdt_d));
   // s^2 mod Q: the product of s (read as ternary) with its own transform
   ZK_CK(launch_rns_ntt<NP>(ctx, true, s_d, LOAD_TERNARY, q, 1, log_n, hat, 0, res, flag));
-  ZK_CK(launch_eval_epilogue(ctx, res, 1, log_n, q, EvEpi{EV_MODQ, nullptr, nullptr, 0, 0, 0, nullptr}, s2_d));
-  ZK_CK(zk_bfv_sample(ctx, seed, 7, 0, 1, l, log_n, q, nullptr, 0, a_d));         // a_i: uniform, domain 7, index i
-  ZK_CK(zk_bfv_sample(ctx, seed, 8, 0, 2, l, log_n, q, cdt_d, n_cdt, e_d));      // e_i: error, domain 8, index i
+  ZK_CK(zk_bfv_eval_epilogue(ctx, res, 1, log_n, q, EvEpi{}, s2_d));
+  ZK_CK(zk_bfv_sample(ctx, seed, DOM_RLK_A, 0, S_UNIFORM, l, log_n, q, nullptr, 0, a_d));    // a_i, index i
+  ZK_CK(zk_bfv_sample(ctx, seed, DOM_RLK_E, 0, S_ERROR, l, log_n, q, cdt_d, n_cdt, e_d));   // e_i, index i
   ZK_CK(launch_rns_ntt<NP>(ctx, true, a_d, LOAD_RESIDUE, q, l, log_n, hat, 0, res, flag));
-  ZK_CK(launch_eval_epilogue(ctx, res, l, log_n, q, EvEpi{EV_RLK, e_d, s2_d, 0, 0, base_bits, nullptr}, r0_d));
-  ZK_CK(zkfhe_download(ctx, rlk0_out, r0_d, (size_t)l * n * 8));
-  ZK_CK(zkfhe_download(ctx, rlk1_out, a_d, (size_t)l * n * 8));
+  ZK_CK(zk_bfv_eval_epilogue(ctx, res, l, log_n, q, EvEpi{.mode = EV_RLK, .add = e_d, .poly = s2_d, .w = base_bits}, r0_d));
+  ZK_CK(zkfhe_download(ctx, rlk0_out, r0_d, lw * 8));
+  ZK_CK(zkfhe_download(ctx, rlk1_out, a_d, lw * 8));
   return ZKFHE_OK;
 }
 
@@ -431,27 +385,23 @@ int zkfhe_bfv_mul(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_pairs
                   const uint64_t *b1, const uint64_t *rlk0, const uint64_t *rlk1, int base_bits, uint64_t *out0, uint64_t *out1) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && a0 && a1 && b0 && b1 && rlk0 && rlk1 && out0 && out1 && n_pairs > 0);
-  ZK_CK(zk_bfv_check_params(ctx, params));
-  ZK_CK(check_base_bits(ctx, base_bits, "bfv_mul"));
+  ZK_CK(check_params(ctx, params));
+  int l = 0;
+  ZK_CK(relin_rows(ctx, params, base_bits, "bfv_mul", &l));
   const uint64_t n = params->n, q = params->q;
-  const int log_n = bit_log2(n), l = relin_digits(q, base_bits);
-  for (const uint64_t *v : {a0, a1, b0, b1}) ZK_CK(check_below_q(ctx, v, n_pairs * n, q, "bfv_mul: a ciphertext"));
-  ZK_CK(check_below_q(ctx, rlk0, (size_t)l * n, q, "bfv_mul: a relinearization-key"));
-  ZK_CK(check_below_q(ctx, rlk1, (size_t)l * n, q, "bfv_mul: a relinearization-key"));
-  const size_t chunk = std::min<size_t>(n_pairs, chunk_polys(n)), plane = (size_t)NP * n * 4;
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, 256 + align256(2 * l * n * 8) + align256(2 * l * plane) + align256(4 * chunk * n * 8) + align256(4 * chunk * plane) +
-                                   align256(3 * chunk * plane) + align256(3 * chunk * n * 8) + align256(2 * chunk * n * 8), &w));
-  int *flag = (int *)w;
-  char *at = w + 256;
-  auto take = [&](size_t bytes) { char *r = at; at += align256(bytes); return r; };
-  uint64_t *rlk_d = (uint64_t *)take(2 * l * n * 8);
-  uint32_t *rlk_hat = (uint32_t *)take(2 * l * plane);
-  uint64_t *in_d = (uint64_t *)take(4 * chunk * n * 8);
-  uint32_t *hat = (uint32_t *)take(4 * chunk * plane), *res = (uint32_t *)take(3 * chunk * plane);
-  uint64_t *chat = (uint64_t *)take(3 * chunk * n * 8), *o_d = (uint64_t *)take(2 * chunk * n * 8);
-  ZK_CK(zkfhe_upload(ctx, rlk_d, rlk0, (size_t)l * n * 8));
-  ZK_CK(zkfhe_upload(ctx, rlk_d + (size_t)l * n, rlk1, (size_t)l * n * 8));
+  const int log_n = bit_log2(n);
+  const size_t lw = (size_t)l * n;
+  ZK_CK(check_below_q(ctx, a0, n_pairs * n, q, "bfv_mul", "a ciphertext", a1));
+  ZK_CK(check_below_q(ctx, b0, n_pairs * n, q, "bfv_mul", "a ciphertext", b1));
+  ZK_CK(check_below_q(ctx, rlk0, lw, q, "bfv_mul", "a relinearization-key", rlk1));
+  const size_t chunk = std::min<size_t>(n_pairs, chunk_polys(n)), cw = chunk * n;
+  int *flag;
+  uint64_t *rlk_d, *in_d, *chat, *o_d;
+  uint32_t *rlk_hat, *hat, *res;
+  ZK_CK(Arena().add(flag, 1).add(rlk_d, 2 * lw).add(rlk_hat, 2 * lw * NP).add(in_d, 4 * cw).add(hat, 4 * cw * NP).add(res, 3 * cw * NP)
+            .add(chat, 3 * cw).add(o_d, 2 * cw).carve(ctx));
+  ZK_CK(zkfhe_upload(ctx, rlk_d, rlk0, lw * 8));
+  ZK_CK(zkfhe_upload(ctx, rlk_d + lw, rlk1, lw * 8));
   ZK_CK(launch_rns_ntt<NP>(ctx, false, rlk_d, LOAD_RESIDUE, q, 2 * l, log_n, nullptr, 0, rlk_hat, flag));
   const uint64_t *src[4] = {a0, a1, b0, b1};
   for (size_t lo = 0; lo < n_pairs; lo += chunk) {
@@ -459,9 +409,9 @@ int zkfhe_bfv_mul(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_pairs
     for (int i = 0; i < 4; ++i) ZK_CK(zkfhe_upload(ctx, in_d + i * c * n, src[i] + lo * n, bytes));
     ZK_CK(launch_rns_ntt<NP>(ctx, false, in_d, LOAD_CENTRED, q, 4 * c, log_n, nullptr, 0, hat, flag));
     ZK_CK(launch_tensor(ctx, hat, c, log_n, res));
-    ZK_CK(launch_eval_epilogue(ctx, res, 3 * c, log_n, q, EvEpi{EV_ROUND, nullptr, nullptr, params->t, 0, 0, nullptr}, chat));
-    ZK_CK(launch_relin(ctx, chat + 2 * c * n, l, base_bits, rlk_hat, c, log_n, res));
-    ZK_CK(launch_eval_epilogue(ctx, res, 2 * c, log_n, q, EvEpi{EV_ADD, chat, nullptr, 0, 0, 0, nullptr}, o_d));
+    ZK_CK(zk_bfv_eval_epilogue(ctx, res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = params->t}, chat));
+    ZK_CK(zk_bfv_key_switch(ctx, chat + 2 * c * n, 0, q, l, base_bits, rlk_hat, c, log_n, res));
+    ZK_CK(zk_bfv_eval_epilogue(ctx, res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = chat}, o_d));
     ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
     ZK_CK(zkfhe_download(ctx, out1 + lo * n, o_d + c * n, bytes));
   }
@@ -472,30 +422,25 @@ int zkfhe_bfv_noise(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64
                     uint64_t *noise_out) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && sk && c0 && c1 && noise_out && n_cts > 0);
-  ZK_CK(zk_bfv_check_params(ctx, params));
+  ZK_CK(check_params(ctx, params));
   const uint64_t n = params->n, q = params->q;
-  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_noise: a ciphertext"));
-  ZK_CK(check_below_q(ctx, c1, n_cts * n, q, "bfv_noise: a ciphertext"));
+  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_noise", "a ciphertext", c1));
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), vec = align256(n * 8), cvec = align256(chunk * n * 8);
-  const size_t plane = (size_t)NP * n * 4;
-  char *w;
-  ZK_CK(zk_bfv_work_arena(ctx, 256 + vec + align256(plane) + 2 * cvec + align256(chunk * 8) + align256(chunk * plane), &w));
-  int *flag = (int *)w;
-  uint64_t *sk_d = (uint64_t *)(w + 256);
-  uint32_t *hat = (uint32_t *)((char *)sk_d + vec);
-  uint64_t *c0_d = (uint64_t *)((char *)hat + align256(plane)), *c1_d = (uint64_t *)((char *)c0_d + cvec);
-  uint64_t *nz_d = (uint64_t *)((char *)c1_d + cvec);
-  uint32_t *res = (uint32_t *)((char *)nz_d + align256(chunk * 8));
-  ZK_CK(secret_hat(ctx, sk, n, q, sk_d, hat, flag, "bfv_noise"));
+  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
+  int *flag;
+  uint64_t *sk_d, *c0_d, *c1_d;
+  unsigned long long *nz_d;
+  uint32_t *hat, *res;
+  ZK_CK(Arena().add(flag, 1).add(sk_d, n).add(hat, NP * n).add(c0_d, cw).add(c1_d, cw).add(nz_d, chunk).add(res, cw * NP).carve(ctx));
+  ZK_CK(secret_hat<NP>(ctx, sk, n, q, sk_d, hat, flag, "bfv_noise"));
+  const EvEpi epi{.mode = EV_NOISE, .add = c0_d, .t = params->t, .delta = q / params->t, .noise = nz_d};
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
     ZK_CK(zkfhe_upload(ctx, c0_d, c0 + lo * n, bytes));
     ZK_CK(zkfhe_upload(ctx, c1_d, c1 + lo * n, bytes));
     ZK_HIP(ctx, hipMemsetAsync(nz_d, 0, c * 8, ctx->stream));
     ZK_CK(launch_rns_ntt<NP>(ctx, true, c1_d, LOAD_RESIDUE, q, c, log_n, hat, 0, res, flag));
-    const EvEpi epi{EV_NOISE, c0_d, nullptr, params->t, q / params->t, 0, (unsigned long long *)nz_d};
-    ZK_CK(launch_eval_epilogue(ctx, res, c, log_n, q, epi, nullptr));
+    ZK_CK(zk_bfv_eval_epilogue(ctx, res, c, log_n, q, epi, nullptr));
     ZK_CK(zkfhe_download(ctx, noise_out + lo, nz_d, c * 8));
   }
   return ZKFHE_OK;

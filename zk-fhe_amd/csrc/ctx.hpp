@@ -45,9 +45,9 @@ struct zkfhe_ctx {
   hipEvent_t pe0 = nullptr, pe1 = nullptr;
   hipEvent_t wait_ev = nullptr;  // hipEventBlockingSync: host waits sleep instead of spinning (zk_wait)
   // [2] = k_msm_table of a call of a few columns, [3] = k_g1_decompress, [4] = k_msm_segmented (verify.hip),
-  // [5] = k_bfv_sample, [6] = k_rns_ntt, [7] = k_rns_epilogue (bfv_enc.hip), [8] = k_bfv_tensor, [9] = k_bfv_relin,
+  // [5] = k_bfv_sample, [6] = k_rns_ntt, [7] = k_rns_epilogue (bfv_enc.hip), [8] = k_bfv_tensor, [9] = k_key_switch<false>,
   // [10] = k_eval_epilogue, [11] = k_bfv_sum / k_bfv_add (bfv_eval.hip), [12] = k_bfv_share_sum, [13] = k_bfv_decrypt_combine
-  // (bfv_threshold.hip), [14] = k_gal_switch / k_gal_epilogue, [15] = k_slot_ntt (bfv_galois.hip)
+  // (bfv_threshold.hip), [14] = k_key_switch<true> / k_eval_epilogue of the Galois calls, [15] = k_slot_ntt (bfv_galois.hip)
   static constexpr int PROF_SLOTS = 16;
   double prof_ms[PROF_SLOTS] = {}, prof_bytes[PROF_SLOTS] = {}, prof_ops[PROF_SLOTS] = {};
   uint64_t prof_launches[PROF_SLOTS] = {};
@@ -59,11 +59,11 @@ struct zkfhe_ctx {
   // host-side marks of the last proof made on this context, ms from its start (zkfhe_ctx_last_proof_marks): [0] the phase-0
   // commitment is back from the GPU, [1] the first challenge is squeezed (behind the public inputs' sponge), [2] the proof is done
   float proof_marks[3] = {0, 0, 0};
-  unsigned *tickets = nullptr;
-  // BFV encryption (bfv_enc.hip): the RNS twiddle tables (built on first use) and a grow-only work arena
+  unsigned *tickets = nullptr;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
+  // the BFV calls (rns_ntt.hip.hpp): the RNS twiddle tables (built on first use) and a grow-only work arena
   uint32_t *bfv_tw = nullptr;
   void *bfv_work = nullptr;
-  size_t bfv_work_sz = 0;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
+  size_t bfv_work_sz = 0;
   // slot batching (bfv_galois.hip): per (T, N), [fwd | inv | slot of NTT index][N] on the device and the constants of T
   struct SlotTables {
     uint32_t *dev = nullptr;

@@ -4,23 +4,13 @@
 // three primes (product 2^89.2: a ternary factor keeps the product below N 2^64), the evaluator all five (product 2^151.2: a
 // product of two centred residues below 2^63 stays below 2^140).
 // Headroom at p < 2^31: a b + m p < 2^62 + 2^63 < 2^64 in mont_mul, and a + b < 2^32 in add_p.
+// Also the pieces every BFV file shares: the device helpers, the two CRT epilogues and the key switch (each defined in one .hip
+// file, launched through the declarations below), the host checks and the work-arena layout.
 #pragma once
 #include <algorithm>
+#include <vector>
 
 #include "ctx.hpp"
-
-// defined in bfv_enc.hip, shared with bfv_eval.hip, bfv_threshold.hip and bfv_galois.hip
-// the twiddle tables of every prime: [prime][fwd | inv][NMAX], psi^br15(k) and psi^-br15(k) in Montgomery form (built on first use)
-int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out);
-// the parameter check of every BFV call (zkfhe.h)
-int zk_bfv_check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm);
-// the context's grow-only BFV work arena
-int zk_bfv_work_arena(zkfhe_ctx *ctx, size_t bytes, char **out);
-// the 2 B thresholds of the error sampler
-void zk_bfv_error_cdt(uint64_t b, uint64_t *t);
-// n_polys samples of ChaCha20 stream (seed, domain, index0 + j); kind 0 ternary, 1 uniform, 2 error (cdt_dev: n_cdt thresholds)
-int zk_bfv_sample(zkfhe_ctx *ctx, const uint8_t seed[32], uint32_t domain, uint64_t index0, int kind, size_t n_polys, int log_n, uint64_t q,
-                  const uint64_t *cdt_dev, int n_cdt, uint64_t *out);
 
 namespace zkrns {
 
@@ -42,6 +32,19 @@ struct RnsConst {
 // else is flagged and read as 0); or centred, v - Q if v > floor(Q/2)
 enum LoadMode { LOAD_RESIDUE = 0, LOAD_TERNARY = 1, LOAD_CENTRED = 2 };
 
+// the samplers of k_bfv_sample (zk_bfv_sample)
+enum SampleKind { S_TERNARY = 0, S_UNIFORM = 1, S_ERROR = 2 };
+
+// the ChaCha20 domains of the BFV samplers, word 13 of the state (the table of zkfhe.h)
+enum Domain : uint32_t {
+  DOM_ENC_U = 1, DOM_ENC_E0 = 2, DOM_ENC_E1 = 3,   // encryption, index first_index + message
+  DOM_KEY_S = 4, DOM_KEY_A = 5, DOM_KEY_E = 6,     // (shared) public key, index 0: s and e from the party seed, a from the CRS
+  DOM_RLK_A = 7, DOM_RLK_E = 8,                    // relinearization key row i (a_i also the CRS of the threshold rows)
+  DOM_SMUDGE = 9,                                  // decryption-share noise, index first_index + ciphertext
+  DOM_THR_U = 10, DOM_THR_E0 = 11, DOM_THR_E1 = 12, DOM_THR_E2 = 13,   // threshold relinearization rounds, row j
+  DOM_GK_A = 14, DOM_GK_E = 15,                    // Galois key row j, index g 64 + j
+};
+
 __device__ __forceinline__ uint32_t mont_mul(uint32_t a, uint32_t b, uint32_t p, uint32_t pinv) {
   const uint64_t x = (uint64_t)a * b;   // < p^2 < 2^62
   const uint32_t m = (uint32_t)x * pinv;
@@ -57,6 +60,25 @@ __device__ __forceinline__ uint32_t sub_p(uint32_t a, uint32_t b, uint32_t p) { 
 __device__ __forceinline__ uint64_t add_q(uint64_t a, uint64_t b, uint64_t q) {
   const uint64_t s = a + b;   // < 2^64: q < 2^63
   return s >= q ? s - q : s;
+}
+__device__ __forceinline__ uint64_t sub_q(uint64_t a, uint64_t b, uint64_t q) { return a >= b ? a - b : a + q - b; }
+
+// v + delta m mod Q for a plaintext m in [0, T/2] or [Q - T/2, Q): delta |m| <= Q / 2, no reduction needed
+__device__ __forceinline__ uint64_t add_delta_m(uint64_t v, uint64_t m, uint64_t delta, uint64_t q) {
+  const bool mneg = m > q / 2;
+  const uint64_t dm = delta * (mneg ? q - m : m);
+  return add_q(v, mneg && dm ? q - dm : dm, q);
+}
+
+// the gadget term of a ternary s in {0, 1, Q - 1}: 0, pw or Q - pw without a branch (pw = 2^(j w) < Q)
+__device__ __forceinline__ uint64_t gadget_select(uint64_t s, uint64_t pw, uint64_t q) { return s == 1 ? pw : (s == q - 1 ? q - pw : 0); }
+
+// degree d of sigma_g(v), v one polynomial in CircuitInput order, ginv = g^-1 mod 2N (zkfhe.h): degree j = d ginv mod 2N of v if
+// j < N, else minus degree j - N.  ginv = 1 reads v[N - 1 - d].
+__device__ __forceinline__ uint64_t auto_coeff(const uint64_t *__restrict__ v, unsigned d, unsigned ginv, unsigned n, uint64_t q) {
+  const unsigned j = (d * ginv) & (2 * n - 1);   // d ginv < 2^15 2^16
+  const uint64_t x = v[n - 1 - (j & (n - 1))];
+  return j >= n && x ? q - x : x;
 }
 
 // (hi 2^64 + lo) mod q, q < 2^63: bit by bit, no data-dependent branch
@@ -136,6 +158,11 @@ __device__ __forceinline__ void crt5(const uint32_t *__restrict__ r, size_t n, c
   const uint64_t d1 = cc.P[1] - x1 - b0, b1 = cc.P[1] < x1 || (cc.P[1] - x1) < b0;
   const uint64_t d2 = cc.P[2] - x2 - b1;
   m[0] = neg ? d0 : x0, m[1] = neg ? d1 : x1, m[2] = neg ? d2 : x2;
+}
+// the integer of crt5 (magnitude m, sign neg) mod q
+__device__ __forceinline__ uint64_t crt5_mod_q(const uint64_t m[3], bool neg, uint64_t q) {
+  const uint64_t rm = mod128(mod128(m[2], m[1], q), m[0], q);
+  return neg && rm ? q - rm : rm;
 }
 
 // the decryption of the residue v = [c0 + c1 s]_Q: round(T x / Q) mod T with x = v centred, as a residue mod Q.  For the residue v
@@ -294,15 +321,120 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // polynomials per chunk of a batch: 2^21 coefficients, at least 8 polynomials
 inline size_t chunk_polys(uint64_t n) { return std::max<size_t>(8, ((size_t)1 << 21) / n); }
 
+// The modes of the three-prime CRT epilogue (k_rns_epilogue, bfv_enc.hip): x = the product mod Q, then
+//   EPI_PLAIN    x
+//   EPI_ADD      x [+ delta m] [+ a - b] [+ e]
+//   EPI_NEG_ADD  -(x + e)
+//   EPI_DECRYPT  decrypt_round(x + c0)
+//   EPI_SHARE    x + r - E, r = e uniform in [0, 2E]
+//   EPI_GADGET   -x + e + 2^(j w) sigma_g(s) for row j, or -x - e + ... with neg_e
+enum EpiMode { EPI_PLAIN = 0, EPI_ADD = 1, EPI_NEG_ADD = 2, EPI_DECRYPT = 3, EPI_SHARE = 4, EPI_GADGET = 5 };
+struct Epi {
+  int mode = EPI_PLAIN;
+  const uint64_t *m = nullptr;                 // EPI_ADD: + delta m (may be null)
+  const uint64_t *e = nullptr;                 // the error (EPI_ADD: may be null); EPI_SHARE: r
+  const uint64_t *c0 = nullptr;                // EPI_DECRYPT
+  const uint64_t *a = nullptr, *b = nullptr;   // EPI_ADD: + a - b (both null or both set)
+  const uint64_t *s = nullptr;                 // EPI_GADGET: s, one polynomial
+  uint64_t delta = 0, t = 0, bound = 0;        // EPI_ADD: delta; EPI_DECRYPT: T; EPI_SHARE: E
+  unsigned ginv = 1;                           // EPI_GADGET: g^-1 mod 2N
+  int w = 0;                                   // EPI_GADGET: the digit width
+  int neg_e = 0;                               // EPI_GADGET: - e
+};
+
+// The modes of the five-prime CRT epilogue (k_eval_epilogue, bfv_eval.hip) on the centred integer x:
+//   EV_MODQ    x mod Q
+//   EV_ROUND   floor((2 T x + Q) / 2Q) mod Q
+//   EV_ADD     x + add mod Q
+//   EV_RLK     2^(i w) s^2 - x - e mod Q for polynomial i
+//   EV_NOISE   |[c0 + x - delta m]_Q| with m = the decryption of [c0 + x]_Q, maximised per polynomial
+//   EV_GALOIS  x mod Q, + sigma_g(c0) on the first c polynomials, + add when set
+enum EvMode { EV_MODQ = 0, EV_ROUND = 1, EV_ADD = 2, EV_RLK = 3, EV_NOISE = 4, EV_GALOIS = 5 };
+struct EvEpi {
+  int mode = EV_MODQ;
+  const uint64_t *add = nullptr;    // EV_ADD: + add[pos]; EV_RLK: - e[pos]; EV_NOISE: + c0[pos]; EV_GALOIS: + x_in[pos] (may be null)
+  const uint64_t *poly = nullptr;   // EV_RLK: s^2, one polynomial; EV_GALOIS: the c0 of the c ciphertexts ([c][N])
+  uint64_t t = 0, delta = 0;
+  int w = 0;                             // EV_RLK: the digit width; polynomial i gets 2^(i w) s^2
+  unsigned long long *noise = nullptr;   // EV_NOISE: the maximum per polynomial (zeroed before the launch)
+  unsigned ginv = 1;                     // EV_GALOIS: g^-1 mod 2N
+  size_t c = 0;                          // EV_GALOIS
+};
+
+// ---- defined in bfv_enc.hip
+// the twiddle tables of every prime: [prime][fwd | inv][NMAX], psi^br15(k) and psi^-br15(k) in Montgomery form (built on first use)
+int zk_rns_tables(zkfhe_ctx *ctx, const uint32_t **out);
+// n_polys samples of ChaCha20 stream (seed, domain, index0 + j) (cdt_dev: the n_cdt thresholds of S_ERROR)
+int zk_bfv_sample(zkfhe_ctx *ctx, const uint8_t seed[32], Domain domain, uint64_t index0, SampleKind kind, size_t n_polys, int log_n,
+                  uint64_t q, const uint64_t *cdt_dev, int n_cdt, uint64_t *out);
+// k_rns_epilogue over res ([n_polys][3][N]) into out (CircuitInput order), in profiling slot ZKFHE_PROF_RNS_EPILOGUE
+int zk_bfv_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const Epi &epi, uint64_t *out);
+// the parameter check of every BFV call (zkfhe.h)
+int check_params(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm);
+// "fn: what coefficient is not below Q" if any v[i] (or v2[i]: a second array of the same kind, checked in the same pass) >= Q
+int check_below_q(zkfhe_ctx *ctx, const uint64_t *v, size_t count, uint64_t q, const char *fn, const char *what,
+                  const uint64_t *v2 = nullptr);
+// "fn: what coefficient is outside [0, T/2] and [Q - T/2, Q - 1]" if any m[i] is (the circuit's range check)
+int check_plain(zkfhe_ctx *ctx, const uint64_t *m, size_t count, uint64_t q, uint64_t t, const char *fn, const char *what = "a plaintext");
+// the rows l = ceil(bitlen(Q - 1) / w) of a key of digit width w = base_bits; refuses base_bits outside [1, 32]
+int relin_rows(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, int base_bits, const char *fn, int *l);
+// the 2 B thresholds of the error sampler
+void error_cdt(uint64_t b, uint64_t *t);
+// error_cdt of prm->b uploaded to cdt_d (2 B words)
+int upload_error_cdt(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, uint64_t *cdt_d);
+// the context's grow-only BFV work arena
+int work_arena(zkfhe_ctx *ctx, size_t bytes, char **out);
+
+// ---- defined in bfv_eval.hip
+// k_eval_epilogue over res ([n_polys][5][N]) into out, in profiling slot ZKFHE_PROF_BFV_EVAL_EPILOGUE (EV_GALOIS: ZKFHE_PROF_BFV_GALOIS)
+int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out);
+// the key switch of c polynomials src ([c][N]) against key_hat ([2 l][5][N]) into acc ([2][c][5][N]): ginv = 0 switches the digits
+// of src itself (relinearization, profiling slot ZKFHE_PROF_BFV_RELIN), else those of sigma_g(src), g^-1 = ginv (ZKFHE_PROF_BFV_GALOIS)
+int zk_bfv_key_switch(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64_t q, int l, int w, const uint32_t *key_hat, size_t c,
+                      int log_n, uint32_t *acc);
+
+// The work buffers of one call, each named once: add() them in order (each 256-byte aligned, so an int flag added first stays in
+// the first 256 bytes), then carve() sizes the work arena from the same list and points every buffer into it.
+class Arena {
+ public:
+  template <class T>
+  Arena &add(T *&ptr, size_t count) {
+    bufs_.push_back({&ptr, align256(count * sizeof(T)), [](void *p, char *at) { *(T **)p = (T *)at; }});
+    return *this;
+  }
+  int carve(zkfhe_ctx *ctx) {
+    size_t total = 0;
+    for (const Buf &b : bufs_) total += b.bytes;
+    char *at;
+    ZK_CK(work_arena(ctx, total, &at));
+    for (const Buf &b : bufs_) b.set(b.ptr, at), at += b.bytes;
+    return ZKFHE_OK;
+  }
+
+ private:
+  struct Buf {
+    void *ptr;
+    size_t bytes;
+    void (*set)(void *ptr, char *at);
+  };
+  std::vector<Buf> bufs_;
+};
+
+// the dynamic LDS of a kernel that holds N = 2^log_n words, opted in above 64 KiB
+inline int ntt_lds(zkfhe_ctx *ctx, const void *kernel, int log_n, int *lds) {
+  *lds = 4 << log_n;
+  if (*lds > 64 * 1024) ZK_CK(zk_func_max_lds(ctx, kernel, 4 << LOG_NMAX));
+  return ZKFHE_OK;
+}
+
 // k_rns_ntt over n_polys polynomials with the first NP primes; mul: the MUL = true instance against hat
 template <int NP>
 int launch_rns_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, int mode, uint64_t q, size_t n_polys, int log_n, const uint32_t *hat,
                    size_t hat_stride, uint32_t *out, int *flag) {
   const uint32_t *tw;
   ZK_CK(zk_rns_tables(ctx, &tw));
-  const int lds = 4 << log_n;
-  const void *kern = mul ? (const void *)k_rns_ntt<NP, true> : (const void *)k_rns_ntt<NP, false>;
-  if (lds > 64 * 1024) ZK_CK(zk_func_max_lds(ctx, kern, 4 << LOG_NMAX));
+  int lds;
+  ZK_CK(ntt_lds(ctx, mul ? (const void *)k_rns_ntt<NP, true> : (const void *)k_rns_ntt<NP, false>, log_n, &lds));
   zk_prof_begin(ctx);
   if (mul)
     k_rns_ntt<NP, true><<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(src, mode, q, log_n, tw, rns_const<NP>(log_n), hat, hat_stride, out, flag);
@@ -310,6 +442,18 @@ int launch_rns_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, int mode, uint
     k_rns_ntt<NP, false><<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(src, mode, q, log_n, tw, rns_const<NP>(log_n), nullptr, 0, out, flag);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, (double)n_polys * NP * (8.0 + (mul ? 8.0 : 4.0)) * ((size_t)1 << log_n));
+  return ZKFHE_OK;
+}
+
+// the secret key uploaded to sk_d and transformed with the first NP primes into hat; refuses a non-ternary key (zeroes flag first)
+template <int NP>
+int secret_hat(zkfhe_ctx *ctx, const uint64_t *sk, uint64_t n, uint64_t q, uint64_t *sk_d, uint32_t *hat, int *flag, const char *fn) {
+  ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
+  ZK_CK(zkfhe_upload(ctx, sk_d, sk, n * 8));
+  ZK_CK(launch_rns_ntt<NP>(ctx, false, sk_d, LOAD_TERNARY, q, 1, bit_log2(n), nullptr, 0, hat, flag));
+  int bad = 0;
+  ZK_CK(zkfhe_download(ctx, &bad, flag, 4));
+  if (bad) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": a secret-key coefficient is not in {0, 1, Q - 1}");
   return ZKFHE_OK;
 }
 
