@@ -9,6 +9,8 @@
 //     64-bit accumulator; the result has limbs 0..7 in [0, 2^29) and a signed top limb, value in (-r, 2 r);
 //   * carries are propagated (24 operations) only where a bound below would otherwise be exceeded.
 // Lz<LO, HI, V>: -LO 2^29 < l[i] < HI 2^29 for i < 8 (LO = 0: non-negative) and |value| < V r; l[8] is whatever is left.
+// The type, lz_add, lz_sub and lz_norm do not depend on the modulus and live in fq29.hip.hpp, where the MSM's
+// point arithmetic over Fq uses them too; this file adds what is particular to the NTT: products against constant twiddles.
 // Every operation states its result bound in its return type and static_asserts what it needs, so a butterfly network that
 // compiles cannot overflow:
 //   add(a, b)      -> Lz<LOa + LOb, HIa + HIb, Va + Vb>     limbs must stay inside int32: LO, HI <= 4
@@ -24,59 +26,15 @@
 
 namespace zk {
 
-template <int LO, int HI, int V>
-struct Lz {
-  int l[9];
-};
 using LzT = Lz<0, 1, 2>;   // what a product returns: tight limbs, value in (-r, 2 r)
 struct LzW : LzT {};       // what lz_weak returns: the same limbs, value in [0, 2 r) -- the only thing lz_store_weak accepts
 struct Lw {   // canonical constant operand (twiddle), limbs in [0, 2^29)
   u32 l[9];
 };
 
-template <int V>
-ZK_HD Lz<0, 1, V> lz_from_f29(const F29 &a) {   // caller's promise: a has tight limbs and a value below V r
-  Lz<0, 1, V> r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = (int)a.l[i];
-  return r;
-}
 // a canonical column value (x * 2^256 < r, packed)
 ZK_HD Lz<0, 1, 1> lz_load(const Fr &w) { return lz_from_f29<1>(fr29_unpack(w)); }
 ZK_HD Lz<0, 1, 1> lz_zero() { return lz_from_f29<1>(f29_zero()); }
-
-template <int L1, int H1, int V1, int L2, int H2, int V2>
-ZK_HD Lz<L1 + L2, H1 + H2, V1 + V2> lz_add(const Lz<L1, H1, V1> &a, const Lz<L2, H2, V2> &b) {
-  static_assert(L1 + L2 <= 4 && H1 + H2 <= 4, "limb overflow");
-  Lz<L1 + L2, H1 + H2, V1 + V2> r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] + b.l[i];
-  return r;
-}
-template <int L1, int H1, int V1, int L2, int H2, int V2>
-ZK_HD Lz<L1 + H2, H1 + L2, V1 + V2> lz_sub(const Lz<L1, H1, V1> &a, const Lz<L2, H2, V2> &b) {
-  static_assert(L1 + H2 <= 4 && H1 + L2 <= 4, "limb overflow");
-  Lz<L1 + H2, H1 + L2, V1 + V2> r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] - b.l[i];
-  return r;
-}
-
-// A limb typed HI = h is a sum of h terms each at most 2^29 - 1, so l + carry (carry <= 3) stays inside int32 for h = 4;
-// likewise on the negative side.
-template <int LO, int HI, int V>
-ZK_HD Lz<0, 1, V> lz_norm(const Lz<LO, HI, V> &a) {
-  Lz<0, 1, V> r;
-  int c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int v = a.l[i] + c;
-    r.l[i] = v & (int)q29::MASK;
-    c = v >> 29;                // arithmetic: floor
-  }
-  r.l[8] = a.l[8] + c;
-  return r;
-}
 
 // value (either sign, |v| < 16 r) -> the same residue in [0, 2 r) (in fact below 1.04 r), limbs normalised.
 // q = floor(t m / 2^16) with t = floor((l[8] - LO) / 2^13) and m = 169 for t >= 0, 170 for t < 0.  The lower limbs sum to more than
