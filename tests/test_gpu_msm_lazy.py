@@ -1,4 +1,4 @@
-"""The MSM kernels on the lazy signed-limb point arithmetic (csrc/fq29.hip.hpp, the generated products of lq29_tied.inc) against
+"""The MSM kernels on the lazy signed-limb point arithmetic (csrc/fq29.hip.hpp, the generated signed products of mont29_tied.inc) against
 the oracle MSM, bit-exact: the table-sum path with few columns (one partial per visit) and many (256 partials per visit), at the
 digit widths the table budgets produce, and the bucket pipeline one size above the table limit.  The bases are brought by the
 caller, so duplicated and negated points make the doubling and the cancellation paths of the additions run on the device:

@@ -50,8 +50,10 @@ def classify(op):
     return "scalar"
 
 
-def compile_to_asm(src, extra):
-    import build
+def compile_to_asm(src, extra, build=None):
+    """build: the build.py module whose flags to use (another tree's, for tools/device_asm_diff.py); this tree's by default"""
+    if build is None:
+        import build
     out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
     cmd = [build.hipcc()] + build.FLAGS + extra + ["--cuda-device-only", "-S", src, "-o", out]
     subprocess.run(cmd, check=True)

@@ -2,6 +2,7 @@
 //   F29_FN(name)  -> the function name (f29_##name for Fq, fr29_##name for Fr)
 //   F29_P, F29_2P, F29_3P  -> limb initialisers of p, 2p, 3p;  F29_INV -> -p^-1 mod 2^29
 // Both BN254 moduli have floor(2^261 / p) = 169, which f29_weak_reduce relies on.
+// Gives F29_FN(mod) too: the modulus in the form the nine-limb products of mont29.hip.hpp take it.
 // value < 16 p  ->  the same residue below 2 p (in fact below 1.03 p): q = floor(v / 2^245) * 169 >> 16 underestimates v / p by
 // less than one (169 = floor(2^261 / p))
 ZK_HD F29 F29_FN(weak_reduce)(const F29 &a) {
@@ -49,114 +50,33 @@ ZK_HD bool F29_FN(is_zero_mod_p)(const F29 &a) {
   return f29_eq(a, P1) || f29_eq(a, P2) || f29_eq(a, P3);
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-#include "f29_tied.inc"
-#define ZK_TIED_RETURN(call) return call;
-#else
-#define ZK_TIED_RETURN(call)
-#endif
+// the modulus as the nine-limb products take it (mont29.hip.hpp); lq_ and lz_ products use it too
+struct F29_FN(mod) {
+  static constexpr u32 INV = F29_INV;
+  static constexpr u32 P[9] = F29_P;
+};
 // Montgomery product a b / 2^261 mod p.  Needs a * b < 2^261 p (e.g. both below 11 p); gives a value below 2 p.
 ZK_HD F29 F29_FN(mul)(const F29 &a, const F29 &b) {
-  ZK_TIED_RETURN(F29_FN(mul_tied)(a, b))
-  const u32 P[9] = F29_P;
-  u32 m[9];
-  F29 r;
-  u64 acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      zk_madu(acc, a.l[j], b.l[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    zk_madu(acc, a.l[k], b.l[0]);
-    m[k] = ((u32)acc * F29_INV) & q29::MASK;
-    zk_madu_s(acc, m[k], P[0]);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      zk_madu(acc, a.l[j], b.l[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    r.l[k - 9] = (u32)acc & q29::MASK;
-    acc >>= 29;
-  }
-  r.l[8] = (u32)acc;
-  return r;
+#ifdef ZK_MONT29_TIED
+  return mont29u_mul_v<F29_FN(mod), F29>(a, b);
+#else
+  return mont29_c<F29_FN(mod), u64, u32, F29>(a, b);
+#endif
 }
 // a^2 / 2^261 mod p: the cross products a_j a_i (j < i) once, against the doubled limb 2 a_i -- 45 product multiply-adds
 // instead of 81 (column sums stay below 2^63: four doubled terms below 2^59, one square and nine reduction terms below 2^58).
 ZK_HD F29 F29_FN(sqr)(const F29 &a) {
-  ZK_TIED_RETURN(F29_FN(sqr_tied)(a))
-  const u32 P[9] = F29_P;
-  u32 m[9], d[9];
-  F29 r;
-  u64 acc = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) d[i] = a.l[i] << 1;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      if (j < k - j) zk_madu(acc, a.l[j], d[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    if ((k & 1) == 0) zk_madu(acc, a.l[k / 2], a.l[k / 2]);
-    m[k] = ((u32)acc * F29_INV) & q29::MASK;
-    zk_madu_s(acc, m[k], P[0]);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      if (j < k - j) zk_madu(acc, a.l[j], d[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    if ((k & 1) == 0) zk_madu(acc, a.l[k / 2], a.l[k / 2]);
-    r.l[k - 9] = (u32)acc & q29::MASK;
-    acc >>= 29;
-  }
-  r.l[8] = (u32)acc;
-  return r;
+#ifdef ZK_MONT29_TIED
+  return mont29u_sqr<F29_FN(mod), F29>(a);
+#else
+  return mont29_c<F29_FN(mod), u64, u32, F29, true>(a, a);
+#endif
 }
-
 // (a b + c d) / 2^261 mod p with one reduction.  Needs a b + c d < 2^261 p; gives a value below 2 p.
 ZK_HD F29 F29_FN(mul2)(const F29 &a, const F29 &b, const F29 &c, const F29 &d) {
-  ZK_TIED_RETURN(F29_FN(mul2_tied)(a, b, c, d))
-  const u32 P[9] = F29_P;
-  u32 m[9];
-  F29 r;
-  u64 acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      zk_madu(acc, a.l[j], b.l[k - j]);
-      zk_madu(acc, c.l[j], d.l[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    zk_madu(acc, a.l[k], b.l[0]);
-    zk_madu(acc, c.l[k], d.l[0]);
-    m[k] = ((u32)acc * F29_INV) & q29::MASK;
-    zk_madu_s(acc, m[k], P[0]);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      zk_madu(acc, a.l[j], b.l[k - j]);
-      zk_madu(acc, c.l[j], d.l[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    r.l[k - 9] = (u32)acc & q29::MASK;
-    acc >>= 29;
-  }
-  r.l[8] = (u32)acc;
-  return r;
+#ifdef ZK_MONT29_TIED
+  return mont29u_mul2<F29_FN(mod), F29>(a, b, c, d);
+#else
+  return mont29_c<F29_FN(mod), u64, u32, F29>(a, b, c, d);
+#endif
 }
-#undef ZK_TIED_RETURN

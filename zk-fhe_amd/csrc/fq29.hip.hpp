@@ -11,7 +11,7 @@
 // buckets keep their size); what changes is the Montgomery constant: the MSM tables and accumulators hold x * 2^261 mod p.
 // g1x29_to_std() converts a result back to the library's standard form (x * 2^256 mod p, canonical) before normalisation.
 //
-// Two forms live here.  F29 with f29_add / f29_sub / f29_mul ...: unsigned limbs < 2^29 (the top limb holds whatever is left: values stay
+// Two forms live here; the products of both are wrappers of the one nine-limb Montgomery multiply of mont29.hip.hpp.  F29 with f29_add / f29_sub / f29_mul ...: unsigned limbs < 2^29 (the top limb holds whatever is left: values stay
 // < 2^261), carries propagated after every addition, a multiple of p added before every subtraction; the comment of each function states
 // the bound on its VALUE (as a multiple of p) it needs and gives.  The Fr kernels that multiply data by table constants (fr29.hip.hpp), the
 // radix-2..16 NTT tiles and the square root of the batch verifier use it.
@@ -21,7 +21,7 @@
 // the accumulator stays unreduced from one addition to the next, and the equal-x test is one multiply and one compare on limb 0.  Against
 // the normalising form this takes about 200 of the 2500 VALU instructions of a mixed addition away (profiles/msm_lazy_limbs.md).
 #pragma once
-#include "bn254.hip.hpp"
+#include "mont29.hip.hpp"
 
 namespace zk {
 
@@ -29,24 +29,8 @@ struct F29 {
   u32 l[9];
 };
 
-// acc += a * b, the multiply-add of the nine-limb products' C bodies (the host pass, the native CPU checks, and -DZK_MAD_C).
-// ON THE DEVICE the products are generated inline assembly since round 6 (f29_tied.inc, lz29_tied.inc; tools/gen_tied_products.py): one
-// asm statement per COLUMN on the running accumulator.  Left to the compiler, `acc += (u64)a * b` after `acc >>= 29` is reassociated so
-// that the previous column's carry is added last: every column starts in a register pair of its own and a v_lshl_add_u64 joins it to the
-// carry -- 17 of a product's ~240 instructions, up to eleven accumulator pairs in flight.  Tied to one pair the joins go (k_msm_table's
-// addition loop: 277 -> 39; k_ntt13: 246 -> 220 VGPRs).  One statement per multiply-add was tried first and lost: the compiler cannot see
-// into an asm statement and puts a wait state before every VALU read of a register one defines (~150 s_nop per product); inside ONE
-// statement it inserts nothing, and the step m_k = (low word * inv) mod 2^29 between two statements costs one wait state per column.
-// Measured (profiles/r6_probes.md section 2): k_msm_table -6 %, k_msm_accumulate -3..4 %, k_ntt13 unchanged, the driver's wave +4.5 %,
-// 96 steps +4 %, one proof alone -2 % (faster), bit-exact.  -DZK_MAD_C (ZKFHE_EXTRA_FLAGS) restores the compiler's form.
-ZK_HD void zk_madu(u64 &acc, u32 a, u32 b) { acc += (u64)a * b; }
-ZK_HD void zk_madu_s(u64 &acc, u32 a, u32 s) { acc += (u64)a * s; }
-ZK_HD void zk_madi(long long &acc, int a, int b) { acc += (long long)a * (long long)b; }
-ZK_HD void zk_madi_s(long long &acc, int a, int s) { acc += (long long)a * (long long)s; }
-
 namespace q29 {
-constexpr u32 MASK = (1u << 29) - 1;
-constexpr u32 INV = 0x04866389u;  // -q^-1 mod 2^29
+constexpr u32 INV = 0x04866389u;  // -q^-1 mod 2^29 (MASK: mont29.hip.hpp)
 #define ZK_Q29_P \
   { 0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu }
 #define ZK_Q29_2P \
@@ -252,9 +236,6 @@ ZK_HD Lz<0, 1, V> lz_norm(const Lz<LO, HI, V> &a) {
 using LqT = Lz<0, 1, 2>;   // what a product returns (tight limbs, value in (-p, 2 p)); any tight value below 2 p in magnitude
 using LqX = Lz<0, 1, 8>;   // an x coordinate of the accumulator: r^2 - ppp - 2 qq after carry propagation, not reduced
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-#include "lq29_tied.inc"
-#endif
 // Montgomery product a b / 2^261 mod p for |a b| < 2^261 p = 169.29 p^2: value in (-p, 2 p), tight limbs.  Column k: nine a_j b_(k-j)
 // below 2 2^58 in magnitude (one operand's limbs below 2^30 and the other's below 2^29, or the like: the product of the two limb bounds
 // is at most 2), nine m_j p_(k-j) below 2^58 and the carry below 2^35: 27 2^58 + 2^35 < 2^63.
@@ -262,37 +243,11 @@ template <int L1, int H1, int V1, int L2, int H2, int V2>
 ZK_HD LqT lq_mul(const Lz<L1, H1, V1> &a, const Lz<L2, H2, V2> &b) {
   static_assert((L1 > H1 ? L1 : H1) * (L2 > H2 ? L2 : H2) <= 2, "product: |a_j b_i| below 2^59");
   static_assert(V1 * V2 <= 160 && V1 <= 64 && V2 <= 64, "product: |a b| < 2^261 p");
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-  return lq_mul_tied(a, b);
+#ifdef ZK_MONT29_TIED
+  return mont29i_mul_v<f29_mod, LqT>(a, b);
+#else
+  return mont29_c<f29_mod, long long, int, LqT>(a, b);
 #endif
-  constexpr u32 P[9] = ZK_Q29_P;
-  int m[9];
-  LqT r;
-  long long acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      zk_madi(acc, a.l[j], b.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    zk_madi(acc, a.l[k], b.l[0]);
-    m[k] = (int)(((u32)acc * q29::INV) & q29::MASK);
-    zk_madi_s(acc, m[k], (int)P[0]);
-    acc >>= 29;   // exact: the low 29 bits are zero
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      zk_madi(acc, a.l[j], b.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    r.l[k - 9] = (int)((u32)acc & q29::MASK);
-    acc >>= 29;
-  }
-  r.l[8] = (int)acc;
-  return r;
 }
 // a^2 / 2^261 mod p for limbs of either sign below 2^29: the cross products a_j a_i (j < i) once, against the doubled limb 2 a_i.
 // A column is at most four doubled terms below 2^59, one square and nine reduction terms below 2^58: 18 2^58 < 2^63.  Value in [0, 2 p).
@@ -300,40 +255,11 @@ template <int LO, int HI, int V>
 ZK_HD LqT lq_sqr(const Lz<LO, HI, V> &a) {
   static_assert(LO <= 1 && HI <= 1, "square: limbs below 2^29 in magnitude");
   static_assert(V * V <= 160, "square: a^2 < 2^261 p");
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-  return lq_sqr_tied(a);
+#ifdef ZK_MONT29_TIED
+  return mont29i_sqr<f29_mod, LqT>(a);
+#else
+  return mont29_c<f29_mod, long long, int, LqT, true>(a, a);
 #endif
-  constexpr u32 P[9] = ZK_Q29_P;
-  int m[9], d[9];
-  LqT r;
-  long long acc = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) d[i] = a.l[i] * 2;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      if (j < k - j) zk_madi(acc, a.l[j], d[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    if ((k & 1) == 0) zk_madi(acc, a.l[k / 2], a.l[k / 2]);
-    m[k] = (int)(((u32)acc * q29::INV) & q29::MASK);
-    zk_madi_s(acc, m[k], (int)P[0]);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      if (j < k - j) zk_madi(acc, a.l[j], d[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    if ((k & 1) == 0) zk_madi(acc, a.l[k / 2], a.l[k / 2]);
-    r.l[k - 9] = (int)((u32)acc & q29::MASK);
-    acc >>= 29;
-  }
-  r.l[8] = (int)acc;
-  return r;
 }
 // (a b + c d) / 2^261 mod p with one reduction, all four operands variable: eighteen products below 2^58 in magnitude per column (every
 // limb below 2^29 in magnitude) and nine m_j p_(k-j) below 2^58: 27 2^58 + 2^35 < 2^63.  Value in (-p, 2 p).
@@ -341,40 +267,11 @@ template <int L1, int H1, int V1, int L2, int H2, int V2, int L3, int H3, int V3
 ZK_HD LqT lq_mul2(const Lz<L1, H1, V1> &a, const Lz<L2, H2, V2> &b, const Lz<L3, H3, V3> &c, const Lz<L4, H4, V4> &d) {
   static_assert(L1 <= 1 && H1 <= 1 && L2 <= 1 && H2 <= 1 && L3 <= 1 && H3 <= 1 && L4 <= 1 && H4 <= 1, "two-product form: limbs below 2^29 in magnitude");
   static_assert(V1 * V2 + V3 * V4 <= 160 && V1 <= 64 && V2 <= 64 && V3 <= 64 && V4 <= 64, "two-product form: |a b + c d| < 2^261 p");
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-  return lq_mul2_tied(a, b, c, d);
+#ifdef ZK_MONT29_TIED
+  return mont29i_mul2<f29_mod, LqT>(a, b, c, d);
+#else
+  return mont29_c<f29_mod, long long, int, LqT>(a, b, c, d);
 #endif
-  constexpr u32 P[9] = ZK_Q29_P;
-  int m[9];
-  LqT r;
-  long long acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      zk_madi(acc, a.l[j], b.l[k - j]);
-      zk_madi(acc, c.l[j], d.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    zk_madi(acc, a.l[k], b.l[0]);
-    zk_madi(acc, c.l[k], d.l[0]);
-    m[k] = (int)(((u32)acc * q29::INV) & q29::MASK);
-    zk_madi_s(acc, m[k], (int)P[0]);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      zk_madi(acc, a.l[j], b.l[k - j]);
-      zk_madi(acc, c.l[j], d.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    r.l[k - 9] = (int)((u32)acc & q29::MASK);
-    acc >>= 29;
-  }
-  r.l[8] = (int)acc;
-  return r;
 }
 
 // value (either sign, |v| < 16 p) -> the same residue in [0, 2 p) (in fact below 1.04 p), tight limbs, top limb included.

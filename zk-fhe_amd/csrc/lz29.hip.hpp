@@ -60,49 +60,20 @@ ZK_HD LzW lz_weak(const Lz<LO, HI, V> &a) {
   return r;
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-#include "lz29_tied.inc"
-#endif
 // Montgomery product a * w / 2^261 mod r for |a w| < 2^261 r: value in (-r, 2 r).  Column k: nine |a_j| w_(k-j) < 2^30 2^29,
 // nine m_j r_(k-j) < 2^58 and the carry: magnitude below 9 2^59 + 9 2^58 + 2^35 < 2^63.
 // UNIFORM: the constant is the same for every lane of the wave (a butterfly constant, n^-1 -- loaded through a uniform address): its
-// limbs are taken from SGPRs, as the compiler did on its own before the multiply-adds became inline assembly (fq29.hip.hpp zk_madi).
+// limbs are taken from SGPRs, as the compiler did on its own before the multiply-adds became inline assembly (mont29.hip.hpp).
 template <bool UNIFORM = false, int LO, int HI, int V>
 ZK_HD LzT lz_mul(const Lz<LO, HI, V> &a, const Lw &b) {
   static_assert(LO <= 2 && HI <= 2, "product: limbs below 2^30 in magnitude");
   static_assert(V <= 160, "product: |a w| < 2^261 r");
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-  if (UNIFORM) return lz_mul_tied_s(a, b);
-  return lz_mul_tied_v(a, b);
+#ifdef ZK_MONT29_TIED
+  if (UNIFORM) return mont29i_mul_s<fr29_mod, LzT>(a, b);
+  return mont29i_mul_v<fr29_mod, LzT>(a, b);
+#else
+  return mont29_c<fr29_mod, long long, int, LzT>(a, b);
 #endif
-  constexpr u32 P[9] = ZK_R29_P;
-  int m[9];
-  LzT r;
-  long long acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      if (UNIFORM) zk_madi_s(acc, a.l[j], (int)b.l[k - j]); else zk_madi(acc, a.l[j], (int)b.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    if (UNIFORM) zk_madi_s(acc, a.l[k], (int)b.l[0]); else zk_madi(acc, a.l[k], (int)b.l[0]);
-    m[k] = (int)(((u32)acc * r29::INV) & q29::MASK);
-    zk_madi_s(acc, m[k], (int)P[0]);
-    acc >>= 29;   // exact: the low 29 bits are zero
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      if (UNIFORM) zk_madi_s(acc, a.l[j], (int)b.l[k - j]); else zk_madi(acc, a.l[j], (int)b.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    r.l[k - 9] = (int)((u32)acc & q29::MASK);
-    acc >>= 29;
-  }
-  r.l[8] = (int)acc;
-  return r;
 }
 
 // (a w + b v) / 2^261 mod r, one reduction: eighteen products below 2^29 2^29 in magnitude per column (limbs of either sign below
@@ -111,84 +82,19 @@ template <int L1, int H1, int V, int L2, int H2, int V2>
 ZK_HD LzT lz_mul2(const Lz<L1, H1, V> &a, const Lw &w, const Lz<L2, H2, V2> &b, const Lw &v) {
   static_assert(L1 <= 1 && H1 <= 1 && L2 <= 1 && H2 <= 1, "two-product form: limbs below 2^29 in magnitude");
   static_assert(V + V2 <= 160, "two-product form: |a w + b v| < 2^261 r");
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_MAD_C)
-  return lz_mul2_tied(a, w, b, v);
+#ifdef ZK_MONT29_TIED
+  return mont29i_mul2<fr29_mod, LzT>(a, w, b, v);
+#else
+  return mont29_c<fr29_mod, long long, int, LzT>(a, w, b, v);
 #endif
-  constexpr u32 P[9] = ZK_R29_P;
-  int m[9];
-  LzT r;
-  long long acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      zk_madi(acc, a.l[j], (int)w.l[k - j]);
-      zk_madi(acc, b.l[j], (int)v.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    zk_madi(acc, a.l[k], (int)w.l[0]);
-    zk_madi(acc, b.l[k], (int)v.l[0]);
-    m[k] = (int)(((u32)acc * r29::INV) & q29::MASK);
-    zk_madi_s(acc, m[k], (int)P[0]);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      zk_madi(acc, a.l[j], (int)w.l[k - j]);
-      zk_madi(acc, b.l[j], (int)v.l[k - j]);
-      zk_madi_s(acc, m[j], (int)P[k - j]);
-    }
-    r.l[k - 9] = (int)((u32)acc & q29::MASK);
-    acc >>= 29;
-  }
-  r.l[8] = (int)acc;
-  return r;
 }
 
 // (a0 w0 + a1 w1 + a2 w2 + a3 w3) / 2^261 mod r with ONE reduction, for canonical data (tight non-negative limbs, values below r)
 // against canonical constants: a column is 36 products below 2^58 and nine m_j r_(k-j) below 2^58 -- 45 2^58 < 2^64, an UNSIGNED
 // accumulator (v_mad_u64_u32).  The value is below 4 r r / 2^261 + r < 2 r.  (The radix-4 first stage of the quarter-column 2^13
-// tile with a coset pre-multiplier: four table products per output for the price of 2.5.)
+// tile with a coset pre-multiplier: four table products per output for the price of 2.5.)  The C body everywhere: no assembly form.
 ZK_HD LzT lz_mul4u(const Lz<0, 1, 1> &a0, const Lw &w0, const Lz<0, 1, 1> &a1, const Lw &w1, const Lz<0, 1, 1> &a2, const Lw &w2, const Lz<0, 1, 1> &a3, const Lw &w3) {
-  constexpr u32 P[9] = ZK_R29_P;
-  u32 m[9];
-  LzT r;
-  u64 acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      zk_madu(acc, (u32)a0.l[j], w0.l[k - j]);
-      zk_madu(acc, (u32)a1.l[j], w1.l[k - j]);
-      zk_madu(acc, (u32)a2.l[j], w2.l[k - j]);
-      zk_madu(acc, (u32)a3.l[j], w3.l[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    zk_madu(acc, (u32)a0.l[k], w0.l[0]);
-    zk_madu(acc, (u32)a1.l[k], w1.l[0]);
-    zk_madu(acc, (u32)a2.l[k], w2.l[0]);
-    zk_madu(acc, (u32)a3.l[k], w3.l[0]);
-    m[k] = ((u32)acc * r29::INV) & q29::MASK;
-    zk_madu_s(acc, m[k], P[0]);
-    acc >>= 29;   // exact: the low 29 bits are zero
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int j = k - 8; j < 9; ++j) {
-      zk_madu(acc, (u32)a0.l[j], w0.l[k - j]);
-      zk_madu(acc, (u32)a1.l[j], w1.l[k - j]);
-      zk_madu(acc, (u32)a2.l[j], w2.l[k - j]);
-      zk_madu(acc, (u32)a3.l[j], w3.l[k - j]);
-      zk_madu_s(acc, m[j], P[k - j]);
-    }
-    r.l[k - 9] = (int)((u32)acc & q29::MASK);
-    acc >>= 29;
-  }
-  r.l[8] = (int)acc;
-  return r;
+  return mont29_c<fr29_mod, u64, u32, LzT>(a0, w0, a1, w1, a2, w2, a3, w3);
 }
 
 // canonical packed column value from a weakly reduced one (value in [0, 2 r), normalised limbs): takes lz_weak's own type, so a
