@@ -676,6 +676,45 @@ int zkfhe_bfv_galois_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const
 #define ZKFHE_PROF_BFV_GALOIS 14     /* k_key_switch<true>, k_eval_epilogue of the key switch */
 #define ZKFHE_PROF_BFV_SLOT_NTT 15   /* k_slot_ntt */
 
+/* ---- Encrypted matrix-vector products: hoisted rotations and slot-wise linear transforms (bfv_linear.hip) ----
+ * out = sum_k diag_k * rot_k(x) for a list of Galois elements, in one call: the digits of c1 are decomposed and transformed once,
+ * sigma_g acts on the transforms as an index permutation, and everything stays on the device until the one reduction mod Q.  The
+ * conventions of "BFV slots and rotations": host arrays, N uint64_t per polynomial in CircuitInput order, residues in [0, Q), the
+ * parameter checks of zkfhe_bfv_encrypt; every call waits for its result; w = base_bits in [1, 32], l = zkfhe_bfv_relin_digits.
+ * Galois keys are exactly those of zkfhe_bfv_galois_keygen, or of zkfhe_bfv_share_aggregate over zkfhe_bfv_galois_share; there is
+ * no new randomness and no new ChaCha20 domain.
+ *   The hoisted rotation of (c0, c1) by g: the digits D_i = (c1 >> i w) & (2^w - 1) are taken from c1 itself, in [0, Q), NOT from
+ *   sigma_g(c1).  They are integer polynomials, and sigma_g(D_i) is the signed integer polynomial: the coefficient of x^j moves to
+ *   j g mod 2N and is negated over Z when that lands past N.  r1 = sum_i sigma_g(D_i) gk1_i and r0 = sigma_g(c0) + sum_i
+ *   sigma_g(D_i) gk0_i, computed exactly over Z in Z[x]/(x^N + 1), then taken mod Q into [0, Q).  For g = 1 the result is (c0, c1)
+ *   itself: no key switch, and that element's key rows are neither read nor checked.  The result decrypts under s to sigma_g(m) with
+ *   the noise size of zkfhe_bfv_apply_galois, but it is NOT bit-equal to it: the digits of Q - v are not those of v.
+ * Range: zkfhe_bfv_linear_transform carries its whole sum in five primes (product 2^151.2) without an intermediate reduction, so it
+ * refuses, with ZKFHE_EINVAL and before any device work, when bitlen(n_elems) + bitlen(N) + bitlen(floor(T/2)) + bitlen(Q - 1) +
+ * bitlen(1 + l N (2^w - 1)) > 150; the message says to narrow base_bits or to split the element list and add the parts.  At
+ * T = 65537 and w <= 16 nothing is refused for any N <= 32768.  zkfhe_bfv_apply_galois_many is bounded by l N 2^w Q < 2^116 and
+ * never refuses on range.  Both calls also refuse, with a message: a NULL argument, n = 0 or n_elems = 0, a g that is even or
+ * >= 2N, a ciphertext or key coefficient >= Q (the key rows of g = 1 excepted), a diagonal out of plaintext range, base_bits outside
+ * [1, 32].  Both are defined for any T.  Noise: every rotated term carries key-switch noise (about l N 2^w B / 2) times the size of
+ * its diagonal (up to N T / 2), so keep w small. */
+/* out0, out1: n_elems x n x N, element-major; block k is the hoisted rotation of every one of the n ciphertexts by g[k].  g: n_elems
+ * odd values below 2N, repeats allowed; gk0, gk1: n_elems x l x N, the key of element k at row block k. */
+int zkfhe_bfv_apply_galois_many(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1,
+                                size_t n_elems, const uint64_t *g, const uint64_t *gk0, const uint64_t *gk1, int base_bits, uint64_t *out0,
+                                uint64_t *out1);
+/* out0, out1: n x N.  diag: n_elems x N plaintexts in [0, T/2] or [Q - T/2, Q - 1], shared by all n ciphertexts.  With p_k the
+ * centred integers of diag_k and (r0_k, r1_k) the hoisted rotation of ciphertext j by g[k]: out_j = sum_k r_{j,k} p_k, exactly over
+ * Z in Z[x]/(x^N + 1), then mod Q.  That is, bit for bit, zkfhe_bfv_mul_plain of block k of zkfhe_bfv_apply_galois_many by diag_k,
+ * summed over k with zkfhe_bfv_add.  Under a batching T with diag_k = zkfhe_bfv_encode_slots(d_k), slot p of the decryption is
+ * sum_k d_k[p] rot_k(v)[p] mod T, rot_k the slot permutation of g[k]. */
+int zkfhe_bfv_linear_transform(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1,
+                               size_t n_elems, const uint64_t *g, const uint64_t *gk0, const uint64_t *gk1, int base_bits,
+                               const uint64_t *diag, uint64_t *out0, uint64_t *out1);
+/* zkfhe_prof_read slots of the two calls (algorithmic bytes: words read and written); the transforms of the keys and diagonals and
+ * the inverse transforms count in ZKFHE_PROF_RNS_NTT, the reduction mod Q in ZKFHE_PROF_BFV_EVAL_EPILOGUE */
+#define ZKFHE_PROF_BFV_HOIST 16    /* k_hoist: c0 and the digits of c1, transformed once per ciphertext */
+#define ZKFHE_PROF_BFV_LINEAR 17   /* k_linear_acc: the pointwise sums over digits and elements */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

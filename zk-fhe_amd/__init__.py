@@ -21,6 +21,7 @@ PROF_BFV_SAMPLE, PROF_RNS_NTT, PROF_RNS_EPILOGUE = 5, 6, 7   # ... and of the BF
 PROF_BFV_TENSOR, PROF_BFV_RELIN, PROF_BFV_EVAL_EPILOGUE, PROF_BFV_ELEMENTWISE = 8, 9, 10, 11   # ... and of the BFV evaluation kernels
 PROF_BFV_SHARE_SUM, PROF_BFV_DECRYPT_COMBINE = 12, 13   # ... and of the threshold kernels
 PROF_BFV_GALOIS, PROF_BFV_SLOT_NTT = 14, 15   # ... and of the slot and rotation kernels
+PROF_BFV_HOIST, PROF_BFV_LINEAR = 16, 17   # ... and of the hoisted rotations and linear transforms
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -48,6 +49,7 @@ EXPORTS = [
     "zkfhe_bfv_decrypt_combine",
     "zkfhe_bfv_slot_count", "zkfhe_bfv_galois_element", "zkfhe_bfv_slot_sum_elements", "zkfhe_bfv_encode_slots", "zkfhe_bfv_decode_slots",
     "zkfhe_bfv_galois_keygen", "zkfhe_bfv_apply_galois", "zkfhe_bfv_slot_sum", "zkfhe_bfv_galois_share",
+    "zkfhe_bfv_apply_galois_many", "zkfhe_bfv_linear_transform",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -725,6 +727,35 @@ class Context:
         self._bfv("zkfhe_bfv_slot_sum", "nppppipp", params, c0.shape[0], c0, c1, gk0, gk1, int(base_bits), *out)
         return tuple(out)
 
+    # ------------------------------------------------------------------ encrypted matrix-vector products (zkfhe.h, bfv_linear.hip)
+    # elements: K Galois elements (repeats allowed); their keys stacked as gk0, gk1 of shape (K, l, N) (the rows of g = 1 are not read).
+
+    def _elements(self, params, elements, gk0, gk1, base_bits):
+        g = np.ascontiguousarray([int(x) for x in elements], dtype=np.uint64).reshape(-1)
+        gk0, gk1 = self._galois_keys(params, gk0, gk1, base_bits, (g.shape[0],))
+        return g, gk0, gk1
+
+    def bfv_apply_galois_many(self, params, c0, c1, elements, gk0, gk1, base_bits=16):
+        """zkfhe_bfv_apply_galois_many: n ciphertexts (n, N) -> (out0, out1) of shape (K, n, N), block k the hoisted rotation of
+        every ciphertext by elements[k] (the digits of c1 are decomposed and transformed once)."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        g, gk0, gk1 = self._elements(params, elements, gk0, gk1, base_bits)
+        out = [np.empty((g.shape[0],) + c0.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_apply_galois_many", "nppnpppipp", params, c0.shape[0], c0, c1, g.shape[0], g, gk0, gk1, int(base_bits), *out)
+        return tuple(out)
+
+    def bfv_linear_transform(self, params, c0, c1, elements, gk0, gk1, diagonals, base_bits=16):
+        """zkfhe_bfv_linear_transform: n ciphertexts (n, N) -> sum_k diagonals[k] * (the hoisted rotation by elements[k]), shape
+        (n, N).  diagonals: K plaintexts (K, N), shared by every ciphertext (bfv_encode_slots of the slot-value diagonals)."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        g, gk0, gk1 = self._elements(params, elements, gk0, gk1, base_bits)
+        d = np.ascontiguousarray(diagonals, dtype=np.uint64)
+        if d.shape != (g.shape[0], int(params[0])):
+            raise ValueError("diagonals must have shape (K, N), one plaintext per element")
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_linear_transform", "nppnpppippp", params, c0.shape[0], c0, c1, g.shape[0], g, gk0, gk1, int(base_bits), d, *out)
+        return tuple(out)
+
 
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 # the parameter letters of Context._bfv
@@ -777,6 +808,29 @@ def bfv_galois_element(params, steps=0, swap_rows=False):
 def bfv_slot_sum_elements(params):
     """zkfhe_bfv_slot_sum_elements (host only): the log2(N) Galois elements of bfv_slot_sum in order, a list of ints."""
     return [int(x) for x in _host_bfv_list("zkfhe_bfv_slot_sum_elements", params)]
+
+
+def bfv_matrix_diagonals(params, matrix):
+    """Host only, Python only: a dense N x N matrix over Z_T acting on the slot vector in slot order (slot p = row N/2 + j) ->
+    (elements, diagonals) with (matrix @ v)[p] = sum_i diagonals[i][p] rot_i(v)[p] mod T, rot_i the slot permutation of
+    elements[i] = 5^k (2N - 1)^swap: both rows left by k, then the rows swapped.  diagonals: slot values of shape (K, N), to be
+    encoded with Context.bfv_encode_slots; all-zero diagonals are dropped (a zero matrix gives K = 0)."""
+    n, t = int(params[0]), int(params[2])
+    bfv_slot_count(params)   # refuses a T that does not batch
+    m = np.asarray(matrix)
+    if m.shape != (n, n):
+        raise ValueError("matrix must have shape (N, N)")
+    m = (m.astype(object) % t).astype(np.uint64) if m.dtype == object else np.mod(m, t).astype(np.uint64)
+    half, p = n // 2, np.arange(n)
+    row, j = p // half, p % half
+    elements, diagonals = [], []
+    for swap in (0, 1):
+        for k in range(half):   # slot (row, j) of the rotated vector holds v[(row ^ swap, j + k)]
+            d = m[p, (row ^ swap) * half + (j + k) % half]
+            if d.any():
+                elements.append(bfv_galois_element(params, k, bool(swap)))
+                diagonals.append(d)
+    return elements, np.array(diagonals, dtype=np.uint64).reshape(-1, n)
 
 
 def bfv_error_cdt(params):
