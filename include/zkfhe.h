@@ -91,6 +91,10 @@ int zkfhe_prof_read_ops(zkfhe_ctx *ctx, int which, double *ops);
  * inputs (examples/bfv.rs:118-122: 5 N + 1 values, one sequential Poseidon chain with the reference's transcript), so [1] - [0]
  * is the time a lone proof waits for the HOST --, [2] the proof is complete. */
 int zkfhe_ctx_last_proof_marks(zkfhe_ctx *ctx, float marks_ms[3]);
+/* Commands the LAST zkfhe_bfv_prove / zkfhe_bfv_prove_words on this context put on its streams (the auxiliary stream of its
+ * workspace included), counted on the host where the library issues them: [0] kernel launches, [1] copy commands
+ * (hipMemcpy*Async), [2] fill commands (hipMemsetAsync).  Reset when a proof starts; costs nothing on the GPU. */
+int zkfhe_ctx_last_proof_commands(zkfhe_ctx *ctx, uint64_t counts[3]);
 
 /* ---- coefficient-wise Fr arithmetic (device buffers, out may alias a or b) ----------------- */
 int zkfhe_fr_add(zkfhe_ctx *ctx, const zkfhe_fr *a_dev, const zkfhe_fr *b_dev, zkfhe_fr *out_dev, size_t n);
@@ -103,6 +107,9 @@ int zkfhe_fr_to_mont(zkfhe_ctx *ctx, const zkfhe_fr *a_dev, zkfhe_fr *out_dev, s
 int zkfhe_fr_from_mont(zkfhe_ctx *ctx, const zkfhe_fr *a_dev, zkfhe_fr *out_dev, size_t n);
 /* in place a[i] <- a[i]^-1, zero stays zero (halo2 batch_invert convention) */
 int zkfhe_fr_batch_invert(zkfhe_ctx *ctx, zkfhe_fr *a_dev, size_t n);
+/* the same inversion with a numerator: num[i] <- num[i] * den[i]^-1 in one kernel (0 where den[i] = 0: what the call above followed
+ * by zkfhe_fr_mul gives); den is only read and must not alias num */
+int zkfhe_fr_batch_invert_mul(zkfhe_ctx *ctx, const zkfhe_fr *den_dev, zkfhe_fr *num_dev, size_t n);
 /* modmul micro-benchmark: out[i] = a[i]^(2^iters) by repeated squaring (ALU-roofline probe) */
 int zkfhe_fr_sqr_chain(zkfhe_ctx *ctx, const zkfhe_fr *a_dev, zkfhe_fr *out_dev, size_t n, int iters);
 /* the same probe for the radix-2^29 product the MSM kernels use (nine 29-bit limbs, Montgomery constant 2^261): a[i] < q as a

@@ -299,6 +299,8 @@ for cfg, stats_f, bench_f, pre, n in (('k13', 'b_single_last_proof.txt', 'bench_
         'zkp::k_quotient_partials': (32.0 * 3 * n * (cc['advice'] + (cc['gate0'] + cc['gate1'] + cc['rlc'] + 2) + cc['perm'] + cc['chunks'] + 3 * cc['lookup'] + 4 + 1),
                                      "32 B x 3 n points x (advice + fixed + sigma + products + lookup polynomials + l_0 / l_last / l_active / X + 1 output)"),
         'k_fr_batch_invert': (64.0 * n * (cc['chunks'] + cc['lookup'] + 6 + 8 + 1), "64 B per element: grand-product denominators, barycentric weights, SHPLONK denominators"),
+        'k_fr_batch_invert<false>': (64.0 * n * (6 + 8 + 1), "64 B per element: barycentric weights, SHPLONK denominators"),
+        'k_fr_batch_invert<true>': (96.0 * n * (cc['chunks'] + cc['lookup']), "96 B per element (denominator and numerator in, ratio out): the grand products"),
         'k_msm_scatter': ((32.0 + 4.0 * 16) * n * (wide + small), "(32 B scalar + 4 B x ~16 entries) per scalar"),
         'k_msm_cscatter': ((32.0 + 4.0 * 16) * n * (wide + small), "(32 B scalar + 4 B x ~16 staged entries) per scalar"),
         'k_msm_fine': ((3 * 4.0 * 16) * n * (wide + small), "4 B x ~16 entries per scalar: two reads of the staged segment, one write of the sorted entries"),

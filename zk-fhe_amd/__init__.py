@@ -26,9 +26,9 @@ PROF_BFV_HOIST, PROF_BFV_LINEAR = 16, 17   # ... and of the hoisted rotations an
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
     "zkfhe_dev_alloc", "zkfhe_dev_free", "zkfhe_upload", "zkfhe_download", "zkfhe_copy_dev", "zkfhe_memset_dev",
-    "zkfhe_timer_start", "zkfhe_timer_stop_ms", "zkfhe_prof_enable", "zkfhe_prof_reset", "zkfhe_prof_read", "zkfhe_prof_read_ops", "zkfhe_ctx_last_proof_marks",
+    "zkfhe_timer_start", "zkfhe_timer_stop_ms", "zkfhe_prof_enable", "zkfhe_prof_reset", "zkfhe_prof_read", "zkfhe_prof_read_ops", "zkfhe_ctx_last_proof_marks", "zkfhe_ctx_last_proof_commands",
     "zkfhe_fr_add", "zkfhe_fr_sub", "zkfhe_fr_mul", "zkfhe_fr_scale", "zkfhe_fr_to_mont", "zkfhe_fr_from_mont",
-    "zkfhe_fr_batch_invert", "zkfhe_fr_sqr_chain", "zkfhe_fq29_sqr_chain",
+    "zkfhe_fr_batch_invert", "zkfhe_fr_batch_invert_mul", "zkfhe_fr_sqr_chain", "zkfhe_fq29_sqr_chain",
     "zkfhe_ntt_batch", "zkfhe_ntt_batch_to", "zkfhe_coset_ntt_batch",
     "zkfhe_basis_create", "zkfhe_basis_destroy", "zkfhe_basis_len", "zkfhe_msm_batch",
     "zkfhe_g1_add", "zkfhe_g1_mul", "zkfhe_msm_sparse", "zkfhe_msm_batch_xyzz", "zkfhe_msm_sparse_xyzz", "zkfhe_g1_xyzz_to_affine", "zkfhe_basis_has_multiples", "zkfhe_basis_table_bits", "zkfhe_basis_table_bytes", "zkfhe_srs_table_bits", "zkfhe_srs_table_info",
@@ -101,6 +101,7 @@ def load_library():
     lib.zkfhe_fr_to_mont.argtypes = [vp, vp, vp, sz]
     lib.zkfhe_fr_from_mont.argtypes = [vp, vp, vp, sz]
     lib.zkfhe_fr_batch_invert.argtypes = [vp, vp, sz]
+    lib.zkfhe_fr_batch_invert_mul.argtypes = [vp, vp, vp, sz]
     lib.zkfhe_fr_sqr_chain.argtypes = [vp, vp, vp, sz, ci]
     lib.zkfhe_ntt_batch.argtypes = [vp, vp, sz, ci, ci]
     lib.zkfhe_coset_ntt_batch.argtypes = [vp, vp, vp, sz, ci, ci, vp, ci]
@@ -225,6 +226,13 @@ class Context:
         self._check(self.lib.zkfhe_ctx_last_proof_marks(self.h, m))
         return list(m)
 
+    def last_proof_commands(self):
+        """zkfhe_ctx_last_proof_commands: what the last proof on this context put on its streams, counted on the host"""
+        c = (ctypes.c_uint64 * 3)()
+        self.lib.zkfhe_ctx_last_proof_commands.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+        self._check(self.lib.zkfhe_ctx_last_proof_commands(self.h, c))
+        return {"kernel_launches": int(c[0]), "copy_commands": int(c[1]), "fill_commands": int(c[2])}
+
     def prof_read(self, which):
         self.lib.zkfhe_prof_read.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                              ctypes.POINTER(ctypes.c_double)]
@@ -277,6 +285,16 @@ class Context:
         self.fr_binop_dev(op, da, db, da, n)
         out = da.download(shape=a.shape)
         da.free(), db.free()
+        return out
+
+    def fr_batch_invert_mul(self, num, den):
+        """zkfhe_fr_batch_invert_mul: num[i] * den[i]^-1 (0 where den[i] = 0)"""
+        num, den = self._fr(num), self._fr(den)
+        n = num.size // 4
+        dn, dd = self.to_device(num), self.to_device(den)
+        self._check(self.lib.zkfhe_fr_batch_invert_mul(self.h, self._p(dd), self._p(dn), n))
+        out = dn.download(shape=num.shape)
+        dn.free(), dd.free()
         return out
 
     def fr_unop(self, name, a, *extra):

@@ -60,6 +60,11 @@ struct zkfhe_ctx {
   // host-side marks of the last proof made on this context, ms from its start (zkfhe_ctx_last_proof_marks): [0] the phase-0
   // commitment is back from the GPU, [1] the first challenge is squeezed (behind the public inputs' sponge), [2] the proof is done
   float proof_marks[3] = {0, 0, 0};
+  // commands the last proof put on its streams, counted on the host where they are issued (zkfhe_ctx_last_proof_commands):
+  // [ZK_CMD_KERNEL] kernel launches, [ZK_CMD_COPY] hipMemcpy*Async, [ZK_CMD_FILL] hipMemsetAsync.  A prover workspace's
+  // auxiliary context counts into the context of the proof (cmd_owner, set by the proof; both are driven by one host thread).
+  uint64_t cmd_count[3] = {0, 0, 0};
+  zkfhe_ctx *cmd_owner = nullptr;
   unsigned *tickets = nullptr;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
   // the BFV calls (rns_ntt.hip.hpp): the RNS twiddle tables (built on first use) and a grow-only work arena
   uint32_t *bfv_tw = nullptr;
@@ -96,7 +101,25 @@ int zk_fail_msg(zkfhe_ctx *ctx, int code, const std::string &msg);
     if (_e != hipSuccess) return zk_fail((ctx), ZKFHE_EHIP, #expr, _e, __FILE__, __LINE__); \
   } while (0)
 
-#define ZK_LAUNCH_CHECK(ctx) ZK_HIP(ctx, hipGetLastError())
+enum { ZK_CMD_KERNEL = 0, ZK_CMD_COPY = 1, ZK_CMD_FILL = 2 };
+static inline void zk_count(zkfhe_ctx *ctx, int which) { ++(ctx->cmd_owner ? ctx->cmd_owner : ctx)->cmd_count[which]; }
+
+// after every kernel launch: counts it and picks up a launch error
+#define ZK_LAUNCH_CHECK(ctx)         \
+  do {                               \
+    zk_count((ctx), ZK_CMD_KERNEL);  \
+    ZK_HIP(ctx, hipGetLastError());  \
+  } while (0)
+
+// the stream-ordered copy and fill commands of the library go through these two: counted like the launches
+static inline hipError_t zk_memcpy_async(zkfhe_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t stream) {
+  zk_count(ctx, ZK_CMD_COPY);
+  return hipMemcpyAsync(dst, src, bytes, kind, stream);
+}
+static inline hipError_t zk_memset_async(zkfhe_ctx *ctx, void *dst, int value, size_t bytes, hipStream_t stream) {
+  zk_count(ctx, ZK_CMD_FILL);
+  return hipMemsetAsync(dst, value, bytes, stream);
+}
 
 // HIP's current device is per host thread: every public entry point selects the context's device first, so contexts
 // of different GPUs (one process per GPU under torchrun, or several worker threads) never launch on the wrong one.

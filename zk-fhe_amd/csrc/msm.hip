@@ -1173,7 +1173,7 @@ int msm_table(zkfhe_ctx *ctx, const zkfhe_basis *basis, const Fr *scalars, size_
   const size_t words = 2 * MSM_MAX_COLS + 4;
   if (!ctx->tickets) {
     ZK_HIP(ctx, hipMalloc((void **)&ctx->tickets, words * sizeof(unsigned)));
-    ZK_HIP(ctx, hipMemsetAsync(ctx->tickets, 0, words * sizeof(unsigned), ctx->stream));
+    ZK_HIP(ctx, zk_memset_async(ctx, ctx->tickets, 0, words * sizeof(unsigned), ctx->stream));
   }
   unsigned *n_part = ctx->tickets, *col_next = ctx->tickets + MSM_MAX_COLS;
   unsigned long long *adds = (unsigned long long *)(ctx->tickets + 2 * MSM_MAX_COLS);
@@ -1194,7 +1194,7 @@ int msm_table(zkfhe_ctx *ctx, const zkfhe_basis *basis, const Fr *scalars, size_
   if (rc) return rc;
   const bool big = n_cols * n > ((size_t)1 << 16);
   const int slot = big ? 0 : 2;
-  if (ctx->prof_on) ZK_HIP(ctx, hipMemsetAsync(adds, 0, 8, ctx->stream));
+  if (ctx->prof_on) ZK_HIP(ctx, zk_memset_async(ctx, adds, 0, 8, ctx->stream));
   zk_prof_begin(ctx);
   if (tree)
     k_msm_table<true><<<(unsigned)grid, 256, 0, ctx->stream>>>(scalars, col_stride, n, basis->mult, c, W, table_bias(c, W), (unsigned)P, (unsigned)cpc, (unsigned)n_cols,
@@ -1276,7 +1276,7 @@ int zk_basis_create_scaled(zkfhe_ctx *ctx, const zkfhe_g1_affine *bases_host, si
   void *tmp;
   int rc = zk_scratch(ctx, 0, n * sizeof(G1Affine), &tmp);
   if (rc) return rc;
-  ZK_HIP(ctx, hipMemcpyAsync(tmp, bases_host, n * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, zk_memcpy_async(ctx, tmp, bases_host, n * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
   k_basis_table<<<zk_blocks(n, 256), 256, 0, ctx->stream>>>((const G1Affine *)tmp, n, c, windows, b->table);
   ZK_LAUNCH_CHECK(ctx);
   int mc = window_bits == 0 && n >= 256 ? table_bits(n, table_budget_scale) : 0;

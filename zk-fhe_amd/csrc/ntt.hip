@@ -325,7 +325,7 @@ int zk_domain(zkfhe_ctx *ctx, int log_n, const NttDomain **out) {
     k_pow_table_scaled<<<grid, 256, 0, ctx->stream>>>(c32, d.omega_inv, d.inv29, n);
     ZK_LAUNCH_CHECK(ctx);
     ZK_HIP(ctx, hipMalloc((void **)&d.n_inv29_dev, 64));
-    ZK_HIP(ctx, hipMemcpyAsync(d.n_inv29_dev, &d.n_inv29, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(ctx, zk_memcpy_async(ctx, d.n_inv29_dev, &d.n_inv29, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the source is a local of this function
     it = ctx->domains.emplace(log_n, d).first;
     guard.d = nullptr;

@@ -86,7 +86,7 @@ int zkfhe_witness_poly_mul_u64(zkfhe_ctx *ctx, const uint64_t *a_dev, const uint
   if (!rc) rc = zkfhe_fr_mul(ctx, (const zkfhe_fr *)buf, (const zkfhe_fr *)(buf + m), (zkfhe_fr *)buf, m);
   if (!rc) rc = zkfhe_ntt_batch(ctx, (zkfhe_fr *)buf, 1, log_m, 1);
   if (!rc) {
-    e = hipMemcpyAsync(out_dev, buf, (2 * n - 1) * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream);
+    e = zk_memcpy_async(ctx, out_dev, buf, (2 * n - 1) * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream);
     if (e != hipSuccess) rc = zk_fail(ctx, ZKFHE_EHIP, "hipMemcpyAsync", e, __FILE__, __LINE__);
   }
   return rc;
@@ -101,14 +101,14 @@ int zkfhe_witness_div_mod(zkfhe_ctx *ctx, const zkfhe_fr *a_dev, uint64_t q, zkf
   int rc = zk_scratch(ctx, 3, 64, &p);
   if (rc) return rc;
   int *err = (int *)p + 8;
-  ZK_HIP(ctx, hipMemsetAsync(err, 0, sizeof(int), ctx->stream));
+  ZK_HIP(ctx, zk_memset_async(ctx, err, 0, sizeof(int), ctx->stream));
   unsigned grid = zk_blocks(n, 256);
   const unsigned cap = (unsigned)ctx->num_cu * 8;
   if (grid > cap) grid = cap;
   k_div_mod<<<grid, 256, 0, ctx->stream>>>((const Fr *)a_dev, q, (Fr *)div_dev, (Fr *)rem_dev, n, err);
   ZK_LAUNCH_CHECK(ctx);
   int h = 0;
-  ZK_HIP(ctx, hipMemcpyAsync(&h, err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(ctx, zk_memcpy_async(ctx, &h, err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (h) return zk_fail_msg(ctx, ZKFHE_EINVAL, "zkfhe_witness_div_mod: an input value does not fit 128 bits");
   return ZKFHE_OK;

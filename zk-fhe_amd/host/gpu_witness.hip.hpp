@@ -12,6 +12,7 @@
 #pragma once
 #include "../csrc/ctx.hpp"
 #include "../csrc/fr29.hip.hpp"
+#include "prover_kernels.hip.hpp"   // the blinding stream (zkp::RngRows): the placement kernels draw the blinding rows of their columns
 
 namespace zkw {
 
@@ -275,12 +276,20 @@ static __global__ void __launch_bounds__(256) k_gadget(const GadgetArgs *__restr
 }
 
 // stream -> columns: column c, rows 0..len_c-1  <-  stream[start_c ..]  (a break-point duplicate is simply the next cell)
+// blind.on: rows >= u are the columns' blinding rows (column c of this call is column c of blind's counters): the first data_blocks
+// workgroups place the rows below u, the workgroups behind them draw (zkp::rng_tail_blocks)
 static __global__ void __launch_bounds__(256) k_place(const Fr *__restrict__ stream, const unsigned *__restrict__ col_start,
-                                               const unsigned *__restrict__ col_len, unsigned n_cols, size_t n, Fr *__restrict__ cols) {
+                                               const unsigned *__restrict__ col_len, unsigned n_cols, size_t n, Fr *__restrict__ cols, zkp::RngRows blind, unsigned u,
+                                               unsigned data_blocks) {
+  if (blockIdx.x >= data_blocks) {
+    zkp::rng_tail_blocks(blind, data_blocks, cols + u, n - u, n, n_cols);
+    return;
+  }
   const size_t total = (size_t)n_cols * n;
-  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)data_blocks * blockDim.x) {
     const unsigned c = (unsigned)(g / n);
     const unsigned r = (unsigned)(g - (size_t)c * n);
+    if (blind.on && r >= u) continue;
     cols[g] = r < col_len[c] ? stream[col_start[c] + r] : Fr::zero();
   }
 }
@@ -290,12 +299,20 @@ struct PatchCell {
   Fr *dst_adv, *dst_patch;
   unsigned value;   // index into the values array
 };
-static __global__ void __launch_bounds__(64) k_patch_cells(const PatchCell *__restrict__ cells, unsigned count, const Fr *__restrict__ values) {
+// cells and values by kernel argument (2 KB): they depend on the challenge, and a table would need a transfer of its own
+struct PatchList {
+  PatchCell cells[64];
+  Fr values[16];
+};
+static __global__ void __launch_bounds__(64) k_patch_cells(PatchList list, unsigned count) {
+  __shared__ PatchList sh;   // a copy the lanes can index
+  if (threadIdx.x == 0) sh = list;
+  __syncthreads();
   const unsigned i = threadIdx.x;
   if (i >= count) return;
-  const Fr v = values[cells[i].value];
-  *cells[i].dst_adv = v;
-  if (cells[i].dst_patch) *cells[i].dst_patch = v;
+  const Fr v = sh.values[sh.cells[i].value];
+  *sh.cells[i].dst_adv = v;
+  if (sh.cells[i].dst_patch) *sh.cells[i].dst_patch = v;
 }
 // up to four runs of four reserved cells back to zero (one launch instead of four fills)
 struct ZeroRuns {
@@ -306,14 +323,22 @@ static __global__ void __launch_bounds__(64) k_zero_runs(ZeroRuns z) {
   const unsigned i = threadIdx.x >> 2, j = threadIdx.x & 3;
   if (i < z.count) z.at[i][j] = Fr::zero();
 }
-// lookup advice columns: the k-th looked-up cell goes to column k / max_rows, row k % max_rows
+// lookup advice columns: the k-th looked-up cell goes to column k / max_rows, row k % max_rows.  blind as in k_place; zero_cols
+// columns behind the lookup columns are cleared by the same launch (the RLC columns of an early phase-1 commitment).
 static __global__ void __launch_bounds__(256) k_place_lookups(const Fr *__restrict__ stream, const unsigned *__restrict__ src_off, size_t n_lookups,
-                                                       unsigned max_rows, size_t n, unsigned n_lookup_cols, Fr *__restrict__ cols) {
-  const size_t total = (size_t)n_lookup_cols * n;
-  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+                                                       unsigned max_rows, size_t n, unsigned n_lookup_cols, Fr *__restrict__ cols, zkp::RngRows blind, unsigned u,
+                                                       unsigned zero_cols, unsigned data_blocks) {
+  if (blockIdx.x >= data_blocks) {
+    zkp::rng_tail_blocks(blind, data_blocks, cols + u, n - u, n, n_lookup_cols);
+    return;
+  }
+  const size_t total = (size_t)(n_lookup_cols + zero_cols) * n;
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)data_blocks * blockDim.x) {
     const size_t c = g / n, r = g - c * n;
     const size_t k = c * max_rows + r;
-    cols[g] = (r < max_rows && k < n_lookups) ? stream[src_off[k]] : Fr::zero();
+    if (c >= n_lookup_cols) cols[g] = Fr::zero();
+    else if (blind.on && r >= u) continue;
+    else cols[g] = (r < max_rows && k < n_lookups) ? stream[src_off[k]] : Fr::zero();
   }
 }
 // deferred inverses: gather the slots, (batch invert), scatter back
@@ -328,8 +353,10 @@ static __global__ void __launch_bounds__(256) k_scatter(Fr *__restrict__ dst, co
 
 // halo2 permute_expression_pair for an 8-bit table, one workgroup per lookup column.
 // in: Lagrange column (Montgomery), rows < u are the inputs.  out_a / out_s rows < u (Montgomery); err set if a value > 255.
+// blind.on: rows >= u of both outputs are blinding rows, drawn here: column c of out_a from blind's counters, column c of out_s
+// n - u draws further on (la_i then ls_i, lookup by lookup: two interleaved runs of the stream).
 static __global__ void __launch_bounds__(1024) k_lookup_permute(const Fr *__restrict__ in, size_t n, unsigned u, Fr *__restrict__ out_a, Fr *__restrict__ out_s,
-                                                        int *__restrict__ err) {
+                                                        int *__restrict__ err, zkp::RngRows blind) {
   __shared__ unsigned cnt[256], start[257], hole0[257], left0[257];
   __shared__ Fr mont[256];
   const Fr *col = in + (size_t)blockIdx.x * n;
@@ -393,6 +420,13 @@ static __global__ void __launch_bounds__(1024) k_lookup_permute(const Fr *__rest
       // a is the LAST value with left0[a] <= j; values with no leftover share left0 with their successor, and the last
       // of such a tie is the one that owns j
       os[i] = mont[a];
+    }
+  }
+  if (blind.on) {
+    const unsigned nbl = (unsigned)n - u;
+    for (unsigned j = t; j < 2 * nbl; j += T) {
+      const Fr v = zkp::rng_row(blind, blockIdx.x, j);   // j < nbl: la's rows, then ls's
+      if (j < nbl) oa[u + j] = v; else os[u + j - nbl] = v;
     }
   }
 }
@@ -469,11 +503,14 @@ static __global__ void __launch_bounds__(1024) k_lookup_fill(const unsigned *__r
   }
 }
 // the launch: one workgroup per column up to n = 2^15, row slices of 2^14 beyond
+// blind (optional): the blinding rows u .. n - 1 of out_a / out_s, counters as k_lookup_permute reads them
 static inline int lookup_permute(zkfhe_ctx *ctx, const Fr *in, size_t n, unsigned u, unsigned n_cols, Fr *out_a, Fr *out_s, int *err,
-                                 unsigned *hist = nullptr /* n_cols * 256 words of the caller's, or scratch slot 3 */) {
+                                 unsigned *hist = nullptr /* n_cols * 256 words of the caller's, or scratch slot 3 */, const zkp::RngRows *blind = nullptr) {
   if (!n_cols) return ZKFHE_OK;
+  zkp::RngRows b{};
+  if (blind) b = *blind;
   if (n <= 32768) {
-    k_lookup_permute<<<n_cols, 1024, 0, ctx->stream>>>(in, n, u, out_a, out_s, err);
+    k_lookup_permute<<<n_cols, 1024, 0, ctx->stream>>>(in, n, u, out_a, out_s, err, b);
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
   }
@@ -482,12 +519,20 @@ static inline int lookup_permute(zkfhe_ctx *ctx, const Fr *in, size_t n, unsigne
     const int rc = zk_scratch(ctx, 3, (size_t)n_cols * 256 * sizeof(unsigned), &p);
     if (rc) return rc;
   }
-  ZK_HIP(ctx, hipMemsetAsync(p, 0, (size_t)n_cols * 256 * sizeof(unsigned), ctx->stream));
+  ZK_HIP(ctx, zk_memset_async(ctx, p, 0, (size_t)n_cols * 256 * sizeof(unsigned), ctx->stream));
   const dim3 grid(n_cols, (unsigned)(n >> 14));
   k_lookup_count<<<grid, 1024, 0, ctx->stream>>>(in, n, u, (unsigned *)p, err);
   ZK_LAUNCH_CHECK(ctx);
   k_lookup_fill<<<grid, 1024, 0, ctx->stream>>>((const unsigned *)p, n, u, out_a, out_s);
   ZK_LAUNCH_CHECK(ctx);
+  if (b.on) {   // long columns keep the blinding rows' own launches
+    const size_t nbl = n - u;
+    const unsigned g = (unsigned)((nbl * n_cols + 255) / 256);
+    zkp::k_rng_fill<<<g, 256, 0, ctx->stream>>>(b.seed, b.ctr0, b.ctr_col_stride, out_a + u, nbl, n, n_cols);
+    ZK_LAUNCH_CHECK(ctx);
+    zkp::k_rng_fill<<<g, 256, 0, ctx->stream>>>(b.seed, b.ctr0 + nbl, b.ctr_col_stride, out_s + u, nbl, n, n_cols);
+    ZK_LAUNCH_CHECK(ctx);
+  }
   return ZKFHE_OK;
 }
 

@@ -22,7 +22,7 @@ const U256 *GpuPolyMul::mul_u64_raw(const std::vector<uint64_t> &a, const std::v
   if (!rc) rc = zkfhe_witness_poly_mul_u64(ctx, da, db, n, (zkfhe_fr *)dout);
   if (!rc) rc = zkfhe_fr_from_mont(ctx, (const zkfhe_fr *)dout, (zkfhe_fr *)dout, 2 * n - 1);
   if (!rc && ws->host_poly && 2 * n - 1 <= ws->host_poly_len) {
-    if (hipMemcpyAsync(ws->host_poly, dout, (2 * n - 1) * 32, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = ZKFHE_EHIP;
+    if (zk_memcpy_async(ctx, ws->host_poly, dout, (2 * n - 1) * 32, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = ZKFHE_EHIP;
     if (!rc) rc = zkfhe_sync(ctx);
   } else if (!rc) {
     pageable.resize(2 * n - 1);
@@ -40,7 +40,7 @@ int up(zkfhe_ctx *ctx, Workspace *ws, void *dst, const void *src, size_t bytes) 
   uint8_t *slot = ws->ring + ws->ring_off;
   ws->ring_off += need;
   memcpy(slot, src, bytes);
-  ZK_HIP(ctx, hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, zk_memcpy_async(ctx, dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream));
   return ZKFHE_OK;
 }
 
@@ -64,7 +64,7 @@ int alloc_workspace(zkfhe_ctx *ctx, const CircuitConfig &c, Workspace *ws, int e
     take(ws->lz_l, ws->lz_ext, c.n_lookup);
     take(ws->inst_l, ws->inst_ext, 1);
   }
-  ZK_HIP(ctx, hipMemsetAsync(ws->inst_l.p, 0, col, ctx->stream));   // the prover only ever writes the public-input rows
+  ZK_HIP(ctx, zk_memset_async(ctx, ws->inst_l.p, 0, col, ctx->stream));   // the prover only ever writes the public-input rows
   ws->inst_count = 0;
   CK(ws->tmp_c.alloc(ctx, std::max<size_t>(n_all, c.n_perm()) * col));
   {
@@ -280,7 +280,7 @@ static int keygen_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, const char *input_j
   CK(pk->sigma_l.alloc(ctx, cells * 32));
   CK(pk->dpow.alloc(ctx, (size_t)cfg.n_perm() * 32));
   for (unsigned c = 0; c < cfg.n_fixed(); ++c) {
-    ZK_HIP(ctx, hipMemcpyAsync(pk->fixed_l.fr() + (size_t)c * n, as.t.fixed[c].data(), n * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(ctx, zk_memcpy_async(ctx, pk->fixed_l.fr() + (size_t)c * n, as.t.fixed[c].data(), n * 32, hipMemcpyHostToDevice, ctx->stream));
   }
   CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)pk->fixed_l.p, (zkfhe_fr *)pk->fixed_l.p, (size_t)cfg.n_fixed() * n));
   U256 dcan;

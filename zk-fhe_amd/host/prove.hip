@@ -133,7 +133,7 @@ class GpuPhase1 {
     n_mg = 0;
     h_used += 16;
     pool_used = h_used;
-    if (!in_ring) ZK_HIP(ctx, hipMemcpyAsync(ws->pool.p, ws->host_pool, mg_slot * 32, hipMemcpyHostToDevice, ctx->stream));
+    if (!in_ring) ZK_HIP(ctx, zk_memcpy_async(ctx, ws->pool.p, ws->host_pool, mg_slot * 32, hipMemcpyHostToDevice, ctx->stream));
 
     CK(in_range(e0, B, Q));
     CK(in_range(e1, B, Q));
@@ -189,13 +189,13 @@ class GpuPhase1 {
   // Everything of phase 1 except the cells that depend on the challenge: the reserved constrain_mul cells stay zero in the
   // stream, then stream -> gate columns (break points) and lookup columns.  The columns can be committed from here on;
   // patch() supplies the missing cells and the correction columns.
-  int place_early() {
+  int place_early(const zkp::RngRows &blind, unsigned zero_cols) {
     zkw::ZeroRuns z{};
     z.count = n_mg;
     for (unsigned i = 0; i < n_mg; ++i) z.at[i] = stream + mg_off[i];
     zkw::k_zero_runs<<<1, 64, 0, ctx->stream>>>(z);
     ZK_LAUNCH_CHECK(ctx);
-    return place();
+    return place(blind, zero_cols);
   }
   // (gate column, row) of every reserved cell -- twice for a cell on a break point, whose value is repeated at the top of the
   // next column.  columns: the distinct affected gate columns, in ascending order.
@@ -254,65 +254,70 @@ class GpuPhase1 {
         terms->push_back(t);
       }
     }
-    std::vector<zkw::PatchCell> cells(plan.cells.size());
-    for (size_t t = 0; t < cells.size(); ++t) {
+    if (plan.cells.size() > 64) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many challenge-dependent gate cells");
+    zkw::PatchList list{};
+    for (size_t t = 0; t < plan.cells.size(); ++t) {
       const auto &c = plan.cells[t];
-      cells[t].dst_adv = ws->adv_l.fr() + ((size_t)cfg.n_gate0 + plan.columns[c.col_slot]) * n + c.row;
-      cells[t].dst_patch = terms ? nullptr : patch_cols + (size_t)c.col_slot * n + c.row;   // dense correction columns only without the sparse MSM
-      cells[t].value = c.value;
+      list.cells[t].dst_adv = ws->adv_l.fr() + ((size_t)cfg.n_gate0 + plan.columns[c.col_slot]) * n + c.row;
+      list.cells[t].dst_patch = terms ? nullptr : patch_cols + (size_t)c.col_slot * n + c.row;   // dense correction columns only without the sparse MSM
+      list.cells[t].value = c.value;
     }
-    if (cells.size() > 64) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many challenge-dependent gate cells");
-    STAGE(vals_dev, Fr, ws, mg, sizeof(mg));
-    STAGE(cells_dev, zkw::PatchCell, ws, cells.data(), cells.size() * sizeof(zkw::PatchCell));
-    CK(flush_staged(ctx, ws));
-    if (!terms) ZK_HIP(ctx, hipMemsetAsync(patch_cols, 0, plan.columns.size() * n * 32, ctx->stream));
-    zkw::k_patch_cells<<<1, 64, 0, ctx->stream>>>(cells_dev, (unsigned)cells.size(), vals_dev);
+    memcpy(list.values, mg, sizeof(mg));
+    if (!terms) ZK_HIP(ctx, zk_memset_async(ctx, patch_cols, 0, plan.columns.size() * n * 32, ctx->stream));
+    zkw::k_patch_cells<<<1, 64, 0, ctx->stream>>>(list, (unsigned)plan.cells.size());
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
   }
 
   // evals[3 i .. 3 i + 2] = a(gamma), b(gamma), c(gamma) of the i-th constrain_mul: fill the reserved gate cells, then
   // stream -> gate columns (break points) and lookup columns
-  int finish(const U256 evals[12]) {
-    // the 16 values and their destinations go up with the staging ring, one small kernel stores them (it used to be one
-    // upload and four device copies)
+  int finish(const U256 evals[12], const zkp::RngRows &blind) {
+    // the 16 values and their destinations are arguments of one small kernel that stores them (it used to be one upload and
+    // four device copies, then a table in the staging ring)
     Fr mg[16];
     for (int i = 0; i < 4; ++i) {
       mg[4 * i] = Fr::zero();
       for (int j = 0; j < 3; ++j) mg[4 * i + 1 + j] = mont(evals[3 * i + j]);
     }
-    zkw::PatchCell cells[16];
+    zkw::PatchList list{};
     unsigned nc = 0;
     for (unsigned i = 0; i < n_mg; ++i)
       for (unsigned j = 0; j < 4; ++j) {
-        cells[nc].dst_adv = stream + mg_off[i] + j;
-        cells[nc].dst_patch = nullptr;
-        cells[nc].value = 4 * i + j;
+        list.cells[nc].dst_adv = stream + mg_off[i] + j;
+        list.cells[nc].dst_patch = nullptr;
+        list.cells[nc].value = 4 * i + j;
         ++nc;
       }
+    memcpy(list.values, mg, sizeof(mg));
     if (nc) {
-      STAGE(vals_dev, Fr, ws, mg, sizeof(mg));
-      STAGE(cells_dev, zkw::PatchCell, ws, cells, nc * sizeof(zkw::PatchCell));
-      CK(flush_staged(ctx, ws));
-      zkw::k_patch_cells<<<1, 64, 0, ctx->stream>>>(cells_dev, nc, vals_dev);
+      zkw::k_patch_cells<<<1, 64, 0, ctx->stream>>>(list, nc);
       ZK_LAUNCH_CHECK(ctx);
     }
-    return place();
+    return place(blind, 0);
   }
 
  private:
-  int place() {
+  // blind: the blinding rows u .. n - 1 of the phase-1 gate and lookup advice columns, drawn by the placement kernels (its counters
+  // start at the first phase-1 gate column); zero_cols: that many columns behind the lookup columns are cleared by the same launch
+  int place(const zkp::RngRows &blind, unsigned zero_cols) {
     const CircuitConfig &cfg = pk->cfg;
     const size_t n = cfg.n();
-    zkw::k_place<<<grid_for(ctx, (size_t)cfg.n_gate1 * n), 256, 0, ctx->stream>>>(stream, (const unsigned *)pk->place_start.p, (const unsigned *)pk->place_len.p,
-                                                                                 cfg.n_gate1, n, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n);
+    const unsigned u = (unsigned)cfg.u();
+    const unsigned g_place = grid_for(ctx, (size_t)cfg.n_gate1 * n);
+    zkw::k_place<<<g_place + zkp::rng_tail_grid(blind, (size_t)cfg.n_gate1 * (n - u), 256), 256, 0, ctx->stream>>>(
+        stream, (const unsigned *)pk->place_start.p, (const unsigned *)pk->place_len.p, cfg.n_gate1, n, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, blind, u, g_place);
     ZK_LAUNCH_CHECK(ctx);
     if (cfg.n_lookup) {
       if (pk->n_lookup_cells > (size_t)cfg.n_lookup * cfg.max_rows()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup cells do not fit the configured lookup columns");
-      zkw::k_place_lookups<<<grid_for(ctx, (size_t)cfg.n_lookup * n), 256, 0, ctx->stream>>>(stream, (const unsigned *)pk->lookup_src.p, pk->n_lookup_cells,
-                                                                                           (unsigned)cfg.max_rows(), n, cfg.n_lookup,
-                                                                                           ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n);
+      zkp::RngRows blind_lk = blind;
+      blind_lk.ctr0 += (unsigned long long)(cfg.adv_lookup0() - cfg.n_gate0) * blind.ctr_col_stride;
+      const unsigned g_lk = grid_for(ctx, (size_t)(cfg.n_lookup + zero_cols) * n);
+      zkw::k_place_lookups<<<g_lk + zkp::rng_tail_grid(blind_lk, (size_t)cfg.n_lookup * (n - u), 256), 256, 0, ctx->stream>>>(
+          stream, (const unsigned *)pk->lookup_src.p, pk->n_lookup_cells, (unsigned)cfg.max_rows(), n, cfg.n_lookup, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, blind_lk, u,
+          zero_cols, g_lk);
       ZK_LAUNCH_CHECK(ctx);
+    } else if (zero_cols) {
+      ZK_HIP(ctx, zk_memset_async(ctx, ws->adv_l.fr() + (size_t)cfg.adv_rlc0() * n, 0, (size_t)zero_cols * n * 32, ctx->stream));
     }
     return ZKFHE_OK;
   }
@@ -540,6 +545,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   const size_t n = cfg.n(), u = cfg.u(), ne = 4 * n;
   const unsigned k = cfg.k;
   const double t_start = now_ms();
+  ctx->cmd_count[ZK_CMD_KERNEL] = ctx->cmd_count[ZK_CMD_COPY] = ctx->cmd_count[ZK_CMD_FILL] = 0;   // zkfhe_ctx_last_proof_commands: this proof's
   Trace trace;
   // The blinding stream (draw i = Blake2b(seed || i) mod r) is evaluated on the device, where each value is needed
   // (prover_kernels.hip.hpp k_rng_fill).  Draw order = oracle/halo2_ref.py: the blinding rows of every advice column in
@@ -555,6 +561,15 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     zkp::k_rng_fill<<<grid_for(ctx, per_col * n_cols), 256, 0, stream>>>(rseed, ctr0, ctr_col_stride, dst, per_col, col_stride, n_cols);
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
+  };
+  // the same draws by the kernel that writes the rest of the columns (zkp::RngRows): counters of column 0, counters per column
+  auto blind_rows = [&](uint64_t ctr0, uint64_t ctr_col_stride) {
+    zkp::RngRows b;
+    b.seed = rseed;
+    b.ctr0 = ctr0;
+    b.ctr_col_stride = ctr_col_stride;
+    b.on = 1;
+    return b;
   };
   Transcript tr(cfg.transcript);
   const NttDomain *dom;
@@ -572,7 +587,9 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   // queued: drain the stream before the buffers are rewritten (free when the stream is idle)
   CK(zkfhe_sync(ctx));
   CK(alloc_witness_buffers(ctx, pk, ws));
+  ws->aux->cmd_owner = ctx;   // the auxiliary stream's commands are this proof's
   ws->ring_off = ws->ring_flushed = 0;
+  ws->inst_pending = false;
   trace.mark("setup (workspace)");
   // random polynomial, early: its coefficients (the tail of the blinding stream) depend on no challenge, so they are drawn and
   // committed on the auxiliary stream beside the phase-0 / witness work.  The main stream is idle here (synchronised above)
@@ -642,10 +659,13 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   // the instance column's values ride up with the proof's first table flush (they are needed from the grand products on)
   if (instances.size() > n) return zk_fail_msg(ctx, ZKFHE_EINVAL, "more public inputs than rows");
   const bool inst_via_ring = instances.size() * 32 <= ((size_t)1 << 20);   // long instance columns (k >= 18) keep their own copy
-  const U256 *inst_staged = nullptr;
   if (inst_via_ring) {
     STAGE(staged, U256, ws, instances.data(), instances.size() * 32);
-    inst_staged = staged;
+    // ... and the flush kernel that carries them converts them into the instance column on its way (the column is idle until the
+    // grand products, and the previous proof on this workspace is complete)
+    ws->inst_src = (const Fr *)(ws->ring + ((const uint8_t *)staged - (const uint8_t *)ws->dev_ring.p));
+    ws->inst_n = instances.size();
+    ws->inst_pending = true;
   }
   auto blind_and_upload = [&](unsigned c_lo, unsigned c_hi) -> int {
     // the table is pinned and column-contiguous; the blinding rows u .. n-1 are drawn on the device.  The conversion kernel reads the
@@ -655,11 +675,14 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     const char *upload_env = getenv("ZKFHE_UPLOAD");   // read per proof, like ZKFHE_WITNESS / ZKFHE_EARLY_P1 (the tests switch it)
     const bool upload_by_copy = upload_env && !strcmp(upload_env, "copy");
     if (upload_by_copy) {
-      ZK_HIP(ctx, hipMemcpyAsync(ws->adv_l.fr() + (size_t)c_lo * n, as.t.advice[c_lo], (size_t)(c_hi - c_lo) * n * 32, hipMemcpyHostToDevice, ctx->stream));
+      ZK_HIP(ctx, zk_memcpy_async(ctx, ws->adv_l.fr() + (size_t)c_lo * n, as.t.advice[c_lo], (size_t)(c_hi - c_lo) * n * 32, hipMemcpyHostToDevice, ctx->stream));
       CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)(ws->adv_l.fr() + (size_t)c_lo * n), (zkfhe_fr *)(ws->adv_l.fr() + (size_t)c_lo * n),
                           (size_t)(c_hi - c_lo) * n));
     } else {
-      CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)as.t.advice[c_lo], (zkfhe_fr *)(ws->adv_l.fr() + (size_t)c_lo * n), (size_t)(c_hi - c_lo) * n));
+      zkp::k_to_mont_blind<<<grid_for(ctx, (size_t)(c_hi - c_lo) * n), 256, 0, ctx->stream>>>((const Fr *)as.t.advice[c_lo], ws->adv_l.fr() + (size_t)c_lo * n, n, (unsigned)u,
+                                                                                               c_hi - c_lo, blind_rows(ctr_adv + (uint64_t)c_lo * nbl_all, nbl_all));
+      ZK_LAUNCH_CHECK(ctx);
+      return ZKFHE_OK;
     }
     return rng_fill(ctx->stream, ctr_adv + (uint64_t)c_lo * nbl_all, nbl_all, ws->adv_l.fr() + (size_t)c_lo * n + u, nbl_all, n, c_hi - c_lo);
   };
@@ -694,14 +717,12 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       // permuted and committed NOW, with those cells zero and the RLC columns zero; afterwards the missing cells are
       // committed as sparse correction columns and added (a commitment is linear in its column).  Same points, same bytes.
       const size_t nbl0 = n - u, n_adv1 = cfg.n_advice() - cfg.n_gate0, n_early = n_adv1 + 2 * cfg.n_lookup;
-      CK(g1.place_early());
-      CK(rng_fill(ctx->stream, ctr_adv + (uint64_t)cfg.n_gate0 * nbl0, nbl0, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n + u, nbl0, n, cfg.adv_rlc0() - cfg.n_gate0));
-      ZK_HIP(ctx, hipMemsetAsync(ws->adv_l.fr() + (size_t)cfg.adv_rlc0() * n, 0, (size_t)cfg.n_rlc * n * 32, ctx->stream));
+      // the placement kernels draw the blinding rows of their columns and clear the RLC columns behind them
+      CK(g1.place_early(blind_rows(ctr_adv + (uint64_t)cfg.n_gate0 * nbl0, nbl0), cfg.n_rlc));
       int *err_dev = ws->host_early_err;   // pinned: written by the kernel, read by the host after ev_early
       *err_dev = 0;
-      CK(zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), err_dev));
-      CK(rng_fill(ctx->stream, ctr_lk, 2 * nbl0, ws->la_l.fr() + u, nbl0, n, cfg.n_lookup));
-      CK(rng_fill(ctx->stream, ctr_lk + nbl0, 2 * nbl0, ws->ls_l.fr() + u, nbl0, n, cfg.n_lookup));
+      const zkp::RngRows blind_lk = blind_rows(ctr_lk, 2 * nbl0);   // la_i then ls_i, lookup by lookup
+      CK(zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), err_dev, nullptr, &blind_lk));
       CK(srs_msm_pts(ctx, srs, small_basis, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, n_early, ws->host_early));
       CK(srs_record(ctx, srs, ws->ev_early));
     }
@@ -730,7 +751,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     as.place(ctx_rlc, true);
     trace.mark("place rlc");
     if (!early_p1) {
-      CK(g1.finish(evals));
+      CK(g1.finish(evals, blind_rows(ctr_adv + (uint64_t)cfg.n_gate0 * nbl, nbl)));   // blinding rows of the device-generated columns: same draw order as the host path
     } else {
       // the challenge-dependent rest: the reserved gate cells (into the columns and into sparse correction columns), the RLC
       // columns; two small commitments, then early + correction on the host
@@ -783,9 +804,6 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   if (host_witness) {
     CK(blind_and_upload(cfg.n_gate0, cfg.n_advice()));
   } else if (!early_p1) {
-    // blinding rows of the device-generated columns (same draw order as the host path: column by column)
-    const unsigned nc = cfg.adv_rlc0() - cfg.n_gate0;
-    CK(rng_fill(ctx->stream, ctr_adv + (uint64_t)cfg.n_gate0 * nbl, nbl, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n + u, nbl, n, nc));
     CK(blind_and_upload(cfg.adv_rlc0(), cfg.n_advice()));
   }
   trace.mark("blind + upload phase 1");
@@ -805,10 +823,9 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     if (cfg.lookup_bits != 8) return zk_fail_msg(ctx, ZKFHE_EINVAL, "the device lookup permutation is built for lookup_bits = 8");
     lookup_err = ws->out_flags() + 2;   // pinned
     *lookup_err = 0;
-    CK(zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), lookup_err));
-    // blinding rows: la_i then ls_i, lookup by lookup -- two interleaved runs of the stream
-    CK(rng_fill(ctx->stream, ctr_lk, 2 * nbl, ws->la_l.fr() + u, nbl, n, cfg.n_lookup));
-    CK(rng_fill(ctx->stream, ctr_lk + nbl, 2 * nbl, ws->ls_l.fr() + u, nbl, n, cfg.n_lookup));
+    // blinding rows: la_i then ls_i, lookup by lookup -- two interleaved runs of the stream, drawn by the permutation kernel
+    const zkp::RngRows blind_lk = blind_rows(ctr_lk, 2 * nbl);
+    CK(zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), lookup_err, nullptr, &blind_lk));
     const size_t n_adv1 = cfg.n_advice() - cfg.n_gate0;
     CK(commit_cols_out(ctx, srs, small_basis, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, n_adv1 + 2 * cfg.n_lookup, ws, pts));
     if (*lookup_err) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup input not in table: a range check of the witness fails");
@@ -834,7 +851,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
         std::copy(sp.begin(), sp.end(), colS);
         for (size_t r = u; r < n; ++r) colA[r] = colS[r] = fe::zero();
       }
-      ZK_HIP(ctx, hipMemcpyAsync(ws->la_l.p, ws->host_blind, 2 * (size_t)cfg.n_lookup * n * 32, hipMemcpyHostToDevice, ctx->stream));
+      ZK_HIP(ctx, zk_memcpy_async(ctx, ws->la_l.p, ws->host_blind, 2 * (size_t)cfg.n_lookup * n * 32, hipMemcpyHostToDevice, ctx->stream));
       CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)ws->la_l.p, (zkfhe_fr *)ws->la_l.p, 2 * (size_t)cfg.n_lookup * n));
       CK(rng_fill(ctx->stream, ctr_lk, 2 * nbl, ws->la_l.fr() + u, nbl, n, cfg.n_lookup));
       CK(rng_fill(ctx->stream, ctr_lk + nbl, 2 * nbl, ws->ls_l.fr() + u, nbl, n, cfg.n_lookup));
@@ -853,15 +870,14 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   if (!srs->sharded()) gate.enter();   // a sharded proof's collectives must not wait for another rank's admission order
   // ------------------------------------------------------------ permutation grand products
   {
-    if (instances.size() < ws->inst_count)
-      ZK_HIP(ctx, hipMemsetAsync(ws->inst_l.fr() + instances.size(), 0, (ws->inst_count - instances.size()) * 32, ctx->stream));
     if (inst_via_ring) {
-      CK(flush_staged(ctx, ws));   // nothing to send when an earlier round's flush took the values along
-      if (!instances.empty()) CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)inst_staged, (zkfhe_fr *)ws->inst_l.p, instances.size()));
+      CK(flush_staged(ctx, ws));   // nothing to launch when an earlier round's flush took the values along and stored the column
     } else {
+      if (instances.size() < ws->inst_count)
+        ZK_HIP(ctx, zk_memset_async(ctx, ws->inst_l.fr() + instances.size(), 0, (ws->inst_count - instances.size()) * 32, ctx->stream));
       CK(upload_canon(ctx, ws->inst_l.fr(), instances.data(), instances.size()));
+      ws->inst_count = instances.size();
     }
-    ws->inst_count = instances.size();
   }
   U256 dcan;
   memcpy(dcan.l, DELTA_CANON, 32);
@@ -885,16 +901,18 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   const size_t nch = cfg.n_chunks();
   zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(pa, ws->num.fr(), ws->den.fr());
   ZK_LAUNCH_CHECK(ctx);
-  CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)ws->den.p, nch * n));
-  CK(zkfhe_fr_mul(ctx, (const zkfhe_fr *)ws->num.p, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nch * n));
+  CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nch * n));   // num <- num / den: the ratios, in one kernel
   Fr *totals_dev = (Fr *)ws->small.p + 4096;
   // running products per column; long columns in segments (prover_kernels.hip.hpp), the segment products in the dead `den` buffer
-  auto prefix_products = [&](const Fr *ratio, Fr *z, size_t n_cols) -> int {
+  // blind: the blinding rows u + 1 .. n - 1 of the product columns (drawn per column, in order)
+  const size_t nb_z = n - u - 1;
+  auto prefix_products = [&](const Fr *ratio, Fr *z, size_t n_cols, const zkp::RngRows &blind) -> int {
     if (n <= 65536) {   // measured at k = 16 (two segments): no gain over one workgroup per column; k = 19: 6.5 -> 1 ms per proof
-      zkp::k_prefix_product<<<(unsigned)n_cols, 1024, 0, ctx->stream>>>(ratio, z, totals_dev, n, (unsigned)u);
+      zkp::k_prefix_product<<<(unsigned)n_cols + zkp::rng_tail_grid(blind, n_cols * nb_z, 1024), 1024, 0, ctx->stream>>>(ratio, z, totals_dev, n, (unsigned)u, (unsigned)n_cols, blind);
       ZK_LAUNCH_CHECK(ctx);
       return ZKFHE_OK;
     }
+    CK(rng_fill(ctx->stream, blind.ctr0, blind.ctr_col_stride, z + (u + 1), nb_z, n, n_cols));   // long columns: the blinding rows keep their own launch
     const unsigned seg_len = 32768, segs = (unsigned)(n / seg_len);   // u < n: the output row z[u] lies inside the last segment
     Fr *seg = ws->den.fr();
     if ((size_t)n_cols * segs * 32 > ws->den.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "prefix products: segment buffer too small");
@@ -906,7 +924,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
   };
-  CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch));
+  CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch, blind_rows(ctr_pz, nb_z)));
   int *const closes = ws->out_flags();   // pinned: [0] permutation, [1] lookups -- read after the commitment of the products below
   closes[0] = closes[1] = 1;
   {
@@ -915,9 +933,6 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     ZK_LAUNCH_CHECK(ctx);
     zkp::k_scale_rows<<<grid_for(ctx, nch * (u + 1)), 256, 0, ctx->stream>>>(ws->pz_l.fr(), totals_dev, n, (unsigned)(u + 1), (unsigned)nch);
     ZK_LAUNCH_CHECK(ctx);
-    // blinding rows u+1 .. n-1 (drawn per chunk, in order)
-    const size_t nb = n - u - 1;
-    CK(rng_fill(ctx->stream, ctr_pz, nb, ws->pz_l.fr() + (u + 1), nb, n, nch));
   }
   // ------------------------------------------------------------ lookup grand products
   if (cfg.n_lookup) {
@@ -926,13 +941,10 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
                                                                           pk->fixed_l.fr() + (size_t)cfg.fix_table() * n, ws->la_l.fr(), ws->ls_l.fr(),
                                                                           beta, gamma, (unsigned)nl, n, ws->num.fr(), ws->den.fr());
     ZK_LAUNCH_CHECK(ctx);
-    CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)ws->den.p, nl * n));
-    CK(zkfhe_fr_mul(ctx, (const zkfhe_fr *)ws->num.p, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nl * n));
-    CK(prefix_products(ws->num.fr(), ws->lz_l.fr(), nl));
+    CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nl * n));
+    CK(prefix_products(ws->num.fr(), ws->lz_l.fr(), nl, blind_rows(ctr_lz, nb_z)));
     zkp::k_chunk_carry<<<1, 1024, 0, ctx->stream>>>(totals_dev, (unsigned)nl, 1, closes + 1);
     ZK_LAUNCH_CHECK(ctx);
-    const size_t nb = n - u - 1;
-    CK(rng_fill(ctx->stream, ctr_lz, nb, ws->lz_l.fr() + (u + 1), nb, n, nl));
   }
   std::vector<AffinePoint> pz_commit, lz_commit;
   CK(commit_cols_out(ctx, srs, srs->g_lagrange, ws->pz_l.fr(), nch + cfg.n_lookup, ws, pz_commit));  // pz | lz contiguous
@@ -1172,30 +1184,6 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     pts_rot[4] = x * fr_pow(w, u);
     pts_rot[5] = x * dom->omega_inv;
   }
-  Fr *pts_dev = nullptr;
-  {
-    // H(X) = h0 + x^n h1 + x^2n h2, and the random polynomial, in Lagrange form
-    const Fr sc[3] = {zk::zk_fr_to_29(Fr::one()), zk::zk_fr_to_29(xn), zk::zk_fr_to_29(xn * xn)};   // k_lincomb_ptrs takes its scalars in the 2^261 form
-    const Fr *ptrs[3] = {ws->h_c.fr(), ws->h_c.fr() + n, ws->h_c.fr() + 2 * n};
-    STAGE(ptrs_dev, const Fr *, ws, ptrs, sizeof(ptrs));
-    STAGE(sc_dev, Fr, ws, sc, sizeof(sc));
-    STAGE(pts_stage, Fr, ws, pts_rot, sizeof(pts_rot));   // the six evaluation points go up with the same copy
-    pts_dev = pts_stage;
-    CK(flush_staged(ctx, ws));
-    zkp::k_lincomb_ptrs<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ptrs_dev, sc_dev, 3, n, H_c);
-    ZK_LAUNCH_CHECK(ctx);
-    CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)H_c, (zkfhe_fr *)H_l, 1, (int)k, 0));
-    if (!early_rand) CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)rand_c, (zkfhe_fr *)rand_l, 1, (int)k, 0));   // early: transformed on the auxiliary stream at the start
-  }
-  Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
-  {
-    zkp::k_bary_den<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, pts_dev, 6, n, bw);
-    ZK_LAUNCH_CHECK(ctx);
-    CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)bw, 6 * n));
-    const Fr c = zk::zk_fr_to_29((xn - Fr::one()) * dom->n_inv);   // the weights in the 2^261 form: the constant operand of k_eval_jobs' nine-limb products
-    zkp::k_bary_weights<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, c, 6 * n, n, bw);
-    ZK_LAUNCH_CHECK(ctx);
-  }
   std::vector<OpenItem> items;
   auto add_item = [&](const Fr *lagr, std::initializer_list<int> rots) {
     OpenItem it;
@@ -1224,16 +1212,42 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     add_item(ws->la_l.fr() + (size_t)i * n, {0, 5});
     add_item(ws->ls_l.fr() + (size_t)i * n, {0});
   }
+  // the evaluation jobs (column, rotations) depend on no challenge: they are staged with the round's first tables
+  std::vector<zkp::EvalJob> jobs(items.size());
+  for (size_t i = 0; i < items.size(); ++i) {
+    jobs[i].col = items[i].lagr;
+    jobs[i].n_rot = items[i].n_rot;
+    for (int r = 0; r < 4; ++r) jobs[i].rot[r] = r < items[i].n_rot ? items[i].rot[r] : 0;
+  }
+  const zkp::EvalJob *jobs_dev = nullptr;
+  Fr *pts_dev = nullptr;
   {
-    std::vector<zkp::EvalJob> jobs(items.size());
-    for (size_t i = 0; i < items.size(); ++i) {
-      jobs[i].col = items[i].lagr;
-      jobs[i].n_rot = items[i].n_rot;
-      for (int r = 0; r < 4; ++r) jobs[i].rot[r] = r < items[i].n_rot ? items[i].rot[r] : 0;
-    }
-    DevBuf &od = ws->evout;
-    STAGE(jobs_dev, zkp::EvalJob, ws, jobs.data(), jobs.size() * sizeof(zkp::EvalJob));
+    // H(X) = h0 + x^n h1 + x^2n h2, and the random polynomial, in Lagrange form
+    const Fr sc[3] = {zk::zk_fr_to_29(Fr::one()), zk::zk_fr_to_29(xn), zk::zk_fr_to_29(xn * xn)};   // k_lincomb_ptrs takes its scalars in the 2^261 form
+    const Fr *ptrs[3] = {ws->h_c.fr(), ws->h_c.fr() + n, ws->h_c.fr() + 2 * n};
+    STAGE(ptrs_dev, const Fr *, ws, ptrs, sizeof(ptrs));
+    STAGE(sc_dev, Fr, ws, sc, sizeof(sc));
+    STAGE(pts_stage, Fr, ws, pts_rot, sizeof(pts_rot));   // the six evaluation points go up with the same flush
+    pts_dev = pts_stage;
+    STAGE(jobs_stage, zkp::EvalJob, ws, jobs.data(), jobs.size() * sizeof(zkp::EvalJob));   // ... and so does the evaluation job list
+    jobs_dev = jobs_stage;
     CK(flush_staged(ctx, ws));
+    zkp::k_lincomb_ptrs<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ptrs_dev, sc_dev, 3, n, H_c);
+    ZK_LAUNCH_CHECK(ctx);
+    CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)H_c, (zkfhe_fr *)H_l, 1, (int)k, 0));
+    if (!early_rand) CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)rand_c, (zkfhe_fr *)rand_l, 1, (int)k, 0));   // early: transformed on the auxiliary stream at the start
+  }
+  Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
+  {
+    zkp::k_bary_den<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, pts_dev, 6, n, bw);
+    ZK_LAUNCH_CHECK(ctx);
+    CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)bw, 6 * n));
+    const Fr c = zk::zk_fr_to_29((xn - Fr::one()) * dom->n_inv);   // the weights in the 2^261 form: the constant operand of k_eval_jobs' nine-limb products
+    zkp::k_bary_weights<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, c, 6 * n, n, bw);
+    ZK_LAUNCH_CHECK(ctx);
+  }
+  {
+    DevBuf &od = ws->evout;
     struct { const void *p; } jd{jobs_dev};
     // One proof over several GPUs, long rows (k >= 14): the evaluation jobs are sharded by index -- rank r takes jobs
     // [per r, per (r + 1)) with per = ceil(J / W), every Lagrange column being present on every rank -- and the scalars are
@@ -1288,8 +1302,9 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   Fr *F = ws->misc.fr() + 12 * n;  // [ns][n]
   if (ns > 8) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many rotation sets");
   std::vector<zkp::ShSet> shsets(ns);
+  const zkp::ShSet *sets_dev = nullptr;
   {
-    // pointer and scalar tables of every set are staged first and go up with one copy; then the launches
+    // pointer and scalar tables of every set are staged first and go up with one flush; then the launches
     std::vector<const Fr *const *> set_ptrs(ns);
     std::vector<const Fr *> set_pw(ns);
     for (size_t j = 0; j < ns; ++j) {
@@ -1331,6 +1346,19 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
         for (size_t q = 0; q < num.size(); ++q) S.rc[q] = S.rc[q] + num[q] * scl;
       }
     }
+    // v follows yq with nothing absorbed in between: it is squeezed here, and the sets (r_j, points, v^j) go up with the same flush
+    {
+      const Fr v = mont(tr.squeeze());
+      Fr cur = Fr::one();
+      for (size_t j = 0; j < ns; ++j) {
+        shsets[j].vj = cur;
+        shsets[j].coef = Fr::zero();
+        shsets[j].r_u = Fr::zero();
+        cur = cur * v;
+      }
+      STAGE(sets_stage, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
+      sets_dev = sets_stage;
+    }
     CK(flush_staged(ctx, ws));
     // One proof over several GPUs, long rows: every rank sums its share of a set's members (a k_lincomb_ptrs over zero members
     // writes zeros), the W partial combinations of all sets are all-gathered (ns n values per rank) and added up.
@@ -1368,23 +1396,10 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       }
     }
   }
-  const Fr v = mont(tr.squeeze());
-  {
-    Fr cur = Fr::one();
-    for (size_t j = 0; j < ns; ++j) {
-      shsets[j].vj = cur;
-      shsets[j].coef = Fr::zero();
-      shsets[j].r_u = Fr::zero();
-      cur = cur * v;
-    }
-  }
-
   Fr *zs = ws->misc.fr() + 20 * n;   // [ns][n]
   Fr *hq = ws->misc.fr() + 28 * n;   // [n]
   Fr *Wq = ws->misc.fr() + 29 * n;   // [n]
   Fr *dinv = ws->misc.fr() + 30 * n; // [n]
-  STAGE(sets_dev, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
-  CK(flush_staged(ctx, ws));
   zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
   ZK_LAUNCH_CHECK(ctx);
   CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)zs, ns * n));
@@ -1401,6 +1416,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     // halo2 normalises the final quotient by the difference vanishing polynomial of the first set ("z_0_diff_inv"): every
     // coefficient below carries that factor, so the kernel is unchanged
     Fr z0_diff_inv = Fr::one();
+    zkp::ShW shw{};   // the constants that depend on u: by kernel argument
     for (size_t j = 0; j < ns; ++j) {
       Fr zdiff = Fr::one();
       for (int r : all_rots)
@@ -1412,14 +1428,14 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       ru = ru * uu + shsets[j].rc[1];
       ru = ru * uu + shsets[j].rc[0];
       shsets[j].r_u = ru;
+      shw.coef[j] = shsets[j].coef;
+      shw.r_u[j] = ru;
     }
     ztu = ztu * z0_diff_inv;
-    STAGE(sets2_dev, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
-    CK(flush_staged(ctx, ws));
     zkp::k_sh_den<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(dom->fwd, uu, n, dinv);
     ZK_LAUNCH_CHECK(ctx);
     CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)dinv, n));
-    zkp::k_sh_w<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(sets2_dev, (unsigned)ns, F, hq, ztu, dinv, n, Wq);
+    zkp::k_sh_w<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(shw, (unsigned)ns, F, hq, ztu, dinv, n, Wq);
     ZK_LAUNCH_CHECK(ctx);
   }
   CK(commit_cols_out(ctx, srs, srs->g_lagrange, Wq, 1, ws, w_commit));
@@ -1512,7 +1528,7 @@ int zkfhe_lookup_permute(zkfhe_ctx *ctx, const zkfhe_fr *cols_dev, size_t n_cols
   ZK_ARG(ctx, cols_dev && a_dev && s_dev && not_in_table && n_cols > 0 && n_cols < 65536 && usable_rows <= n && usable_rows >= 256);
   void *flag;   // the flag, then the histogram of the sliced kernels (long columns)
   CK(zk_scratch(ctx, 3, 64 + n_cols * 256 * sizeof(unsigned), &flag));
-  ZK_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
+  ZK_HIP(ctx, zk_memset_async(ctx, flag, 0, 4, ctx->stream));
   CK(zkw::lookup_permute(ctx, (const Fr *)cols_dev, n, usable_rows, (unsigned)n_cols, (Fr *)a_dev, (Fr *)s_dev, (int *)flag, (unsigned *)((char *)flag + 64)));
   return zkfhe_download(ctx, not_in_table, flag, 4);
 }
@@ -1603,9 +1619,9 @@ int zkfhe_bfv_witness_stream(zkfhe_ctx *ctx, const zkfhe_bfv_pk *pk_c, const cha
     GpuPhase1 g1(ctx, pk, ws);
     CK(g1.launch(st));
     bfv_phase1_rlc(st, ctx_rlc, gamma, evals);
-    CK(g1.finish(evals));
+    CK(g1.finish(evals, zkp::RngRows{}));   // the cells only: no blinding rows here
     CK(zkfhe_fr_from_mont(ctx, (const zkfhe_fr *)ws->stream.p, (zkfhe_fr *)ws->stream.p, pk->gate1_cells));
-    ZK_HIP(ctx, hipMemcpyAsync(cells_out, ws->stream.p, pk->gate1_cells * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, zk_memcpy_async(ctx, cells_out, ws->stream.p, pk->gate1_cells * 32, hipMemcpyDeviceToHost, ctx->stream));
     CK(zkfhe_sync(ctx));
     return ZKFHE_OK;
   } catch (const std::exception &e) {

@@ -118,10 +118,14 @@ struct Workspace {
   size_t ring_off = 0;
   static constexpr size_t RING_BYTES = (size_t)4 << 20;
   // device mirror of the ring: stage() places a table in the ring and returns its address in the mirror, flush_staged() moves
-  // everything staged since the last flush with ONE copy (a Fiat-Shamir round has a dozen small tables: expression groups,
+  // everything staged since the last flush with ONE launch (a Fiat-Shamir round has a dozen small tables: expression groups,
   // powers, pointer / scalar lists, rotation sets ...)
   DevBuf dev_ring;
   size_t ring_flushed = 0;
+  // the public inputs of the proof in flight, staged in the ring: the next flush converts them into the instance column (inst_l)
+  const Fr *inst_src = nullptr;   // canonical values, in the ring (host address: the flush kernel reads the mapped ring)
+  size_t inst_n = 0;
+  bool inst_pending = false;
   // results that the host reads (commitments, evaluations, check flags) are WRITTEN by the kernels into this pinned,
   // device-visible block -- no device-to-host copy commands: [points | evaluations | flags]
   uint8_t *host_out = nullptr;
@@ -195,12 +199,12 @@ static inline unsigned grid_for(zkfhe_ctx *ctx, size_t work) {
 
 // upload canonical values and convert to Montgomery on the device
 static inline int upload_canon(zkfhe_ctx *ctx, Fr *dst, const U256 *src, size_t count) {
-  ZK_HIP(ctx, hipMemcpyAsync(dst, src, count * 32, hipMemcpyHostToDevice, ctx->stream));
+  ZK_HIP(ctx, zk_memcpy_async(ctx, dst, src, count * 32, hipMemcpyHostToDevice, ctx->stream));
   return zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)dst, (zkfhe_fr *)dst, count);
 }
 
 // Small host -> device tables of a proof (expression groups, powers, pointer lists, ...): staged in the workspace's pinned
-// arena and copied without waiting -- the arena is only recycled at the start of the next proof, after a stream sync.
+// arena and moved without waiting -- the arena is only recycled at the start of the next proof, after a stream sync.
 
 
 // A small host table of the proof in flight -> device: copied into the pinned ring now, visible on the device (at the returned
@@ -224,9 +228,20 @@ static inline void *stage_reserve(Workspace *ws, size_t bytes, void **host) {
   return dev;
 }
 static inline int flush_staged(zkfhe_ctx *ctx, Workspace *ws) {
-  if (ws->ring_off > ws->ring_flushed) {
-    ZK_HIP(ctx, hipMemcpyAsync((char *)ws->dev_ring.p + ws->ring_flushed, ws->ring + ws->ring_flushed, ws->ring_off - ws->ring_flushed, hipMemcpyHostToDevice, ctx->stream));
-    ws->ring_flushed = ws->ring_off;
+  // by a kernel that reads the mapped ring (zkp::k_ring_flush), not by a copy command: the runtime's copy path costs every proof of
+  // a wave host time and a command of its own, and the same launch stores the instance column
+  const size_t lo = ws->ring_flushed, hi = ws->ring_off;   // multiples of 64
+  const size_t n16 = hi > lo ? (hi - lo) / 16 : 0;
+  const size_t inst_n = ws->inst_pending ? ws->inst_n : 0, inst_zero = ws->inst_pending && ws->inst_count > ws->inst_n ? ws->inst_count - ws->inst_n : 0;
+  if (n16 || ws->inst_pending) {
+    if (n16 + inst_n + inst_zero) {
+      zkp::k_ring_flush<<<grid_for(ctx, n16 + inst_n + inst_zero), 256, 0, ctx->stream>>>((const uint4 *)(ws->ring + lo), (uint4 *)((char *)ws->dev_ring.p + lo), n16, ws->inst_src,
+                                                                                         ws->inst_l.fr(), inst_n, inst_zero);
+      ZK_LAUNCH_CHECK(ctx);
+    }
+    ws->ring_flushed = hi;
+    if (ws->inst_pending) ws->inst_count = ws->inst_n;
+    ws->inst_pending = false;
   }
   return ZKFHE_OK;
 }

@@ -102,6 +102,27 @@ __device__ __forceinline__ Fr rng_draw(const unsigned long long seed[4], unsigne
 struct RngSeed {
   unsigned long long w[4];
 };
+// Blinding rows drawn by the kernel that writes the rest of the column (no launch of their own): row u + j of column c takes
+// draw(ctr0 + c * ctr_col_stride + j) -- k_rng_fill's counter layout, so every value is the one k_rng_fill would store.
+// on = 0: the kernel treats those rows as it does without blinding.
+struct RngRows {
+  RngSeed seed;
+  unsigned long long ctr0, ctr_col_stride;
+  int on;
+};
+__device__ __forceinline__ Fr rng_row(const RngRows &b, size_t col, size_t j) { return rng_draw(b.seed.w, b.ctr0 + col * b.ctr_col_stride + j); }
+// A draw is one long dependent chain (about 8 us): a kernel whose threads own runs of rows must not draw a column's rows one after
+// the other in the lane that owns them.  Such a kernel is launched with a few workgroups more -- [first_block, gridDim.x) -- which
+// do what k_rng_fill does, one draw per thread, beside the workgroups that move the data:
+// dst[c * col_stride + j] = draw of row j of column c, j < per_col.
+__device__ __forceinline__ void rng_tail_blocks(const RngRows &b, unsigned first_block, Fr *__restrict__ dst, size_t per_col, size_t col_stride, size_t n_cols) {
+  const size_t total = per_col * n_cols, T = (size_t)(gridDim.x - first_block) * blockDim.x;
+  for (size_t g = (size_t)(blockIdx.x - first_block) * blockDim.x + threadIdx.x; g < total; g += T) {
+    const size_t c = g / per_col, j = g - c * per_col;
+    dst[c * col_stride + j] = rng_row(b, c, j);
+  }
+}
+static inline unsigned rng_tail_grid(const RngRows &b, size_t draws, unsigned threads) { return b.on ? (unsigned)((draws + threads - 1) / threads) : 0u; }
 // dst[c * col_stride + j] = draw(ctr0 + c * ctr_col_stride + j)   (Montgomery), j < per_col, c < n_cols
 static __global__ void __launch_bounds__(256) k_rng_fill(RngSeed seed, unsigned long long ctr0, unsigned long long ctr_col_stride, Fr *__restrict__ dst,
                                                   size_t per_col, size_t col_stride, size_t n_cols) {
@@ -109,6 +130,28 @@ static __global__ void __launch_bounds__(256) k_rng_fill(RngSeed seed, unsigned 
   for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
     const size_t c = g / per_col, j = g - c * per_col;
     dst[c * col_stride + j] = rng_draw(seed.w, ctr0 + c * ctr_col_stride + j);
+  }
+}
+
+// Canonical values of a column-contiguous table (pinned host memory mapped into the device, or device memory) -> Montgomery
+// columns, rows >= u drawn from the blinding stream in the same pass: the upload of a witness phase in one launch.
+static __global__ void __launch_bounds__(256) k_to_mont_blind(const Fr *__restrict__ src, Fr *__restrict__ dst, size_t n, unsigned u, size_t n_cols, RngRows blind) {
+  const size_t total = n_cols * n;
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = g / n, r = g - c * n;
+    dst[g] = r >= u ? rng_row(blind, c, r - u) : zk::fr29_to_mont(src[g]);
+  }
+}
+// The proof's staging ring (pinned, mapped) -> its device mirror, by a kernel: 16-byte units [0, n16) of src go to dst.  Every unit
+// is read once, coalesced.  The same launch carries the public inputs into the instance column: inst_n canonical values (read from
+// the ring) -> Montgomery, and inst_zero rows behind them back to zero (a shorter instance than the previous proof's).
+static __global__ void __launch_bounds__(256) k_ring_flush(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16, const Fr *__restrict__ inst_src,
+                                                    Fr *__restrict__ inst_dst, size_t inst_n, size_t inst_zero) {
+  const size_t total = n16 + inst_n + inst_zero;
+  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+    if (g < n16) dst[g] = src[g];
+    else if (g < n16 + inst_n) inst_dst[g - n16] = zk::fr29_to_mont(inst_src[g - n16]);
+    else inst_dst[g - n16] = Fr::zero();
   }
 }
 
@@ -179,10 +222,15 @@ static __global__ void __launch_bounds__(256) k_lookup_num_den(const Fr *__restr
 }
 
 // Exclusive running product per column: z[0] = 1, z[i+1] = z[i] * r[i] for i < u; z has u+1 defined entries.
-// One workgroup of 1024 threads per column; thread t owns rows [t*per, (t+1)*per).  `total[col]` = z[u].
+// One workgroup of 1024 threads per column; thread t owns rows [t*per, (t+1)*per).  `total[col]` = z[u].  blind.on: the rows
+// u + 1 .. n - 1 of the columns are their blinding rows, drawn by the workgroups behind the n_cols of the columns (rng_tail_blocks).
 static __global__ void __launch_bounds__(1024) k_prefix_product(const Fr *__restrict__ ratio, Fr *__restrict__ z, Fr *__restrict__ total, size_t n,
-                                                         unsigned u) {
+                                                         unsigned u, unsigned n_cols, RngRows blind) {
   __shared__ Fr sh[1024];
+  if (blockIdx.x >= n_cols) {
+    rng_tail_blocks(blind, n_cols, z + u + 1, n - u - 1, n, n_cols);
+    return;
+  }
   const size_t col = blockIdx.x;
   const Fr *r = ratio + col * n;
   Fr *o = z + col * n;
@@ -602,11 +650,17 @@ static __global__ void __launch_bounds__(256) k_sh_den(const Fr *__restrict__ wp
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i < n) out[i] = wpow[i] - u;
 }
-static __global__ void __launch_bounds__(256) k_sh_w(const ShSet *__restrict__ sets, unsigned n_sets, const Fr *__restrict__ F, const Fr *__restrict__ hq,
+// the per-set constants of k_sh_w, by kernel argument (they depend on the last challenge: no table to send for them)
+struct ShW {
+  Fr coef[8], r_u[8];   // v^j * Z_{T\S_j}(u) and r_j(u), at most 8 rotation sets
+};
+static __global__ void __launch_bounds__(256) k_sh_w(ShW sets, unsigned n_sets, const Fr *__restrict__ F, const Fr *__restrict__ hq,
                                               Fr ztu, const Fr *__restrict__ inv, size_t n, Fr *__restrict__ W) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     Fr acc = Fr::zero();
-    for (unsigned j = 0; j < n_sets; ++j) acc = acc + sets[j].coef * (F[(size_t)j * n + i] - sets[j].r_u);
+#pragma unroll
+    for (unsigned j = 0; j < 8; ++j)   // unrolled: a run-time index into a kernel argument would put the struct into scratch memory
+      if (j < n_sets) acc = acc + sets.coef[j] * (F[(size_t)j * n + i] - sets.r_u[j]);
     W[i] = (acc - ztu * hq[i]) * inv[i];
   }
 }
