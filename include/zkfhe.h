@@ -722,6 +722,43 @@ int zkfhe_bfv_linear_transform(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, s
 #define ZKFHE_PROF_BFV_HOIST 16    /* k_hoist: c0 and the digits of c1, transformed once per ciphertext */
 #define ZKFHE_PROF_BFV_LINEAR 17   /* k_linear_acc: the pointwise sums over digits and elements */
 
+/* ---- Baby-step/giant-step linear transforms: dense encrypted matrix products (bfv_linear.hip) ----
+ * out = sum_i rot_{G_i}( sum_j diag_{i,j} * rot_{b_j}(x) ) for n_baby baby elements b_j and n_giant giant elements G_i, in one call:
+ * n_baby + n_giant Galois keys serve n_baby n_giant diagonals (a dense N x N matrix over the slots: about 2 sqrt(N) keys instead of
+ * N), and the whole two-level sum stays on the device between the upload and the download.  The conventions of "Encrypted
+ * matrix-vector products": host arrays, N uint64_t per polynomial in CircuitInput order, residues in [0, Q), the parameter checks of
+ * zkfhe_bfv_encrypt; the call waits for its result; w = base_bits in [1, 32], l = zkfhe_bfv_relin_digits; Galois keys are those of
+ * zkfhe_bfv_galois_keygen, or of zkfhe_bfv_share_aggregate over zkfhe_bfv_galois_share; "hoisted rotation" is the definition above
+ * (digits of c1 itself, sigma_g on the signed integer digits).  The result is exact and bit for bit; there is no new randomness and
+ * no new ChaCha20 domain.
+ *   g_baby: n_baby odd values below 2N with keys bk0, bk1 (n_baby x l x N); g_giant: n_giant odd values below 2N with keys hk0, hk1
+ *   (n_giant x l x N); repeats are allowed in both lists; g = 1 in either list is the identity, and its key rows are neither read
+ *   nor checked.  diag: n_giant x n_baby x N plaintexts in [0, T/2] or [Q - T/2, Q - 1], giant-major, shared by all n ciphertexts.
+ *   For ciphertext x and giant step i, inner_i = zkfhe_bfv_linear_transform(x; g_baby, bk, diag[i]): exact over Z, then mod Q into
+ *   [0, Q).  out = sum_i (the hoisted rotation of inner_i by g_giant[i] with key hk[i]), exactly over Z in Z[x]/(x^N + 1), then mod
+ *   Q.  That is, bit for bit, the zkfhe_bfv_add-sum over i of block 0 of zkfhe_bfv_apply_galois_many(inner_i, [g_giant[i]]).
+ *   diag arrives already pre-rotated: the library does not rotate plaintexts.  Under a batching T with diag[i][j] =
+ *   zkfhe_bfv_encode_slots(d'_{i,j}), slot p of the decryption is sum_i sum_j rot_{G_i}(d'_{i,j})[p] rot_{G_i b_j}(v)[p] mod T; for
+ *   the diagonal d of the element G_i b_j that means d'_{i,j} = rot_{G_i}^-1(d).
+ * Range: the inner sum is carried in five primes as in zkfhe_bfv_linear_transform, so the call refuses, with ZKFHE_EINVAL and before
+ * any pass over the inputs and any device work, when bitlen(n_baby) + bitlen(N) + bitlen(floor(T/2)) + bitlen(Q - 1) + bitlen(1 + l N
+ * (2^w - 1)) > 150, with that call's message.  The outer sum is over rotations of inner ciphertexts in [0, Q): it is below n_giant Q
+ * (1 + l N (2^w - 1)) < 2^20 2^63 2^49 = 2^132 and never needs a refusal.  The call also refuses, with a message: a NULL argument;
+ * n, n_baby or n_giant equal to 0; either count >= 2^20; a g that is even or >= 2N; a ciphertext or key coefficient >= Q (the key
+ * rows of g = 1 excepted); a diagonal out of plaintext range; base_bits outside [1, 32].  Defined for any T.  Noise: the inner sum
+ * has the noise of zkfhe_bfv_linear_transform over n_baby elements, and every giant step adds one more key switch (about l N 2^w B /
+ * 2) that no diagonal multiplies. */
+/* out0, out1: n x N. */
+int zkfhe_bfv_linear_transform_bsgs(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1,
+                                    size_t n_baby, const uint64_t *g_baby, const uint64_t *bk0, const uint64_t *bk1,
+                                    size_t n_giant, const uint64_t *g_giant, const uint64_t *hk0, const uint64_t *hk1, int base_bits,
+                                    const uint64_t *diag, uint64_t *out0, uint64_t *out1);
+/* zkfhe_prof_read slots of the call's own kernels (algorithmic bytes: words read and written); k_hoist and the baby rotations count
+ * in ZKFHE_PROF_BFV_HOIST and ZKFHE_PROF_BFV_LINEAR, the transforms in ZKFHE_PROF_RNS_NTT, the reductions mod Q in
+ * ZKFHE_PROF_BFV_EVAL_EPILOGUE */
+#define ZKFHE_PROF_BFV_BSGS_INNER 18   /* k_bsgs_inner: the pointwise products of the diagonals with the baby rotations */
+#define ZKFHE_PROF_BFV_BSGS_GIANT 19   /* k_linear_acc<ACC_GIANT>: the giant rotations of the inner sums, accumulated */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

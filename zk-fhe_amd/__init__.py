@@ -22,6 +22,7 @@ PROF_BFV_TENSOR, PROF_BFV_RELIN, PROF_BFV_EVAL_EPILOGUE, PROF_BFV_ELEMENTWISE = 
 PROF_BFV_SHARE_SUM, PROF_BFV_DECRYPT_COMBINE = 12, 13   # ... and of the threshold kernels
 PROF_BFV_GALOIS, PROF_BFV_SLOT_NTT = 14, 15   # ... and of the slot and rotation kernels
 PROF_BFV_HOIST, PROF_BFV_LINEAR = 16, 17   # ... and of the hoisted rotations and linear transforms
+PROF_BFV_BSGS_INNER, PROF_BFV_BSGS_GIANT = 18, 19   # ... and of the baby-step/giant-step transform's own kernels
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -49,7 +50,7 @@ EXPORTS = [
     "zkfhe_bfv_decrypt_combine",
     "zkfhe_bfv_slot_count", "zkfhe_bfv_galois_element", "zkfhe_bfv_slot_sum_elements", "zkfhe_bfv_encode_slots", "zkfhe_bfv_decode_slots",
     "zkfhe_bfv_galois_keygen", "zkfhe_bfv_apply_galois", "zkfhe_bfv_slot_sum", "zkfhe_bfv_galois_share",
-    "zkfhe_bfv_apply_galois_many", "zkfhe_bfv_linear_transform",
+    "zkfhe_bfv_apply_galois_many", "zkfhe_bfv_linear_transform", "zkfhe_bfv_linear_transform_bsgs",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -774,6 +775,22 @@ class Context:
         self._bfv("zkfhe_bfv_linear_transform", "nppnpppippp", params, c0.shape[0], c0, c1, g.shape[0], g, gk0, gk1, int(base_bits), d, *out)
         return tuple(out)
 
+    def bfv_linear_transform_bsgs(self, params, c0, c1, baby_elements, bk0, bk1, giant_elements, hk0, hk1, diagonals, base_bits=16):
+        """zkfhe_bfv_linear_transform_bsgs: n ciphertexts (n, N) -> sum_i (the hoisted rotation by giant_elements[i] of sum_j
+        diagonals[i][j] * (the hoisted rotation by baby_elements[j])), shape (n, N).  bk0, bk1: the baby keys (n_baby, l, N); hk0, hk1:
+        the giant keys (n_giant, l, N); diagonals: plaintexts (n_giant, n_baby, N), already rotated by the inverse of their giant
+        step and shared by every ciphertext (bfv_encode_slots of the slot values of bfv_matrix_bsgs)."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        gb, bk0, bk1 = self._elements(params, baby_elements, bk0, bk1, base_bits)
+        gg, hk0, hk1 = self._elements(params, giant_elements, hk0, hk1, base_bits)
+        d = np.ascontiguousarray(diagonals, dtype=np.uint64)
+        if d.shape != (gg.shape[0], gb.shape[0], int(params[0])):
+            raise ValueError("diagonals must have shape (n_giant, n_baby, N), one plaintext per pair of elements")
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_linear_transform_bsgs", "nppnpppnpppippp", params, c0.shape[0], c0, c1, gb.shape[0], gb, bk0, bk1, gg.shape[0], gg,
+                  hk0, hk1, int(base_bits), d, *out)
+        return tuple(out)
+
 
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 # the parameter letters of Context._bfv
@@ -849,6 +866,41 @@ def bfv_matrix_diagonals(params, matrix):
                 elements.append(bfv_galois_element(params, k, bool(swap)))
                 diagonals.append(d)
     return elements, np.array(diagonals, dtype=np.uint64).reshape(-1, n)
+
+
+def bfv_matrix_bsgs(params, matrix, n_baby=None):
+    """Host only, Python only: the baby-step/giant-step split of bfv_matrix_diagonals for Context.bfv_linear_transform_bsgs ->
+    (baby_elements, giant_elements, diagonals).  Baby column b is the element 5^b, giant row (i, swap) the element 5^(i n_baby)
+    (2N - 1)^swap for i < ceil((N/2) / n_baby), the swap = 0 rows first.  diagonals: slot values of shape (n_giant, n_baby, N), to be
+    encoded with Context.bfv_encode_slots: entry (i, swap), b is the diagonal of k = i n_baby + b and swap (zero where k >= N/2),
+    rotated by the inverse of its giant step, d'[(row, j)] = d[(row ^ swap, (j - i n_baby) mod N/2)].  n_baby defaults to
+    2^ceil(log2(N) / 2); any 1 <= n_baby <= N/2 is accepted.  Giant rows that are all zero are dropped, then baby columns that are
+    all zero (a zero matrix gives empty lists)."""
+    n, t = int(params[0]), int(params[2])
+    bfv_slot_count(params)   # refuses a T that does not batch
+    m = np.asarray(matrix)
+    if m.shape != (n, n):
+        raise ValueError("matrix must have shape (N, N)")
+    half, log_n = n // 2, n.bit_length() - 1
+    n_baby = 1 << -(-log_n // 2) if n_baby is None else int(n_baby)
+    if not 1 <= n_baby <= half:
+        raise ValueError("n_baby must be in [1, N/2]")
+    m = (m.astype(object) % t).astype(np.uint64) if m.dtype == object else np.mod(m, t).astype(np.uint64)
+    p = np.arange(n)
+    row, j = p // half, p % half
+    steps = -(-half // n_baby)
+    giants, d = [], np.zeros((2 * steps, n_baby, n), dtype=np.uint64)
+    for swap in (0, 1):
+        for i in range(steps):
+            giants.append(bfv_galois_element(params, i * n_baby, bool(swap)))
+            src = (row ^ swap) * half + (j - i * n_baby) % half   # the slot that the giant step moves to p
+            for b in range(min(n_baby, half - i * n_baby)):
+                k = i * n_baby + b
+                d[swap * steps + i, b] = m[src, (src // half ^ swap) * half + (src % half + k) % half]
+    keep_g = [i for i in range(2 * steps) if d[i].any()]
+    d = d[keep_g]
+    keep_b = [b for b in range(n_baby) if d[:, b].any()]
+    return [bfv_galois_element(params, b, False) for b in keep_b], [giants[i] for i in keep_g], np.ascontiguousarray(d[:, keep_b])
 
 
 def bfv_error_cdt(params):

@@ -16,6 +16,10 @@
 //                  within the top bits).
 //   k_rns_intt     one inverse transform per output polynomial and prime, in place
 //   k_eval_epilogue (bfv_eval.hip) EV_MODQ: Garner over the five primes, x mod Q.  sigma_g(c0) is already inside the sum.
+// linear_transform_bsgs is the same at two levels, out = sum_i rot_{G_i}(sum_j diag_{i,j} * rot_{b_j}(x)): k_hoist and
+// k_linear_acc<ACC_MANY> leave the baby rotations in the transform domain, k_bsgs_inner multiplies them by the diagonals (a small
+// matrix product per point), k_rns_intt and the epilogue reduce the inner sums mod Q (the definition takes their digits), k_hoist
+// transforms those, and k_linear_acc<ACC_GIANT> rotates inner ciphertext i by giant element i and accumulates (bsgs_call).
 // Sizes: |r| < Q + l N (2^w - 1) Q < 2^116 for a rotation; the transform's sum is below n_elems N floor(T/2) times that, which the
 // call bounds by 2^150 (check_range) under the half of the primes' product 2^151.2.  No kernel uses scratch.
 #include <string>
@@ -68,9 +72,13 @@ __device__ __forceinline__ unsigned galois_index(unsigned k, unsigned g, int log
 // One thread per (index, prime, group of CT ciphertexts): blockIdx.x tiles the N indices, blockIdx.y is the prime, blockIdx.z the
 // group.  hst: [c][1 + l][NP][N] (k_hoist); elem: [n_elems][2] = (g, key slot or NO_KEY); key_hat: [slot][2 l][NP][N], the gk0 rows
 // then the gk1 rows; diag_hat: [n_elems][NP][N].
-// LINEAR = false: out[k][comp][ct][prime][index] = t_comp of element k.  LINEAR = true: out[comp][ct][prime][index] = sum_k p^_k t_comp.
+// ACC_MANY: out[k][comp][ct][prime][index] = t_comp of element k.  ACC_LINEAR: out[comp][ct][prime][index] = sum_k p^_k t_comp.
+// ACC_GIANT (the outer sum of linear_transform_bsgs): element k reads the hoisted rows of ciphertext k c + ct (hst: [n_elems][c][1 + l]
+// [NP][N], the inner ciphertexts of giant step k) and out[comp][ct][prime][index] += sum_k t_comp: no diagonal, and the sum starts
+// from what out holds, so that groups of giant steps add up (the host zeroes out before the first group).
 // Every value is a residue below p < 2^31, every product a mont_mul and every sum an add_p: nothing is carried unreduced.
-template <bool LINEAR>
+enum AccMode { ACC_MANY = 0, ACC_LINEAR = 1, ACC_GIANT = 2 };
+template <int MODE>
 __global__ __launch_bounds__(ACC_THREADS) void k_linear_acc(const uint32_t *__restrict__ hst, const uint32_t *__restrict__ elem, int n_elems,
                                                              const uint32_t *__restrict__ key_hat, const uint32_t *__restrict__ diag_hat,
                                                              int l, size_t c, int log_n, RnsConst<NP> rc, GadgetStep gs,
@@ -84,10 +92,17 @@ __global__ __launch_bounds__(ACC_THREADS) void k_linear_acc(const uint32_t *__re
   for (int t = 0; t < CT; ++t) h[t] = hst + std::min(ct0 + t, c - 1) * (size_t)(l + 1) * plane + (size_t)j * n;
   uint32_t acc0[CT], acc1[CT];
 #pragma unroll
-  for (int t = 0; t < CT; ++t) acc0[t] = acc1[t] = 0;
+  for (int t = 0; t < CT; ++t) {
+    acc0[t] = acc1[t] = 0;
+    if (MODE == ACC_GIANT && ct0 + t < c) acc0[t] = out[(ct0 + t) * plane + (size_t)j * n + idx], acc1[t] = out[(c + ct0 + t) * plane + (size_t)j * n + idx];
+  }
   for (int k = 0; k < n_elems; ++k) {
     const uint32_t g = elem[2 * k], slot = elem[2 * k + 1];   // uniform over the grid
     const unsigned kp = galois_index(idx, g, log_n);
+    if (MODE == ACC_GIANT && k) {
+#pragma unroll
+      for (int t = 0; t < CT; ++t) h[t] += c * (size_t)(l + 1) * plane;   // the inner ciphertexts of the next giant step
+    }
     uint32_t t0[CT], t1[CT];
 #pragma unroll
     for (int t = 0; t < CT; ++t) t0[t] = h[t][kp], t1[t] = 0;
@@ -110,13 +125,16 @@ __global__ __launch_bounds__(ACC_THREADS) void k_linear_acc(const uint32_t *__re
         pw = mont_mul(pw, gs.step[j], p, pinv);
       }
     }
-    if (LINEAR) {
+    if (MODE == ACC_LINEAR) {
       const uint32_t ph = diag_hat[((size_t)k * NP + j) * n + idx];
 #pragma unroll
       for (int t = 0; t < CT; ++t) {
         acc0[t] = add_p(acc0[t], mont_mul(t0[t], ph, p, pinv), p);
         acc1[t] = add_p(acc1[t], mont_mul(t1[t], ph, p, pinv), p);
       }
+    } else if (MODE == ACC_GIANT) {
+#pragma unroll
+      for (int t = 0; t < CT; ++t) acc0[t] = add_p(acc0[t], t0[t], p), acc1[t] = add_p(acc1[t], t1[t], p);
     } else {
       uint32_t *o = out + (size_t)k * 2 * c * plane + (size_t)j * n + idx;
 #pragma unroll
@@ -124,12 +142,64 @@ __global__ __launch_bounds__(ACC_THREADS) void k_linear_acc(const uint32_t *__re
         if (ct0 + t < c) o[(ct0 + t) * plane] = t0[t], o[(c + ct0 + t) * plane] = t1[t];
     }
   }
-  if (LINEAR) {
+  if (MODE != ACC_MANY) {
     uint32_t *o = out + (size_t)j * n + idx;
 #pragma unroll
     for (int t = 0; t < CT; ++t)
       if (ct0 + t < c) o[(ct0 + t) * plane] = acc0[t], o[(c + ct0 + t) * plane] = acc1[t];
   }
+}
+
+// The inner sums of linear_transform_bsgs: per (index, prime) the small matrix product acc[i][comp][ct] = sum_b p^_{i,b} t_b[comp][ct]
+// of the diagonals ([n_giant][n_baby]) with the baby rotations ([n_baby][2 c]).  One thread per (index, prime, tile of GT giant steps
+// x CTI ciphertexts x 2 components): blockIdx.x tiles the N indices, blockIdx.y is the prime, blockIdx.z = giant tile * ciphertext
+// groups + ciphertext group.  baby: [n_baby][2][c][NP][N] (the output of k_linear_acc<ACC_MANY>); diag_hat: [n_giant][n_baby][NP][N]
+// (the rows of this launch's n_giant steps); out: [2][n_giant][c][NP][N], so that after the inverse transform and the reduction mod Q
+// the n_giant c inner ciphertexts are the [c0 | c1] input of k_hoist.  Every diagonal word is read once per ciphertext group and
+// every baby word once per giant tile, coalesced along the index; a tile past the last giant step or ciphertext reads the last one
+// again and stores nothing.  Residues below p, mont_mul and add_p only, as in k_linear_acc.
+template <int GT, int CTI>
+__global__ __launch_bounds__(ACC_THREADS) void k_bsgs_inner(const uint32_t *__restrict__ baby, const uint32_t *__restrict__ diag_hat,
+                                                             int n_baby, int n_giant, size_t c, int log_n, RnsConst<NP> rc,
+                                                             uint32_t *__restrict__ out) {
+  const unsigned n = 1u << log_n, idx = blockIdx.x * ACC_THREADS + threadIdx.x, j = blockIdx.y;
+  if (idx >= n) return;
+  const uint32_t p = rc.p[j], pinv = rc.pinv[j];
+  const size_t plane = (size_t)NP * n, groups = (c + CTI - 1) / CTI, at = (size_t)j * n + idx;
+  const size_t ct0 = (size_t)(blockIdx.z % groups) * CTI;
+  const int i0 = (int)(blockIdx.z / groups) * GT;
+  const uint32_t *d[GT], *t[CTI];
+#pragma unroll
+  for (int a = 0; a < GT; ++a) d[a] = diag_hat + (size_t)std::min(i0 + a, n_giant - 1) * n_baby * plane + at;
+#pragma unroll
+  for (int b = 0; b < CTI; ++b) t[b] = baby + std::min(ct0 + b, c - 1) * plane + at;
+  uint32_t acc[GT][CTI][2];
+#pragma unroll
+  for (int a = 0; a < GT; ++a)
+#pragma unroll
+    for (int b = 0; b < CTI; ++b) acc[a][b][0] = acc[a][b][1] = 0;
+  for (int k = 0; k < n_baby; ++k) {
+    uint32_t ph[GT], t0[CTI], t1[CTI];
+#pragma unroll
+    for (int a = 0; a < GT; ++a) ph[a] = d[a][(size_t)k * plane];
+#pragma unroll
+    for (int b = 0; b < CTI; ++b) t0[b] = t[b][(size_t)k * 2 * c * plane], t1[b] = t[b][((size_t)k * 2 + 1) * c * plane];
+#pragma unroll
+    for (int a = 0; a < GT; ++a)
+#pragma unroll
+      for (int b = 0; b < CTI; ++b) {
+        acc[a][b][0] = add_p(acc[a][b][0], mont_mul(t0[b], ph[a], p, pinv), p);
+        acc[a][b][1] = add_p(acc[a][b][1], mont_mul(t1[b], ph[a], p, pinv), p);
+      }
+  }
+#pragma unroll
+  for (int a = 0; a < GT; ++a)
+#pragma unroll
+    for (int b = 0; b < CTI; ++b)
+      if (i0 + a < n_giant && ct0 + b < c) {
+        uint32_t *o = out + ((size_t)(i0 + a) * c + ct0 + b) * plane + at;
+        o[0] = acc[a][b][0], o[(size_t)n_giant * c * plane] = acc[a][b][1];
+      }
 }
 
 // One workgroup per (polynomial, prime) of res ([polys][NP][N]): the inverse transform in place, times scale[prime]
@@ -242,9 +312,9 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
     const dim3 grid(zk_blocks(n, ACC_THREADS), NP, zk_blocks(c, CT));
     zk_prof_begin(ctx);
     if (diag)
-      k_linear_acc<true><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_elems, key_hat, diag_hat, l, c, log_n, rc, gs, res);
+      k_linear_acc<ACC_LINEAR><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_elems, key_hat, diag_hat, l, c, log_n, rc, gs, res);
     else
-      k_linear_acc<false><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_elems, key_hat, nullptr, l, c, log_n, rc, gs, res);
+      k_linear_acc<ACC_MANY><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_elems, key_hat, nullptr, l, c, log_n, rc, gs, res);
     ZK_LAUNCH_CHECK(ctx);
     // read: every hoisted row per element, every key word once per CT ciphertexts, the diagonals likewise; written: the outputs
     zk_prof_end(ctx, ZKFHE_PROF_BFV_LINEAR, 4.0 * words * ((double)n_elems * c * rows + (double)zk_blocks(c, CT) * (2.0 * slots * l + (diag ? n_elems : 0)) + polys));
@@ -257,6 +327,140 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
       ZK_CK(zkfhe_download(ctx, out0 + (k * n_cts + lo) * n, o_d + 2 * k * c * n, bytes));
       ZK_CK(zkfhe_download(ctx, out1 + (k * n_cts + lo) * n, o_d + (2 * k + 1) * c * n, bytes));
     }
+  }
+  return ZKFHE_OK;
+}
+
+// The chunk rule of linear_transform_bsgs.  A ciphertext holds max(1 + l, 2 n_baby) polynomials of hoisted rows or baby rotations
+// and (1 + l) hoisted rows per giant step; cts ciphertexts with all their giant steps fit the budget of chunk_polys(N).  Where one
+// ciphertext's giant rows alone exceed it (cts = 1), the giant steps go in groups of giants and the groups add up in the transform
+// domain.  A chunk that is not the whole batch is a multiple of the kernels' tile of CT ciphertexts.
+void bsgs_chunks(uint64_t n, size_t n_cts, size_t n_baby, size_t n_giant, size_t rows, size_t *cts, size_t *giants) {
+  *cts = chunk_cts(n, n_cts, std::max(rows, 2 * n_baby) + n_giant * rows);
+  if (*cts > CT && *cts < n_cts) *cts -= *cts % CT;   // whole ciphertext tiles, unless the chunk is the batch
+  *giants = std::min(n_giant, std::max<size_t>(1, chunk_polys(n) / (*cts * rows)));
+}
+
+template <int GT, int CTI>
+void launch_bsgs_inner(zkfhe_ctx *ctx, const uint32_t *baby, const uint32_t *diag_hat, size_t n_baby, size_t n_giant, size_t c, int log_n,
+                       const RnsConst<NP> &rc, uint32_t *out) {
+  const dim3 grid(zk_blocks((size_t)1 << log_n, ACC_THREADS), NP, (unsigned)(zk_blocks(n_giant, GT) * zk_blocks(c, CTI)));
+  k_bsgs_inner<GT, CTI><<<grid, ACC_THREADS, 0, ctx->stream>>>(baby, diag_hat, (int)n_baby, (int)n_giant, c, log_n, rc, out);
+}
+
+int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, size_t n_baby,
+              const uint64_t *g_baby, const uint64_t *bk0, const uint64_t *bk1, size_t n_giant, const uint64_t *g_giant, const uint64_t *hk0,
+              const uint64_t *hk1, int base_bits, const uint64_t *diag, uint64_t *out0, uint64_t *out1) {
+  const char *fn = "bfv_linear_transform_bsgs";
+  ZK_CK(check_params(ctx, params));
+  int l = 0;
+  ZK_CK(relin_rows(ctx, params, base_bits, fn, &l));
+  const uint64_t n = params->n, q = params->q;
+  if ((n_baby >> 20) || (n_giant >> 20)) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": more than 2^20 Galois elements");
+  const size_t n_elems = n_baby + n_giant;   // the baby elements, then the giant ones
+  const auto g_of = [&](size_t k) { return k < n_baby ? g_baby[k] : g_giant[k - n_baby]; };
+  for (size_t k = 0; k < n_elems; ++k)
+    if (!(g_of(k) & 1) || g_of(k) >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": every Galois element g must be odd and below 2N");
+  ZK_CK(check_range(ctx, params, n_baby, l, base_bits, fn));   // the inner sum; before any O(n) pass and any device work
+  const int log_n = bit_log2(n);
+  const size_t lw = (size_t)l * n;
+  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, fn, "a ciphertext", c1));
+  std::vector<uint32_t> elem(2 * n_elems);
+  size_t slots = 0;
+  for (size_t k = 0; k < n_elems; ++k) {   // the key rows of g = 1 are neither read nor checked
+    const uint64_t *k0 = k < n_baby ? bk0 + k * lw : hk0 + (k - n_baby) * lw, *k1 = k < n_baby ? bk1 + k * lw : hk1 + (k - n_baby) * lw;
+    elem[2 * k] = (uint32_t)g_of(k);
+    elem[2 * k + 1] = g_of(k) == 1 ? NO_KEY : (uint32_t)slots++;
+    if (g_of(k) != 1) ZK_CK(check_below_q(ctx, k0, lw, q, fn, "a Galois-key", k1));
+  }
+  const size_t n_diag = n_giant * n_baby;
+  ZK_CK(check_plain(ctx, diag, n_diag * n, q, params->t, fn, "a diagonal"));
+
+  const size_t rows = (size_t)l + 1;
+  size_t chunk, group;
+  bsgs_chunks(n, n_cts, n_baby, n_giant, rows, &chunk, &group);
+  const size_t cw = chunk * n;
+  int *flag;
+  uint64_t *key_d, *diag_d, *x_d, *inner_q, *o_d;
+  uint32_t *key_hat, *diag_hat, *elem_d, *hst, *baby, *inner, *hst_in, *res;
+  ZK_CK(Arena().add(flag, 1).add(elem_d, 2 * n_elems).add(key_d, 2 * slots * lw).add(key_hat, 2 * slots * lw * NP).add(diag_d, n_diag * n)
+            .add(diag_hat, n_diag * n * NP).add(x_d, 2 * cw).add(hst, rows * cw * NP).add(baby, 2 * n_baby * cw * NP)
+            .add(inner, 2 * group * cw * NP).add(inner_q, 2 * group * cw).add(hst_in, group * rows * cw * NP).add(res, 2 * cw * NP)
+            .add(o_d, 2 * cw).carve(ctx));
+  ZK_CK(zkfhe_upload(ctx, elem_d, elem.data(), elem.size() * 4));
+  for (size_t k = 0; k < n_elems; ++k) {   // key slot s: its gk0 rows, then its gk1 rows
+    if (elem[2 * k + 1] == NO_KEY) continue;
+    const uint64_t *k0 = k < n_baby ? bk0 + k * lw : hk0 + (k - n_baby) * lw, *k1 = k < n_baby ? bk1 + k * lw : hk1 + (k - n_baby) * lw;
+    ZK_CK(zkfhe_upload(ctx, key_d + (size_t)elem[2 * k + 1] * 2 * lw, k0, lw * 8));
+    ZK_CK(zkfhe_upload(ctx, key_d + ((size_t)elem[2 * k + 1] * 2 + 1) * lw, k1, lw * 8));
+  }
+  if (slots) ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * slots * l, log_n, nullptr, 0, key_hat, flag));
+  ZK_CK(zkfhe_upload(ctx, diag_d, diag, n_diag * n * 8));
+  ZK_CK(launch_rns_ntt<NP>(ctx, false, diag_d, LOAD_CENTRED, q, n_diag, log_n, nullptr, 0, diag_hat, flag));
+  const uint32_t *tw;
+  ZK_CK(zk_rns_tables(ctx, &tw));
+  int lds_h, lds_i;
+  ZK_CK(ntt_lds(ctx, (const void *)k_hoist, log_n, &lds_h));
+  ZK_CK(ntt_lds(ctx, (const void *)k_rns_intt, log_n, &lds_i));
+  // Montgomery factors: a rotation carries R^-1 (one product with a key word), the inner sum one more product with a diagonal
+  const RnsConst<NP> rc = rns_const<NP>(log_n), rc_inner = intt_const(log_n, 2), rc_outer = intt_const(log_n, 1);
+  GadgetStep gs;
+  for (int j = 0; j < NP; ++j) gs.step[j] = (uint32_t)((((uint64_t)1 << base_bits) % PRIMES[j]) * (((uint64_t)1 << 32) % PRIMES[j]) % PRIMES[j]);
+  size_t baby_slots = 0;
+  for (size_t k = 0; k < n_baby; ++k) baby_slots += elem[2 * k + 1] != NO_KEY;
+  const double words = (double)NP * n;   // one polynomial at every prime
+  for (size_t lo = 0; lo < n_cts; lo += chunk) {
+    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
+    ZK_CK(zkfhe_upload(ctx, x_d, c0 + lo * n, bytes));
+    ZK_CK(zkfhe_upload(ctx, x_d + c * n, c1 + lo * n, bytes));
+    zk_prof_begin(ctx);
+    k_hoist<<<(unsigned)(c * rows * NP), NTT_THREADS, lds_h, ctx->stream>>>(x_d, c, l, base_bits, q, log_n, tw, rc, hst);
+    ZK_LAUNCH_CHECK(ctx);
+    zk_prof_end(ctx, ZKFHE_PROF_BFV_HOIST, (double)c * rows * words * (8.0 + 4.0));
+    const dim3 grid(zk_blocks(n, ACC_THREADS), NP, zk_blocks(c, CT));
+    zk_prof_begin(ctx);   // the baby rotations stay in the transform domain
+    k_linear_acc<ACC_MANY><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_baby, key_hat, nullptr, l, c, log_n, rc, gs, baby);
+    ZK_LAUNCH_CHECK(ctx);
+    zk_prof_end(ctx, ZKFHE_PROF_BFV_LINEAR, 4.0 * words * ((double)n_baby * c * rows + (double)zk_blocks(c, CT) * 2.0 * baby_slots * l + 2.0 * n_baby * c));
+    ZK_HIP(ctx, hipMemsetAsync(res, 0, 2 * c * n * NP * 4, ctx->stream));
+    for (size_t g0 = 0; g0 < n_giant; g0 += group) {
+      const size_t gg = std::min(group, n_giant - g0), inner_cts = gg * c;
+      const uint32_t *dh = diag_hat + g0 * n_baby * NP * n;
+      const int cti = c == 1 ? 1 : c == 2 ? 2 : 4;   // a single ciphertext (the tally) does not pay for a padded ciphertext tile
+      zk_prof_begin(ctx);
+      if (cti == 1)
+        launch_bsgs_inner<8, 1>(ctx, baby, dh, n_baby, gg, c, log_n, rc, inner);
+      else if (cti == 2)
+        launch_bsgs_inner<4, 2>(ctx, baby, dh, n_baby, gg, c, log_n, rc, inner);
+      else
+        launch_bsgs_inner<4, 4>(ctx, baby, dh, n_baby, gg, c, log_n, rc, inner);
+      ZK_LAUNCH_CHECK(ctx);
+      // read: every baby word once per giant tile, every diagonal word once per ciphertext group; written: the inner sums
+      zk_prof_end(ctx, ZKFHE_PROF_BFV_BSGS_INNER, 4.0 * words * ((double)zk_blocks(gg, cti == 1 ? 8 : 4) * 2.0 * n_baby * c + (double)zk_blocks(c, cti) * gg * n_baby + 2.0 * inner_cts));
+      zk_prof_begin(ctx);
+      k_rns_intt<<<(unsigned)(2 * inner_cts * NP), NTT_THREADS, lds_i, ctx->stream>>>(inner, log_n, tw, rc_inner);
+      ZK_LAUNCH_CHECK(ctx);
+      zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, 2.0 * inner_cts * words * 8.0);
+      ZK_CK(zk_bfv_eval_epilogue(ctx, inner, 2 * inner_cts, log_n, q, EvEpi{}, inner_q));   // [c0 | c1] of the gg c inner ciphertexts
+      zk_prof_begin(ctx);
+      k_hoist<<<(unsigned)(inner_cts * rows * NP), NTT_THREADS, lds_h, ctx->stream>>>(inner_q, inner_cts, l, base_bits, q, log_n, tw, rc, hst_in);
+      ZK_LAUNCH_CHECK(ctx);
+      zk_prof_end(ctx, ZKFHE_PROF_BFV_HOIST, (double)inner_cts * rows * words * (8.0 + 4.0));
+      size_t giant_slots = 0;
+      for (size_t k = 0; k < gg; ++k) giant_slots += elem[2 * (n_baby + g0 + k) + 1] != NO_KEY;
+      zk_prof_begin(ctx);
+      k_linear_acc<ACC_GIANT><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst_in, elem_d + 2 * (n_baby + g0), (int)gg, key_hat, nullptr, l, c, log_n, rc, gs, res);
+      ZK_LAUNCH_CHECK(ctx);
+      // read: the hoisted rows of every inner ciphertext, every key word once per CT ciphertexts, the sum so far; written: the sum
+      zk_prof_end(ctx, ZKFHE_PROF_BFV_BSGS_GIANT, 4.0 * words * ((double)inner_cts * rows + (double)zk_blocks(c, CT) * 2.0 * giant_slots * l + 4.0 * c));
+    }
+    zk_prof_begin(ctx);
+    k_rns_intt<<<(unsigned)(2 * c * NP), NTT_THREADS, lds_i, ctx->stream>>>(res, log_n, tw, rc_outer);
+    ZK_LAUNCH_CHECK(ctx);
+    zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, 2.0 * c * words * 8.0);
+    ZK_CK(zk_bfv_eval_epilogue(ctx, res, 2 * c, log_n, q, EvEpi{}, o_d));
+    ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
+    ZK_CK(zkfhe_download(ctx, out1 + lo * n, o_d + c * n, bytes));
   }
   return ZKFHE_OK;
 }
@@ -279,6 +483,15 @@ int zkfhe_bfv_linear_transform(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, s
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && c0 && c1 && g && gk0 && gk1 && diag && out0 && out1 && n_cts > 0 && n_elems > 0);
   return linear_call(ctx, params, n_cts, c0, c1, n_elems, g, gk0, gk1, base_bits, diag, out0, out1, "bfv_linear_transform");
+}
+
+int zkfhe_bfv_linear_transform_bsgs(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1,
+                                    size_t n_baby, const uint64_t *g_baby, const uint64_t *bk0, const uint64_t *bk1, size_t n_giant,
+                                    const uint64_t *g_giant, const uint64_t *hk0, const uint64_t *hk1, int base_bits, const uint64_t *diag,
+                                    uint64_t *out0, uint64_t *out1) {
+  ZK_ENTER(ctx);
+  ZK_ARG(ctx, ctx && c0 && c1 && g_baby && bk0 && bk1 && g_giant && hk0 && hk1 && diag && out0 && out1 && n_cts > 0 && n_baby > 0 && n_giant > 0);
+  return bsgs_call(ctx, params, n_cts, c0, c1, n_baby, g_baby, bk0, bk1, n_giant, g_giant, hk0, hk1, base_bits, diag, out0, out1);
 }
 
 }  // extern "C"
