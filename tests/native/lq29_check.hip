@@ -1,7 +1,8 @@
 // Host-side check of the lazy signed-limb arithmetic over Fq in csrc/fq29.hip.hpp (Lz<LO, HI, V>, lq_mul / lq_sqr / lq_mul2 and the
 // point operations of the MSM kernels written on them) against the standard 8 x 32-bit arithmetic of bn254.hip.hpp.  The value a
 // limb vector stands for is computed here by Horner's rule in the standard arithmetic, independently of the code under test.  The host
-// pass compiles the C bodies of the products (what -DZK_MAD_C selects on the device); the generated assembly is covered by the GPU tests.
+// pass compiles the C bodies of the products (what -DZK_MAD_C selects on the device); the generated assembly runs on the same
+// extreme operands in tests/native/tied_products_check.hip.
 #include "fq29.hip.hpp"
 #include <cstdio>
 #include <random>

@@ -39,8 +39,11 @@ def test_radix29_field_and_point_arithmetic(tmp_path):
 
 def test_lazy_signed_limb_arithmetic(tmp_path):
     """csrc/lz29.hip.hpp (the arithmetic of the 2^13 NTT tile: signed lazy limbs with compile-time bounds, products against unpacked
-    twiddles, weak reduction of values of either sign, canonical store) against the standard 8 x 32-bit Fr arithmetic.  Host
-    instantiation of the same host+device code (no GPU)."""
+    twiddles, weak reduction of values of either sign, canonical store) against the standard 8 x 32-bit Fr arithmetic: random
+    operands, then the largest operands of either sign each declared bound admits (lz_mul at 160 r with limbs below 2^30, lz_mul2 at
+    80 r twice, lz_mul4u on the largest canonical data) against the largest canonical twiddle, r - 1 and random twiddles, and
+    lz_weak / lz_store / lz_store_weak on every multiple of r within 16 r and its two neighbours.  Host instantiation of the same
+    host+device code (no GPU)."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
@@ -48,7 +51,7 @@ def test_lazy_signed_limb_arithmetic(tmp_path):
     subprocess.run([hipcc, "-O2", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "zk-fhe_amd", "csrc"),
                     "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "native", "lz29_check.hip"), "-o", exe], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    assert "lz29: 0 bad" in out, out
+    assert "lz29: 0 bad" in out and "lz29 edges: 0 bad" in out, out
 
 
 def test_fr_nine_limb_sums_of_the_element_wise_kernels(tmp_path):

@@ -1,7 +1,9 @@
 """The lazy signed-limb arithmetic over Fq and the point operations of the MSM kernels written on it (zk-fhe_amd/csrc/fq29.hip.hpp:
 Lz<LO, HI, V>, lq_mul / lq_sqr / lq_mul2, g1x29_add_affine / g1x29_add / g1x29_dbl) against the 8 x 32-bit arithmetic of
 bn254.hip.hpp.  The code is host+device; this builds and runs its host instantiation (the C bodies of the products, which
--DZK_MAD_C also selects on the device) -- no GPU.  The generated assembly is covered by tests/test_gpu_msm_lazy.py."""
+-DZK_MAD_C also selects on the device) -- no GPU.  The generated assembly the device runs instead (csrc/mont29_tied.inc) meets the
+same extreme operands in tests/test_gpu_tied_products.py; tests/test_gpu_msm_lazy.py reaches it only through whole MSMs on random
+scalars, which stay far below the bounds."""
 import os
 import shutil
 import subprocess
