@@ -110,6 +110,11 @@ int zkfhe_fr_batch_invert(zkfhe_ctx *ctx, zkfhe_fr *a_dev, size_t n);
 /* the same inversion with a numerator: num[i] <- num[i] * den[i]^-1 in one kernel (0 where den[i] = 0: what the call above followed
  * by zkfhe_fr_mul gives); den is only read and must not alias num */
 int zkfhe_fr_batch_invert_mul(zkfhe_ctx *ctx, const zkfhe_fr *den_dev, zkfhe_fr *num_dev, size_t n);
+/* The nine-limb Fr arithmetic of the prover's kernels, element by element (a test entry).  in_dev holds five operand arrays of n
+ * elements one after the other (a, b, c, d, e; an operation reads the ones it names), out_dev n results, canonical.
+ * op 0: a b;  1: a^2;  2: a b + c d;  3: a (b + c d + e), a step of a permutation product;  4: (a + b)(c + d), a lookup term;
+ * 5: a b c, the first product regrouped in registers as the constant operand of the second. */
+int zkfhe_fr9_op(zkfhe_ctx *ctx, int op, const zkfhe_fr *in_dev, zkfhe_fr *out_dev, size_t n);
 /* modmul micro-benchmark: out[i] = a[i]^(2^iters) by repeated squaring (ALU-roofline probe) */
 int zkfhe_fr_sqr_chain(zkfhe_ctx *ctx, const zkfhe_fr *a_dev, zkfhe_fr *out_dev, size_t n, int iters);
 /* the same probe for the radix-2^29 product the MSM kernels use (nine 29-bit limbs, Montgomery constant 2^261): a[i] < q as a

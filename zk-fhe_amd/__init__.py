@@ -29,7 +29,7 @@ EXPORTS = [
     "zkfhe_dev_alloc", "zkfhe_dev_free", "zkfhe_upload", "zkfhe_download", "zkfhe_copy_dev", "zkfhe_memset_dev",
     "zkfhe_timer_start", "zkfhe_timer_stop_ms", "zkfhe_prof_enable", "zkfhe_prof_reset", "zkfhe_prof_read", "zkfhe_prof_read_ops", "zkfhe_ctx_last_proof_marks", "zkfhe_ctx_last_proof_commands",
     "zkfhe_fr_add", "zkfhe_fr_sub", "zkfhe_fr_mul", "zkfhe_fr_scale", "zkfhe_fr_to_mont", "zkfhe_fr_from_mont",
-    "zkfhe_fr_batch_invert", "zkfhe_fr_batch_invert_mul", "zkfhe_fr_sqr_chain", "zkfhe_fq29_sqr_chain",
+    "zkfhe_fr_batch_invert", "zkfhe_fr_batch_invert_mul", "zkfhe_fr9_op", "zkfhe_fr_sqr_chain", "zkfhe_fq29_sqr_chain",
     "zkfhe_ntt_batch", "zkfhe_ntt_batch_to", "zkfhe_coset_ntt_batch",
     "zkfhe_basis_create", "zkfhe_basis_destroy", "zkfhe_basis_len", "zkfhe_msm_batch",
     "zkfhe_g1_add", "zkfhe_g1_mul", "zkfhe_msm_sparse", "zkfhe_msm_batch_xyzz", "zkfhe_msm_sparse_xyzz", "zkfhe_g1_xyzz_to_affine", "zkfhe_basis_has_multiples", "zkfhe_basis_table_bits", "zkfhe_basis_table_bytes", "zkfhe_srs_table_bits", "zkfhe_srs_table_info",
@@ -103,6 +103,7 @@ def load_library():
     lib.zkfhe_fr_from_mont.argtypes = [vp, vp, vp, sz]
     lib.zkfhe_fr_batch_invert.argtypes = [vp, vp, sz]
     lib.zkfhe_fr_batch_invert_mul.argtypes = [vp, vp, vp, sz]
+    lib.zkfhe_fr9_op.argtypes = [vp, ci, vp, vp, sz]
     lib.zkfhe_fr_sqr_chain.argtypes = [vp, vp, vp, sz, ci]
     lib.zkfhe_ntt_batch.argtypes = [vp, vp, sz, ci, ci]
     lib.zkfhe_coset_ntt_batch.argtypes = [vp, vp, vp, sz, ci, ci, vp, ci]
@@ -296,6 +297,19 @@ class Context:
         self._check(self.lib.zkfhe_fr_batch_invert_mul(self.h, self._p(dd), self._p(dn), n))
         out = dn.download(shape=num.shape)
         dn.free(), dd.free()
+        return out
+
+    FR9_OPS = {"mul": 0, "sqr": 1, "mul2": 2, "perm": 3, "lookup": 4, "chain": 5}
+
+    def fr9_op(self, op, operands):
+        """zkfhe_fr9_op: the nine-limb Fr arithmetic of the prover's kernels on five operand arrays (n, 4) each"""
+        ops = self._fr(np.stack([self._fr(o) for o in operands]))
+        assert ops.shape[0] == 5
+        n = ops.shape[1]
+        din, dout = self.to_device(ops), self.alloc(max(n, 1) * 32)
+        self._check(self.lib.zkfhe_fr9_op(self.h, self.FR9_OPS[op], self._p(din), self._p(dout), n))
+        out = dout.download(shape=(n, 4))
+        din.free(), dout.free()
         return out
 
     def fr_unop(self, name, a, *extra):

@@ -11,6 +11,7 @@
 #include "ctx.hpp"
 #include "fq29.hip.hpp"
 #include "fr29.hip.hpp"
+#include "fr9.hip.hpp"
 
 using namespace zk;
 
@@ -344,6 +345,29 @@ __global__ void __launch_bounds__(256) k_fq29_sqr_chain(const Fq *__restrict__ a
   out[i] = f29_pack(f29_canonical(x));
 }
 
+// The operations of the nine-limb Fr type (fr9.hip.hpp) as the prover's kernels compose them, one element per thread, for the tests:
+// operand array j of element i is in[j * n + i]; every result is stored canonical.
+enum { FR9_MUL = 0, FR9_SQR = 1, FR9_MUL2 = 2, FR9_PERM = 3, FR9_LOOKUP = 4, FR9_CHAIN = 5, FR9_OPS = 6 };
+__global__ void __launch_bounds__(256) k_fr9_op(int op, const Fr *__restrict__ in, Fr *__restrict__ out, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const Fr a = in[i], b = in[n + i], c = in[2 * n + i], d = in[3 * n + i], e = in[4 * n + i];
+    Fr r;
+    switch (op) {
+      case FR9_MUL: r = fr9_store(fr9_mul(fr9_load(a), fr9_load32(b))); break;
+      // the square of an S value is x^2 2^251; the product with 2^266 that fr9_cc is takes it back to S
+      case FR9_SQR: r = fr9_store(fr9_cc(fr9_sqr(fr9_load(a)))); break;
+      case FR9_MUL2: r = fr9_store(fr9_mul2(fr9_load(a), fr9_load32(b), fr9_load32(c), fr9_load(d))); break;
+      // a (b + c d + e): one step of a permutation product -- c is the constant turned to the 2^266 form
+      case FR9_PERM: r = fr9_store(fr9_perm_step(fr9_load(a), fr9_perm_factor(fr9_load32(b), fr9_mul(fr9_load(d), fr9_cc(fr9_load32(c))), fr9_load32(e)))); break;
+      // a b c: the product a b regrouped in registers (fr9_times32) as the C operand of the next product
+      case FR9_CHAIN: r = fr9_store(fr9_mul(fr9_load(c), fr9_times32(fr9_mul(fr9_load(a), fr9_load32(b))))); break;
+      // (a + b)(c + d): one term of the lookup argument
+      default: r = fr9_store(fr9_lookup_term(fr9_load(a), fr9_load(b), fr9_lookup_sum(fr9_load32(c), fr9_load32(d)))); break;
+    }
+    out[i] = r;
+  }
+}
+
 // Batch inversion, Montgomery trick per thread over a strided chunk of CHUNK elements:
 // thread t owns elements t, t+T, t+2T, ... (T = total threads) so every load/store is coalesced.
 // prefix products go to `tmp` (n elements).  Zero elements are skipped and stay zero.  NUM: num[i] <- num[i] * a[i]^-1 in the same
@@ -356,14 +380,16 @@ template <bool NUM>
 __global__ void __launch_bounds__(256) k_fr_batch_invert(Fr *__restrict__ a, Fr *__restrict__ num, Fr *__restrict__ tmp, size_t n, size_t T) {
   size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (t >= T) return;
-  Fr acc = Fr::one();
+  // The chains run on nine-limb values (fr9.hip.hpp): acc stays in the standard form in limbs from element to element, what it is
+  // multiplied by is read in the 2^261 form (the same word five bits up); tmp[] and the results are canonical packed words.
+  Lz<0, 1, 2> acc = lz_widen<0, 1, 2>(fr9_one());
   int cnt = 0;
   for (size_t i = t; i < n; i += T, ++cnt) {
-    tmp[i] = acc;
+    tmp[i] = fr9_store(acc);
     Fr x = a[i];
-    if (!x.is_zero()) acc = acc * x;
+    if (!x.is_zero()) acc = fr9_mul(acc, fr9_load32(x));
   }
-  acc = fp_inv<FrP>(acc);
+  acc = lz_widen<0, 1, 2>(fr9_load(fp_inv<FrP>(fr9_store(acc))));
   for (int k = cnt - 1; k >= 0; --k) {
     size_t i = t + (size_t)k * T;
     Fr x = a[i];
@@ -371,10 +397,10 @@ __global__ void __launch_bounds__(256) k_fr_batch_invert(Fr *__restrict__ a, Fr 
       if (NUM) num[i] = Fr::zero();   // what the product with the plain call's "inverse" of zero would be
       continue;
     }
-    Fr inv = acc * tmp[i];
-    acc = acc * x;
-    if (NUM) num[i] = num[i] * inv;   // NUM: the quotient goes to the numerator's array, `a` is only read
-    else a[i] = inv;
+    const Lz<0, 1, 2> inv = fr9_mul(acc, fr9_load32(tmp[i]));
+    acc = fr9_mul(acc, fr9_load32(x));
+    if (NUM) num[i] = fr9_store(fr9_mul(inv, fr9_load32(num[i])));   // NUM: the quotient goes to the numerator's array, `a` is only read
+    else a[i] = fr9_store(inv);
   }
 }
 
@@ -458,6 +484,15 @@ int zkfhe_fr_batch_invert_mul(zkfhe_ctx *ctx, const zkfhe_fr *den, zkfhe_fr *num
   ZK_ENTER(ctx);
   ZK_ARG(ctx, n == 0 || (den != nullptr && num != nullptr && (const void *)den != (const void *)num));
   return batch_invert(ctx, (Fr *)den, (Fr *)num, n);
+}
+int zkfhe_fr9_op(zkfhe_ctx *ctx, int op, const zkfhe_fr *in, zkfhe_fr *out, size_t n) {
+  ZK_ENTER(ctx);
+  ZK_ARG(ctx, op >= 0 && op < FR9_OPS);
+  if (!n) return ZKFHE_OK;
+  ZK_ARG(ctx, in != nullptr && out != nullptr);
+  k_fr9_op<<<ew_grid(ctx, n), 256, 0, ctx->stream>>>(op, (const Fr *)in, (Fr *)out, n);
+  ZK_LAUNCH_CHECK(ctx);
+  return ZKFHE_OK;
 }
 int zkfhe_fr_sqr_chain(zkfhe_ctx *ctx, const zkfhe_fr *a, zkfhe_fr *out, size_t n, int iters) {
   ZK_ENTER(ctx);

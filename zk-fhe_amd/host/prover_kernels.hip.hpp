@@ -4,7 +4,7 @@
 // omega is an index shift inside a row and X^n - 1 is constant per row.
 #pragma once
 #include "../csrc/ctx.hpp"
-#include "../csrc/fr29.hip.hpp"
+#include "../csrc/fr9.hip.hpp"
 
 namespace zkp {
 
@@ -214,10 +214,12 @@ static __global__ void __launch_bounds__(256) k_lookup_num_den(const Fr *__restr
                                                         const Fr *__restrict__ ls, Fr beta, Fr gamma, unsigned n_lookup, size_t n,
                                                         Fr *__restrict__ num, Fr *__restrict__ den) {
   const size_t total = (size_t)n_lookup * n;
+  const zk::Fr9S beta9 = zk::fr9_load(beta);
+  const zk::Fr9C gamma9 = zk::fr9_load32(gamma);
   for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
     const size_t i = g % n;
-    num[g] = (a_cols[g] + beta) * (table[i] + gamma);
-    den[g] = (la[g] + beta) * (ls[g] + gamma);
+    num[g] = zk::fr9_store(zk::fr9_lookup_term(zk::fr9_load(a_cols[g]), beta9, zk::fr9_lookup_sum(zk::fr9_load32(table[i]), gamma9)));
+    den[g] = zk::fr9_store(zk::fr9_lookup_term(zk::fr9_load(la[g]), beta9, zk::fr9_lookup_sum(zk::fr9_load32(ls[g]), gamma9)));
   }
 }
 
@@ -236,26 +238,27 @@ static __global__ void __launch_bounds__(1024) k_prefix_product(const Fr *__rest
   Fr *o = z + col * n;
   const unsigned per = (unsigned)((n + 1023) / 1024);
   const unsigned lo = threadIdx.x * per;
-  Fr local = Fr::one();
+  // the runs and the scan on nine-limb values (csrc/fr9.hip.hpp): the running product S, every ratio read in the C form; the LDS
+  // keeps packed canonical words
+  zk::Lz<0, 1, 2> local = zk::lz_widen<0, 1, 2>(zk::fr9_one());
   for (unsigned k = 0; k < per; ++k) {
     const unsigned i = lo + k;
-    if (i < u) local = local * r[i];
+    if (i < u) local = zk::fr9_mul(local, zk::fr9_load32(r[i]));
   }
-  sh[threadIdx.x] = local;
+  sh[threadIdx.x] = zk::fr9_store(local);
   __syncthreads();
   // inclusive Hillis-Steele scan of the 1024 partial products
   for (unsigned d = 1; d < 1024; d <<= 1) {
-    Fr v = sh[threadIdx.x];
-    Fr other = threadIdx.x >= d ? sh[threadIdx.x - d] : Fr::one();
+    if (threadIdx.x >= d) local = zk::fr9_mul(local, zk::fr9_load32(sh[threadIdx.x - d]));
     __syncthreads();
-    if (threadIdx.x >= d) sh[threadIdx.x] = other * v;
+    if (threadIdx.x >= d) sh[threadIdx.x] = zk::fr9_store(local);
     __syncthreads();
   }
-  Fr acc = threadIdx.x ? sh[threadIdx.x - 1] : Fr::one();  // product of everything before this thread's rows
+  zk::Lz<0, 1, 2> acc = zk::lz_widen<0, 1, 2>(threadIdx.x ? zk::fr9_load(sh[threadIdx.x - 1]) : zk::fr9_one());  // product of everything before this thread's rows
   for (unsigned k = 0; k < per; ++k) {
     const unsigned i = lo + k;
-    if (i <= u) o[i] = acc;
-    if (i < u) acc = acc * r[i];
+    if (i <= u) o[i] = zk::fr9_store(acc);
+    if (i < u) acc = zk::fr9_mul(acc, zk::fr9_load32(r[i]));
   }
   if (threadIdx.x == 1023) total[col] = sh[1023];
 }
@@ -405,76 +408,85 @@ static __global__ void __launch_bounds__(256) k_quotient_partials(QArgs a) {
   const size_t row0 = p & ~(n - 1);           // k1 * n
   const size_t k2 = p & (n - 1);
   auto at = [&](const Fr *base, unsigned col, unsigned rot) -> Fr { return base[(size_t)col * ne + row0 + ((k2 + rot) & (n - 1))]; };
-  const Fr one = Fr::one();
-  Fr acc = Fr::zero();
-  // acc * y + u * v with one Montgomery reduction (bn254.hip.hpp fp_mul2): the Horner step of every expression
-  auto horner = [&](const Fr &u, const Fr &v) { acc = zk::fp_mul2<zk::FrP>(acc, a.y, u, v); };
+  // Nine-limb values throughout (csrc/fr9.hip.hpp): of every product one operand is read in the standard form (S: ld) and one in the
+  // 2^261 form (C: ld32, the same word five bits up), the result is S; acc and the running products never leave limb form.
+  auto ld = [&](const Fr *base, unsigned col, unsigned rot) { return zk::fr9_load(at(base, col, rot)); };
+  auto ld32 = [&](const Fr *base, unsigned col, unsigned rot) { return zk::fr9_load32(at(base, col, rot)); };
+  const zk::Fr9C y = zk::fr9_load32(a.y);
+  zk::Lz<0, 1, 3> acc = zk::lz_widen<0, 1, 3>(zk::lz_zero());
+  // acc * y + u * v with one Montgomery reduction (fr9_mul2): the Horner step of every expression; u is C, v is S
+  auto horner = [&](const zk::Fr9C &u, const auto &v) { acc = zk::lz_widen<0, 1, 3>(zk::fr9_mul2(acc, y, u, v)); };
   switch (g.type) {
     case QG_GATE:
       for (int j = g.first; j < g.first + g.count; ++j) {
         const Fr q = at(a.fix, j, 0);
-        if (!q.is_zero()) horner(q, at(a.adv, j, 0) + at(a.adv, j, 1) * at(a.adv, j, 2) - at(a.adv, j, 3));
-        else acc = acc * a.y;
+        if (!q.is_zero())
+          horner(zk::fr9_load32(q), zk::fr9_norm(zk::lz_sub(zk::lz_add(ld(a.adv, j, 0), zk::fr9_mul(ld(a.adv, j, 1), ld32(a.adv, j, 2))), ld(a.adv, j, 3))));
+        else acc = zk::lz_widen<0, 1, 3>(zk::fr9_mul(acc, y));
       }
       break;
-    case QG_RLC:
+    case QG_RLC: {
+      const zk::Fr9C gamma_rlc = zk::fr9_load32(a.gamma_rlc);
       for (int j = g.first; j < g.first + g.count; ++j) {
         const unsigned col = a.adv_rlc0 + j;
-        const Fr q = at(a.fix, a.fix_qrlc0 + j, 0);
-        horner(q, at(a.adv, col, 0) * a.gamma_rlc + at(a.adv, col, 1) - at(a.adv, col, 2));
+        horner(ld32(a.fix, a.fix_qrlc0 + j, 0), zk::fr9_norm(zk::lz_sub(zk::lz_add(zk::fr9_mul(ld(a.adv, col, 0), gamma_rlc), ld(a.adv, col, 1)), ld(a.adv, col, 2))));
       }
       break;
+    }
     case QG_PERM_HEAD: {
-      const Fr l0 = a.lext[p], ll = a.lext[ne + p];
-      const Fr z0 = at(a.pz, 0, 0), zm = at(a.pz, a.n_chunks - 1, 0);
-      acc = l0 * (one - z0);
-      horner(ll, zm * zm - zm);
+      const Fr zm = at(a.pz, a.n_chunks - 1, 0);
+      acc = zk::lz_widen<0, 1, 3>(zk::fr9_mul(zk::fr9_load32(a.lext[p]), zk::lz_sub(zk::fr9_one(), ld(a.pz, 0, 0))));
+      horner(zk::fr9_load32(a.lext[ne + p]), zk::lz_sub(zk::fr9_mul(zk::fr9_load(zm), zk::fr9_load32(zm)), zk::fr9_load(zm)));
       break;
     }
     case QG_PERM_FIRST:   // the two expressions of QG_PERM_HEAD as groups of their own (they belong to different ranks when the
-      acc = a.lext[p] * (one - at(a.pz, 0, 0));   // quotient is sharded by column)
+      acc = zk::lz_widen<0, 1, 3>(zk::fr9_mul(zk::fr9_load32(a.lext[p]), zk::lz_sub(zk::fr9_one(), ld(a.pz, 0, 0))));   // quotient is sharded by column)
       break;
     case QG_PERM_LAST: {
       const Fr zm = at(a.pz, a.n_chunks - 1, 0);
-      acc = a.lext[ne + p] * (zm * zm - zm);
+      acc = zk::lz_widen<0, 1, 3>(zk::fr9_mul(zk::fr9_load32(a.lext[ne + p]), zk::lz_sub(zk::fr9_mul(zk::fr9_load(zm), zk::fr9_load32(zm)), zk::fr9_load(zm))));
       break;
     }
     case QG_PERM_C: {
-      const Fr l0 = a.lext[p];
-      for (int j = g.first; j < g.first + g.count; ++j) horner(l0, at(a.pz, j, 0) - at(a.pz, j - 1, a.u));
+      const zk::Fr9C l0 = zk::fr9_load32(a.lext[p]);
+      for (int j = g.first; j < g.first + g.count; ++j) horner(l0, zk::lz_sub(ld(a.pz, j, 0), ld(a.pz, j - 1, a.u)));
       break;
     }
     case QG_PERM_D: {
-      const Fr lact = a.lext[2 * ne + p];
-      const Fr x = a.xs[p];
+      // a factor v + beta sigma + gamma is built in the C form (v, gamma read five bits up; beta and the thread's x turned to the
+      // 2^266 form once, so that their products with the S values sigma and beta_delta[c] come out C): the running products stay S
+      const zk::Fr9C lact = zk::fr9_load32(a.lext[2 * ne + p]), gamma = zk::fr9_load32(a.gamma);
+      const zk::Lz<0, 1, 2> beta = zk::fr9_cc(zk::fr9_load32(a.beta)), x = zk::fr9_cc(zk::fr9_load32(a.xs[p]));
       for (int j = g.first; j < g.first + g.count; ++j) {
-        Fr left = at(a.pz, j, 1), right = at(a.pz, j, 0);
+        zk::Lz<0, 1, 3> left = zk::lz_widen<0, 1, 3>(ld(a.pz, j, 1)), right = zk::lz_widen<0, 1, 3>(ld(a.pz, j, 0));
         for (unsigned c = j * a.chunk; c < (j + 1) * a.chunk && c < a.n_perm; ++c) {
-          const Fr v = c < a.n_advice ? at(a.adv, c, 0) : (c == a.n_advice ? at(a.fix, a.fix_const, 0) : a.inst[p]);
-          left = left * (v + a.beta * at(a.sig, c, 0) + a.gamma);
-          right = right * (v + a.beta_delta[c] * x + a.gamma);
+          const zk::Fr9C v = zk::fr9_load32(c < a.n_advice ? at(a.adv, c, 0) : (c == a.n_advice ? at(a.fix, a.fix_const, 0) : a.inst[p]));
+          left = zk::fr9_perm_step(left, zk::fr9_perm_factor(v, zk::fr9_mul(ld(a.sig, c, 0), beta), gamma));
+          right = zk::fr9_perm_step(right, zk::fr9_perm_factor(v, zk::fr9_mul(zk::fr9_load(a.beta_delta[c]), x), gamma));
         }
-        horner(lact, left - right);
+        horner(lact, zk::lz_sub(left, right));
       }
       break;
     }
     case QG_LOOKUP: {
-      const Fr l0 = a.lext[p], ll = a.lext[ne + p], lact = a.lext[2 * ne + p];
-      const Fr s = at(a.fix, a.fix_table, 0);
+      const zk::Fr9C l0 = zk::fr9_load32(a.lext[p]), ll = zk::fr9_load32(a.lext[ne + p]), lact = zk::fr9_load32(a.lext[2 * ne + p]);
+      const zk::Fr9C gamma = zk::fr9_load32(a.gamma);
+      const zk::Fr9S beta = zk::fr9_load(a.beta), one = zk::fr9_one();
+      const zk::Lz<0, 1, 64> s_gamma = zk::fr9_lookup_sum(ld32(a.fix, a.fix_table, 0), gamma);
       for (int i = g.first; i < g.first + g.count; ++i) {
-        const Fr z0 = at(a.lz, i, 0), z1 = at(a.lz, i, 1);
-        const Fr av = at(a.adv, a.adv_lookup0 + i, 0);
-        const Fr ap = at(a.la, i, 0), apm = at(a.la, i, (unsigned)(n - 1)), sp = at(a.ls, i, 0);
-        horner(l0, one - z0);
-        horner(ll, z0 * z0 - z0);
-        horner(lact, zk::fp_mul2<zk::FrP>(z1, (ap + a.beta) * (sp + a.gamma), zk::fp_neg<zk::FrP>(z0), (av + a.beta) * (s + a.gamma)));
-        horner(l0, ap - sp);
-        horner(lact, (ap - sp) * (ap - apm));
+        const Fr z0 = at(a.lz, i, 0), ap = at(a.la, i, 0), sp = at(a.ls, i, 0);
+        const auto d = zk::lz_sub(zk::fr9_load(ap), zk::fr9_load(sp));   // ap - sp
+        horner(l0, zk::lz_sub(one, zk::fr9_load(z0)));
+        horner(ll, zk::lz_sub(zk::fr9_mul(zk::fr9_load(z0), zk::fr9_load32(z0)), zk::fr9_load(z0)));
+        horner(lact, zk::fr9_mul2(ld32(a.lz, i, 1), zk::fr9_lookup_term(zk::fr9_load(ap), beta, zk::fr9_lookup_sum(zk::fr9_load32(sp), gamma)), zk::fr9_load32(z0),
+                                  zk::lz_neg(zk::fr9_lookup_term(ld(a.adv, a.adv_lookup0 + i, 0), beta, s_gamma))));
+        horner(l0, d);
+        horner(lact, zk::fr9_mul(zk::lz_sub(zk::fr9_load32(ap), ld32(a.la, i, (unsigned)(n - 1))), d));
       }
       break;
     }
   }
-  a.partials[(size_t)blockIdx.y * ne + p] = acc;
+  a.partials[(size_t)blockIdx.y * ne + p] = zk::fr9_store(acc);
 }
 
 // h_ext[p] = (sum_g ypow[g] * partials[g][p]) * zinv[k1]
