@@ -575,11 +575,47 @@ int zkfhe_bfv_mul(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, cons
  * noise that decryption tolerates while it stays below floor(Q/T) / 2 */
 int zkfhe_bfv_noise(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk, size_t n, const uint64_t *c0, const uint64_t *c1,
                     uint64_t *noise_out);
+/* Host only. The largest n_terms the two calls below accept, saturating at SIZE_MAX.
+ * P = 3291839576991896151990342918866792881986076673 is the product of the five RNS primes.
+ *   plain == 0: the largest n with n * 2 N floor(Q/2)^2          <= floor(P/2)
+ *   plain != 0: the largest n with n *   N floor(Q/2) floor(T/2) <= floor(P/2) */
+int zkfhe_bfv_dot_max_terms(const zkfhe_bfv_params *params, int plain, size_t *max_terms);
+/* n_groups inner products of n_terms relinearized products each (bfv_dot.hip): one rescale and one relinearization per sum.
+ * a0, a1: [n_groups][n_terms][N].
+ * b0, b1: [b_groups][n_terms][N], b_groups = 1 (one b vector for every group) or n_groups.
+ * Defined exactly. Every coefficient is lifted to its centred integer.
+ *   x0 = sum_i a0_i b0_i, x1 = sum_i (a0_i b1_i + a1_i b0_i), x2 = sum_i a1_i b1_i,
+ *   over Z in Z[x]/(x^N + 1).
+ *   c^_j = floor((2 T x_j + Q) / 2Q) mod Q.
+ * Then the digits and key sum of zkfhe_bfv_mul:
+ *   out0 = c^0 + sum_i d_i rlk0_i, out1 = c^1 + sum_i d_i rlk1_i.
+ * out0, out1: [n_groups][N].
+ * n_terms = 1 is zkfhe_bfv_mul bit for bit.
+ * For n_terms > 1 the result differs from the sum of the products only in the roundings.
+ * Refused with ZKFHE_EINVAL and a message "bfv_dot: ...", in this order and before any pass over the inputs and any device work: a
+ * NULL argument, a zero count or bad parameters; base_bits outside [1, 32]; b_groups other than 1 or n_groups; n_terms above
+ * zkfhe_bfv_dot_max_terms (the message states the limit).  Then the range checks of zkfhe_bfv_mul.  The noise of the result grows
+ * with n_terms (zkfhe_bfv_noise). */
+int zkfhe_bfv_dot(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, size_t n_terms,
+                  const uint64_t *a0, const uint64_t *a1, size_t b_groups,
+                  const uint64_t *b0, const uint64_t *b1,
+                  const uint64_t *rlk0, const uint64_t *rlk1, int base_bits,
+                  uint64_t *out0, uint64_t *out1);
+/* n_groups weighted sums with public weights:
+ *   out_j = sum_i c_j,i m_i mod (x^N + 1, Q), j = 0, 1.
+ * This is bit for bit the zkfhe_bfv_sum of the zkfhe_bfv_mul_plain products.
+ * c0, c1: [n_groups][n_terms][N].
+ * m: [m_groups][n_terms][N], m_groups = 1 or n_groups, plaintexts in the range of zkfhe_bfv_mul_plain.
+ * Refusals as for zkfhe_bfv_dot, with the prefix "bfv_dot_plain:" and the limit of plain != 0. */
+int zkfhe_bfv_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, size_t n_terms,
+                        const uint64_t *c0, const uint64_t *c1, size_t m_groups, const uint64_t *m,
+                        uint64_t *out0, uint64_t *out1);
 /* zkfhe_prof_read slots of the BFV evaluation kernels */
 #define ZKFHE_PROF_BFV_TENSOR 8            /* k_bfv_tensor */
 #define ZKFHE_PROF_BFV_RELIN 9             /* k_key_switch<false> (the relinearization) */
 #define ZKFHE_PROF_BFV_EVAL_EPILOGUE 10    /* k_eval_epilogue */
 #define ZKFHE_PROF_BFV_ELEMENTWISE 11      /* k_bfv_sum, k_bfv_add */
+#define ZKFHE_PROF_BFV_DOT 20              /* k_bfv_dot_acc, and k_bfv_dot_fold where a pass is split into slices */
 
 /* ---- Threshold BFV on the GPU: collective keys and decryption by shares (bfv_threshold.hip) ----
  * The multiparty BFV of Mouchet et al. (collective key generation, relinearization key generation, threshold decryption with

@@ -23,6 +23,7 @@ PROF_BFV_SHARE_SUM, PROF_BFV_DECRYPT_COMBINE = 12, 13   # ... and of the thresho
 PROF_BFV_GALOIS, PROF_BFV_SLOT_NTT = 14, 15   # ... and of the slot and rotation kernels
 PROF_BFV_HOIST, PROF_BFV_LINEAR = 16, 17   # ... and of the hoisted rotations and linear transforms
 PROF_BFV_BSGS_INNER, PROF_BFV_BSGS_GIANT = 18, 19   # ... and of the baby-step/giant-step transform's own kernels
+PROF_BFV_DOT = 20   # ... and of the fused inner product's accumulation
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -45,7 +46,7 @@ EXPORTS = [
     "zkfhe_g1_decompress", "zkfhe_msm_segmented", "zkfhe_bfv_verify_batch",
     "zkfhe_poly_mul_ternary_negacyclic", "zkfhe_bfv_error_cdt", "zkfhe_bfv_fhe_keypair", "zkfhe_bfv_encrypt", "zkfhe_bfv_decrypt", "zkfhe_bfv_prove_words",
     "zkfhe_bfv_add", "zkfhe_bfv_sum", "zkfhe_bfv_add_plain", "zkfhe_bfv_mul_plain", "zkfhe_bfv_relin_digits", "zkfhe_bfv_relin_keygen",
-    "zkfhe_bfv_mul", "zkfhe_bfv_noise",
+    "zkfhe_bfv_mul", "zkfhe_bfv_noise", "zkfhe_bfv_dot_max_terms", "zkfhe_bfv_dot", "zkfhe_bfv_dot_plain",
     "zkfhe_bfv_keygen_share", "zkfhe_bfv_share_aggregate", "zkfhe_bfv_relin_share1", "zkfhe_bfv_relin_share2", "zkfhe_bfv_decrypt_share",
     "zkfhe_bfv_decrypt_combine",
     "zkfhe_bfv_slot_count", "zkfhe_bfv_galois_element", "zkfhe_bfv_slot_sum_elements", "zkfhe_bfv_encode_slots", "zkfhe_bfv_decode_slots",
@@ -621,6 +622,47 @@ class Context:
         self._bfv("zkfhe_bfv_mul", "nppppppipp", params, a0.shape[0], a0, a1, b0, b1, rlk0, rlk1, int(base_bits), *out)
         return tuple(out)
 
+    def _dot_arrays(self, params, x, y, what):
+        """two arrays of one operand of an inner product, (n_terms, N) or (n_groups, n_terms, N) -> ((groups, n_terms, N) views, ndim)"""
+        n = int(params[0])
+        x = np.ascontiguousarray(x, dtype=np.uint64)
+        y = np.ascontiguousarray(y, dtype=np.uint64)
+        if x.shape != y.shape or x.ndim not in (2, 3) or x.shape[-1] != n or 0 in x.shape:
+            raise ValueError("%s must have the same shape (n_terms, N) or (n_groups, n_terms, N)" % what)
+        return x.reshape(-1, x.shape[-2], n), y.reshape(-1, x.shape[-2], n), x.ndim
+
+    def _dot_operands(self, params, a, b, names):
+        a0, a1, a_dim = self._dot_arrays(params, a[0], a[1], names[0])
+        b0, b1, b_dim = self._dot_arrays(params, b[0], b[1], names[1])
+        if b0.shape[1] != a0.shape[1] or b_dim > a_dim:
+            raise ValueError("%s must hold the n_terms = %d of %s, as (n_terms, N)%s" %
+                             (names[1], a0.shape[1], names[0], " (shared by every group) or (n_groups, n_terms, N)" if a_dim == 3 else ""))
+        out = [np.empty((a0.shape[0], a0.shape[2]) if a_dim == 3 else a0.shape[2], dtype=np.uint64) for _ in range(2)]
+        return a0, a1, b0, b1, out
+
+    def bfv_dot(self, params, a0, a1, b0, b1, rlk0, rlk1, base_bits=16):
+        """zkfhe_bfv_dot: the inner product sum_i a_i * b_i of relinearized products, rescaled and relinearized once per sum, under
+        the key (rlk0, rlk1) made with base_bits.  a0, a1 of shape (n_terms, N) give one ciphertext (two arrays of N); of shape
+        (n_groups, n_terms, N) one per group, (n_groups, N).  b0, b1: like a, or (n_terms, N) beside a 3-D a: one b vector shared
+        by every group.  n_terms is at most bfv_dot_max_terms(params)."""
+        a0, a1, b0, b1, out = self._dot_operands(params, (a0, a1), (b0, b1), ("a0 and a1", "b0 and b1"))
+        n = int(params[0])
+        rlk0 = np.ascontiguousarray(rlk0, dtype=np.uint64)
+        rlk1 = np.ascontiguousarray(rlk1, dtype=np.uint64)
+        l = self._relin_rows(params, base_bits) or rlk0.shape[0]   # else the call refuses base_bits
+        if rlk0.shape != (l, n) or rlk1.shape != (l, n):
+            raise ValueError("rlk0 and rlk1 must have shape (l, N) = (%d, %d) for base_bits %d" % (l, n, base_bits))
+        self._bfv("zkfhe_bfv_dot", "nnppnppppipp", params, a0.shape[0], a0.shape[1], a0, a1, b0.shape[0], b0, b1, rlk0, rlk1, int(base_bits), *out)
+        return tuple(out)
+
+    def bfv_dot_plain(self, params, c0, c1, m):
+        """zkfhe_bfv_dot_plain: the weighted sum sum_i c_i * m_i mod (x^N + 1, Q) with public plaintexts m_i, bit for bit the bfv_sum
+        of the bfv_mul_plain products.  Shapes as for bfv_dot: c0, c1 (n_terms, N) or (n_groups, n_terms, N); m like c, or
+        (n_terms, N) beside a 3-D c: one weight vector shared by every group.  n_terms is at most bfv_dot_max_terms(params, True)."""
+        c0, c1, m, _, out = self._dot_operands(params, (c0, c1), (m, m), ("c0 and c1", "m"))
+        self._bfv("zkfhe_bfv_dot_plain", "nnppnppp", params, c0.shape[0], c0.shape[1], c0, c1, m.shape[0], m, *out)
+        return tuple(out)
+
     def bfv_noise(self, params, sk, c0, c1):
         """zkfhe_bfv_noise: per ciphertext, max |[c0 + c1 s - floor(Q/T) m]_Q| with m the decryption; shape (n,)."""
         sk = self._sk(params, sk)
@@ -836,6 +878,14 @@ def bfv_relin_digits(params, base_bits):
     l = ctypes.c_size_t()
     _host_bfv("zkfhe_bfv_relin_digits", [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)], params, int(base_bits), ctypes.byref(l))
     return l.value
+
+
+def bfv_dot_max_terms(params, plain=False):
+    """zkfhe_bfv_dot_max_terms (host only): the largest n_terms of Context.bfv_dot (plain=True: of Context.bfv_dot_plain), for which
+    the exact sum stays within half of the five RNS primes' product; saturates at 2^64 - 1."""
+    out = ctypes.c_size_t()
+    _host_bfv("zkfhe_bfv_dot_max_terms", [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)], params, int(bool(plain)), ctypes.byref(out))
+    return out.value
 
 
 def bfv_slot_count(params):

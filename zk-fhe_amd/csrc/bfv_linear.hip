@@ -202,7 +202,8 @@ __global__ __launch_bounds__(ACC_THREADS) void k_bsgs_inner(const uint32_t *__re
       }
 }
 
-// One workgroup per (polynomial, prime) of res ([polys][NP][N]): the inverse transform in place, times scale[prime]
+// One workgroup per (polynomial, prime) of res ([polys][NP][N]): the inverse transform in place, times scale[prime].  Launched through
+// zk_rns_intt (rns_ntt.hip.hpp), which bfv_dot.hip calls too.
 __global__ __launch_bounds__(NTT_THREADS) void k_rns_intt(uint32_t *__restrict__ res, int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc) {
   extern __shared__ uint32_t lds[];
   const unsigned j = blockIdx.x % NP, n = 1u << log_n, tid = threadIdx.x;
@@ -294,9 +295,8 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
   }
   const uint32_t *tw;
   ZK_CK(zk_rns_tables(ctx, &tw));
-  int lds_h, lds_i;
+  int lds_h;
   ZK_CK(ntt_lds(ctx, (const void *)k_hoist, log_n, &lds_h));
-  ZK_CK(ntt_lds(ctx, (const void *)k_rns_intt, log_n, &lds_i));
   const RnsConst<NP> rc = rns_const<NP>(log_n), rc_inv = intt_const(log_n, diag ? 2 : 1);
   GadgetStep gs;
   for (int j = 0; j < NP; ++j) gs.step[j] = (uint32_t)((((uint64_t)1 << base_bits) % PRIMES[j]) * (((uint64_t)1 << 32) % PRIMES[j]) % PRIMES[j]);
@@ -318,10 +318,7 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
     ZK_LAUNCH_CHECK(ctx);
     // read: every hoisted row per element, every key word once per CT ciphertexts, the diagonals likewise; written: the outputs
     zk_prof_end(ctx, ZKFHE_PROF_BFV_LINEAR, 4.0 * words * ((double)n_elems * c * rows + (double)zk_blocks(c, CT) * (2.0 * slots * l + (diag ? n_elems : 0)) + polys));
-    zk_prof_begin(ctx);
-    k_rns_intt<<<(unsigned)(polys * NP), NTT_THREADS, lds_i, ctx->stream>>>(res, log_n, tw, rc_inv);
-    ZK_LAUNCH_CHECK(ctx);
-    zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, (double)polys * words * 8.0);
+    ZK_CK(zk_rns_intt(ctx, res, polys, log_n, rc_inv));
     ZK_CK(zk_bfv_eval_epilogue(ctx, res, polys, log_n, q, EvEpi{}, o_d));
     for (size_t k = 0; k < (diag ? 1 : n_elems); ++k) {   // o_d: [element][component][c][N]
       ZK_CK(zkfhe_download(ctx, out0 + (k * n_cts + lo) * n, o_d + 2 * k * c * n, bytes));
@@ -399,9 +396,8 @@ int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, cons
   ZK_CK(launch_rns_ntt<NP>(ctx, false, diag_d, LOAD_CENTRED, q, n_diag, log_n, nullptr, 0, diag_hat, flag));
   const uint32_t *tw;
   ZK_CK(zk_rns_tables(ctx, &tw));
-  int lds_h, lds_i;
+  int lds_h;
   ZK_CK(ntt_lds(ctx, (const void *)k_hoist, log_n, &lds_h));
-  ZK_CK(ntt_lds(ctx, (const void *)k_rns_intt, log_n, &lds_i));
   // Montgomery factors: a rotation carries R^-1 (one product with a key word), the inner sum one more product with a diagonal
   const RnsConst<NP> rc = rns_const<NP>(log_n), rc_inner = intt_const(log_n, 2), rc_outer = intt_const(log_n, 1);
   GadgetStep gs;
@@ -437,10 +433,7 @@ int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, cons
       ZK_LAUNCH_CHECK(ctx);
       // read: every baby word once per giant tile, every diagonal word once per ciphertext group; written: the inner sums
       zk_prof_end(ctx, ZKFHE_PROF_BFV_BSGS_INNER, 4.0 * words * ((double)zk_blocks(gg, cti == 1 ? 8 : 4) * 2.0 * n_baby * c + (double)zk_blocks(c, cti) * gg * n_baby + 2.0 * inner_cts));
-      zk_prof_begin(ctx);
-      k_rns_intt<<<(unsigned)(2 * inner_cts * NP), NTT_THREADS, lds_i, ctx->stream>>>(inner, log_n, tw, rc_inner);
-      ZK_LAUNCH_CHECK(ctx);
-      zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, 2.0 * inner_cts * words * 8.0);
+      ZK_CK(zk_rns_intt(ctx, inner, 2 * inner_cts, log_n, rc_inner));
       ZK_CK(zk_bfv_eval_epilogue(ctx, inner, 2 * inner_cts, log_n, q, EvEpi{}, inner_q));   // [c0 | c1] of the gg c inner ciphertexts
       zk_prof_begin(ctx);
       k_hoist<<<(unsigned)(inner_cts * rows * NP), NTT_THREADS, lds_h, ctx->stream>>>(inner_q, inner_cts, l, base_bits, q, log_n, tw, rc, hst_in);
@@ -454,10 +447,7 @@ int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, cons
       // read: the hoisted rows of every inner ciphertext, every key word once per CT ciphertexts, the sum so far; written: the sum
       zk_prof_end(ctx, ZKFHE_PROF_BFV_BSGS_GIANT, 4.0 * words * ((double)inner_cts * rows + (double)zk_blocks(c, CT) * 2.0 * giant_slots * l + 4.0 * c));
     }
-    zk_prof_begin(ctx);
-    k_rns_intt<<<(unsigned)(2 * c * NP), NTT_THREADS, lds_i, ctx->stream>>>(res, log_n, tw, rc_outer);
-    ZK_LAUNCH_CHECK(ctx);
-    zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, 2.0 * c * words * 8.0);
+    ZK_CK(zk_rns_intt(ctx, res, 2 * c, log_n, rc_outer));
     ZK_CK(zk_bfv_eval_epilogue(ctx, res, 2 * c, log_n, q, EvEpi{}, o_d));
     ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
     ZK_CK(zkfhe_download(ctx, out1 + lo * n, o_d + c * n, bytes));
@@ -466,6 +456,22 @@ int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, cons
 }
 
 }  // namespace
+
+namespace zkrns {
+
+int zk_rns_intt(zkfhe_ctx *ctx, uint32_t *res, size_t n_polys, int log_n, const RnsConst<NP_MAX> &rc) {
+  const uint32_t *tw;
+  ZK_CK(zk_rns_tables(ctx, &tw));
+  int lds;
+  ZK_CK(ntt_lds(ctx, (const void *)k_rns_intt, log_n, &lds));
+  zk_prof_begin(ctx);
+  k_rns_intt<<<(unsigned)(n_polys * NP), NTT_THREADS, lds, ctx->stream>>>(res, log_n, tw, rc);
+  ZK_LAUNCH_CHECK(ctx);
+  zk_prof_end(ctx, ZKFHE_PROF_RNS_NTT, (double)n_polys * NP * 8.0 * ((size_t)1 << log_n));
+  return ZKFHE_OK;
+}
+
+}  // namespace zkrns
 
 extern "C" {
 

@@ -4,7 +4,7 @@
 // three primes (product 2^89.2: a ternary factor keeps the product below N 2^64), the evaluator all five (product 2^151.2: a
 // product of two centred residues below 2^63 stays below 2^140).
 // Headroom at p < 2^31: a b + m p < 2^62 + 2^63 < 2^64 in mont_mul, and a + b < 2^32 in add_p.
-// Also the pieces every BFV file shares: the device helpers, the two CRT epilogues and the key switch (each defined in one .hip
+// Also the pieces every BFV file shares: the device helpers, the two CRT epilogues, the key switch and the in-place inverse transform (each defined in one .hip
 // file, launched through the declarations below), the host checks and the work-arena layout.
 #pragma once
 #include <algorithm>
@@ -392,6 +392,11 @@ int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, in
 // of src itself (relinearization, profiling slot ZKFHE_PROF_BFV_RELIN), else those of sigma_g(src), g^-1 = ginv (ZKFHE_PROF_BFV_GALOIS)
 int zk_bfv_key_switch(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64_t q, int l, int w, const uint32_t *key_hat, size_t c,
                       int log_n, uint32_t *acc);
+
+// ---- defined in bfv_linear.hip
+// k_rns_intt over res ([n_polys][5][N]): one inverse transform per polynomial and prime in place, times rc.scale, in profiling slot
+// ZKFHE_PROF_RNS_NTT
+int zk_rns_intt(zkfhe_ctx *ctx, uint32_t *res, size_t n_polys, int log_n, const RnsConst<NP_MAX> &rc);
 
 // The work buffers of one call, each named once: add() them in order (each 256-byte aligned, so an int flag added first stays in
 // the first 256 bytes), then carve() sizes the work arena from the same list and points every buffer into it.
