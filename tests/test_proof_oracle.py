@@ -14,8 +14,35 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden", "bfv")
 
 
+def negacyclic(a, b, N, Q):
+    """a * b mod (x^N + 1, Q), exactly, on big-endian (file order) coefficient lists"""
+    a, b = a[::-1], b[::-1]
+    out = [0] * N
+    for i in range(N):
+        if b[i] == 0:
+            continue
+        for j in range(N):
+            k = i + j
+            if k < N:
+                out[k] += a[j] * b[i]
+            else:
+                out[k - N] -= a[j] * b[i]
+    return [x % Q for x in out][::-1]
+
+
+def craft(N, Q, T, pk0, pk1, u, m, e0, e1):
+    """The input file of the encryption (c0, c1) = (pk0 u + (Q // T) m + e0, pk1 u + e1) of exactly these polynomials (lists of N
+    residues in file order, which is big-endian); the formula is checked against bfv.in in test_witness_oracle (KAT 1)."""
+    assert all(len(v) == N and all(0 <= x < Q for x in v) for v in (pk0, pk1, u, m, e0, e1))
+    pu0, pu1 = negacyclic(pk0, u, N, Q), negacyclic(pk1, u, N, Q)
+    c0 = [(pu0[i] + (Q // T) * m[i] + e0[i]) % Q for i in range(N)]
+    c1 = [(pu1[i] + e1[i]) % Q for i in range(N)]
+    s = lambda v: [str(x) for x in v]  # noqa: E731
+    return dict(pk0=s(pk0), pk1=s(pk1), m=s(m), u=s(u), e0=s(e0), e1=s(e1), c0=s(c0), c1=s(c1), cyclo=s([1] + [0] * (N - 1) + [1]))
+
+
 def synth_input(N, Q, T, B, seed):
-    """BFV encryption of a random message, formula checked against bfv.in in test_witness_oracle (KAT 1)."""
+    """BFV encryption of a random message"""
     rng = random.Random(seed)
     pk0 = [rng.randrange(Q) for _ in range(N)]
     pk1 = [rng.randrange(Q) for _ in range(N)]
@@ -23,23 +50,7 @@ def synth_input(N, Q, T, B, seed):
     m = [rng.choice(list(range(0, T // 2 + 1)) + [Q - i for i in range(1, T // 2 + 1)]) for _ in range(N)]
     e0 = [rng.choice(list(range(0, B + 1)) + [Q - i for i in range(1, B + 1)]) for _ in range(N)]
     e1 = [rng.choice(list(range(0, B + 1)) + [Q - i for i in range(1, B + 1)]) for _ in range(N)]
-
-    def nega(a, b):
-        a, b = a[::-1], b[::-1]
-        out = [0] * N
-        for i in range(N):
-            for j in range(N):
-                k = i + j
-                if k < N:
-                    out[k] += a[j] * b[i]
-                else:
-                    out[k - N] -= a[j] * b[i]
-        return [x % Q for x in out][::-1]
-    pu0, pu1 = nega(pk0, u), nega(pk1, u)
-    c0 = [(pu0[i] + (Q // T) * m[i] + e0[i]) % Q for i in range(N)]
-    c1 = [(pu1[i] + e1[i]) % Q for i in range(N)]
-    s = lambda v: [str(x) for x in v]  # noqa: E731
-    return dict(pk0=s(pk0), pk1=s(pk1), m=s(m), u=s(u), e0=s(e0), e1=s(e1), c0=s(c0), c1=s(c1), cyclo=s([1] + [0] * (N - 1) + [1]))
+    return craft(N, Q, T, pk0, pk1, u, m, e0, e1)
 
 
 @pytest.fixture(scope="module")
