@@ -668,6 +668,66 @@ int zkfhe_bfv_decrypt_combine(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, si
 #define ZKFHE_PROF_BFV_SHARE_SUM 12         /* k_bfv_share_sum */
 #define ZKFHE_PROF_BFV_DECRYPT_COMBINE 13   /* k_bfv_decrypt_combine */
 
+/* ---- Collective refresh and key switching (bfv_refresh.hip) ----
+ * Two more protocols of Mouchet et al. for a committee that holds s = sum_i s_i jointly.  Collective refresh re-encrypts a worn
+ * ciphertext into a nearly noiseless one under the same collective key without anyone seeing the plaintext, so that
+ * mul -> refresh -> mul -> ... has no depth limit at a single-word Q.  Public collective key switching (PCKS) re-encrypts a
+ * ciphertext from the collective secret to any public key (an auditor, a recipient, a second committee): the committee never sees
+ * the plaintext and the recipient need not be online.  The conventions of "Threshold BFV": host arrays, N uint64_t per polynomial
+ * in CircuitInput order, residues in [0, Q), the parameter checks of zkfhe_bfv_encrypt; every call waits for its result.  Below,
+ * delta = floor(Q/T), P = n_parties, E = smudge_bound, B the error bound of the parameters.
+ * Randomness: the ChaCha20 streams and samplers of zkfhe_bfv_encrypt.  Domains 1 to 15 keep their meaning and the new ones are 16
+ * to 22; in every row the index is first_index + j for ciphertext j:
+ *   PCKS u_ij                 share seed (secret)  domain 16   ternary
+ *   PCKS e0_ij                share seed           domain 17   uniform mod 2E + 1, minus E
+ *   PCKS e1_ij                share seed           domain 18   error
+ *   refresh CRS a_j           crs_seed (public)    domain 19   uniform mod Q
+ *   refresh mask M_ij         share seed           domain 20   uniform mod T (the uniform sampler with modulus T)
+ *   refresh e0_ij             share seed           domain 21   uniform mod 2E + 1, minus E
+ *   refresh e1_ij             share seed           domain 22   error
+ * Refusals: all four calls refuse with ZKFHE_EINVAL and a message prefixed "bfv_pcks_share:", "bfv_pcks_combine:",
+ * "bfv_refresh_share:" or "bfv_refresh_combine:", in this order and before any work on the ciphertexts: (1) a NULL argument, a zero
+ * n_parties or n_cts, or bad parameters; (2) 2 E + 1 > delta (share calls); (3) any input coefficient >= Q; (4) a non-ternary sk_i.
+ * No output is written then.
+ * SHARE SEEDS ARE SECRET, like every seed here.  NEVER REUSE a (share seed, index) pair: a second refresh share with the same mask
+ * and noise on another c1 gives (c1 - c1') s_i, and a second PCKS share with the same u_ij gives the same.  E is the caller's
+ * choice; the library claims no statistical hiding for it.  crs_seed and first_index of a refresh are PUBLIC and agreed by all
+ * parties (every party and the combiner must pass the same pair), and THEY MUST DIFFER BETWEEN REFRESHES: a_j repeated under two
+ * refreshes relates their outputs. */
+/* party i's key-switch shares of n_cts ciphertexts towards the public key (pk0_to, pk1_to), mod (x^N + 1, Q):
+ *   h0_ij = s_i c1_j + u_ij pk0_to + e0_ij,   h1_ij = u_ij pk1_to + e1_ij.
+ * c1, h0_out, h1_out: n_cts x N; pk0_to, pk1_to: N. */
+int zkfhe_bfv_pcks_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, const uint64_t *pk0_to,
+                         const uint64_t *pk1_to, size_t n_cts, const uint64_t *c1, const uint8_t seed[32], uint64_t first_index,
+                         uint64_t smudge_bound, uint64_t *h0_out, uint64_t *h1_out);
+/* out0 = c0 + sum_i h0_i, out1 = sum_i h1_i mod Q; c0, out0, out1: n_cts x N, h0, h1: n_parties x n_cts x N.  If pk0_to + pk1_to s'
+ * = -e', then out0 + out1 s' = [c0 + c1 s] - u e' + sum e0 + (sum e1) s' (u, e0, e1 summed over the parties): the same plaintext
+ * under s', with that much added noise.  The recipient decrypts with zkfhe_bfv_decrypt, or a second committee with its shares. */
+int zkfhe_bfv_pcks_combine(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_parties, size_t n_cts, const uint64_t *c0,
+                           const uint64_t *h0, const uint64_t *h1, uint64_t *out0, uint64_t *out1);
+/* party i's refresh shares of n_cts ciphertexts, mod (x^N + 1, Q), a_j the CRS stream (crs_seed, 19, first_index + j):
+ *   h0_ij = s_i c1_j - delta M_ij + e0_ij,   h1_ij = -s_i a_j + delta M_ij + e1_ij.
+ * c1, h0_out, h1_out: n_cts x N. */
+int zkfhe_bfv_refresh_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk_i, const uint8_t crs_seed[32],
+                            size_t n_cts, const uint64_t *c1, const uint8_t seed[32], uint64_t first_index, uint64_t smudge_bound,
+                            uint64_t *h0_out, uint64_t *h1_out);
+/* the refreshed ciphertexts, per coefficient:
+ *   v = [c0 + sum_i h0_i]_Q;  mu = floor((2 T v + Q) / 2Q) mod T, in [0, T) (the rounding of zkfhe_bfv_decrypt before centring);
+ *   out0 = delta mu + sum_i h1_i mod Q;  out1 = a_j, regenerated from crs_seed and first_index.
+ * c0, out0, out1: n_cts x N, h0, h1: n_parties x n_cts x N.  mu is the plaintext masked by sum_i M_i mod T: nobody sees the plaintext.
+ * Correctness condition (sufficient, not tight): the result decrypts to the input's plaintext under s = sum_i s_i whenever
+ *   noise(input) + P E + (P + 1) (Q mod T) < delta / 2 - T.
+ * Noise bound: the result's noise is then at most P B + (P + 1) (Q mod T), whatever the input's noise was (checked numerically on
+ * the CPU at N = 8 ... 32, 29-, 60- and 62-bit Q, 1 to 5 parties); at the k = 13 parameters with P = 3 that is 61.
+ * CRS agreement: first_index and crs_seed are public, the same for all parties and the combiner, and differ between refreshes. */
+int zkfhe_bfv_refresh_combine(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_parties, size_t n_cts, const uint8_t crs_seed[32],
+                              uint64_t first_index, const uint64_t *c0, const uint64_t *h0, const uint64_t *h1, uint64_t *out0,
+                              uint64_t *out1);
+/* zkfhe_prof_read slots of the two combine kernels (algorithmic bytes: words read and written); the share products count in
+ * ZKFHE_PROF_RNS_NTT and ZKFHE_PROF_RNS_EPILOGUE, the samplers in ZKFHE_PROF_BFV_SAMPLE */
+#define ZKFHE_PROF_BFV_PCKS_COMBINE 21      /* k_bfv_pcks_combine */
+#define ZKFHE_PROF_BFV_REFRESH_COMBINE 22   /* k_bfv_refresh_combine */
+
 /* ---- BFV slots and rotations on the GPU (bfv_galois.hip) ----
  * SIMD batching and Galois automorphisms.  The conventions above: host arrays, N uint64_t per polynomial in CircuitInput order,
  * residues in [0, Q), the parameter checks of zkfhe_bfv_encrypt; every call waits for its result.  Below, coefficient i is the

@@ -24,6 +24,7 @@ PROF_BFV_GALOIS, PROF_BFV_SLOT_NTT = 14, 15   # ... and of the slot and rotation
 PROF_BFV_HOIST, PROF_BFV_LINEAR = 16, 17   # ... and of the hoisted rotations and linear transforms
 PROF_BFV_BSGS_INNER, PROF_BFV_BSGS_GIANT = 18, 19   # ... and of the baby-step/giant-step transform's own kernels
 PROF_BFV_DOT = 20   # ... and of the fused inner product's accumulation
+PROF_BFV_PCKS_COMBINE, PROF_BFV_REFRESH_COMBINE = 21, 22   # ... and of the key-switch and refresh combines
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -49,6 +50,7 @@ EXPORTS = [
     "zkfhe_bfv_mul", "zkfhe_bfv_noise", "zkfhe_bfv_dot_max_terms", "zkfhe_bfv_dot", "zkfhe_bfv_dot_plain",
     "zkfhe_bfv_keygen_share", "zkfhe_bfv_share_aggregate", "zkfhe_bfv_relin_share1", "zkfhe_bfv_relin_share2", "zkfhe_bfv_decrypt_share",
     "zkfhe_bfv_decrypt_combine",
+    "zkfhe_bfv_pcks_share", "zkfhe_bfv_pcks_combine", "zkfhe_bfv_refresh_share", "zkfhe_bfv_refresh_combine",
     "zkfhe_bfv_slot_count", "zkfhe_bfv_galois_element", "zkfhe_bfv_slot_sum_elements", "zkfhe_bfv_encode_slots", "zkfhe_bfv_decode_slots",
     "zkfhe_bfv_galois_keygen", "zkfhe_bfv_apply_galois", "zkfhe_bfv_slot_sum", "zkfhe_bfv_galois_share",
     "zkfhe_bfv_apply_galois_many", "zkfhe_bfv_linear_transform", "zkfhe_bfv_linear_transform_bsgs",
@@ -739,6 +741,66 @@ class Context:
         out = np.empty(c0.shape, dtype=np.uint64)
         self._bfv("zkfhe_bfv_decrypt_combine", "nnppp", params, d.shape[0], c0.shape[0], c0, d, out)
         return out
+
+    # ------------------------------------------------------------------ collective refresh and key switching (zkfhe.h, bfv_refresh.hip)
+    # Shapes follow bfv_decrypt_share / bfv_decrypt_combine: c0, c1 of shape (N,) or (n, N), shares (P, n, N) (or (P, N)).  Share
+    # seeds are 32 SECRET bytes (None: os.urandom); never reuse a (seed, index) pair.  A refresh's crs_seed and first_index are
+    # public, the same for every party and the combiner, and differ between refreshes.
+
+    def _share_planes(self, c0, h0, h1):
+        out = []
+        for h in (h0, h1):
+            h = np.ascontiguousarray(h, dtype=np.uint64)
+            h = h.reshape(h.shape[0], 1, c0.shape[1]) if h.ndim == 2 else h
+            if h.ndim != 3 or h.shape[1:] != c0.shape:
+                raise ValueError("shares must have shape (P, n, N) for c0 of shape (n, N)")
+            out.append(h)
+        if out[0].shape != out[1].shape:
+            raise ValueError("h0 and h1 shares must come from the same parties")
+        return out
+
+    def bfv_pcks_share(self, params, sk, pk0_to, pk1_to, c1, seed=None, first_index=0, smudge_bound=0):
+        """zkfhe_bfv_pcks_share: c1 of shape (N,) or (n, N) -> (h0, h1) of shape (n, N): h0_j = s_i c1_j + u_j pk0_to + e0_j,
+        h1_j = u_j pk1_to + e1_j, towards the public key (pk0_to, pk1_to); e0_j uniform in [-smudge_bound, smudge_bound]."""
+        n, sk = int(params[0]), self._sk(params, sk)
+        pk0_to = np.ascontiguousarray(pk0_to, dtype=np.uint64)
+        pk1_to = np.ascontiguousarray(pk1_to, dtype=np.uint64)
+        if pk0_to.size != n or pk1_to.size != n:
+            raise ValueError("pk0_to / pk1_to must hold N coefficients")
+        seed = self._seed(seed, "share seed", fresh=True)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1, n)
+        out = [np.empty(c1.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_pcks_share", "pppnpsuupp", params, sk, pk0_to, pk1_to, c1.shape[0], c1, seed, int(first_index), int(smudge_bound), *out)
+        return tuple(out)
+
+    def bfv_pcks_combine(self, params, c0, h0_shares, h1_shares):
+        """zkfhe_bfv_pcks_combine: c0 of shape (N,) or (n, N) and the parties' shares (P, n, N) (or (P, N)) -> (c0', c1') of shape
+        (n, N), the same plaintext under the key the shares were made towards: c0' = c0 + sum_i h0_i, c1' = sum_i h1_i."""
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64).reshape(-1, int(params[0]))
+        h0, h1 = self._share_planes(c0, h0_shares, h1_shares)
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_pcks_combine", "nnppppp", params, h0.shape[0], c0.shape[0], c0, h0, h1, *out)
+        return tuple(out)
+
+    def bfv_refresh_share(self, params, sk, crs_seed, c1, seed=None, first_index=0, smudge_bound=0):
+        """zkfhe_bfv_refresh_share: c1 of shape (N,) or (n, N) -> (h0, h1) of shape (n, N): h0_j = s_i c1_j - delta M_j + e0_j,
+        h1_j = -s_i a_j + delta M_j + e1_j, a_j from the public (crs_seed, first_index + j)."""
+        n, sk = int(params[0]), self._sk(params, sk)
+        crs_seed, seed = self._seed(crs_seed, "CRS seed"), self._seed(seed, "share seed", fresh=True)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1, n)
+        out = [np.empty(c1.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_refresh_share", "psnpsuupp", params, sk, crs_seed, c1.shape[0], c1, seed, int(first_index), int(smudge_bound), *out)
+        return tuple(out)
+
+    def bfv_refresh_combine(self, params, crs_seed, c0, h0_shares, h1_shares, first_index=0):
+        """zkfhe_bfv_refresh_combine: c0 of shape (N,) or (n, N) and the parties' shares (P, n, N) (or (P, N)) -> the refreshed
+        (c0', c1') of shape (n, N) under the same collective key; crs_seed and first_index are those of the shares."""
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64).reshape(-1, int(params[0]))
+        crs_seed = self._seed(crs_seed, "CRS seed")
+        h0, h1 = self._share_planes(c0, h0_shares, h1_shares)
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_refresh_combine", "nnsuppppp", params, h0.shape[0], c0.shape[0], crs_seed, int(first_index), c0, h0, h1, *out)
+        return tuple(out)
 
     # ------------------------------------------------------------------ slots and rotations (zkfhe.h, bfv_galois.hip)
     # Slot values and plaintexts are (n, N) uint64 arrays like the calls above; a Galois key is (gk0, gk1) of shape (l, N), and

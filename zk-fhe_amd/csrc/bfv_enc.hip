@@ -55,6 +55,12 @@ __global__ __launch_bounds__(256) void k_rns_epilogue(const uint32_t *__restrict
     const uint64_t x = v ? q - v : 0, e = epi.e[pos];
     v = epi.neg_e ? sub_q(x, e, q) : add_q(x, e, q);
     v = add_q(v, gadget_select(auto_coeff(epi.s, (unsigned)d, epi.ginv, (unsigned)n, q), (uint64_t)1 << (poly * epi.w), q), q);
+  } else if (epi.mode == EPI_MASK) {
+    const uint64_t dm = epi.delta * epi.m[pos];   // M < T: delta M <= Q - delta < Q
+    v = epi.neg_x ? add_q(v ? q - v : 0, dm, q) : sub_q(v, dm, q);
+    v = sub_q(add_q(v, epi.e[pos], q), epi.bound, q);   // e < Q, E < Q
+  } else if (epi.mode == EPI_SHARE_ADD) {
+    v = sub_q(add_q(add_q(v, epi.a[pos], q), epi.e[pos], q), epi.bound, q);   // r <= 2E < Q
   }
   out[pos] = v;
 }
@@ -267,7 +273,7 @@ int zk_bfv_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log
   k_rns_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt3_const(), epi, out);
   ZK_LAUNCH_CHECK(ctx);
   const int addends = !!epi.m + !!epi.e + !!epi.c0 + !!epi.s;
-  zk_prof_end(ctx, ZKFHE_PROF_RNS_EPILOGUE, (double)total * (12 + 8 + 8 * addends + (epi.a ? 16 : 0)));
+  zk_prof_end(ctx, ZKFHE_PROF_RNS_EPILOGUE, (double)total * (12 + 8 + 8 * addends + (epi.a ? (epi.b ? 16 : 8) : 0)));
   return ZKFHE_OK;
 }
 

@@ -58,11 +58,6 @@ int party_u_hat(zkfhe_ctx *ctx, const uint8_t party_seed[32], uint64_t n, uint64
   return launch_rns_ntt<NP>(ctx, false, u_d, LOAD_TERNARY, q, 1, log_n, nullptr, 0, hat, flag);
 }
 
-// polynomials per chunk when n_planes planes of the chunk are resident at once: the budget of chunk_polys per four planes
-size_t plane_chunk(uint64_t n, size_t n_planes, size_t count) {
-  return std::min(count, std::max<size_t>(1, chunk_polys(n) * 4 / n_planes));
-}
-
 }  // namespace
 
 extern "C" {

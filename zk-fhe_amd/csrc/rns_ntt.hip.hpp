@@ -1,4 +1,4 @@
-// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip, bfv_threshold.hip, bfv_galois.hip): an RNS NTT
+// The exact negacyclic product behind the BFV kernels (bfv_enc.hip, bfv_eval.hip, bfv_threshold.hip, bfv_refresh.hip, bfv_galois.hip): an RNS NTT
 // over NP primes below 2^31, one workgroup per (polynomial, prime), the whole transform of N <= 2^15 words in LDS (128 KiB at
 // N = 2^15), with 32-bit Montgomery arithmetic.  Templated on the prime count: encryption and the threshold calls use the first
 // three primes (product 2^89.2: a ternary factor keeps the product below N 2^64), the evaluator all five (product 2^151.2: a
@@ -43,6 +43,9 @@ enum Domain : uint32_t {
   DOM_SMUDGE = 9,                                  // decryption-share noise, index first_index + ciphertext
   DOM_THR_U = 10, DOM_THR_E0 = 11, DOM_THR_E1 = 12, DOM_THR_E2 = 13,   // threshold relinearization rounds, row j
   DOM_GK_A = 14, DOM_GK_E = 15,                    // Galois key row j, index g 64 + j
+  DOM_PCKS_U = 16, DOM_PCKS_E0 = 17, DOM_PCKS_E1 = 18,   // public collective key switch, index first_index + ciphertext
+  DOM_RFR_A = 19,                                        // refresh: CRS a_j, index first_index + ciphertext
+  DOM_RFR_M = 20, DOM_RFR_E0 = 21, DOM_RFR_E1 = 22,      // refresh: mask M_ij (uniform mod T), e0_ij (smudging), e1_ij
 };
 
 __device__ __forceinline__ uint32_t mont_mul(uint32_t a, uint32_t b, uint32_t p, uint32_t pinv) {
@@ -320,6 +323,10 @@ inline Crt5 crt5_const() {
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // polynomials per chunk of a batch: 2^21 coefficients, at least 8 polynomials
 inline size_t chunk_polys(uint64_t n) { return std::max<size_t>(8, ((size_t)1 << 21) / n); }
+// polynomials per chunk when n_planes planes of the chunk are resident at once: the budget of chunk_polys per four planes
+inline size_t plane_chunk(uint64_t n, size_t n_planes, size_t count) {
+  return std::min(count, std::max<size_t>(1, chunk_polys(n) * 4 / n_planes));
+}
 
 // The modes of the three-prime CRT epilogue (k_rns_epilogue, bfv_enc.hip): x = the product mod Q, then
 //   EPI_PLAIN    x
@@ -328,18 +335,21 @@ inline size_t chunk_polys(uint64_t n) { return std::max<size_t>(8, ((size_t)1 <<
 //   EPI_DECRYPT  decrypt_round(x + c0)
 //   EPI_SHARE    x + r - E, r = e uniform in [0, 2E]
 //   EPI_GADGET   -x + e + 2^(j w) sigma_g(s) for row j, or -x - e + ... with neg_e
-enum EpiMode { EPI_PLAIN = 0, EPI_ADD = 1, EPI_NEG_ADD = 2, EPI_DECRYPT = 3, EPI_SHARE = 4, EPI_GADGET = 5 };
+//   EPI_MASK     x - delta M + e - E, or -x + delta M + e - E with neg_x; M = m in [0, T)   (the refresh shares)
+//   EPI_SHARE_ADD  x + a + r - E, r = e uniform in [0, 2E]                                  (the key-switch share h0)
+enum EpiMode { EPI_PLAIN = 0, EPI_ADD = 1, EPI_NEG_ADD = 2, EPI_DECRYPT = 3, EPI_SHARE = 4, EPI_GADGET = 5, EPI_MASK = 6, EPI_SHARE_ADD = 7 };
 struct Epi {
   int mode = EPI_PLAIN;
-  const uint64_t *m = nullptr;                 // EPI_ADD: + delta m (may be null)
-  const uint64_t *e = nullptr;                 // the error (EPI_ADD: may be null); EPI_SHARE: r
+  const uint64_t *m = nullptr;                 // EPI_ADD: + delta m (may be null); EPI_MASK: M
+  const uint64_t *e = nullptr;                 // the error (EPI_ADD: may be null); EPI_SHARE, EPI_SHARE_ADD: r; EPI_MASK: e or r
   const uint64_t *c0 = nullptr;                // EPI_DECRYPT
-  const uint64_t *a = nullptr, *b = nullptr;   // EPI_ADD: + a - b (both null or both set)
+  const uint64_t *a = nullptr, *b = nullptr;   // EPI_ADD: + a - b (both null or both set); EPI_SHARE_ADD: + a
   const uint64_t *s = nullptr;                 // EPI_GADGET: s, one polynomial
-  uint64_t delta = 0, t = 0, bound = 0;        // EPI_ADD: delta; EPI_DECRYPT: T; EPI_SHARE: E
+  uint64_t delta = 0, t = 0, bound = 0;        // EPI_ADD, EPI_MASK: delta; EPI_DECRYPT: T; EPI_SHARE, EPI_SHARE_ADD, EPI_MASK: E
   unsigned ginv = 1;                           // EPI_GADGET: g^-1 mod 2N
   int w = 0;                                   // EPI_GADGET: the digit width
   int neg_e = 0;                               // EPI_GADGET: - e
+  int neg_x = 0;                               // EPI_MASK: -x + delta M
 };
 
 // The modes of the five-prime CRT epilogue (k_eval_epilogue, bfv_eval.hip) on the centred integer x:
