@@ -92,7 +92,6 @@ class GpuPhase1 {
   // while the host hashes that commitment and evaluates the RLC context.
   int launch(const BfvState &st) {
     const uint64_t Q = pk->prm.Q, T = pk->prm.T, B = pk->prm.B;
-    CK(alloc_witness_buffers(ctx, pk, ws));
     stream = ws->stream.fr();
     pool_used = 0;
     off = 0;
@@ -127,7 +126,6 @@ class GpuPhase1 {
     const Fr *delta = in_dev + h_used;
     const uint64_t delta_bits = st.delta.value.bits();
     ++h_used;
-    pool_used = h_used;
     // the four gate cells of each constrain_mul (filled in by finish()), staged after the inputs
     mg_slot = h_used;
     n_mg = 0;
@@ -449,15 +447,8 @@ class GpuPhase1 {
   }
 };
 
-bool witness_on_host() {
-  const char *e = getenv("ZKFHE_WITNESS");
-  return e && strcmp(e, "host") == 0;
-}
-
 struct OpenItem {
-  const Fr *lagr;        // device pointer, Lagrange form
-  int n_rot;
-  int rot[4];            // rotation ids: 0,1,2,3, 4 = last (w^u), 5 = -1
+  zkp::EvalJob job;      // col: device pointer, Lagrange form; rot: rotation ids: 0,1,2,3, 4 = last (w^u), 5 = -1 (unused ones 0)
   U256 ev[4];            // canonical evaluations
 };
 
@@ -538,176 +529,206 @@ struct Trace {
   }
 };
 
-// input_json: the CircuitInput text; or words (input_json == nullptr): the same numbers as machine words (zkfhe_bfv_prove_words)
-int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const char *input_json, const FastInput *words, const uint8_t seed[32],
-               std::vector<uint8_t> &proof, std::vector<U256> &instances, float *timings) {
-  const CircuitConfig &cfg = pk->cfg;
-  const size_t n = cfg.n(), u = cfg.u(), ne = 4 * n;
+struct BackendGuard {
+  GpuPolyMul gpu_mul;
+  BackendGuard(zkfhe_ctx *ctx, Workspace *ws) : gpu_mul(ctx, ws) { poly_mul_backend() = &gpu_mul; }
+  ~BackendGuard() { poly_mul_backend() = nullptr; }
+};
+
+// inverse of V[k1][m] = c_k1^m by Lagrange basis polynomials: column k1 of V^-1 holds the coefficients of
+// L_k1(X) = prod_{j != k1} (X - c_j) / (c_k1 - c_j)
+zkp::Mat3 vandermonde3_inverse(const Fr c[3]) {
+  zkp::Mat3 vinv;
+  for (int k1 = 0; k1 < 3; ++k1) {
+    const Fr &a = c[(k1 + 1) % 3], &b = c[(k1 + 2) % 3];
+    const Fr den = fr_inv((c[k1] - a) * (c[k1] - b));
+    vinv.v[0 * 3 + k1] = a * b * den;              // X^0
+    vinv.v[1 * 3 + k1] = (Fr::zero() - (a + b)) * den;  // X^1
+    vinv.v[2 * 3 + k1] = den;                      // X^2
+  }
+  return vinv;
+}
+
+// interpolation through (pts[t], vals[t]), t < np <= 4: ascending coefficients, the unused ones zero
+void interpolate4(const Fr *pts, const Fr *vals, size_t np, Fr rc[4]) {
+  for (int q = 0; q < 4; ++q) rc[q] = Fr::zero();
+  for (size_t i = 0; i < np; ++i) {
+    Fr num[4] = {Fr::one(), Fr::zero(), Fr::zero(), Fr::zero()};   // prod_{t != i} (X - pts[t])
+    Fr den = Fr::one();
+    size_t deg = 0;
+    for (size_t t = 0; t < np; ++t) {
+      if (t == i) continue;
+      for (size_t q = ++deg; q > 0; --q) num[q] = num[q - 1] - pts[t] * num[q];
+      num[0] = Fr::zero() - pts[t] * num[0];
+      den = den * (pts[i] - pts[t]);
+    }
+    const Fr scl = vals[i] * fr_inv(den);
+    for (size_t q = 0; q <= deg; ++q) rc[q] = rc[q] + num[q] * scl;
+  }
+}
+
+// a commitment batch [n_adv advice columns | la_0 .. | ls_0 ..] -> the advice points stay in pts, the points of the permuted
+// lookup columns go to `permuted` in transcript order: la_0, ls_0, la_1, ls_1, ...
+void split_permuted(std::vector<AffinePoint> &pts, size_t n_adv, std::vector<AffinePoint> &permuted) {
+  const size_t nl = (pts.size() - n_adv) / 2;
+  permuted.resize(2 * nl);
+  for (size_t i = 0; i < nl; ++i) permuted[2 * i] = pts[n_adv + i], permuted[2 * i + 1] = pts[n_adv + nl + i];
+  pts.resize(n_adv);
+}
+
+// One proof: the state that crosses a round of the protocol, one method per round (called in order by prove_impl).
+struct Proof {
+  zkfhe_ctx *const ctx;
+  const zkfhe_srs *const srs;
+  zkfhe_bfv_pk *const pk;
+  const CircuitConfig &cfg;
+  std::vector<U256> &instances;
+  Trace &trace;
+  Workspace *const ws;
+  const NttDomain *const dom;
+  const size_t n = cfg.n(), u = cfg.u(), nbl = n - u;   // rows, usable rows, blinding rows of an advice column
   const unsigned k = cfg.k;
-  const double t_start = now_ms();
-  ctx->cmd_count[ZK_CMD_KERNEL] = ctx->cmd_count[ZK_CMD_COPY] = ctx->cmd_count[ZK_CMD_FILL] = 0;   // zkfhe_ctx_last_proof_commands: this proof's
-  Trace trace;
   // The blinding stream (draw i = Blake2b(seed || i) mod r) is evaluated on the device, where each value is needed
   // (prover_kernels.hip.hpp k_rng_fill).  Draw order = oracle/halo2_ref.py: the blinding rows of every advice column in
   // column order, then per lookup its permuted input and permuted table, then the permutation and lookup products, then
   // the n coefficients of the random polynomial.
   zkp::RngSeed rseed;
-  memcpy(rseed.w, seed, 32);
-  const size_t nbl_all = n - u;
-  const uint64_t ctr_adv = 0, ctr_lk = (uint64_t)cfg.n_advice() * nbl_all, ctr_pz = ctr_lk + 2 * (uint64_t)cfg.n_lookup * nbl_all,
-                 ctr_lz = ctr_pz + (uint64_t)cfg.n_chunks() * (nbl_all - 1), ctr_rand = ctr_lz + (uint64_t)cfg.n_lookup * (nbl_all - 1);
-  auto rng_fill = [&](hipStream_t stream, uint64_t ctr0, uint64_t ctr_col_stride, Fr *dst, size_t per_col, size_t col_stride, size_t n_cols) -> int {
+  const uint64_t ctr_adv = 0, ctr_lk = (uint64_t)cfg.n_advice() * nbl, ctr_pz = ctr_lk + 2 * (uint64_t)cfg.n_lookup * nbl,
+                 ctr_lz = ctr_pz + (uint64_t)cfg.n_chunks() * (nbl - 1), ctr_rand = ctr_lz + (uint64_t)cfg.n_lookup * (nbl - 1);
+  Transcript tr{cfg.transcript};
+  bool host_witness = false, early_p1 = false, early_rand = false, inst_via_ring = false;
+  // one proof over several GPUs: rank r_sh of W_sh owns the permutation chunks [c_lo, c_hi) (see quotient()); one GPU owns them all
+  const unsigned W_sh = srs->sharded() ? (unsigned)zkfhe_comm_world(srs->comm) : 1u, r_sh = srs->sharded() ? (unsigned)zkfhe_comm_rank(srs->comm) : 0u;
+  const size_t c_lo = (size_t)cfg.n_chunks() * r_sh / W_sh, c_hi = (size_t)cfg.n_chunks() * (r_sh + 1) / W_sh;
+  // the witness while it is built: phase 0 fills it, phase 1 completes it, the lookup round reads it
+  BfvState st;
+  Assigner as{cfg, false, ws->host_adv};   // host_adv is the workspace's pinned table (get_workspace): a null pointer here would mean a pageable table the kernels cannot read
+  GpuPhase1 g1{ctx, pk, ws};
+  std::vector<AffinePoint> permuted;   // commitments of the permuted lookup columns (split_permuted): the device paths commit them with the phase-1 advice
+  U256 gamma_rlc;
+  Fr beta, gamma, y, x;
+  Fr *beta_delta_dev = nullptr;   // [n_perm] beta * delta^i
+  Fr pts_rot[6];                  // x * w^rot by rotation id: 0,1,2,3 -> w^r ; 4 -> w^u ("last") ; 5 -> w^-1
+  std::vector<OpenItem> items;    // the opened polynomials, in evaluation-write order (shplonk.hpp OpenLayout)
+  size_t idx_H = 0;               // H(X) among them
+  double t_wit = 0;               // when the phase-1 witness was queued: the end of the first of prove_impl's timings
+
+  int rng_fill(hipStream_t stream, uint64_t ctr0, uint64_t ctr_col_stride, Fr *dst, size_t per_col, size_t col_stride, size_t n_cols) {
     if (!per_col || !n_cols) return ZKFHE_OK;
     zkp::k_rng_fill<<<grid_for(ctx, per_col * n_cols), 256, 0, stream>>>(rseed, ctr0, ctr_col_stride, dst, per_col, col_stride, n_cols);
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
-  };
+  }
   // the same draws by the kernel that writes the rest of the columns (zkp::RngRows): counters of column 0, counters per column
-  auto blind_rows = [&](uint64_t ctr0, uint64_t ctr_col_stride) {
-    zkp::RngRows b;
-    b.seed = rseed;
-    b.ctr0 = ctr0;
-    b.ctr_col_stride = ctr_col_stride;
-    b.on = 1;
-    return b;
-  };
-  Transcript tr(cfg.transcript);
-  const NttDomain *dom;
-  CK(zk_domain(ctx, (int)k, &dom));
-  Workspace *ws;
-  CK(get_workspace(ctx, pk, &ws));
-  GpuPolyMul gpu_mul(ctx, ws);
-  struct BackendGuard {
-    explicit BackendGuard(PolyMulBackend *b) { poly_mul_backend() = b; }
-    ~BackendGuard() { poly_mul_backend() = nullptr; }
-  } guard(&gpu_mul);
-  // ------------------------------------------------------------ phase 0 witness
-  const zkfhe_basis *small_basis = srs->g_lagrange_small ? srs->g_lagrange_small : srs->g_lagrange;
-  // a previous proof on this context may have been abandoned on an error with copies from the pinned staging buffers still
-  // queued: drain the stream before the buffers are rewritten (free when the stream is idle)
-  CK(zkfhe_sync(ctx));
-  CK(alloc_witness_buffers(ctx, pk, ws));
-  ws->aux->cmd_owner = ctx;   // the auxiliary stream's commands are this proof's
-  ws->ring_off = ws->ring_flushed = 0;
-  ws->inst_pending = false;
-  trace.mark("setup (workspace)");
-  // random polynomial, early: its coefficients (the tail of the blinding stream) depend on no challenge, so they are drawn and
-  // committed on the auxiliary stream beside the phase-0 / witness work.  The main stream is idle here (synchronised above)
-  // and only touches this region again after waiting for ev_rand.  A sharded commitment is a collective: it stays on the
-  // main stream, in protocol order.
-  const bool early_rand = !srs->sharded();
-  if (early_rand) {
+  zkp::RngRows blind_rows(uint64_t ctr0, uint64_t ctr_col_stride) const {
+    return zkp::RngRows{rseed, ctr0, ctr_col_stride, 1};
+  }
+  const zkfhe_basis *small_basis() const { return srs->g_lagrange_small ? srs->g_lagrange_small : srs->g_lagrange; }
+  bool owns_chunk(size_t j) const { return j >= c_lo && j < c_hi; }
+  bool owns_col(size_t perm_col) const { return owns_chunk(perm_col / cfg.chunk()); }
+  int setup() {
+    // a previous proof on this context may have been abandoned on an error with copies from the pinned staging buffers still
+    // queued: drain the stream before the buffers are rewritten (free when the stream is idle)
+    CK(zkfhe_sync(ctx));
+    CK(alloc_witness_buffers(ctx, pk, ws));
+    ws->aux->cmd_owner = ctx;   // the auxiliary stream's commands are this proof's
+    ws->ring_off = ws->ring_flushed = 0;
+    ws->inst_pending = false;
+    trace.mark("setup (workspace)");
+    // random polynomial, early: its coefficients (the tail of the blinding stream) depend on no challenge, so they are drawn and
+    // committed on the auxiliary stream beside the phase-0 / witness work.  The main stream is idle here (synchronised above)
+    // and only touches this region again after waiting for ev_rand.  A sharded commitment is a collective: it stays on the
+    // main stream, in protocol order.
+    early_rand = !srs->sharded();
+    if (!early_rand) return ZKFHE_OK;
     zkfhe_ctx *aux = ws->aux;
-    Fr *rand_dev = ws->misc.fr() + 8 * n;
-    G1Affine *pt_dev = (G1Affine *)ws->points.p + std::max<size_t>(ws->n_all, cfg.n_perm());
-    CK(rng_fill(aux->stream, ctr_rand, 0, rand_dev, n, n, 1));
-    (void)pt_dev;   // the commitment is stored by the MSM's last kernel into pinned memory: no copy command
-    if (int rc = zkfhe_msm_batch_xyzz(aux, srs->g, (const zkfhe_fr *)rand_dev, 1, (zkfhe_g1_xyzz *)ws->host_rand_pt))
+    Fr *rand_c = ws->misc.fr() + 8 * n, *rand_l = ws->misc.fr() + 9 * n;
+    CK(rng_fill(aux->stream, ctr_rand, 0, rand_c, n, n, 1));
+    // the commitment is stored by the MSM's last kernel into pinned memory: no copy command
+    if (int rc = zkfhe_msm_batch_xyzz(aux, srs->g, (const zkfhe_fr *)rand_c, 1, (zkfhe_g1_xyzz *)ws->host_rand_pt))
       return zk_fail_msg(ctx, rc, std::string("random polynomial commitment (auxiliary stream): ") + zkfhe_last_error(aux));
     // ... and its Lagrange form, which the evaluation round reads: one single-column transform less on the proof's critical path
-    if (int rc = zkfhe_ntt_batch_to(aux, (const zkfhe_fr *)rand_dev, (zkfhe_fr *)(ws->misc.fr() + 9 * n), 1, (int)k, 0))
+    if (int rc = zkfhe_ntt_batch_to(aux, (const zkfhe_fr *)rand_c, (zkfhe_fr *)rand_l, 1, (int)k, 0))
       return zk_fail_msg(ctx, rc, std::string("random polynomial, Lagrange form (auxiliary stream): ") + zkfhe_last_error(aux));
     ZK_HIP(ctx, hipEventRecord(ws->ev_rand, aux->stream));
+    return ZKFHE_OK;
   }
-  Context ctx0(CTX_PHASE0, false, false), ctx_gate(CTX_GATE1, false, false), ctx_rlc(CTX_RLC1, true, false);
-  std::vector<Cell> make_public;
-  instances.clear();
-  tr.common_scalar(pk->vk_digest);
-  // the 5121 public inputs are hashed on a helper thread, started as soon as they are known: it runs beside the phase-0
-  // precomputation, upload and commitment (a Poseidon sponge is one sequential chain of 2561 permutations here)
-  // The first 2 N of them are pk0 | pk1 (examples/bfv.rs:118-119), the same for every encryption under one public key: the
-  // transcript state behind them is kept per key (prefix_cache.hpp), and a proof that finds its key there starts from it --
-  // 1 024 of the 2 561 permutations at k = 13.
-  const auto on_public = [&](const std::vector<Cell> &pub) {
-    instances.reserve(pub.size());
-    for (const Cell &c : pub) instances.push_back(c.value);
-    const size_t n_key = std::min<size_t>(instances.size(), 2 * (size_t)pk->prm.N);
-    Transcript::State mid;
-    if (input_json && pk->prehash.take(input_json, strlen(input_json), instances.data(), instances.size(), mid)) {
-      tr.restore(mid);   // announced ahead of time (zkfhe_bfv_pk_prehash): `vk digest | public inputs` are absorbed already
-    } else if (!n_key || !pk->prefix.capacity()) {
-      tr.common_scalars_async(instances);
-    } else if (pk->prefix.lookup(instances.data(), n_key, mid)) {
-      tr.restore(mid);
-      tr.common_scalars_async(std::vector<U256>(instances.begin() + (long)n_key, instances.end()));
-    } else {
-      PrefixCache *cache = &pk->prefix;
-      std::vector<U256> key(instances.begin(), instances.begin() + (long)n_key);
-      tr.common_scalars_async_marked(instances, n_key, [cache, key](const Transcript::State &st) { cache->insert(key.data(), key.size(), st); });
+  // ------------------------------------------------------------ phase 0 witness
+  // the phase-0 commitment (pts), with everything of phase 1 that does not wait for its challenge queued behind it
+  int phase0(const char *input_json, const FastInput *words, std::vector<AffinePoint> &pts) {
+    Context ctx0(CTX_PHASE0, false, false);
+    std::vector<Cell> make_public;
+    instances.clear();
+    tr.common_scalar(pk->vk_digest);
+    // the 5121 public inputs are hashed on a helper thread, started as soon as they are known: it runs beside the phase-0
+    // precomputation, upload and commitment (a Poseidon sponge is one sequential chain of 2561 permutations here)
+    // The first 2 N of them are pk0 | pk1 (examples/bfv.rs:118-119), the same for every encryption under one public key: the
+    // transcript state behind them is kept per key (prefix_cache.hpp), and a proof that finds its key there starts from it --
+    // 1 024 of the 2 561 permutations at k = 13.
+    const auto on_public = [&](const std::vector<Cell> &pub) {
+      instances.reserve(pub.size());
+      for (const Cell &c : pub) instances.push_back(c.value);
+      const size_t n_key = std::min<size_t>(instances.size(), 2 * (size_t)pk->prm.N);
+      Transcript::State mid;
+      if (input_json && pk->prehash.take(input_json, strlen(input_json), instances.data(), instances.size(), mid)) {
+        tr.restore(mid);   // announced ahead of time (zkfhe_bfv_pk_prehash): `vk digest | public inputs` are absorbed already
+      } else if (!n_key || !pk->prefix.capacity()) {
+        tr.common_scalars_async(instances);
+      } else if (pk->prefix.lookup(instances.data(), n_key, mid)) {
+        tr.restore(mid);
+        tr.common_scalars_async(std::vector<U256>(instances.begin() + (long)n_key, instances.end()));
+      } else {
+        PrefixCache *cache = &pk->prefix;
+        std::vector<U256> key(instances.begin(), instances.begin() + (long)n_key);
+        tr.common_scalars_async_marked(instances, n_key, [cache, key](const Transcript::State &st) { cache->insert(key.data(), key.size(), st); });
+      }
+    };
+    // machine-word phase 0 (bfv_phase0_fast.hpp) for every input in its domain; anything else goes through the line-by-line
+    // restatement of the reference, which also words the errors
+    // words the values stage declines are rendered as the JSON that spells them and take the text path: the same outcome as
+    // zkfhe_bfv_prove on that text by construction (the announcements of zkfhe_bfv_pk_prehash are keyed on text and serve text only)
+    std::string rendered;
+    if (words ? !bfv_phase0_fast_values(ctx0, *words, pk->prm, make_public, st, on_public)
+              : !bfv_phase0_fast(ctx0, input_json, strlen(input_json), pk->prm, make_public, st, on_public)) {
+      if (words) {
+        rendered = render_input_json(*words);
+        input_json = rendered.c_str();
+      }
+      const CircuitInput in = CircuitInput::parse_json(input_json);
+      trace.mark("parse_json");
+      st = bfv_phase0(ctx0, in, pk->prm, make_public, on_public);
     }
-  };
-  // machine-word phase 0 (bfv_phase0_fast.hpp) for every input in its domain; anything else goes through the line-by-line
-  // restatement of the reference, which also words the errors
-  // words the values stage declines are rendered as the JSON that spells them and take the text path: the same outcome as
-  // zkfhe_bfv_prove on that text by construction (the announcements of zkfhe_bfv_pk_prehash are keyed on text and serve text only)
-  BfvState st;
-  std::string rendered;
-  if (words ? !bfv_phase0_fast_values(ctx0, *words, pk->prm, make_public, st, on_public)
-            : !bfv_phase0_fast(ctx0, input_json, strlen(input_json), pk->prm, make_public, st, on_public)) {
-    if (words) {
-      rendered = render_input_json(*words);
-      input_json = rendered.c_str();
+    trace.mark("bfv_phase0");
+    as.place(ctx0, true);
+    trace.mark("place phase 0");
+    // the instance column's values ride up with the proof's first table flush (they are needed from the grand products on)
+    if (instances.size() > n) return zk_fail_msg(ctx, ZKFHE_EINVAL, "more public inputs than rows");
+    inst_via_ring = instances.size() * 32 <= ((size_t)1 << 20);   // long instance columns (k >= 18) keep their own copy
+    if (inst_via_ring) {
+      STAGE(staged, U256, ws, instances.data(), instances.size() * 32);
+      // ... and the flush kernel that carries them converts them into the instance column on its way (the column is idle until the
+      // grand products, and the previous proof on this workspace is complete)
+      ws->inst_src = (const Fr *)(ws->ring + ((const uint8_t *)staged - (const uint8_t *)ws->dev_ring.p));
+      ws->inst_n = instances.size();
+      ws->inst_pending = true;
     }
-    const CircuitInput in = CircuitInput::parse_json(input_json);
-    trace.mark("parse_json");
-    st = bfv_phase0(ctx0, in, pk->prm, make_public, on_public);
-  }
-  trace.mark("bfv_phase0");
-  Assigner as(cfg, false, ws->host_adv);
-  as.place(ctx0, true);
-  trace.mark("place phase 0");
-  // the instance column's values ride up with the proof's first table flush (they are needed from the grand products on)
-  if (instances.size() > n) return zk_fail_msg(ctx, ZKFHE_EINVAL, "more public inputs than rows");
-  const bool inst_via_ring = instances.size() * 32 <= ((size_t)1 << 20);   // long instance columns (k >= 18) keep their own copy
-  if (inst_via_ring) {
-    STAGE(staged, U256, ws, instances.data(), instances.size() * 32);
-    // ... and the flush kernel that carries them converts them into the instance column on its way (the column is idle until the
-    // grand products, and the previous proof on this workspace is complete)
-    ws->inst_src = (const Fr *)(ws->ring + ((const uint8_t *)staged - (const uint8_t *)ws->dev_ring.p));
-    ws->inst_n = instances.size();
-    ws->inst_pending = true;
-  }
-  auto blind_and_upload = [&](unsigned c_lo, unsigned c_hi) -> int {
-    // the table is pinned and column-contiguous; the blinding rows u .. n-1 are drawn on the device.  The conversion kernel reads the
-    // pinned table itself (hipHostMalloc memory is mapped into the device's address space): no copy command on the stream -- with twenty
-    // proofs starting together the runtime's copy path cost each of them 2-5 ms of CPU before their first kernel (ZKFHE_UPLOAD=copy: one
-    // DMA for the whole phase, then the conversion in place)
-    const char *upload_env = getenv("ZKFHE_UPLOAD");   // read per proof, like ZKFHE_WITNESS / ZKFHE_EARLY_P1 (the tests switch it)
-    const bool upload_by_copy = upload_env && !strcmp(upload_env, "copy");
-    if (upload_by_copy) {
-      ZK_HIP(ctx, zk_memcpy_async(ctx, ws->adv_l.fr() + (size_t)c_lo * n, as.t.advice[c_lo], (size_t)(c_hi - c_lo) * n * 32, hipMemcpyHostToDevice, ctx->stream));
-      CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)(ws->adv_l.fr() + (size_t)c_lo * n), (zkfhe_fr *)(ws->adv_l.fr() + (size_t)c_lo * n),
-                          (size_t)(c_hi - c_lo) * n));
-    } else {
-      zkp::k_to_mont_blind<<<grid_for(ctx, (size_t)(c_hi - c_lo) * n), 256, 0, ctx->stream>>>((const Fr *)as.t.advice[c_lo], ws->adv_l.fr() + (size_t)c_lo * n, n, (unsigned)u,
-                                                                                               c_hi - c_lo, blind_rows(ctr_adv + (uint64_t)c_lo * nbl_all, nbl_all));
-      ZK_LAUNCH_CHECK(ctx);
-      return ZKFHE_OK;
-    }
-    return rng_fill(ctx->stream, ctr_adv + (uint64_t)c_lo * nbl_all, nbl_all, ws->adv_l.fr() + (size_t)c_lo * n + u, nbl_all, n, c_hi - c_lo);
-  };
-  std::vector<AffinePoint> adv_commit(cfg.n_advice()), pts;
-  trace.mark("transcript: instances");
-  CK(blind_and_upload(0, cfg.n_gate0));
-  trace.mark("blind + upload phase 0");
-  const bool host_witness = witness_on_host();
-  // see "Early phase-1 commitment" below.  On with the Poseidon transcript, whose challenge after the phase-0 commitment is
-  // 2561 sequential permutations (the public inputs, ~20 ms of host time) away: measured on a wave of 20 concurrent proofs
-  // +9 % (the GPU commits while every proof hashes), -1.5 % in steady state (two extra small commitments per proof).  With
-  // Blake2b there is no hash to hide -- but on long rows (k >= 18) the RLC witness the host computes from that challenge is
-  // (k = 19: 6 ms of Horner chains and placement with the GPU idle): 155.8 -> 151.5 ms per proof; at k = 16 it costs 0.7 ms.
-  // ZKFHE_EARLY_P1=0 / 1 overrides.
-  const char *early_env = getenv("ZKFHE_EARLY_P1");
-  const bool early_want = early_env ? early_env[0] == '1' : (cfg.transcript == TR_POSEIDON || k >= 18);
-  const bool early_p1 = early_want && !host_witness && cfg.n_lookup > 0 && cfg.lookup_bits == 8;
-  GpuPhase1 g1(ctx, pk, ws);
-  const zkfhe_basis *p0_basis = small_basis;
-  if (host_witness) {
-    CK(commit_cols(ctx, srs, p0_basis, ws->adv_l.fr(), cfg.n_gate0, (G1Affine *)ws->points.p, pts));
-  } else {
+    trace.mark("transcript: instances");
+    CK(blind_and_upload(0, cfg.n_gate0));
+    trace.mark("blind + upload phase 0");
+    const char *witness_env = getenv("ZKFHE_WITNESS");
+    host_witness = witness_env && strcmp(witness_env, "host") == 0;
+    // see "Early phase-1 commitment" below.  On with the Poseidon transcript, whose challenge after the phase-0 commitment is
+    // 2561 sequential permutations (the public inputs, ~20 ms of host time) away: measured on a wave of 20 concurrent proofs
+    // +9 % (the GPU commits while every proof hashes), -1.5 % in steady state (two extra small commitments per proof).  With
+    // Blake2b there is no hash to hide -- but on long rows (k >= 18) the RLC witness the host computes from that challenge is
+    // (k = 19: 6 ms of Horner chains and placement with the GPU idle): 155.8 -> 151.5 ms per proof; at k = 16 it costs 0.7 ms.
+    // ZKFHE_EARLY_P1=0 / 1 overrides.
+    const char *early_env = getenv("ZKFHE_EARLY_P1");
+    const bool early_want = early_env ? early_env[0] == '1' : (cfg.transcript == TR_POSEIDON || k >= 18);
+    early_p1 = early_want && !host_witness && cfg.n_lookup > 0 && cfg.lookup_bits == 8;
+    if (host_witness) return commit_cols(ctx, srs, small_basis(), ws->adv_l.fr(), cfg.n_gate0, (G1Affine *)ws->points.p, pts);
     // the commitment's points come back through an event; the phase-1 gadget launches queue up behind the MSM
-    CK(alloc_witness_buffers(ctx, pk, ws));
-    CK(srs_msm_pts(ctx, srs, p0_basis, ws->adv_l.fr(), cfg.n_gate0, ws->host_pts));   // stored into pinned memory by the MSM itself
+    CK(srs_msm_pts(ctx, srs, small_basis(), ws->adv_l.fr(), cfg.n_gate0, ws->host_pts));   // stored into pinned memory by the MSM itself
     CK(srs_record(ctx, srs, ws->ev_pts));   // sharded: behind the all-gather on the communicator's stream, which the gadget launches below overlap
     CK(g1.launch(st));
     if (early_p1) {
@@ -716,136 +737,142 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       // is 2561 sequential permutations away (the public inputs).  So the gate and lookup columns are placed, blinded,
       // permuted and committed NOW, with those cells zero and the RLC columns zero; afterwards the missing cells are
       // committed as sparse correction columns and added (a commitment is linear in its column).  Same points, same bytes.
-      const size_t nbl0 = n - u, n_adv1 = cfg.n_advice() - cfg.n_gate0, n_early = n_adv1 + 2 * cfg.n_lookup;
       // the placement kernels draw the blinding rows of their columns and clear the RLC columns behind them
-      CK(g1.place_early(blind_rows(ctr_adv + (uint64_t)cfg.n_gate0 * nbl0, nbl0), cfg.n_rlc));
-      int *err_dev = ws->host_early_err;   // pinned: written by the kernel, read by the host after ev_early
-      *err_dev = 0;
-      const zkp::RngRows blind_lk = blind_rows(ctr_lk, 2 * nbl0);   // la_i then ls_i, lookup by lookup
-      CK(zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), err_dev, nullptr, &blind_lk));
-      CK(srs_msm_pts(ctx, srs, small_basis, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, n_early, ws->host_early));
+      CK(g1.place_early(blind_rows(ctr_adv + (uint64_t)cfg.n_gate0 * nbl, nbl), cfg.n_rlc));
+      CK(permute_lookups(ws->host_early_err));   // pinned: written by the kernel, read by the host after ev_early
+      CK(srs_msm_pts(ctx, srs, small_basis(), ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, cfg.n_advice() - cfg.n_gate0 + 2 * cfg.n_lookup, ws->host_early));
       CK(srs_record(ctx, srs, ws->ev_early));
     }
     ZK_HIP(ctx, hipEventSynchronize(ws->ev_pts));
     pts.resize(cfg.n_gate0);
     points_canon(srs, ws->host_pts, cfg.n_gate0, pts.data());
+    return ZKFHE_OK;
   }
-  trace.mark("commit phase 0 (GPU)");
-  ctx->proof_marks[0] = (float)(now_ms() - t_start);
-  for (unsigned c = 0; c < cfg.n_gate0; ++c) tr.write_point(adv_commit[c] = pts[c]);
-  const U256 gamma_rlc = tr.squeeze();
-  ctx->proof_marks[1] = (float)(now_ms() - t_start);
+  // advice columns [col_lo, col_hi) of the host table -> device, Montgomery form, with their blinding rows
+  int blind_and_upload(unsigned col_lo, unsigned col_hi) {
+    // the table is pinned and column-contiguous; the blinding rows u .. n-1 are drawn on the device.  The conversion kernel reads the
+    // pinned table itself (hipHostMalloc memory is mapped into the device's address space): no copy command on the stream -- with twenty
+    // proofs starting together the runtime's copy path cost each of them 2-5 ms of CPU before their first kernel (ZKFHE_UPLOAD=copy: one
+    // DMA for the whole phase, then the conversion in place)
+    const char *upload_env = getenv("ZKFHE_UPLOAD");   // read per proof, like ZKFHE_WITNESS / ZKFHE_EARLY_P1 (the tests switch it)
+    const bool upload_by_copy = upload_env && !strcmp(upload_env, "copy");
+    Fr *dst = ws->adv_l.fr() + (size_t)col_lo * n;
+    if (!upload_by_copy) {
+      zkp::k_to_mont_blind<<<grid_for(ctx, (size_t)(col_hi - col_lo) * n), 256, 0, ctx->stream>>>((const Fr *)as.t.advice[col_lo], dst, n, (unsigned)u, col_hi - col_lo,
+                                                                                                   blind_rows(ctr_adv + (uint64_t)col_lo * nbl, nbl));
+      ZK_LAUNCH_CHECK(ctx);
+      return ZKFHE_OK;
+    }
+    ZK_HIP(ctx, zk_memcpy_async(ctx, dst, as.t.advice[col_lo], (size_t)(col_hi - col_lo) * n * 32, hipMemcpyHostToDevice, ctx->stream));
+    CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)dst, (zkfhe_fr *)dst, (size_t)(col_hi - col_lo) * n));
+    return rng_fill(ctx->stream, ctr_adv + (uint64_t)col_lo * nbl, nbl, dst + u, nbl, n, col_hi - col_lo);
+  }
+  // The device lookup permutation of every lookup column into la | ls, which also draws their blinding rows (la_i then ls_i, lookup by
+  // lookup -- two interleaved runs of the stream).  err is pinned: raised by the kernel, read by the caller once the host has waited.
+  int permute_lookups(int *err) {
+    *err = 0;
+    const zkp::RngRows blind_lk = blind_rows(ctr_lk, 2 * nbl);
+    return zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), err, nullptr, &blind_lk);
+  }
   // ------------------------------------------------------------ phase 1 witness
-  const size_t nbl = n - u;
-  int *lookup_err = nullptr;
-  if (host_witness) {
+  // The three ways to the phase-1 advice commitment (pts): host, device, and device with the early commitment; each records t_wit once its witness is queued.
+  // ZKFHE_WITNESS=host: the whole witness on the host (the tests' reference for the device generator)
+  int phase1_host(std::vector<AffinePoint> &pts) {
+    Context ctx_gate(CTX_GATE1, false, false), ctx_rlc(CTX_RLC1, true, false);
     bfv_phase1(st, pk->prm, ctx_gate, ctx_rlc, gamma_rlc);
     as.place(ctx_gate, true);
     as.place(ctx_rlc, true);
     as.place_lookups(ctx_gate);
-  } else {
+    t_wit = now_ms();
+    CK(blind_and_upload(cfg.n_gate0, cfg.n_advice()));
+    trace.mark("blind + upload phase 1");
+    return commit_cols_out(ctx, srs, small_basis(), ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, cfg.n_advice() - cfg.n_gate0, ws, pts);
+  }
+  int phase1_device(std::vector<AffinePoint> &pts) {
+    const size_t n_adv1 = cfg.n_advice() - cfg.n_gate0;
     // RLC context on the host (6 K cells), gate context (1.2 M cells) on the device
+    Context ctx_rlc(CTX_RLC1, true, false);
     U256 evals[12];
     bfv_phase1_rlc(st, ctx_rlc, gamma_rlc, evals);
     trace.mark("rlc context");
     as.place(ctx_rlc, true);
     trace.mark("place rlc");
-    if (!early_p1) {
-      CK(g1.finish(evals, blind_rows(ctr_adv + (uint64_t)cfg.n_gate0 * nbl, nbl)));   // blinding rows of the device-generated columns: same draw order as the host path
-    } else {
-      // the challenge-dependent rest: the reserved gate cells (into the columns and into sparse correction columns), the RLC
-      // columns; two small commitments, then early + correction on the host
-      const GpuPhase1::PatchPlan plan = g1.patch_plan();
-      const size_t np = plan.columns.size(), n_adv1 = cfg.n_advice() - cfg.n_gate0;
-      Fr *patch_cols = ws->tmp_c.fr();
-      std::vector<zkfhe_sparse_term> terms;
-      const bool sparse = !srs->sharded() && zkfhe_basis_has_multiples(srs->g_lagrange);
-      CK(g1.patch(evals, plan, patch_cols, sparse ? &terms : nullptr));
-      CK(blind_and_upload(cfg.adv_rlc0(), cfg.n_advice()));
-      // the corrections sit behind the early commitments in ws->points; the last slot of that buffer belongs to the random
-      // polynomial's commitment (auxiliary stream)
-      if (np + cfg.n_rlc > ws->out_pts_cap)
-        return zk_fail_msg(ctx, ZKFHE_EINVAL, "early phase-1 commitment: correction points do not fit the workspace (set ZKFHE_EARLY_P1=0)");
-      (void)n_adv1;
-      uint8_t *fix_dev = ws->out_pts();   // pinned: the correction points are read by the host right below
-      const size_t ps = pt_stride(srs);
-      if (np && sparse) {
-        // a dozen non-zero cells: one wave per correction column over the digit-multiple table
-        STAGE(terms_dev, zkfhe_sparse_term, ws, terms.data(), terms.size() * sizeof(zkfhe_sparse_term));
-        CK(flush_staged(ctx, ws));
-        CK(zkfhe_msm_sparse_xyzz(ctx, srs->g_lagrange, terms_dev, terms.size(), np, (zkfhe_g1_xyzz *)fix_dev));   // sparse => one GPU => accumulator-form slots
-      } else if (np) {
-        CK(srs_msm_pts(ctx, srs, srs->g_lagrange, patch_cols, np, fix_dev));
-      }
-      if (cfg.n_rlc) CK(srs_msm_pts(ctx, srs, srs->g_lagrange, ws->adv_l.fr() + (size_t)cfg.adv_rlc0() * n, cfg.n_rlc, fix_dev + np * ps));
-      CK(srs_join(ctx, srs, false));
-      ZK_HIP(ctx, zk_wait(ctx));   // everything queued so far, the early commitment (ev_early) included
-      if (*ws->host_early_err) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup input not in table: a range check of the witness fails");
-      // early commitment + correction, on the host (at most a handful of additions), in the form the slots hold; the sums are
-      // normalised with the rest of the round below
-      for (size_t t = 0; t < np; ++t) {
-        if (srs->sharded()) {
-          G1Affine &e = ((G1Affine *)ws->host_early)[plan.columns[t]];
-          zk::G1X acc = zk::g1x_from_affine(e);
-          zk::g1x_add_affine(acc, ((const G1Affine *)fix_dev)[t], false);
-          e = zk::g1x_to_affine(acc);
-        } else {
-          zk::g1x_add(((zk::G1X *)ws->host_early)[plan.columns[t]], ((const zk::G1X *)fix_dev)[t]);
-        }
-      }
-      for (unsigned j = 0; j < cfg.n_rlc; ++j) memcpy(ws->host_early + (size_t)(cfg.adv_rlc0() - cfg.n_gate0 + j) * ps, fix_dev + (np + j) * ps, ps);
-    }
+    if (early_p1) return phase1_early_finish(evals, n_adv1, pts);
+    CK(g1.finish(evals, blind_rows(ctr_adv + (uint64_t)cfg.n_gate0 * nbl, nbl)));   // blinding rows of the device-generated columns: same draw order as the host path
     trace.mark("gpu phase 1 (enqueue)");
-  }
-  std::vector<std::vector<U256>> lookup_inputs(host_witness ? cfg.n_lookup : 0);
-  for (unsigned i = 0; i < lookup_inputs.size(); ++i)
-    lookup_inputs[i].assign(as.t.advice[cfg.adv_lookup0() + i], as.t.advice[cfg.adv_lookup0() + i] + u);
-  const double t_wit = now_ms();
-  if (host_witness) {
-    CK(blind_and_upload(cfg.n_gate0, cfg.n_advice()));
-  } else if (!early_p1) {
+    t_wit = now_ms();
     CK(blind_and_upload(cfg.adv_rlc0(), cfg.n_advice()));
-  }
-  trace.mark("blind + upload phase 1");
-  std::vector<AffinePoint> la_commit, ls_commit;
-  const bool merged = !host_witness && cfg.n_lookup > 0;   // permuted lookup columns committed together with the advice
-  if (early_p1) {
-    const size_t n_adv1 = cfg.n_advice() - cfg.n_gate0;
-    pts.resize(n_adv1 + 2 * (size_t)cfg.n_lookup);
-    points_canon(srs, ws->host_early, pts.size(), pts.data());   // one inversion for the round: advice | permuted inputs | permuted tables
-    la_commit.assign(pts.begin() + (long)n_adv1, pts.begin() + (long)(n_adv1 + cfg.n_lookup));
-    ls_commit.assign(pts.begin() + (long)(n_adv1 + cfg.n_lookup), pts.end());
-    pts.resize(n_adv1);
-  } else if (merged) {
+    trace.mark("blind + upload phase 1");
+    if (!cfg.n_lookup) return commit_cols_out(ctx, srs, small_basis(), ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, n_adv1, ws, pts);
     // Single-expression lookups do not use theta, so the permuted columns can be built before the advice commitment is
     // hashed: one MSM call over [phase-1 advice | la | ls] (contiguous in all_l) instead of two, same points, same
     // transcript order, same draw order of the blinding values.
     if (cfg.lookup_bits != 8) return zk_fail_msg(ctx, ZKFHE_EINVAL, "the device lookup permutation is built for lookup_bits = 8");
-    lookup_err = ws->out_flags() + 2;   // pinned
-    *lookup_err = 0;
-    // blinding rows: la_i then ls_i, lookup by lookup -- two interleaved runs of the stream, drawn by the permutation kernel
-    const zkp::RngRows blind_lk = blind_rows(ctr_lk, 2 * nbl);
-    CK(zkw::lookup_permute(ctx, ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, n, (unsigned)u, cfg.n_lookup, ws->la_l.fr(), ws->ls_l.fr(), lookup_err, nullptr, &blind_lk));
-    const size_t n_adv1 = cfg.n_advice() - cfg.n_gate0;
-    CK(commit_cols_out(ctx, srs, small_basis, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, n_adv1 + 2 * cfg.n_lookup, ws, pts));
+    int *lookup_err = ws->out_flags() + 2;   // pinned
+    CK(permute_lookups(lookup_err));
+    CK(commit_cols_out(ctx, srs, small_basis(), ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, n_adv1 + 2 * cfg.n_lookup, ws, pts));
     if (*lookup_err) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup input not in table: a range check of the witness fails");
-    la_commit.assign(pts.begin() + n_adv1, pts.begin() + n_adv1 + cfg.n_lookup);
-    ls_commit.assign(pts.begin() + n_adv1 + cfg.n_lookup, pts.end());
-    pts.resize(n_adv1);
-  } else {
-    CK(commit_cols_out(ctx, srs, small_basis, ws->adv_l.fr() + (size_t)cfg.n_gate0 * n, cfg.n_advice() - cfg.n_gate0, ws, pts));
+    split_permuted(pts, n_adv1, permuted);
+    return ZKFHE_OK;
   }
-  trace.mark("commit phase 1 (GPU)");
-  for (unsigned c = cfg.n_gate0; c < cfg.n_advice(); ++c) adv_commit[c] = pts[c - cfg.n_gate0];
-  tr.write_points(pts);
-  tr.squeeze();  // theta: squeezed in protocol order, unused by single-expression lookups
+  // the challenge-dependent rest of the early phase-1 commitment: the reserved gate cells (into the columns and into sparse
+  // correction columns), the RLC columns; two small commitments, then early + correction on the host
+  int phase1_early_finish(const U256 evals[12], size_t n_adv1, std::vector<AffinePoint> &pts) {
+    const GpuPhase1::PatchPlan plan = g1.patch_plan();
+    const size_t np = plan.columns.size();
+    Fr *patch_cols = ws->tmp_c.fr();
+    std::vector<zkfhe_sparse_term> terms;
+    const bool sparse = !srs->sharded() && zkfhe_basis_has_multiples(srs->g_lagrange);
+    CK(g1.patch(evals, plan, patch_cols, sparse ? &terms : nullptr));
+    CK(blind_and_upload(cfg.adv_rlc0(), cfg.n_advice()));
+    // the corrections sit behind the early commitments in ws->points; the last slot of that buffer belongs to the random
+    // polynomial's commitment (auxiliary stream)
+    if (np + cfg.n_rlc > ws->out_pts_cap)
+      return zk_fail_msg(ctx, ZKFHE_EINVAL, "early phase-1 commitment: correction points do not fit the workspace (set ZKFHE_EARLY_P1=0)");
+    uint8_t *fix_dev = ws->out_pts();   // pinned: the correction points are read by the host right below
+    const size_t ps = pt_stride(srs);
+    if (np && sparse) {
+      // a dozen non-zero cells: one wave per correction column over the digit-multiple table
+      STAGE(terms_dev, zkfhe_sparse_term, ws, terms.data(), terms.size() * sizeof(zkfhe_sparse_term));
+      CK(flush_staged(ctx, ws));
+      CK(zkfhe_msm_sparse_xyzz(ctx, srs->g_lagrange, terms_dev, terms.size(), np, (zkfhe_g1_xyzz *)fix_dev));   // sparse => one GPU => accumulator-form slots
+    } else if (np) {
+      CK(srs_msm_pts(ctx, srs, srs->g_lagrange, patch_cols, np, fix_dev));
+    }
+    if (cfg.n_rlc) CK(srs_msm_pts(ctx, srs, srs->g_lagrange, ws->adv_l.fr() + (size_t)cfg.adv_rlc0() * n, cfg.n_rlc, fix_dev + np * ps));
+    CK(srs_join(ctx, srs, false));
+    ZK_HIP(ctx, zk_wait(ctx));   // everything queued so far, the early commitment (ev_early) included
+    if (*ws->host_early_err) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup input not in table: a range check of the witness fails");
+    // early commitment + correction, on the host (at most a handful of additions), in the form the slots hold; the sums are
+    // normalised with the rest of the round below
+    for (size_t t = 0; t < np; ++t) {
+      if (srs->sharded()) {
+        G1Affine &e = ((G1Affine *)ws->host_early)[plan.columns[t]];
+        zk::G1X acc = zk::g1x_from_affine(e);
+        zk::g1x_add_affine(acc, ((const G1Affine *)fix_dev)[t], false);
+        e = zk::g1x_to_affine(acc);
+      } else {
+        zk::g1x_add(((zk::G1X *)ws->host_early)[plan.columns[t]], ((const zk::G1X *)fix_dev)[t]);
+      }
+    }
+    for (unsigned j = 0; j < cfg.n_rlc; ++j) memcpy(ws->host_early + (size_t)(cfg.adv_rlc0() - cfg.n_gate0 + j) * ps, fix_dev + (np + j) * ps, ps);
+    trace.mark("gpu phase 1 (enqueue)");
+    t_wit = now_ms();
+    trace.mark("blind + upload phase 1");
+    pts.resize(n_adv1 + 2 * (size_t)cfg.n_lookup);
+    points_canon(srs, ws->host_early, pts.size(), pts.data());   // one inversion for the round: advice | permuted inputs | permuted tables
+    split_permuted(pts, n_adv1, permuted);
+    return ZKFHE_OK;
+  }
   // ------------------------------------------------------------ lookups: permuted input / table
-  if (cfg.n_lookup) {
-    if (!merged) {
-      std::vector<U256> ap, sp;
+  int lookup_columns() {
+    if (!cfg.n_lookup) return ZKFHE_OK;
+    if (host_witness) {   // the device paths committed la | ls with the phase-1 advice
+      std::vector<U256> input, ap, sp;
       U256 *stA = ws->host_blind, *stS = ws->host_blind + (size_t)cfg.n_lookup * n;  // la | ls, as on the device
       for (unsigned i = 0; i < cfg.n_lookup; ++i) {
-        permute_lookup(lookup_inputs[i], u, 1u << cfg.lookup_bits, ap, sp);
+        input.assign(as.t.advice[cfg.adv_lookup0() + i], as.t.advice[cfg.adv_lookup0() + i] + u);
+        permute_lookup(input, u, 1u << cfg.lookup_bits, ap, sp);
         U256 *colA = stA + (size_t)i * n, *colS = stS + (size_t)i * n;
         std::copy(ap.begin(), ap.end(), colA);
         std::copy(sp.begin(), sp.end(), colS);
@@ -855,58 +882,35 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       CK(zkfhe_fr_to_mont(ctx, (const zkfhe_fr *)ws->la_l.p, (zkfhe_fr *)ws->la_l.p, 2 * (size_t)cfg.n_lookup * n));
       CK(rng_fill(ctx->stream, ctr_lk, 2 * nbl, ws->la_l.fr() + u, nbl, n, cfg.n_lookup));
       CK(rng_fill(ctx->stream, ctr_lk + nbl, 2 * nbl, ws->ls_l.fr() + u, nbl, n, cfg.n_lookup));
-      CK(commit_cols_out(ctx, srs, small_basis, ws->la_l.fr(), 2 * cfg.n_lookup, ws, la_commit));  // la | ls contiguous
-      ls_commit.assign(la_commit.begin() + cfg.n_lookup, la_commit.end());
-      la_commit.resize(cfg.n_lookup);
+      std::vector<AffinePoint> pts;
+      CK(commit_cols_out(ctx, srs, small_basis(), ws->la_l.fr(), 2 * cfg.n_lookup, ws, pts));  // la | ls contiguous
+      split_permuted(pts, 0, permuted);
     }
-    std::vector<AffinePoint> both(2 * (size_t)cfg.n_lookup);
-    for (unsigned i = 0; i < cfg.n_lookup; ++i) both[2 * i] = la_commit[i], both[2 * i + 1] = ls_commit[i];
-    tr.write_points(both);
+    tr.write_points(permuted);
+    return ZKFHE_OK;
   }
-  trace.mark("lookup permute + commit");
-  const U256 beta_c = tr.squeeze(), gamma_c = tr.squeeze();
-  const Fr beta = mont(beta_c), gamma = mont(gamma_c);
-  GateHold gate;
-  if (!srs->sharded()) gate.enter();   // a sharded proof's collectives must not wait for another rank's admission order
-  // ------------------------------------------------------------ permutation grand products
-  {
-    if (inst_via_ring) {
-      CK(flush_staged(ctx, ws));   // nothing to launch when an earlier round's flush took the values along and stored the column
-    } else {
-      if (instances.size() < ws->inst_count)
-        ZK_HIP(ctx, zk_memset_async(ctx, ws->inst_l.fr() + instances.size(), 0, (ws->inst_count - instances.size()) * 32, ctx->stream));
-      CK(upload_canon(ctx, ws->inst_l.fr(), instances.data(), instances.size()));
-      ws->inst_count = instances.size();
-    }
+  // ------------------------------------------------------------ permutation and lookup grand products
+  zkp::PermArgs perm_args() const {
+    zkp::PermArgs pa;
+    pa.adv = ws->adv_l.fr();
+    pa.constcol = pk->fixed_l.fr() + (size_t)cfg.fix_const() * n;
+    pa.inst = ws->inst_l.fr();
+    pa.sigma = pk->sigma_l.fr();
+    pa.wpow = dom->fwd;
+    pa.beta_delta = beta_delta_dev;
+    pa.beta = beta;
+    pa.gamma = gamma;
+    pa.n_advice = cfg.n_advice();
+    pa.n_perm = cfg.n_perm();
+    pa.chunk = cfg.chunk();
+    pa.n_chunks = cfg.n_chunks();
+    pa.n = n;
+    return pa;
   }
-  U256 dcan;
-  memcpy(dcan.l, DELTA_CANON, 32);
-  Fr *beta_delta_dev = (Fr *)ws->small.p;  // [n_perm]
-  zkp::k_powers<<<1, 256, 0, ctx->stream>>>(beta, mont(dcan), beta_delta_dev, cfg.n_perm());
-  ZK_LAUNCH_CHECK(ctx);
-  zkp::PermArgs pa;
-  pa.adv = ws->adv_l.fr();
-  pa.constcol = pk->fixed_l.fr() + (size_t)cfg.fix_const() * n;
-  pa.inst = ws->inst_l.fr();
-  pa.sigma = pk->sigma_l.fr();
-  pa.wpow = dom->fwd;
-  pa.beta_delta = beta_delta_dev;
-  pa.beta = beta;
-  pa.gamma = gamma;
-  pa.n_advice = cfg.n_advice();
-  pa.n_perm = cfg.n_perm();
-  pa.chunk = cfg.chunk();
-  pa.n_chunks = cfg.n_chunks();
-  pa.n = n;
-  const size_t nch = cfg.n_chunks();
-  zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(pa, ws->num.fr(), ws->den.fr());
-  ZK_LAUNCH_CHECK(ctx);
-  CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nch * n));   // num <- num / den: the ratios, in one kernel
-  Fr *totals_dev = (Fr *)ws->small.p + 4096;
   // running products per column; long columns in segments (prover_kernels.hip.hpp), the segment products in the dead `den` buffer
   // blind: the blinding rows u + 1 .. n - 1 of the product columns (drawn per column, in order)
-  const size_t nb_z = n - u - 1;
-  auto prefix_products = [&](const Fr *ratio, Fr *z, size_t n_cols, const zkp::RngRows &blind) -> int {
+  int prefix_products(const Fr *ratio, Fr *z, size_t n_cols, const zkp::RngRows &blind, Fr *totals_dev) {
+    const size_t nb_z = nbl - 1;
     if (n <= 65536) {   // measured at k = 16 (two segments): no gain over one workgroup per column; k = 19: 6.5 -> 1 ms per proof
       zkp::k_prefix_product<<<(unsigned)n_cols + zkp::rng_tail_grid(blind, n_cols * nb_z, 1024), 1024, 0, ctx->stream>>>(ratio, z, totals_dev, n, (unsigned)u, (unsigned)n_cols, blind);
       ZK_LAUNCH_CHECK(ctx);
@@ -923,140 +927,89 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     zkp::k_prefix_seg_apply<<<dim3(segs, (unsigned)n_cols), 1024, 0, ctx->stream>>>(ratio, seg, z, n, (unsigned)u, seg_len);
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
-  };
-  CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch, blind_rows(ctr_pz, nb_z)));
-  int *const closes = ws->out_flags();   // pinned: [0] permutation, [1] lookups -- read after the commitment of the products below
-  closes[0] = closes[1] = 1;
-  {
+  }
+  int grand_products() {
+    if (inst_via_ring) {
+      CK(flush_staged(ctx, ws));   // nothing to launch when an earlier round's flush took the values along and stored the column
+    } else {
+      if (instances.size() < ws->inst_count)
+        ZK_HIP(ctx, zk_memset_async(ctx, ws->inst_l.fr() + instances.size(), 0, (ws->inst_count - instances.size()) * 32, ctx->stream));
+      CK(upload_canon(ctx, ws->inst_l.fr(), instances.data(), instances.size()));
+      ws->inst_count = instances.size();
+    }
+    U256 dcan;
+    memcpy(dcan.l, DELTA_CANON, 32);
+    beta_delta_dev = (Fr *)ws->small.p;
+    zkp::k_powers<<<1, 256, 0, ctx->stream>>>(beta, mont(dcan), beta_delta_dev, cfg.n_perm());
+    ZK_LAUNCH_CHECK(ctx);
+    const size_t nch = cfg.n_chunks(), nb_z = nbl - 1;
+    zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(perm_args(), ws->num.fr(), ws->den.fr());
+    ZK_LAUNCH_CHECK(ctx);
+    CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nch * n));   // num <- num / den: the ratios, in one kernel
+    Fr *totals_dev = (Fr *)ws->small.p + 4096;
+    CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch, blind_rows(ctr_pz, nb_z), totals_dev));
+    int *const closes = ws->out_flags();   // pinned: [0] permutation, [1] lookups -- read after the commitment of the products below
+    closes[0] = closes[1] = 1;
     // chunk j starts where chunk j - 1 ended: the carries are the running product of the chunk totals, formed on the device
     zkp::k_chunk_carry<<<1, 1024, 0, ctx->stream>>>(totals_dev, (unsigned)nch, 0, closes);
     ZK_LAUNCH_CHECK(ctx);
     zkp::k_scale_rows<<<grid_for(ctx, nch * (u + 1)), 256, 0, ctx->stream>>>(ws->pz_l.fr(), totals_dev, n, (unsigned)(u + 1), (unsigned)nch);
     ZK_LAUNCH_CHECK(ctx);
-  }
-  // ------------------------------------------------------------ lookup grand products
-  if (cfg.n_lookup) {
-    const size_t nl = cfg.n_lookup;
-    zkp::k_lookup_num_den<<<grid_for(ctx, nl * n), 256, 0, ctx->stream>>>(ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n,
-                                                                          pk->fixed_l.fr() + (size_t)cfg.fix_table() * n, ws->la_l.fr(), ws->ls_l.fr(),
-                                                                          beta, gamma, (unsigned)nl, n, ws->num.fr(), ws->den.fr());
-    ZK_LAUNCH_CHECK(ctx);
-    CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nl * n));
-    CK(prefix_products(ws->num.fr(), ws->lz_l.fr(), nl, blind_rows(ctr_lz, nb_z)));
-    zkp::k_chunk_carry<<<1, 1024, 0, ctx->stream>>>(totals_dev, (unsigned)nl, 1, closes + 1);
-    ZK_LAUNCH_CHECK(ctx);
-  }
-  std::vector<AffinePoint> pz_commit, lz_commit;
-  CK(commit_cols_out(ctx, srs, srs->g_lagrange, ws->pz_l.fr(), nch + cfg.n_lookup, ws, pz_commit));  // pz | lz contiguous
-  if (!closes[0]) return zk_fail_msg(ctx, ZKFHE_EINVAL, "permutation argument does not close: a copy constraint is violated");
-  if (!closes[1]) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup argument does not close");
-  tr.write_points(pz_commit);   // permutation products, then lookup products
-  lz_commit.assign(pz_commit.begin() + nch, pz_commit.end());
-  pz_commit.resize(nch);
-  // ------------------------------------------------------------ vanishing: random polynomial (coefficient form)
-  Fr *rand_c = ws->misc.fr() + 8 * n, *rand_l = ws->misc.fr() + 9 * n, *H_c = ws->misc.fr() + 10 * n, *H_l = ws->misc.fr() + 11 * n;
-  // committed at the start of the proof on the auxiliary stream ("random polynomial, early"): the last n draws of the stream
-  if (early_rand) {
-    ZK_HIP(ctx, hipEventSynchronize(ws->ev_rand));
-    ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ws->ev_rand, 0));   // later reads of rand_c on the main stream
-    AffinePoint rp;
-    points_canon(srs, ws->host_rand_pt, 1, &rp);
-    tr.write_point(rp);
-  } else {
-    CK(rng_fill(ctx->stream, ctr_rand, 0, rand_c, n, n, 1));
-    std::vector<AffinePoint> rand_commit;
-    CK(commit_cols_out(ctx, srs, srs->g, rand_c, 1, ws, rand_commit));
-    tr.write_point(rand_commit[0]);
-  }
-  const Fr y = mont(tr.squeeze());
-  const double t_commit = now_ms();
-  trace.mark("grand products + commits");
-  // ------------------------------------------------------------ quotient
-  // The quotient has degree < 3n, so three cosets determine it (one quarter less extension and evaluation work).  The
-  // fourth coset is only needed for the degree check below (a violated gate shows up as a non-zero top quarter):
-  // a key built with ZKFHE_CHECK_QUOTIENT=1 in the environment keeps it (pk->ext_rows).
-  const int q_rows = pk->ext_rows;
-  // (Extending the challenge-independent columns -- 264 of 402 -- right after the early commitment, on the main or on the
-  // auxiliary stream, was measured and dropped: 165-172 proofs/s on a wave of 20 against 172-177 without, 185-192 in steady
-  // state against 192-203; the smaller NTT batches and the extra launches cost more than the idle time they fill.)
-  // One proof over several GPUs (srs->sharded()): besides the commitments (point ranges, comm.hip) the extension to the coset
-  // domain and the quotient are sharded BY COLUMN.  Rank r owns the permutation chunks [nch r / W, nch (r+1) / W), hence the
-  // advice columns of those chunks, their gates / RLC gates / lookups and the chunks' permutation terms; it extends only those
-  // columns (plus the grand product of the chunk before its first one, which the chaining term reads), evaluates only the
-  // expression groups that belong to them, and the W partial quotients (rows * n values each) are all-gathered and summed on
-  // every rank.  With W = 1 everything is owned: the same code.
-  const unsigned W_sh = srs->sharded() ? (unsigned)zkfhe_comm_world(srs->comm) : 1u, r_sh = srs->sharded() ? (unsigned)zkfhe_comm_rank(srs->comm) : 0u;
-  const size_t c_lo = nch * r_sh / W_sh, c_hi = nch * (r_sh + 1) / W_sh;
-  auto owns_chunk = [&](size_t j) { return j >= c_lo && j < c_hi; };
-  auto owns_col = [&](size_t perm_col) { return owns_chunk(perm_col / cfg.chunk()); };
-  if (W_sh == 1) {
-    CK(extend_cols(ctx, pk, ws, ws->all_l.fr(), ws->n_all, ws->all_ext.fr()));
-  } else {
-    const size_t ecol = n * (size_t)q_rows;
-    auto ext_range = [&](const View &l, const View &e, size_t lo, size_t hi) -> int {
-      if (hi <= lo) return ZKFHE_OK;
-      return extend_cols(ctx, pk, ws, l.fr() + lo * n, hi - lo, e.fr() + lo * ecol);
-    };
-    const size_t a_lo = std::min<size_t>(c_lo * cfg.chunk(), cfg.n_advice()), a_hi = std::min<size_t>(c_hi * cfg.chunk(), cfg.n_advice());
-    CK(ext_range(ws->adv_l, ws->adv_ext, a_lo, a_hi));
-    const size_t l_lo = a_lo > cfg.adv_lookup0() ? std::min<size_t>(a_lo - cfg.adv_lookup0(), cfg.n_lookup) : 0;
-    const size_t l_hi = a_hi > cfg.adv_lookup0() ? std::min<size_t>(a_hi - cfg.adv_lookup0(), cfg.n_lookup) : 0;
-    CK(ext_range(ws->la_l, ws->la_ext, l_lo, l_hi));
-    CK(ext_range(ws->ls_l, ws->ls_ext, l_lo, l_hi));
-    CK(ext_range(ws->lz_l, ws->lz_ext, l_lo, l_hi));
-    CK(ext_range(ws->pz_l, ws->pz_ext, c_lo ? c_lo - 1 : 0, c_hi));
-    if (owns_col(cfg.perm_inst())) CK(ext_range(ws->inst_l, ws->inst_ext, 0, 1));
-  }
-  {
-    // expression groups, in the folding order of oracle/halo2_ref.py expressions_at: the expressions are numbered globally (the
-    // power of y of a group is fixed by the number of its last expression); a group is a run of owned, consecutive units of one
-    // kind, cut at the kernel's group sizes
-    std::vector<zkp::QGroup> groups;
-    std::vector<size_t> last_e;  // global index of the last expression of each group
-    size_t e = 0;
-    auto run = [&](int type, size_t first, size_t count, size_t max_group, size_t expr_per_unit, const std::function<bool(size_t)> &owned) {
-      size_t j = first;
-      while (j < first + count) {
-        if (!owned(j)) {
-          e += expr_per_unit;
-          ++j;
-          continue;
-        }
-        size_t len = 0;
-        while (j + len < first + count && len < max_group && owned(j + len)) ++len;
-        groups.push_back(zkp::QGroup{type, (int)j, (int)len, 0});
-        e += len * expr_per_unit;
-        last_e.push_back(e - 1);
-        j += len;
-      }
-    };
-    run(zkp::QG_GATE, 0, cfg.n_gate(), 8, 1, [&](size_t j) { return owns_col(j); });
-    run(zkp::QG_RLC, 0, cfg.n_rlc, cfg.n_rlc ? cfg.n_rlc : 1, 1, [&](size_t j) { return owns_col(cfg.adv_rlc0() + j); });
-    run(zkp::QG_PERM_FIRST, 0, 1, 1, 1, [&](size_t) { return owns_chunk(0); });
-    run(zkp::QG_PERM_LAST, 0, 1, 1, 1, [&](size_t) { return owns_chunk(nch - 1); });
-    run(zkp::QG_PERM_C, 1, nch - 1, 32, 1, [&](size_t j) { return owns_chunk(j); });
-    run(zkp::QG_PERM_D, 0, nch, 4, 1, [&](size_t j) { return owns_chunk(j); });
-    run(zkp::QG_LOOKUP, 0, cfg.n_lookup, 3, 5, [&](size_t i) { return owns_col(cfg.adv_lookup0() + i); });
-    const size_t E = e;
-    // (The same expressions cut by COLUMN BLOCK instead of by kind -- k_quotient_blocks, round 5 -- read a quarter less and were 29 %
-    // slower: tools/exp/patches/quotient_blocks.patch, profiles/r5_probes.md section 2.)
-    const size_t G = groups.size();
-    if (G > 96 || G * n * (size_t)q_rows * 32 > ws->partials.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many quotient groups for the workspace");
-    std::vector<Fr> ypow(G);
-    for (size_t g = 0; g < G; ++g) ypow[g] = zk::zk_fr_to_29(fr_pow(y, E - 1 - last_e[g]));   // 2^261 form: constant operands of k_quotient_combine
-    if (groups.empty()) groups.push_back(zkp::QGroup{});     // a rank that owns nothing still stages a (unread) entry
-    if (ypow.empty()) ypow.push_back(Fr::zero());
-    STAGE(groups_dev, zkp::QGroup, ws, groups.data(), groups.size() * sizeof(zkp::QGroup));
-    STAGE(ypow_dev, Fr, ws, ypow.data(), ypow.size() * 32);
-    const Fr wext = zk_fr_root_of_unity((int)k + 2);
-    const Fr gn = fr_pow(mont_u64(COSET_G), n), i4 = fr_pow(wext, n);
-    Fr zinv[4], cur = gn;
-    for (int t = 0; t < 4; ++t) {
-      zinv[t] = zk::zk_fr_to_29(fr_inv(cur - Fr::one()));
-      cur = cur * i4;
+    // ---------------------------------------------------------- lookup grand products
+    if (cfg.n_lookup) {
+      const size_t nl = cfg.n_lookup;
+      zkp::k_lookup_num_den<<<grid_for(ctx, nl * n), 256, 0, ctx->stream>>>(ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n,
+                                                                            pk->fixed_l.fr() + (size_t)cfg.fix_table() * n, ws->la_l.fr(), ws->ls_l.fr(),
+                                                                            beta, gamma, (unsigned)nl, n, ws->num.fr(), ws->den.fr());
+      ZK_LAUNCH_CHECK(ctx);
+      CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nl * n));
+      CK(prefix_products(ws->num.fr(), ws->lz_l.fr(), nl, blind_rows(ctr_lz, nb_z), totals_dev));
+      zkp::k_chunk_carry<<<1, 1024, 0, ctx->stream>>>(totals_dev, (unsigned)nl, 1, closes + 1);
+      ZK_LAUNCH_CHECK(ctx);
     }
-    STAGE(zinv_dev, Fr, ws, zinv, 4 * 32);
-    CK(flush_staged(ctx, ws));
+    std::vector<AffinePoint> pz_commit;
+    CK(commit_cols_out(ctx, srs, srs->g_lagrange, ws->pz_l.fr(), nch + cfg.n_lookup, ws, pz_commit));  // pz | lz contiguous
+    if (!closes[0]) return zk_fail_msg(ctx, ZKFHE_EINVAL, "permutation argument does not close: a copy constraint is violated");
+    if (!closes[1]) return zk_fail_msg(ctx, ZKFHE_EINVAL, "lookup argument does not close");
+    tr.write_points(pz_commit);   // permutation products, then lookup products
+    return ZKFHE_OK;
+  }
+  // ------------------------------------------------------------ vanishing: random polynomial (coefficient form)
+  int random_poly() {
+    // committed at the start of the proof on the auxiliary stream ("random polynomial, early"): the last n draws of the stream
+    Fr *rand_c = ws->misc.fr() + 8 * n;
+    if (early_rand) {
+      ZK_HIP(ctx, hipEventSynchronize(ws->ev_rand));
+      ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ws->ev_rand, 0));   // later reads of rand_c on the main stream
+      AffinePoint rp;
+      points_canon(srs, ws->host_rand_pt, 1, &rp);
+      tr.write_point(rp);
+    } else {
+      CK(rng_fill(ctx->stream, ctr_rand, 0, rand_c, n, n, 1));
+      std::vector<AffinePoint> rand_commit;
+      CK(commit_cols_out(ctx, srs, srs->g, rand_c, 1, ws, rand_commit));
+      tr.write_point(rand_commit[0]);
+    }
+    return ZKFHE_OK;
+  }
+  // ------------------------------------------------------------ quotient
+  // the buffer of the gathered shares of a sharded proof (quotient rows, SHPLONK sets), grown to `bytes`
+  int grow_qgather(size_t bytes) {
+    if (ws->qgather.bytes >= bytes) return ZKFHE_OK;
+    CK(zkfhe_sync(ctx));
+    ws->qgather.release();
+    return ws->qgather.alloc(ctx, bytes);
+  }
+  // once the gathers are queued: dst[j] = the sum of the W_sh shares of slot j of ws->qgather ([slot][rank][n]), j < slots
+  int sum_shares(size_t slots, Fr *dst) {
+    CK(zkfhe_comm_join(ctx, srs->comm, 0));
+    for (size_t j = 0; j < slots; ++j) {
+      zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->qgather.fr() + j * (size_t)W_sh * n, W_sh, n, dst + j * n);
+      ZK_LAUNCH_CHECK(ctx);
+    }
+    return ZKFHE_OK;
+  }
+  zkp::QArgs quotient_args(const zkp::QGroup *groups_dev, int q_rows) const {
     zkp::QArgs qa;
     qa.adv = ws->adv_ext.fr();
     qa.fix = pk->fixed_ext.fr();
@@ -1090,42 +1043,117 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     qa.chunk = cfg.chunk();
     qa.n_chunks = cfg.n_chunks();
     qa.rows = (unsigned)q_rows;
+    return qa;
+  }
+  // the G expression groups at the points [pt0, pt0 + count) of the extended domain, folded with the powers of y into h_ext
+  int launch_quotient(zkp::QArgs &qa, size_t pt0, size_t count, size_t G, const Fr *ypow_dev, const Fr *zinv_dev) {
+    qa.pt0 = pt0;
+    qa.pt_count = count;
+    const unsigned blocks = (unsigned)((count + 255) / 256);
+    if (G) {   // a rank of a sharded proof may own no group
+      zkp::k_quotient_partials<<<dim3(blocks, (unsigned)G), 256, 0, ctx->stream>>>(qa);
+      ZK_LAUNCH_CHECK(ctx);
+    }
+    zkp::k_quotient_combine<<<blocks, 256, 0, ctx->stream>>>(ws->partials.fr(), ypow_dev, (unsigned)G, zinv_dev, k, qa.rows, pt0, count, ws->h_ext.fr());
+    ZK_LAUNCH_CHECK(ctx);
+    return ZKFHE_OK;
+  }
+  // The quotient has degree < 3n, so three cosets determine it (one quarter less extension and evaluation work).  The
+  // fourth coset is only needed for the degree check below (a violated gate shows up as a non-zero top quarter):
+  // a key built with ZKFHE_CHECK_QUOTIENT=1 in the environment keeps it (pk->ext_rows).
+  // (Extending the challenge-independent columns -- 264 of 402 -- right after the early commitment, on the main or on the
+  // auxiliary stream, was measured and dropped: 165-172 proofs/s on a wave of 20 against 172-177 without, 185-192 in steady
+  // state against 192-203; the smaller NTT batches and the extra launches cost more than the idle time they fill.)
+  // One proof over several GPUs (srs->sharded()): besides the commitments (point ranges, comm.hip) the extension to the coset
+  // domain and the quotient are sharded BY COLUMN.  Rank r owns the permutation chunks [nch r / W, nch (r+1) / W), hence the
+  // advice columns of those chunks, their gates / RLC gates / lookups and the chunks' permutation terms; it extends only those
+  // columns (plus the grand product of the chunk before its first one, which the chaining term reads), evaluates only the
+  // expression groups that belong to them, and the W partial quotients (rows * n values each) are all-gathered and summed on
+  // every rank.  With W = 1 everything is owned: the same code.
+  int quotient(std::vector<AffinePoint> &h_commit) {
+    const int q_rows = pk->ext_rows;
+    const Fr wext = zk_fr_root_of_unity((int)k + 2);
+    if (W_sh == 1) {
+      CK(extend_cols(ctx, pk, ws, ws->all_l.fr(), ws->n_all, ws->all_ext.fr()));
+    } else {
+      const size_t ecol = n * (size_t)q_rows;
+      auto ext_range = [&](const View &l, const View &e, size_t lo, size_t hi) -> int {
+        if (hi <= lo) return ZKFHE_OK;
+        return extend_cols(ctx, pk, ws, l.fr() + lo * n, hi - lo, e.fr() + lo * ecol);
+      };
+      const size_t a_lo = std::min<size_t>(c_lo * cfg.chunk(), cfg.n_advice()), a_hi = std::min<size_t>(c_hi * cfg.chunk(), cfg.n_advice());
+      CK(ext_range(ws->adv_l, ws->adv_ext, a_lo, a_hi));
+      const size_t l_lo = a_lo > cfg.adv_lookup0() ? std::min<size_t>(a_lo - cfg.adv_lookup0(), cfg.n_lookup) : 0;
+      const size_t l_hi = a_hi > cfg.adv_lookup0() ? std::min<size_t>(a_hi - cfg.adv_lookup0(), cfg.n_lookup) : 0;
+      CK(ext_range(ws->la_l, ws->la_ext, l_lo, l_hi));
+      CK(ext_range(ws->ls_l, ws->ls_ext, l_lo, l_hi));
+      CK(ext_range(ws->lz_l, ws->lz_ext, l_lo, l_hi));
+      CK(ext_range(ws->pz_l, ws->pz_ext, c_lo ? c_lo - 1 : 0, c_hi));
+      if (owns_col(cfg.perm_inst())) CK(ext_range(ws->inst_l, ws->inst_ext, 0, 1));
+    }
+    // expression groups, in the folding order of oracle/halo2_ref.py expressions_at: the expressions are numbered globally (the
+    // power of y of a group is fixed by the number of its last expression); a group is a run of owned, consecutive units of one
+    // kind, cut at the kernel's group sizes
+    const size_t nch = cfg.n_chunks();
+    std::vector<zkp::QGroup> groups;
+    std::vector<size_t> last_e;  // global index of the last expression of each group
+    size_t e = 0;
+    auto run = [&](int type, size_t first, size_t count, size_t max_group, size_t expr_per_unit, const std::function<bool(size_t)> &owned) {
+      size_t j = first;
+      while (j < first + count) {
+        if (!owned(j)) {
+          e += expr_per_unit;
+          ++j;
+          continue;
+        }
+        size_t len = 0;
+        while (j + len < first + count && len < max_group && owned(j + len)) ++len;
+        groups.push_back(zkp::QGroup{type, (int)j, (int)len, 0});
+        e += len * expr_per_unit;
+        last_e.push_back(e - 1);
+        j += len;
+      }
+    };
+    run(zkp::QG_GATE, 0, cfg.n_gate(), 8, 1, [&](size_t j) { return owns_col(j); });
+    run(zkp::QG_RLC, 0, cfg.n_rlc, cfg.n_rlc ? cfg.n_rlc : 1, 1, [&](size_t j) { return owns_col(cfg.adv_rlc0() + j); });
+    run(zkp::QG_PERM_FIRST, 0, 1, 1, 1, [&](size_t) { return owns_chunk(0); });
+    run(zkp::QG_PERM_LAST, 0, 1, 1, 1, [&](size_t) { return owns_chunk(nch - 1); });
+    run(zkp::QG_PERM_C, 1, nch - 1, 32, 1, [&](size_t j) { return owns_chunk(j); });
+    run(zkp::QG_PERM_D, 0, nch, 4, 1, [&](size_t j) { return owns_chunk(j); });
+    run(zkp::QG_LOOKUP, 0, cfg.n_lookup, 3, 5, [&](size_t i) { return owns_col(cfg.adv_lookup0() + i); });
+    // (The same expressions cut by COLUMN BLOCK instead of by kind -- k_quotient_blocks, round 5 -- read a quarter less and were 29 %
+    // slower: tools/exp/patches/quotient_blocks.patch, profiles/r5_probes.md section 2.)
+    const size_t E = e, G = groups.size();
+    if (G > 96 || G * n * (size_t)q_rows * 32 > ws->partials.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many quotient groups for the workspace");
+    std::vector<Fr> ypow(G);
+    for (size_t g = 0; g < G; ++g) ypow[g] = zk::zk_fr_to_29(fr_pow(y, E - 1 - last_e[g]));   // 2^261 form: constant operands of k_quotient_combine
+    if (groups.empty()) groups.push_back(zkp::QGroup{});     // a rank that owns nothing still stages a (unread) entry
+    if (ypow.empty()) ypow.push_back(Fr::zero());
+    STAGE(groups_dev, zkp::QGroup, ws, groups.data(), groups.size() * sizeof(zkp::QGroup));
+    STAGE(ypow_dev, Fr, ws, ypow.data(), ypow.size() * 32);
+    const Fr gn = fr_pow(mont_u64(COSET_G), n), i4 = fr_pow(wext, n);
+    Fr zinv[4], cur = gn;
+    for (int t = 0; t < 4; ++t) {
+      zinv[t] = zk::zk_fr_to_29(fr_inv(cur - Fr::one()));
+      cur = cur * i4;
+    }
+    STAGE(zinv_dev, Fr, ws, zinv, 4 * 32);
+    CK(flush_staged(ctx, ws));
+    zkp::QArgs qa = quotient_args(groups_dev, q_rows);
     const size_t npts = n * (size_t)q_rows;
     if (W_sh == 1) {
-      qa.pt0 = 0;
-      qa.pt_count = npts;
-      dim3 grid((unsigned)((npts + 255) / 256), (unsigned)G);
-      zkp::k_quotient_partials<<<grid, 256, 0, ctx->stream>>>(qa);
-      ZK_LAUNCH_CHECK(ctx);
-      zkp::k_quotient_combine<<<(unsigned)((npts + 255) / 256), 256, 0, ctx->stream>>>(ws->partials.fr(), ypow_dev, (unsigned)G, zinv_dev, k, (unsigned)q_rows, 0, npts, ws->h_ext.fr());
-      ZK_LAUNCH_CHECK(ctx);
+      CK(launch_quotient(qa, 0, npts, G, ypow_dev, zinv_dev));
     } else {
       // h_ext receives this rank's share of the quotient (the sum over ITS expression groups); the W shares are gathered and added up
       // -- field addition is not an RCCL reduction either.  One coset row at a time: the share of row k1 (n values: 16 MB at k = 19)
       // goes onto the communicator's stream as soon as it is formed and travels over xGMI while the groups of row k1 + 1 are
       // evaluated; only the last row's gather is exposed.  (The callback transport of the tests completes each gather in place.)
-      if (ws->qgather.bytes < (size_t)W_sh * npts * 32) {
-        CK(zkfhe_sync(ctx));
-        ws->qgather.release();
-        CK(ws->qgather.alloc(ctx, (size_t)W_sh * npts * 32));
-      }
+      CK(grow_qgather((size_t)W_sh * npts * 32));
       for (int k1 = 0; k1 < q_rows; ++k1) {
-        qa.pt0 = (size_t)k1 * n;
-        qa.pt_count = n;
-        dim3 grid((unsigned)((n + 255) / 256), (unsigned)G);
-        if (G) {
-          zkp::k_quotient_partials<<<grid, 256, 0, ctx->stream>>>(qa);
-          ZK_LAUNCH_CHECK(ctx);
-        }
-        zkp::k_quotient_combine<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(ws->partials.fr(), ypow_dev, (unsigned)G, zinv_dev, k, (unsigned)q_rows, qa.pt0, n, ws->h_ext.fr());
-        ZK_LAUNCH_CHECK(ctx);
-        CK(zkfhe_comm_all_gather_async(ctx, srs->comm, ws->h_ext.fr() + qa.pt0, ws->qgather.fr() + (size_t)k1 * W_sh * n, n * 32));
+        CK(launch_quotient(qa, (size_t)k1 * n, n, G, ypow_dev, zinv_dev));
+        CK(zkfhe_comm_all_gather_async(ctx, srs->comm, ws->h_ext.fr() + (size_t)k1 * n, ws->qgather.fr() + (size_t)k1 * W_sh * n, n * 32));
       }
-      CK(zkfhe_comm_join(ctx, srs->comm, 0));
-      for (int k1 = 0; k1 < q_rows; ++k1) {
-        zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->qgather.fr() + (size_t)k1 * W_sh * n, W_sh, n, ws->h_ext.fr() + (size_t)k1 * n);
-        ZK_LAUNCH_CHECK(ctx);
-      }
+      CK(sum_shares((size_t)q_rows, ws->h_ext.fr()));
     }
     const Fr g = mont_u64(COSET_G);
     if (q_rows == 4) {
@@ -1135,47 +1163,44 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       Fr *rows3 = ws->partials.fr();            // the partials are dead after the combine; 3n values
       const Fr *pw = pk->ext3_pw.fr();           // (g w_ext^t)^-i, resident in the key
       CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)ws->h_ext.p, (zkfhe_fr *)rows3, 3, (int)k, 1));
-      Fr gk[3], c[3];
-      gk[0] = g;
-      gk[1] = g * wext;
-      gk[2] = gk[1] * wext;
-      zkp::Mat3 vinv;
-      {
-        for (int t = 0; t < 3; ++t) c[t] = fr_pow(gk[t], n);
-        // inverse of V[k1][m] = c_k1^m by Lagrange basis polynomials: column k1 of V^-1 holds the coefficients of
-        // L_k1(X) = prod_{j != k1} (X - c_j) / (c_k1 - c_j)
-        for (int k1 = 0; k1 < 3; ++k1) {
-          const Fr &a = c[(k1 + 1) % 3], &b = c[(k1 + 2) % 3];
-          const Fr den = fr_inv((c[k1] - a) * (c[k1] - b));
-          vinv.v[0 * 3 + k1] = a * b * den;              // X^0
-          vinv.v[1 * 3 + k1] = (Fr::zero() - (a + b)) * den;  // X^1
-          vinv.v[2 * 3 + k1] = den;                      // X^2
-        }
-      }
-      zkp::k_ext3_combine<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(rows3, pw, vinv, n, ws->h_c.fr());
+      const Fr c[3] = {fr_pow(g, n), fr_pow(g * wext, n), fr_pow(g * wext * wext, n)};   // (g w_ext^t)^n
+      zkp::k_ext3_combine<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(rows3, pw, vandermonde3_inverse(c), n, ws->h_c.fr());
       ZK_LAUNCH_CHECK(ctx);
     }
+    CK(commit_cols_out(ctx, srs, srs->g, ws->h_c.fr(), 3, ws, h_commit));
+    if (q_rows == 4) {
+      // the quotient must have degree < 3n: a non-zero top quarter means a violated constraint
+      std::vector<U256> top(8);
+      CK(zkfhe_download(ctx, top.data(), ws->h_c.fr() + 3 * n, 8 * 32));
+      for (const auto &v : top)
+        if (!v.is_zero()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "quotient degree too high: a constraint is violated");
+    }
+    return ZKFHE_OK;
   }
-  std::vector<AffinePoint> h_commit;
-  CK(commit_cols_out(ctx, srs, srs->g, ws->h_c.fr(), 3, ws, h_commit));
-  if (q_rows == 4) {
-    // the quotient must have degree < 3n: a non-zero top quarter means a violated constraint
-    std::vector<U256> top(8);
-    CK(zkfhe_download(ctx, top.data(), ws->h_c.fr() + 3 * n, 8 * 32));
-    for (const auto &v : top)
-      if (!v.is_zero()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "quotient degree too high: a constraint is violated");
-  }
-  gate.leave();
-  for (const auto &p : h_commit) tr.write_point(p);
-  const U256 x_c = tr.squeeze();
-  const Fr x = mont(x_c);
-  const double t_quot = now_ms();
-  trace.mark("quotient");
   // ------------------------------------------------------------ evaluations at x * w^rot (barycentric, Lagrange form)
-  const Fr xn = fr_pow(x, n);
-  // rotation ids: 0,1,2,3 -> w^r ; 4 -> w^u ("last") ; 5 -> w^-1
-  Fr pts_rot[6];
-  {
+  void add_item(const Fr *lagr, std::initializer_list<int> rots) {
+    OpenItem it{{lagr, 0, {0, 0, 0, 0}}};
+    for (int r : rots) it.job.rot[it.job.n_rot++] = r;
+    items.push_back(it);
+  }
+  // dst = sum over m < msz of pw[m] * (column pp[m]), n rows; pw in the 2^261 form.  Long lists in chunks of 48 members (partial
+  // sums in the dead quotient buffer), then one small reduction
+  int lincomb(const Fr *const *pp, const Fr *pw, unsigned msz, Fr *dst) {
+    const unsigned per = 48, chunks = (msz + per - 1) / per;
+    if (chunks > 1 && (size_t)chunks * n * 32 <= ws->partials.bytes) {
+      dim3 lg(grid_for(ctx, n), chunks);
+      zkp::k_lincomb_ptrs_chunked<<<lg, 256, 0, ctx->stream>>>(pp, pw, msz, per, n, ws->partials.fr());
+      ZK_LAUNCH_CHECK(ctx);
+      zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->partials.fr(), chunks, n, dst);
+    } else {
+      zkp::k_lincomb_ptrs<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(pp, pw, msz, n, dst);
+    }
+    ZK_LAUNCH_CHECK(ctx);
+    return ZKFHE_OK;
+  }
+  int evaluations() {
+    Fr *rand_c = ws->misc.fr() + 8 * n, *rand_l = ws->misc.fr() + 9 * n, *H_c = ws->misc.fr() + 10 * n, *H_l = ws->misc.fr() + 11 * n;
+    const Fr xn = fr_pow(x, n);
     const Fr w = dom->omega;
     pts_rot[0] = x;
     pts_rot[1] = x * w;
@@ -1183,72 +1208,49 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     pts_rot[3] = pts_rot[2] * w;
     pts_rot[4] = x * fr_pow(w, u);
     pts_rot[5] = x * dom->omega_inv;
-  }
-  std::vector<OpenItem> items;
-  auto add_item = [&](const Fr *lagr, std::initializer_list<int> rots) {
-    OpenItem it;
-    it.lagr = lagr;
-    it.n_rot = 0;
-    for (int r : rots) it.rot[it.n_rot++] = r;
-    items.push_back(it);
-  };
-  for (unsigned c = 0; c < cfg.n_advice(); ++c) {
-    const Fr *p = ws->adv_l.fr() + (size_t)c * n;
-    if (c < cfg.n_gate()) add_item(p, {0, 1, 2, 3});
-    else if (c < cfg.adv_rlc0()) add_item(p, {0});
-    else add_item(p, {0, 1, 2});
-  }
-  for (unsigned c = 0; c < cfg.n_fixed(); ++c) add_item(pk->fixed_l.fr() + (size_t)c * n, {0});
-  const size_t idx_H = items.size();
-  add_item(H_l, {0});
-  add_item(rand_l, {0});
-  for (unsigned c = 0; c < cfg.n_perm(); ++c) add_item(pk->sigma_l.fr() + (size_t)c * n, {0});
-  for (unsigned j = 0; j < nch; ++j) {
-    if (j + 1 != nch) add_item(ws->pz_l.fr() + (size_t)j * n, {0, 1, 4});
-    else add_item(ws->pz_l.fr() + (size_t)j * n, {0, 1});
-  }
-  for (unsigned i = 0; i < cfg.n_lookup; ++i) {
-    add_item(ws->lz_l.fr() + (size_t)i * n, {0, 1});
-    add_item(ws->la_l.fr() + (size_t)i * n, {0, 5});
-    add_item(ws->ls_l.fr() + (size_t)i * n, {0});
-  }
-  // the evaluation jobs (column, rotations) depend on no challenge: they are staged with the round's first tables
-  std::vector<zkp::EvalJob> jobs(items.size());
-  for (size_t i = 0; i < items.size(); ++i) {
-    jobs[i].col = items[i].lagr;
-    jobs[i].n_rot = items[i].n_rot;
-    for (int r = 0; r < 4; ++r) jobs[i].rot[r] = r < items[i].n_rot ? items[i].rot[r] : 0;
-  }
-  const zkp::EvalJob *jobs_dev = nullptr;
-  Fr *pts_dev = nullptr;
-  {
+    const size_t nch = cfg.n_chunks();
+    for (unsigned c = 0; c < cfg.n_advice(); ++c) {
+      const Fr *p = ws->adv_l.fr() + (size_t)c * n;
+      if (c < cfg.n_gate()) add_item(p, {0, 1, 2, 3});
+      else if (c < cfg.adv_rlc0()) add_item(p, {0});
+      else add_item(p, {0, 1, 2});
+    }
+    for (unsigned c = 0; c < cfg.n_fixed(); ++c) add_item(pk->fixed_l.fr() + (size_t)c * n, {0});
+    idx_H = items.size();
+    add_item(H_l, {0});
+    add_item(rand_l, {0});
+    for (unsigned c = 0; c < cfg.n_perm(); ++c) add_item(pk->sigma_l.fr() + (size_t)c * n, {0});
+    for (unsigned j = 0; j < nch; ++j) {
+      if (j + 1 != nch) add_item(ws->pz_l.fr() + (size_t)j * n, {0, 1, 4});
+      else add_item(ws->pz_l.fr() + (size_t)j * n, {0, 1});
+    }
+    for (unsigned i = 0; i < cfg.n_lookup; ++i) {
+      add_item(ws->lz_l.fr() + (size_t)i * n, {0, 1});
+      add_item(ws->la_l.fr() + (size_t)i * n, {0, 5});
+      add_item(ws->ls_l.fr() + (size_t)i * n, {0});
+    }
+    // the evaluation jobs (column, rotations) depend on no challenge: they are staged with the round's first tables
+    std::vector<zkp::EvalJob> jobs(items.size());
+    for (size_t i = 0; i < items.size(); ++i) jobs[i] = items[i].job;
     // H(X) = h0 + x^n h1 + x^2n h2, and the random polynomial, in Lagrange form
     const Fr sc[3] = {zk::zk_fr_to_29(Fr::one()), zk::zk_fr_to_29(xn), zk::zk_fr_to_29(xn * xn)};   // k_lincomb_ptrs takes its scalars in the 2^261 form
     const Fr *ptrs[3] = {ws->h_c.fr(), ws->h_c.fr() + n, ws->h_c.fr() + 2 * n};
     STAGE(ptrs_dev, const Fr *, ws, ptrs, sizeof(ptrs));
     STAGE(sc_dev, Fr, ws, sc, sizeof(sc));
-    STAGE(pts_stage, Fr, ws, pts_rot, sizeof(pts_rot));   // the six evaluation points go up with the same flush
-    pts_dev = pts_stage;
-    STAGE(jobs_stage, zkp::EvalJob, ws, jobs.data(), jobs.size() * sizeof(zkp::EvalJob));   // ... and so does the evaluation job list
-    jobs_dev = jobs_stage;
+    STAGE(pts_dev, Fr, ws, pts_rot, sizeof(pts_rot));   // the six evaluation points go up with the same flush
+    STAGE(jobs_dev, zkp::EvalJob, ws, jobs.data(), jobs.size() * sizeof(zkp::EvalJob));   // ... and so does the evaluation job list
     CK(flush_staged(ctx, ws));
-    zkp::k_lincomb_ptrs<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ptrs_dev, sc_dev, 3, n, H_c);
-    ZK_LAUNCH_CHECK(ctx);
+    CK(lincomb(ptrs_dev, sc_dev, 3, H_c));
     CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)H_c, (zkfhe_fr *)H_l, 1, (int)k, 0));
     if (!early_rand) CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)rand_c, (zkfhe_fr *)rand_l, 1, (int)k, 0));   // early: transformed on the auxiliary stream at the start
-  }
-  Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
-  {
+    Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
     zkp::k_bary_den<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, pts_dev, 6, n, bw);
     ZK_LAUNCH_CHECK(ctx);
     CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)bw, 6 * n));
     const Fr c = zk::zk_fr_to_29((xn - Fr::one()) * dom->n_inv);   // the weights in the 2^261 form: the constant operand of k_eval_jobs' nine-limb products
     zkp::k_bary_weights<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, c, 6 * n, n, bw);
     ZK_LAUNCH_CHECK(ctx);
-  }
-  {
     DevBuf &od = ws->evout;
-    struct { const void *p; } jd{jobs_dev};
     // One proof over several GPUs, long rows (k >= 14): the evaluation jobs are sharded by index -- rank r takes jobs
     // [per r, per (r + 1)) with per = ceil(J / W), every Lagrange column being present on every rank -- and the scalars are
     // all-gathered (per * 128 bytes per rank).  Short rows are not worth a collective.
@@ -1261,7 +1263,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     // long columns: 16 row slices per job (partial sums in the dead quotient buffer), then one small reduction
     const unsigned slices = (n > 32768 && (size_t)16 * jobs.size() * 4 * 32 <= ws->partials.bytes) ? 16u : 1u;
     if (j_hi > j_lo) {
-      const zkp::EvalJob *jp = (const zkp::EvalJob *)jd.p + j_lo;
+      const zkp::EvalJob *jp = jobs_dev + j_lo;
       const unsigned nj = (unsigned)(j_hi - j_lo);
       if (slices == 1) {
         zkp::k_eval_jobs<<<nj, 256, 0, ctx->stream>>>(jp, bw, n, ev_dst + (shard_open ? 0 : j_lo * 4));
@@ -1280,30 +1282,28 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     trace.mark("evaluations (GPU)");
     const U256 *ev = ws->out_ev();
     for (size_t i = 0; i < items.size(); ++i)
-      for (int r = 0; r < items[i].n_rot; ++r) items[i].ev[r] = ev[i * 4 + r];
+      for (int r = 0; r < items[i].job.n_rot; ++r) items[i].ev[r] = ev[i * 4 + r];
+    return ZKFHE_OK;
   }
-  const OpenLayout layout(cfg);
-  if (items.size() != layout.count || idx_H != layout.H) return zk_fail_msg(ctx, ZKFHE_EINVAL, "opening layout mismatch");
-  {
+  // ------------------------------------------------------------ SHPLONK (halo2 ProverSHPLONK; Lagrange form, commitments are basis independent)
+  int shplonk() {
+    const OpenLayout layout(cfg);
+    if (items.size() != layout.count || idx_H != layout.H) return zk_fail_msg(ctx, ZKFHE_EINVAL, "opening layout mismatch");
     std::vector<U256> evs;
     evs.reserve(items.size() * 2);
     for (size_t i = 0; i < items.size(); ++i) {
       if (i == idx_H) continue;  // implied by the identity, not written
-      for (int r = 0; r < items[i].n_rot; ++r) evs.push_back(items[i].ev[r]);
+      for (int r = 0; r < items[i].job.n_rot; ++r) evs.push_back(items[i].ev[r]);
     }
     tr.write_scalars(evs);
-  }
-  // ------------------------------------------------------------ SHPLONK (halo2 ProverSHPLONK; Lagrange form, commitments are basis independent)
-  const Fr yq = mont(tr.squeeze());
-  trace.mark("transcript: evaluations");
-  std::vector<int> all_rots;
-  const std::vector<OpenSet> sets = intermediate_sets(layout, open_queries(cfg, layout), all_rots);
-  const size_t ns = sets.size();
-  Fr *F = ws->misc.fr() + 12 * n;  // [ns][n]
-  if (ns > 8) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many rotation sets");
-  std::vector<zkp::ShSet> shsets(ns);
-  const zkp::ShSet *sets_dev = nullptr;
-  {
+    const Fr yq = mont(tr.squeeze());
+    trace.mark("transcript: evaluations");
+    std::vector<int> all_rots;
+    const std::vector<OpenSet> sets = intermediate_sets(layout, open_queries(cfg, layout), all_rots);
+    const size_t ns = sets.size();
+    Fr *F = ws->misc.fr() + 12 * n;  // [ns][n]
+    if (ns > 8) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many rotation sets");
+    std::vector<zkp::ShSet> shsets(ns);
     // pointer and scalar tables of every set are staged first and go up with one flush; then the launches
     std::vector<const Fr *const *> set_ptrs(ns);
     std::vector<const Fr *> set_pw(ns);
@@ -1313,9 +1313,10 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       std::vector<Fr> pw(mem.size());
       Fr cur = Fr::one();
       const size_t np = sets[j].rots.size();
-      std::vector<Fr> comb(np, Fr::zero());
+      if (np > 4) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many points in a rotation set");
+      Fr comb[4] = {Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
       for (size_t m = 0; m < mem.size(); ++m) {
-        ptrs[m] = items[mem[m]].lagr;
+        ptrs[m] = items[mem[m]].job.col;
         pw[m] = zk::zk_fr_to_29(cur);   // 2^261 form: the constant operand of k_lincomb_ptrs
         for (size_t t = 0; t < np; ++t) comb[t] = comb[t] + cur * mont(items[mem[m]].ev[layout.eval_slot(mem[m], sets[j].rots[t])]);
         cur = cur * yq;
@@ -1326,91 +1327,48 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       set_pw[j] = sd;
       // r_j: interpolation through (pts, comb), ascending coefficients
       zkp::ShSet &S = shsets[j];
-      for (int t = 0; t < 4; ++t) S.rc[t] = S.pts[t] = Fr::zero();
       S.n_pts = (int)np;
-      for (size_t t = 0; t < np; ++t) S.pts[t] = pts_rot[sets[j].rots[t]];
-      for (size_t i = 0; i < np; ++i) {
-        std::vector<Fr> num(1, Fr::one());
-        Fr den = Fr::one();
-        for (size_t t = 0; t < np; ++t) {
-          if (t == i) continue;
-          std::vector<Fr> nxt(num.size() + 1, Fr::zero());
-          for (size_t q = 0; q < num.size(); ++q) {
-            nxt[q + 1] = nxt[q + 1] + num[q];
-            nxt[q] = nxt[q] - S.pts[t] * num[q];
-          }
-          num = nxt;
-          den = den * (S.pts[i] - S.pts[t]);
-        }
-        const Fr scl = comb[i] * fr_inv(den);
-        for (size_t q = 0; q < num.size(); ++q) S.rc[q] = S.rc[q] + num[q] * scl;
-      }
+      for (size_t t = 0; t < 4; ++t) S.pts[t] = t < np ? pts_rot[sets[j].rots[t]] : Fr::zero();
+      interpolate4(S.pts, comb, np, S.rc);
     }
     // v follows yq with nothing absorbed in between: it is squeezed here, and the sets (r_j, points, v^j) go up with the same flush
-    {
-      const Fr v = mont(tr.squeeze());
-      Fr cur = Fr::one();
-      for (size_t j = 0; j < ns; ++j) {
-        shsets[j].vj = cur;
-        shsets[j].coef = Fr::zero();
-        shsets[j].r_u = Fr::zero();
-        cur = cur * v;
-      }
-      STAGE(sets_stage, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
-      sets_dev = sets_stage;
+    const Fr v = mont(tr.squeeze());
+    Fr vj = Fr::one();
+    for (size_t j = 0; j < ns; ++j) {
+      shsets[j].vj = vj;
+      shsets[j].coef = Fr::zero();
+      shsets[j].r_u = Fr::zero();
+      vj = vj * v;
     }
+    STAGE(sets_dev, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
     CK(flush_staged(ctx, ws));
     // One proof over several GPUs, long rows: every rank sums its share of a set's members (a k_lincomb_ptrs over zero members
     // writes zeros), the W partial combinations of all sets are all-gathered (ns n values per rank) and added up.
     const bool shard_sets = W_sh > 1 && k >= 14;
-    if (shard_sets && ws->qgather.bytes < (size_t)W_sh * ns * n * 32) {   // [set][rank][n]: the buffer of the quotient shares, grown if there are more sets than coset rows
-      CK(zkfhe_sync(ctx));
-      ws->qgather.release();
-      CK(ws->qgather.alloc(ctx, (size_t)W_sh * ns * n * 32));
-    }
+    if (shard_sets) CK(grow_qgather((size_t)W_sh * ns * n * 32));   // [set][rank][n]: the buffer of the quotient shares, grown if there are more sets than coset rows
     for (size_t j = 0; j < ns; ++j) {
       const size_t all = sets[j].members.size();
       const size_t m_lo = shard_sets ? all * r_sh / W_sh : 0, m_hi = shard_sets ? all * (r_sh + 1) / W_sh : all;
-      const unsigned msz = (unsigned)(m_hi - m_lo);
-      const Fr *const *pp = set_ptrs[j] + m_lo;
-      const Fr *pw = set_pw[j] + m_lo;
-      const unsigned per = 48, chunks = (msz + per - 1) / per;
-      if (chunks > 1 && (size_t)chunks * n * 32 <= ws->partials.bytes) {
-        dim3 lg(grid_for(ctx, n), chunks);
-        zkp::k_lincomb_ptrs_chunked<<<lg, 256, 0, ctx->stream>>>(pp, pw, msz, per, n, ws->partials.fr());
-        ZK_LAUNCH_CHECK(ctx);
-        zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->partials.fr(), chunks, n, F + j * n);
-      } else {
-        zkp::k_lincomb_ptrs<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(pp, pw, msz, n, F + j * n);
-      }
-      ZK_LAUNCH_CHECK(ctx);
+      CK(lincomb(set_ptrs[j] + m_lo, set_pw[j] + m_lo, (unsigned)(m_hi - m_lo), F + j * n));
       // set j's share goes onto the communicator's stream as soon as it is formed (16 MB per rank at k = 19) and travels while the
       // next set is combined; the sums wait for the join below
       if (shard_sets) CK(zkfhe_comm_all_gather_async(ctx, srs->comm, F + j * n, ws->qgather.fr() + j * (size_t)W_sh * n, n * 32));
     }
-    if (shard_sets) {
-      CK(zkfhe_comm_join(ctx, srs->comm, 0));
-      for (size_t j = 0; j < ns; ++j) {
-        zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->qgather.fr() + j * (size_t)W_sh * n, W_sh, n, F + j * n);
-        ZK_LAUNCH_CHECK(ctx);
-      }
-    }
-  }
-  Fr *zs = ws->misc.fr() + 20 * n;   // [ns][n]
-  Fr *hq = ws->misc.fr() + 28 * n;   // [n]
-  Fr *Wq = ws->misc.fr() + 29 * n;   // [n]
-  Fr *dinv = ws->misc.fr() + 30 * n; // [n]
-  zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
-  ZK_LAUNCH_CHECK(ctx);
-  CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)zs, ns * n));
-  zkp::k_sh_h<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, F, zs, dom->fwd, n, hq);
-  ZK_LAUNCH_CHECK(ctx);
-  std::vector<AffinePoint> hq_commit, w_commit;
-  CK(commit_cols_out(ctx, srs, srs->g_lagrange, hq, 1, ws, hq_commit));
-  tr.write_point(hq_commit[0]);
-  const Fr uu = mont(tr.squeeze());
-  trace.mark("shplonk h (GPU)");
-  {
+    if (shard_sets) CK(sum_shares(ns, F));
+    Fr *zs = ws->misc.fr() + 20 * n;   // [ns][n]
+    Fr *hq = ws->misc.fr() + 28 * n;   // [n]
+    Fr *Wq = ws->misc.fr() + 29 * n;   // [n]
+    Fr *dinv = ws->misc.fr() + 30 * n; // [n]
+    zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
+    ZK_LAUNCH_CHECK(ctx);
+    CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)zs, ns * n));
+    zkp::k_sh_h<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, F, zs, dom->fwd, n, hq);
+    ZK_LAUNCH_CHECK(ctx);
+    std::vector<AffinePoint> hq_commit, w_commit;
+    CK(commit_cols_out(ctx, srs, srs->g_lagrange, hq, 1, ws, hq_commit));
+    tr.write_point(hq_commit[0]);
+    const Fr uu = mont(tr.squeeze());
+    trace.mark("shplonk h (GPU)");
     Fr ztu = Fr::one();
     for (int r : all_rots) ztu = ztu * (uu - pts_rot[r]);
     // halo2 normalises the final quotient by the difference vanishing polynomial of the first set ("z_0_diff_inv"): every
@@ -1424,9 +1382,7 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
       if (j == 0) z0_diff_inv = fr_inv(zdiff);
       shsets[j].coef = shsets[j].vj * zdiff * z0_diff_inv;
       Fr ru = shsets[j].rc[3];
-      ru = ru * uu + shsets[j].rc[2];
-      ru = ru * uu + shsets[j].rc[1];
-      ru = ru * uu + shsets[j].rc[0];
+      for (int q = 2; q >= 0; --q) ru = ru * uu + shsets[j].rc[q];
       shsets[j].r_u = ru;
       shw.coef[j] = shsets[j].coef;
       shw.r_u[j] = ru;
@@ -1437,16 +1393,63 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
     CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)dinv, n));
     zkp::k_sh_w<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(shw, (unsigned)ns, F, hq, ztu, dinv, n, Wq);
     ZK_LAUNCH_CHECK(ctx);
+    CK(commit_cols_out(ctx, srs, srs->g_lagrange, Wq, 1, ws, w_commit));
+    tr.write_point(w_commit[0]);
+    return ZKFHE_OK;
   }
-  CK(commit_cols_out(ctx, srs, srs->g_lagrange, Wq, 1, ws, w_commit));
-  tr.write_point(w_commit[0]);
-  proof = tr.out;
+};
+
+// input_json: the CircuitInput text; or words (input_json == nullptr): the same numbers as machine words (zkfhe_bfv_prove_words)
+int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const char *input_json, const FastInput *words, const uint8_t seed[32],
+               std::vector<uint8_t> &proof, std::vector<U256> &instances, float *timings) {
+  const double t_start = now_ms();
+  ctx->cmd_count[ZK_CMD_KERNEL] = ctx->cmd_count[ZK_CMD_COPY] = ctx->cmd_count[ZK_CMD_FILL] = 0;   // zkfhe_ctx_last_proof_commands: this proof's
+  Trace trace;
+  const NttDomain *dom;
+  CK(zk_domain(ctx, (int)pk->cfg.k, &dom));
+  Workspace *ws;
+  CK(get_workspace(ctx, pk, &ws));
+  BackendGuard guard(ctx, ws);
+  Proof P{ctx, srs, pk, pk->cfg, instances, trace, ws, dom};
+  memcpy(P.rseed.w, seed, 32);
+  CK(P.setup());
+  std::vector<AffinePoint> pts;   // the commitments of the round in flight
+  CK(P.phase0(input_json, words, pts));
+  trace.mark("commit phase 0 (GPU)");
+  ctx->proof_marks[0] = (float)(now_ms() - t_start);
+  for (const auto &p : pts) P.tr.write_point(p);
+  P.gamma_rlc = P.tr.squeeze();
+  ctx->proof_marks[1] = (float)(now_ms() - t_start);
+  CK(P.host_witness ? P.phase1_host(pts) : P.phase1_device(pts));
+  trace.mark("commit phase 1 (GPU)");
+  P.tr.write_points(pts);
+  P.tr.squeeze();  // theta: squeezed in protocol order, unused by single-expression lookups
+  CK(P.lookup_columns());
+  trace.mark("lookup permute + commit");
+  P.beta = mont(P.tr.squeeze());
+  P.gamma = mont(P.tr.squeeze());
+  GateHold gate;
+  if (!srs->sharded()) gate.enter();   // a sharded proof's collectives must not wait for another rank's admission order
+  CK(P.grand_products());
+  CK(P.random_poly());
+  P.y = mont(P.tr.squeeze());
+  const double t_commit = now_ms();
+  trace.mark("grand products + commits");
+  CK(P.quotient(pts));
+  gate.leave();
+  for (const auto &p : pts) P.tr.write_point(p);
+  P.x = mont(P.tr.squeeze());
+  const double t_quot = now_ms();
+  trace.mark("quotient");
+  CK(P.evaluations());
+  CK(P.shplonk());
+  proof = P.tr.out;
   const double t_end = now_ms();
   trace.mark("evaluations + shplonk");
   ctx->proof_marks[2] = (float)(t_end - t_start);
   if (timings) {
-    timings[0] = (float)(t_wit - t_start);
-    timings[1] = (float)(t_commit - t_wit);
+    timings[0] = (float)(P.t_wit - t_start);
+    timings[1] = (float)(t_commit - P.t_wit);
     timings[2] = (float)(t_quot - t_commit);
     timings[3] = (float)(t_end - t_quot);
     timings[4] = (float)(t_end - t_start);
@@ -1454,8 +1457,11 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   return ZKFHE_OK;
 }
 
-int copy_proof_out(zkfhe_ctx *ctx, const std::vector<uint8_t> &proof, const std::vector<U256> &inst, uint8_t *proof_out, size_t proof_cap,
-                   size_t *proof_len, uint8_t *instances_out, size_t *n_instances) {
+int prove_out(zkfhe_ctx *ctx, const zkfhe_srs *srs, const zkfhe_bfv_pk *pk, const char *input_json, const FastInput *words, const uint8_t seed[32],
+              uint8_t *proof_out, size_t proof_cap, size_t *proof_len, uint8_t *instances_out, size_t *n_instances, float *timings_ms) {
+  std::vector<uint8_t> proof;
+  std::vector<U256> inst;
+  CK(prove_impl(ctx, srs, const_cast<zkfhe_bfv_pk *>(pk), input_json, words, seed, proof, inst, timings_ms));
   if (proof.size() > proof_cap) return zk_fail_msg(ctx, ZKFHE_EINVAL, "proof buffer too small");
   memcpy(proof_out, proof.data(), proof.size());
   *proof_len = proof.size();
@@ -1480,11 +1486,7 @@ int zkfhe_bfv_prove(zkfhe_ctx *ctx, const zkfhe_srs *srs, const zkfhe_bfv_pk *pk
   ZK_ARG(ctx, srs && pk && input_json && seed && proof_out && proof_len);
   try {
     pos::BulkClientScope in_flight;   // transcript.hpp bulk_ok(): the hash service is shared by the provers in flight
-    std::vector<uint8_t> proof;
-    std::vector<U256> inst;
-    int rc = prove_impl(ctx, srs, const_cast<zkfhe_bfv_pk *>(pk), input_json, nullptr, seed, proof, inst, timings_ms);
-    if (rc) return rc;
-    return copy_proof_out(ctx, proof, inst, proof_out, proof_cap, proof_len, instances_out, n_instances);
+    return prove_out(ctx, srs, pk, input_json, nullptr, seed, proof_out, proof_cap, proof_len, instances_out, n_instances, timings_ms);
   } catch (const std::exception &e) {
     return zk_fail_msg(ctx, ZKFHE_EINVAL, e.what());
   }
@@ -1505,16 +1507,11 @@ int zkfhe_bfv_prove_words(zkfhe_ctx *ctx, const zkfhe_srs *srs, const zkfhe_bfv_
     for (int k = 0; k < 8; ++k) in.a[k].assign(src[k], src[k] + N);
     in.a[8].assign(N + 1, 0);
     in.a[8][0] = in.a[8][N] = 1;
-    std::vector<uint8_t> proof;
-    std::vector<U256> inst;
-    int rc = prove_impl(ctx, srs, const_cast<zkfhe_bfv_pk *>(pk), nullptr, &in, seed, proof, inst, timings_ms);
-    if (rc) return rc;
-    return copy_proof_out(ctx, proof, inst, proof_out, proof_cap, proof_len, instances_out, n_instances);
+    return prove_out(ctx, srs, pk, nullptr, &in, seed, proof_out, proof_cap, proof_len, instances_out, n_instances, timings_ms);
   } catch (const std::exception &e) {
     return zk_fail_msg(ctx, ZKFHE_EINVAL, e.what());
   }
 }
-
 
 // Admission gate of the GPU-heavy middle of the proofs of this process (HeavyGate above): n > 0 = that many proofs inside at once,
 // 0 = no gate, negative = query.  Returns the previous setting.  For a service that keeps its streams full (measured: 16 streams,
@@ -1602,11 +1599,7 @@ int zkfhe_bfv_witness_stream(zkfhe_ctx *ctx, const zkfhe_bfv_pk *pk_c, const cha
     Workspace *ws;
     CK(get_workspace(ctx, pk, &ws));
     CK(zkfhe_sync(ctx));
-    GpuPolyMul gpu_mul(ctx, ws);
-    struct BackendGuard {
-      explicit BackendGuard(PolyMulBackend *b) { poly_mul_backend() = b; }
-      ~BackendGuard() { poly_mul_backend() = nullptr; }
-    } guard(&gpu_mul);
+    BackendGuard guard(ctx, ws);
     Context ctx0(CTX_PHASE0, false, false), ctx_rlc(CTX_RLC1, true, false);
     std::vector<Cell> make_public;
     BfvState st;
