@@ -860,6 +860,54 @@ int zkfhe_bfv_linear_transform_bsgs(zkfhe_ctx *ctx, const zkfhe_bfv_params *para
 #define ZKFHE_PROF_BFV_BSGS_INNER 18   /* k_bsgs_inner: the pointwise products of the diagonals with the baby rotations */
 #define ZKFHE_PROF_BFV_BSGS_GIANT 19   /* k_linear_acc<ACC_GIANT>: the giant rotations of the inner sums, accumulated */
 
+/* ---- Prepared plans: a linear transform's keys and diagonals kept on the device (bfv_linear.hip) ----
+ * zkfhe_bfv_linear_transform and zkfhe_bfv_linear_transform_bsgs check, upload and forward-transform every Galois key and every
+ * diagonal on every call.  A plan does that once: it is opaque, immutable and device-resident, and holds exactly what those calls
+ * build before they touch a ciphertext (the element table, the transformed keys, the transformed diagonals; params, base_bits, l
+ * and the counts), not the untransformed copies.  zkfhe_bfv_plan_apply is the rest of the call.
+ * Exactness: zkfhe_bfv_plan_apply on a plan of zkfhe_bfv_plan_create returns, bit for bit, zkfhe_bfv_linear_transform of the same
+ * ciphertexts with the plan's arguments; on a plan of zkfhe_bfv_plan_create_bsgs, bit for bit, zkfhe_bfv_linear_transform_bsgs:
+ * for every n, across ciphertext chunks and groups of giant steps, and with the same kernels.  No new arithmetic is defined; there
+ * is no new randomness and no new ChaCha20 domain.  g = 1 keeps its meaning: its key rows are neither read nor checked, and it
+ * takes no key slot.  The conventions are those of the two calls (host arrays, N uint64_t per polynomial in CircuitInput order).
+ * Refusals at creation are those of the host-array call that do not concern ciphertexts, in that call's order and with its texts,
+ * under the prefix "bfv_plan_create:" / "bfv_plan_create_bsgs:" (bad parameters: the text of every BFV call): a NULL argument, a
+ * zero count or bad parameters; base_bits outside [1, 32]; a count >= 2^20; a g that is even or >= 2N; the 150-bit range rule
+ * (over n_elems, or over n_baby), before any pass over the inputs and any device work; a key coefficient >= Q (the key rows of g = 1
+ * excepted); a diagonal out of plaintext range.  On any failure, a failed allocation (ZKFHE_ENOMEM) included, everything allocated
+ * so far is freed and *out is NULL.
+ * Refusals at apply, under the prefix "bfv_plan_apply:": a NULL argument or n = 0; a context on another device than the plan's; a
+ * ciphertext coefficient >= Q.  No output is written in any of these cases.
+ * Ownership: the plan's buffers are device allocations of its own, not part of a context's workspace (which the next call
+ * reuses), and live until zkfhe_bfv_plan_destroy.  Creation waits for its device work, and the plan is read-only afterwards, so
+ * any context of the same device may apply it, each with its own workspace and from its own thread.  zkfhe_bfv_plan_destroy waits
+ * for the context it is given and then frees; destroying a plan that another context is still applying is the caller's error.
+ * device_bytes of zkfhe_bfv_plan_info and zkfhe_bfv_plan_bytes are the sum of the sizes requested from the device:
+ * 4 (2 n_elems_total + 2 n_key_slots l N 5 + n_diagonals N 5) with l = zkfhe_bfv_relin_digits, n_elems_total = n_elems or n_baby +
+ * n_giant, n_diagonals = n_elems or n_baby n_giant.  The dense N = 1024 matrix at a 60-bit Q and w = 8 (l = 8; 32 x 32 elements,
+ * 62 key slots): 512 + 20316160 + 20971520 = 41288192 bytes. */
+typedef struct zkfhe_bfv_plan zkfhe_bfv_plan;
+/* flat: the arguments of zkfhe_bfv_linear_transform without the ciphertexts */
+int zkfhe_bfv_plan_create(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_elems, const uint64_t *g, const uint64_t *gk0,
+                          const uint64_t *gk1, int base_bits, const uint64_t *diag, zkfhe_bfv_plan **out);
+/* two-level: the arguments of zkfhe_bfv_linear_transform_bsgs without the ciphertexts */
+int zkfhe_bfv_plan_create_bsgs(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_baby, const uint64_t *g_baby, const uint64_t *bk0,
+                               const uint64_t *bk1, size_t n_giant, const uint64_t *g_giant, const uint64_t *hk0, const uint64_t *hk1,
+                               int base_bits, const uint64_t *diag, zkfhe_bfv_plan **out);
+/* n ciphertexts through the plan: c0, c1, out0, out1 host arrays n x N; waits for its result, like every evaluation call.  The
+ * zkfhe_prof_read slots are those of the host-array call, less the transforms of the keys and the diagonals. */
+int zkfhe_bfv_plan_apply(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, size_t n, const uint64_t *c0, const uint64_t *c1, uint64_t *out0,
+                         uint64_t *out1);
+/* host only; any output pointer may be NULL.  counts = { n_elems (flat) or n_baby, n_giant (0 for a flat plan), the key slots (the
+ * elements with g != 1) } */
+int zkfhe_bfv_plan_info(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int *base_bits, size_t counts[3], uint64_t *device_bytes);
+/* host only: what a plan will hold, so that a service can budget its HBM before it creates one.  Refuses bad parameters and
+ * base_bits outside [1, 32]. */
+int zkfhe_bfv_plan_bytes(const zkfhe_bfv_params *params, int base_bits, size_t n_elems_total, size_t n_key_slots, size_t n_diagonals,
+                         uint64_t *bytes);
+/* waits for ctx (a context of the plan's device), then frees the plan; a NULL plan is not an error */
+int zkfhe_bfv_plan_destroy(zkfhe_ctx *ctx, zkfhe_bfv_plan *plan);
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

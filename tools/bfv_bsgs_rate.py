@@ -3,8 +3,10 @@ the same K diagonals in the same process.  The three parts of profiles/bfv_bsgs.
 
   --static    registers, LDS and scratch of the kernels of bfv_linear.hip from the compiler's resource report (no GPU)
   --counts    keys, key bytes, transforms and pointwise products per call, counted (no GPU)
-  (default)   measured on the GPU: after a warm-up the two calls alternate A/B/A/B, wall time around each call, then one profiled
-              pass of each for the kernel times of the zkfhe_prof_* slots.  One JSON line per row, then the table.
+  (default)   measured on the GPU: after a warm-up the two calls and zkfhe_bfv_plan_apply of a plan of each (made outside the timed
+              region) alternate A/B/C/D, wall time around each call, then one profiled pass of each for the kernel times of the
+              zkfhe_prof_* slots.  One JSON line per row, then the tables: the two calls as in profiles/bfv_bsgs.md, and the plans
+              beside them with their creation time and device bytes (profiles/bfv_plan.md).
 
 K diagonals are the first K of the order of zk.bfv_matrix_diagonals (unswapped offsets 0 .. N/2 - 1, then the swapped ones); the BSGS
 side splits them as zk.bfv_matrix_bsgs does with its default n_baby.  Diagonals and ciphertexts are random: no cost depends on a
@@ -113,16 +115,25 @@ def measure(reps):
             bk0, bk1 = keys(baby)
             hk0, hk1 = keys(giant)
             fd, bd = plain((K,)), plain((len(giant), len(baby)))
+            plans, create_ms = {}, {}
+            for name, make in (("flat", lambda: ctx.bfv_plan(prm, gf, fk0, fk1, fd, base_bits=W)),
+                               ("bsgs", lambda: ctx.bfv_plan_bsgs(prm, gb, bk0, bk1, gg, hk0, hk1, bd, base_bits=W))):
+                make().close()   # warm-up: tables, arena
+                t0 = time.perf_counter()
+                plans[name] = make()   # waits for its device work
+                create_ms[name] = (time.perf_counter() - t0) * 1e3
             for count in CTS:
                 c0 = rng.integers(0, q, size=(count, n), dtype=np.uint64)
                 c1 = rng.integers(0, q, size=(count, n), dtype=np.uint64)
                 calls = {"flat": lambda: ctx.bfv_linear_transform(prm, c0, c1, gf, fk0, fk1, fd, base_bits=W),
-                         "bsgs": lambda: ctx.bfv_linear_transform_bsgs(prm, c0, c1, gb, bk0, bk1, gg, hk0, hk1, bd, base_bits=W)}
+                         "bsgs": lambda: ctx.bfv_linear_transform_bsgs(prm, c0, c1, gb, bk0, bk1, gg, hk0, hk1, bd, base_bits=W),
+                         "flat_plan": lambda: plans["flat"].apply(c0, c1),
+                         "bsgs_plan": lambda: plans["bsgs"].apply(c0, c1)}
                 for fn in calls.values():
                     fn()   # warm-up: tables, arena
-                wall = {"flat": [], "bsgs": []}
+                wall = {name: [] for name in calls}
                 for _ in range(reps):
-                    for name, fn in calls.items():   # A/B/A/B
+                    for name, fn in calls.items():   # A/B/C/D
                         t0 = time.perf_counter()
                         fn()   # waits for its result
                         wall[name].append((time.perf_counter() - t0) * 1e3)
@@ -135,8 +146,12 @@ def measure(reps):
                     row[name] = dict(wall_ms=[round(x, 3) for x in wall[name]],
                                      kernel_ms={NAMES.get(s, str(s)): round(p["total_ms"], 4) for s, p in prof.items() if p["launches"]})
                 row["ratio"] = round(min(wall["flat"]) / min(wall["bsgs"]), 2)
+                for name, plan in plans.items():
+                    row[name + "_plan"].update(create_ms=round(create_ms[name], 3), device_bytes=plan.info()["device_bytes"])
                 print(json.dumps(row), flush=True)
                 rows.append(row)
+            for plan in plans.values():
+                plan.close()
     ctx.close()
     lines = ["| N | K | n_baby x n_giant | ciphertexts | wall ms flat (min of %d) | wall ms BSGS | flat / BSGS | kernel ms flat | kernel ms BSGS | BSGS inner ms | BSGS giant ms |" % reps,
              "|---|---|---|---|---|---|---|---|---|---|---|"]
@@ -149,6 +164,15 @@ def measure(reps):
         for count in CTS:
             wins = [r["K"] for r in rows if r["N"] == n and r["cts"] == count and r["ratio"] > 1.0]
             lines.append("N = %d, %d ciphertext(s): the smallest K at which BSGS wins on wall time: %s" % (n, count, min(wins) if wins else "none of %s" % (ks,)))
+    lines += ["", "| N | K | ciphertexts | wall ms flat (min of %d) | flat plan apply | flat / plan | wall ms BSGS | BSGS plan apply | BSGS / plan | "
+              "kernel ms flat plan | kernel ms BSGS plan | create ms flat plan | BSGS plan | plan MB flat | BSGS |" % reps,
+              "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        w = {name: min(r[name]["wall_ms"]) for name in ("flat", "flat_plan", "bsgs", "bsgs_plan")}
+        lines.append("| %d | %d | %d | %.3f | %.3f | %.2f | %.3f | %.3f | %.2f | %.3f | %.3f | %.1f | %.1f | %.1f | %.1f |" % (
+            r["N"], r["K"], r["cts"], w["flat"], w["flat_plan"], w["flat"] / w["flat_plan"], w["bsgs"], w["bsgs_plan"], w["bsgs"] / w["bsgs_plan"],
+            sum(r["flat_plan"]["kernel_ms"].values()), sum(r["bsgs_plan"]["kernel_ms"].values()), r["flat_plan"]["create_ms"],
+            r["bsgs_plan"]["create_ms"], r["flat_plan"]["device_bytes"] / 1e6, r["bsgs_plan"]["device_bytes"] / 1e6))
     print("\n".join(lines))
 
 

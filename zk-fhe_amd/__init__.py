@@ -54,6 +54,7 @@ EXPORTS = [
     "zkfhe_bfv_slot_count", "zkfhe_bfv_galois_element", "zkfhe_bfv_slot_sum_elements", "zkfhe_bfv_encode_slots", "zkfhe_bfv_decode_slots",
     "zkfhe_bfv_galois_keygen", "zkfhe_bfv_apply_galois", "zkfhe_bfv_slot_sum", "zkfhe_bfv_galois_share",
     "zkfhe_bfv_apply_galois_many", "zkfhe_bfv_linear_transform", "zkfhe_bfv_linear_transform_bsgs",
+    "zkfhe_bfv_plan_create", "zkfhe_bfv_plan_create_bsgs", "zkfhe_bfv_plan_apply", "zkfhe_bfv_plan_info", "zkfhe_bfv_plan_bytes", "zkfhe_bfv_plan_destroy",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -476,7 +477,7 @@ class Context:
 
     def _bfv(self, fn, sig, params, *args):
         """fn(ctx, &params, *args) for a BFV entry point; sig spells its remaining parameters, one letter each (_BFV_ARGS):
-        p a uint64 array, n size_t, s a 32-byte seed, u uint64, i int.  argtypes are assigned on every call."""
+        p a uint64 array, n size_t, s a 32-byte seed, u uint64, i int, P the address of a handle.  argtypes are assigned on every call."""
         f = getattr(self.lib, fn)
         f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC)] + [_BFV_ARGS[c] for c in sig]
         prm = BfvParamsC(*[int(x) for x in params])
@@ -909,10 +910,96 @@ class Context:
                   hk0, hk1, int(base_bits), d, *out)
         return tuple(out)
 
+    # ---- prepared plans: the keys and diagonals of a linear transform checked, uploaded and transformed once
+
+    def bfv_plan(self, params, elements, gk0, gk1, diagonals, base_bits=16):
+        """zkfhe_bfv_plan_create: the arguments of bfv_linear_transform without the ciphertexts -> a BfvLinearPlan, resident on this
+        context's device until it is closed; plan.apply(c0, c1) is bit for bit bfv_linear_transform with these arguments."""
+        g, gk0, gk1 = self._elements(params, elements, gk0, gk1, base_bits)
+        d = np.ascontiguousarray(diagonals, dtype=np.uint64)
+        if d.shape != (g.shape[0], int(params[0])):
+            raise ValueError("diagonals must have shape (K, N), one plaintext per element")
+        h = ctypes.c_void_p()
+        self._bfv("zkfhe_bfv_plan_create", "npppipP", params, g.shape[0], g, gk0, gk1, int(base_bits), d, ctypes.byref(h))
+        return BfvLinearPlan(self, h)
+
+    def bfv_plan_bsgs(self, params, baby_elements, bk0, bk1, giant_elements, hk0, hk1, diagonals, base_bits=16):
+        """zkfhe_bfv_plan_create_bsgs: the arguments of bfv_linear_transform_bsgs without the ciphertexts -> a BfvLinearPlan;
+        plan.apply(c0, c1) is bit for bit bfv_linear_transform_bsgs with these arguments."""
+        gb, bk0, bk1 = self._elements(params, baby_elements, bk0, bk1, base_bits)
+        gg, hk0, hk1 = self._elements(params, giant_elements, hk0, hk1, base_bits)
+        d = np.ascontiguousarray(diagonals, dtype=np.uint64)
+        if d.shape != (gg.shape[0], gb.shape[0], int(params[0])):
+            raise ValueError("diagonals must have shape (n_giant, n_baby, N), one plaintext per pair of elements")
+        h = ctypes.c_void_p()
+        self._bfv("zkfhe_bfv_plan_create_bsgs", "npppnpppipP", params, gb.shape[0], gb, bk0, bk1, gg.shape[0], gg, hk0, hk1, int(base_bits), d,
+                  ctypes.byref(h))
+        return BfvLinearPlan(self, h)
+
+
+class BfvLinearPlan:
+    """A prepared linear transform (zkfhe_bfv_plan): the element table, the transformed Galois keys and the transformed diagonals
+    of Context.bfv_plan / Context.bfv_plan_bsgs, resident on the device and read-only.  Any Context of the same device may apply it;
+    close() (or leaving the with block) frees it, and no context may still be applying it then."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.h = handle
+        self.params = self.info()["params"]
+
+    def _handle(self):
+        if not self.h:
+            raise ZkfheError("the plan is closed")
+        return self.h
+
+    def apply(self, c0, c1, ctx=None):
+        """zkfhe_bfv_plan_apply: n ciphertexts (n, N) -> (out0, out1) of shape (n, N), on ctx (default: the creating context)."""
+        ctx = ctx or self.ctx
+        plan = self._handle()
+        c0, c1 = ctx._eval_arrays(self.params, c0, c1)
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        f = ctx.lib.zkfhe_bfv_plan_apply
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [_U64P] * 4
+        ctx._check(f(ctx.h, plan, c0.shape[0], *[a.ctypes.data_as(_U64P) for a in (c0, c1, *out)]))
+        return tuple(out)
+
+    def info(self):
+        """zkfhe_bfv_plan_info -> params (N, Q, T, B), base_bits, n_elems (n_baby of a two-level plan), n_giant (0: a flat plan),
+        key_slots (the elements with g != 1) and device_bytes."""
+        f = self.ctx.lib.zkfhe_bfv_plan_info
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t),
+                      ctypes.POINTER(ctypes.c_uint64)]
+        prm, w, counts, nbytes = BfvParamsC(), ctypes.c_int(), (ctypes.c_size_t * 3)(), ctypes.c_uint64()
+        rc = f(self._handle(), ctypes.byref(prm), ctypes.byref(w), counts, ctypes.byref(nbytes))
+        if rc != 0:
+            raise ZkfheError("zkfhe_bfv_plan_info failed (%d): %s" % (rc, self.ctx.lib.zkfhe_last_error(None).decode()))
+        return {"params": tuple(int(getattr(prm, name)) for name, _ in BfvParamsC._fields_), "base_bits": w.value, "n_elems": counts[0],
+                "n_giant": counts[1], "key_slots": counts[2], "device_bytes": nbytes.value}
+
+    def close(self):
+        if self.h:
+            f = self.ctx.lib.zkfhe_bfv_plan_destroy
+            f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            h, self.h = self.h, None
+            self.ctx._check(f(self.ctx.h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 # the parameter letters of Context._bfv
-_BFV_ARGS = {"p": _U64P, "n": ctypes.c_size_t, "s": ctypes.c_char_p, "u": ctypes.c_uint64, "i": ctypes.c_int}
+_BFV_ARGS = {"p": _U64P, "n": ctypes.c_size_t, "s": ctypes.c_char_p, "u": ctypes.c_uint64, "i": ctypes.c_int, "P": ctypes.POINTER(ctypes.c_void_p)}
 
 
 def _host_bfv(fn, argtypes, params, *args):
@@ -940,6 +1027,16 @@ def bfv_relin_digits(params, base_bits):
     l = ctypes.c_size_t()
     _host_bfv("zkfhe_bfv_relin_digits", [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)], params, int(base_bits), ctypes.byref(l))
     return l.value
+
+
+def bfv_plan_bytes(params, base_bits, n_elems_total, n_key_slots, n_diagonals):
+    """zkfhe_bfv_plan_bytes (host only): the device bytes of a plan, 4 (2 n_elems_total + 2 n_key_slots l N 5 + n_diagonals N 5) with
+    l = bfv_relin_digits.  n_elems_total: K, or n_baby + n_giant; n_key_slots: the elements with g != 1; n_diagonals: K, or
+    n_baby n_giant."""
+    out = ctypes.c_uint64()
+    _host_bfv("zkfhe_bfv_plan_bytes", [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)], params,
+              int(base_bits), int(n_elems_total), int(n_key_slots), int(n_diagonals), ctypes.byref(out))
+    return out.value
 
 
 def bfv_dot_max_terms(params, plain=False):

@@ -22,6 +22,10 @@
 // transforms those, and k_linear_acc<ACC_GIANT> rotates inner ciphertext i by giant element i and accumulates (bsgs_call).
 // Sizes: |r| < Q + l N (2^w - 1) Q < 2^116 for a rotation; the transform's sum is below n_elems N floor(T/2) times that, which the
 // call bounds by 2^150 (check_range) under the half of the primes' product 2^151.2.  No kernel uses scratch.
+// Every call is a prepare half (the checks of elements, keys and diagonals; the element table, the keys and the diagonals uploaded
+// and transformed: struct zkfhe_bfv_plan) and a run half (the ciphertext check and the chunk loop, from that struct alone).  The
+// host-array calls prepare into the context's work arena and run; zkfhe_bfv_plan_create* prepare into allocations of the plan's own,
+// and zkfhe_bfv_plan_apply is the run half.
 #include <string>
 
 #include "rns_ntt.hip.hpp"
@@ -250,49 +254,151 @@ RnsConst<NP> intt_const(int log_n, int products) {
 // polynomials of five primes
 size_t chunk_cts(uint64_t n, size_t n_cts, size_t rows) { return std::min(n_cts, std::max<size_t>(1, chunk_polys(n) / rows)); }
 
-// both calls: diag == nullptr is apply_galois_many
-int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, size_t n_elems,
-                const uint64_t *g, const uint64_t *gk0, const uint64_t *gk1, int base_bits, const uint64_t *diag, uint64_t *out0,
-                uint64_t *out1, const char *fn) {
+// The chunk rule of linear_transform_bsgs.  A ciphertext holds max(1 + l, 2 n_baby) polynomials of hoisted rows or baby rotations
+// and (1 + l) hoisted rows per giant step; cts ciphertexts with all their giant steps fit the budget of chunk_polys(N).  Where one
+// ciphertext's giant rows alone exceed it (cts = 1), the giant steps go in groups of giants and the groups add up in the transform
+// domain.  A chunk that is not the whole batch is a multiple of the kernels' tile of CT ciphertexts.
+void bsgs_chunks(uint64_t n, size_t n_cts, size_t n_baby, size_t n_giant, size_t rows, size_t *cts, size_t *giants) {
+  *cts = chunk_cts(n, n_cts, std::max(rows, 2 * n_baby) + n_giant * rows);
+  if (*cts > CT && *cts < n_cts) *cts -= *cts % CT;   // whole ciphertext tiles, unless the chunk is the batch
+  *giants = std::min(n_giant, std::max<size_t>(1, chunk_polys(n) / (*cts * rows)));
+}
+
+// the words of a plan's three buffers: elem_d, key_hat, diag_hat (zkfhe_bfv_plan_bytes is four times their sum)
+unsigned __int128 plan_words(uint64_t n, int l, size_t n_elems, size_t slots, size_t n_diag, int which) {
+  typedef unsigned __int128 u128;
+  return which == 0 ? (u128)2 * n_elems : which == 1 ? (u128)2 * slots * l * n * NP : (u128)n_diag * n * NP;
+}
+
+}  // namespace
+
+// What a linear transform holds before it sees a ciphertext: the element table, the transformed keys and the transformed diagonals,
+// with the counts that their layout depends on.  The host-array calls fill one on the stack whose buffers are carved from the
+// context's work arena (prepare_*), and run from it (linear_run, bsgs_run); a zkfhe_bfv_plan owns its three buffers, and
+// zkfhe_bfv_plan_apply runs from it.  Nothing is written to it after prepare_device, and a run reads nothing else that outlives the
+// call, so keys of other calls can be kept resident the same way: a struct of transformed buffers and counts beside this one.
+struct zkfhe_bfv_plan {
+  zkfhe_bfv_params params{};
+  int base_bits = 0, l = 0, log_n = 0;
+  int device = 0;                   // of the context that prepared it
+  bool bsgs = false;                // two-level: n_baby baby elements, then n_giant giant ones; flat: n_baby elements, n_giant = 0
+  size_t n_baby = 0, n_giant = 0;
+  size_t slots = 0;                 // key slots: the elements with g != 1
+  size_t n_diag = 0;                // diagonals: n_baby (flat), n_giant n_baby (two-level), 0 (apply_galois_many)
+  std::vector<uint32_t> elem;       // the host copy of elem_d: [n_baby + n_giant][2] = (g, key slot or NO_KEY)
+  uint32_t *elem_d = nullptr, *key_hat = nullptr, *diag_hat = nullptr;
+  bool owned = false;               // the three buffers are this plan's own allocations (plan_free), not a carve of the arena
+  uint64_t device_bytes = 0;        // owned: the sum of the three requested sizes
+};
+
+namespace {
+
+// The elements and keys of a call: list a (all elements of a flat call, the baby elements of a two-level one), then list b (the
+// giant elements; empty for a flat call).  Element k of the joint list has its key rows at block k of its own list.
+struct KeyLists {
+  size_t n_a, n_b;
+  const uint64_t *g_a, *a0, *a1, *g_b, *b0, *b1;
+  size_t count() const { return n_a + n_b; }
+  uint64_t g(size_t k) const { return k < n_a ? g_a[k] : g_b[k - n_a]; }
+  const uint64_t *k0(size_t k, size_t lw) const { return k < n_a ? a0 + k * lw : b0 + (k - n_a) * lw; }
+  const uint64_t *k1(size_t k, size_t lw) const { return k < n_a ? a1 + k * lw : b1 + (k - n_a) * lw; }
+};
+
+// The prepare half comes in three steps, so that a host-array call keeps the order of its refusals (a ciphertext coefficient is
+// checked after the range rule and before the keys) and carves its one arena between the checks and the device work.
+// Step 1, no pass over an input array and no device work: the parameters, base_bits, the counts, every g, the range rule of the
+// sum over n_a elements (has_diag; the inner sum of a two-level call); fills the counts and the element table of p.
+int prepare_head(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const KeyLists &ks, int base_bits, bool bsgs, bool has_diag, const char *fn,
+                 zkfhe_bfv_plan *p) {
   ZK_CK(check_params(ctx, params));
   int l = 0;
   ZK_CK(relin_rows(ctx, params, base_bits, fn, &l));
-  const uint64_t n = params->n, q = params->q;
-  if (n_elems >> 20) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": more than 2^20 Galois elements");
+  const uint64_t n = params->n;
+  if ((ks.n_a >> 20) || (ks.n_b >> 20)) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": more than 2^20 Galois elements");
+  const size_t n_elems = ks.count();
   for (size_t k = 0; k < n_elems; ++k)
-    if (!(g[k] & 1) || g[k] >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": every Galois element g must be odd and below 2N");
-  if (diag) ZK_CK(check_range(ctx, params, n_elems, l, base_bits, fn));   // before any O(n) pass and any device work
-  const int log_n = bit_log2(n);
-  const size_t lw = (size_t)l * n;
-  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, fn, "a ciphertext", c1));
-  std::vector<uint32_t> elem(2 * n_elems);
-  size_t slots = 0;
-  for (size_t k = 0; k < n_elems; ++k) {   // the key rows of g = 1 are neither read nor checked
-    elem[2 * k] = (uint32_t)g[k];
-    elem[2 * k + 1] = g[k] == 1 ? NO_KEY : (uint32_t)slots++;
-    if (g[k] != 1) ZK_CK(check_below_q(ctx, gk0 + k * lw, lw, q, fn, "a Galois-key", gk1 + k * lw));
+    if (!(ks.g(k) & 1) || ks.g(k) >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": every Galois element g must be odd and below 2N");
+  if (has_diag) ZK_CK(check_range(ctx, params, ks.n_a, l, base_bits, fn));   // before any O(n) pass and any device work
+  p->params = *params;
+  p->base_bits = base_bits, p->l = l, p->log_n = bit_log2(n), p->device = ctx->device;
+  p->bsgs = bsgs, p->n_baby = ks.n_a, p->n_giant = ks.n_b, p->n_diag = !has_diag ? 0 : bsgs ? ks.n_b * ks.n_a : ks.n_a;
+  p->elem.resize(2 * n_elems);
+  p->slots = 0;
+  for (size_t k = 0; k < n_elems; ++k) {   // g = 1 takes no key slot
+    p->elem[2 * k] = (uint32_t)ks.g(k);
+    p->elem[2 * k + 1] = ks.g(k) == 1 ? NO_KEY : (uint32_t)p->slots++;
   }
-  if (diag) ZK_CK(check_plain(ctx, diag, n_elems * n, q, params->t, fn, "a diagonal"));
+  return ZKFHE_OK;
+}
 
-  const size_t rows = (size_t)l + 1, per_ct = diag ? 2 : 2 * n_elems;   // output polynomials per ciphertext
-  const size_t chunk = chunk_cts(n, n_cts, std::max(rows, per_ct)), cw = chunk * n;
-  int *flag;
-  uint64_t *key_d, *diag_d, *x_d, *o_d;
-  uint32_t *key_hat, *diag_hat, *elem_d, *hst, *res;
-  ZK_CK(Arena().add(flag, 1).add(elem_d, 2 * n_elems).add(key_d, 2 * slots * lw).add(key_hat, 2 * slots * lw * NP)
-            .add(diag_d, diag ? n_elems * n : 0).add(diag_hat, diag ? n_elems * n * NP : 0).add(x_d, 2 * cw).add(hst, rows * cw * NP)
-            .add(res, per_ct * cw * NP).add(o_d, per_ct * cw).carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, elem_d, elem.data(), elem.size() * 4));
-  for (size_t k = 0; k < n_elems; ++k) {   // key slot s: its gk0 rows, then its gk1 rows
-    if (elem[2 * k + 1] == NO_KEY) continue;
-    ZK_CK(zkfhe_upload(ctx, key_d + (size_t)elem[2 * k + 1] * 2 * lw, gk0 + k * lw, lw * 8));
-    ZK_CK(zkfhe_upload(ctx, key_d + ((size_t)elem[2 * k + 1] * 2 + 1) * lw, gk1 + k * lw, lw * 8));
+// Step 2, the passes over the keys and the diagonals: a key coefficient >= Q, then a diagonal out of plaintext range.
+int prepare_check(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, const KeyLists &ks, const uint64_t *diag, const char *fn) {
+  const uint64_t n = p.params.n, q = p.params.q;
+  const size_t lw = (size_t)p.l * n;
+  for (size_t k = 0; k < ks.count(); ++k)   // the key rows of g = 1 are neither read nor checked
+    if (ks.g(k) != 1) ZK_CK(check_below_q(ctx, ks.k0(k, lw), lw, q, fn, "a Galois-key", ks.k1(k, lw)));
+  if (p.n_diag) ZK_CK(check_plain(ctx, diag, p.n_diag * n, q, p.params.t, fn, "a diagonal"));
+  return ZKFHE_OK;
+}
+
+// Step 3, the device work: the element table, the keys and the diagonals uploaded and transformed into p.elem_d, p.key_hat and
+// p.diag_hat, which the caller has pointed at plan_words() words each.  key_d (2 slots l N words) and diag_d (n_diag N words) are
+// the staging copies and flag the transform's flag word: work buffers of the call, not kept.
+int prepare_device(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, const KeyLists &ks, const uint64_t *diag, uint64_t *key_d, uint64_t *diag_d, int *flag) {
+  const uint64_t n = p.params.n, q = p.params.q;
+  const size_t lw = (size_t)p.l * n;
+  ZK_CK(zkfhe_upload(ctx, p.elem_d, p.elem.data(), p.elem.size() * 4));
+  for (size_t k = 0; k < ks.count(); ++k) {   // key slot s: its gk0 rows, then its gk1 rows
+    if (p.elem[2 * k + 1] == NO_KEY) continue;
+    ZK_CK(zkfhe_upload(ctx, key_d + (size_t)p.elem[2 * k + 1] * 2 * lw, ks.k0(k, lw), lw * 8));
+    ZK_CK(zkfhe_upload(ctx, key_d + ((size_t)p.elem[2 * k + 1] * 2 + 1) * lw, ks.k1(k, lw), lw * 8));
   }
-  if (slots) ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * slots * l, log_n, nullptr, 0, key_hat, flag));
-  if (diag) {
-    ZK_CK(zkfhe_upload(ctx, diag_d, diag, n_elems * n * 8));
-    ZK_CK(launch_rns_ntt<NP>(ctx, false, diag_d, LOAD_CENTRED, q, n_elems, log_n, nullptr, 0, diag_hat, flag));
+  if (p.slots) ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * p.slots * p.l, p.log_n, nullptr, 0, p.key_hat, flag));
+  if (p.n_diag) {
+    ZK_CK(zkfhe_upload(ctx, diag_d, diag, p.n_diag * n * 8));
+    ZK_CK(launch_rns_ntt<NP>(ctx, false, diag_d, LOAD_CENTRED, q, p.n_diag, p.log_n, nullptr, 0, p.diag_hat, flag));
   }
+  return ZKFHE_OK;
+}
+
+// the prepared buffers and the staging copies as arena entries, in the order the host-array calls have always carved them
+void add_prepared(Arena &a, zkfhe_bfv_plan &p, int *&flag, uint64_t *&key_d, uint64_t *&diag_d) {
+  const uint64_t n = p.params.n;
+  const size_t n_elems = p.n_baby + p.n_giant;
+  a.add(flag, 1).add(p.elem_d, (size_t)plan_words(n, p.l, n_elems, p.slots, p.n_diag, 0)).add(key_d, 2 * p.slots * p.l * n)
+      .add(p.key_hat, (size_t)plan_words(n, p.l, n_elems, p.slots, p.n_diag, 1)).add(diag_d, p.n_diag * n)
+      .add(p.diag_hat, (size_t)plan_words(n, p.l, n_elems, p.slots, p.n_diag, 2));
+}
+
+// the run half's first step: a ciphertext coefficient >= Q
+int check_cts(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64_t *c0, const uint64_t *c1, const char *fn) {
+  return check_below_q(ctx, c0, n_cts * p.params.n, p.params.q, fn, "a ciphertext", c1);
+}
+
+// the work buffers of linear_run for n_cts ciphertexts
+struct LinearWork {
+  size_t chunk;
+  uint64_t *x_d, *o_d;
+  uint32_t *hst, *res;
+};
+void add_linear_work(Arena &a, const zkfhe_bfv_plan &p, size_t n_cts, LinearWork &w) {
+  const uint64_t n = p.params.n;
+  const size_t rows = (size_t)p.l + 1, per_ct = p.n_diag ? 2 : 2 * p.n_baby;   // output polynomials per ciphertext
+  w.chunk = chunk_cts(n, n_cts, std::max(rows, per_ct));
+  const size_t cw = w.chunk * n;
+  a.add(w.x_d, 2 * cw).add(w.hst, rows * cw * NP).add(w.res, per_ct * cw * NP).add(w.o_d, per_ct * cw);
+}
+
+// The run half of the flat calls: the chunk loop over the ciphertexts, from the prepared buffers of p.  p.n_diag == 0 is
+// apply_galois_many.
+int linear_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0, uint64_t *out1,
+               const LinearWork &w) {
+  const uint64_t n = p.params.n, q = p.params.q;
+  const int l = p.l, log_n = p.log_n, base_bits = p.base_bits;
+  const bool diag = p.n_diag != 0;
+  const size_t n_elems = p.n_baby, slots = p.slots, rows = (size_t)l + 1, per_ct = diag ? 2 : 2 * n_elems, chunk = w.chunk;
+  uint64_t *x_d = w.x_d, *o_d = w.o_d;
+  uint32_t *hst = w.hst, *res = w.res;
   const uint32_t *tw;
   ZK_CK(zk_rns_tables(ctx, &tw));
   int lds_h;
@@ -312,9 +418,9 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
     const dim3 grid(zk_blocks(n, ACC_THREADS), NP, zk_blocks(c, CT));
     zk_prof_begin(ctx);
     if (diag)
-      k_linear_acc<ACC_LINEAR><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_elems, key_hat, diag_hat, l, c, log_n, rc, gs, res);
+      k_linear_acc<ACC_LINEAR><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, p.elem_d, (int)n_elems, p.key_hat, p.diag_hat, l, c, log_n, rc, gs, res);
     else
-      k_linear_acc<ACC_MANY><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, elem_d, (int)n_elems, key_hat, nullptr, l, c, log_n, rc, gs, res);
+      k_linear_acc<ACC_MANY><<<grid, ACC_THREADS, 0, ctx->stream>>>(hst, p.elem_d, (int)n_elems, p.key_hat, nullptr, l, c, log_n, rc, gs, res);
     ZK_LAUNCH_CHECK(ctx);
     // read: every hoisted row per element, every key word once per CT ciphertexts, the diagonals likewise; written: the outputs
     zk_prof_end(ctx, ZKFHE_PROF_BFV_LINEAR, 4.0 * words * ((double)n_elems * c * rows + (double)zk_blocks(c, CT) * (2.0 * slots * l + (diag ? n_elems : 0)) + polys));
@@ -328,14 +434,24 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
   return ZKFHE_OK;
 }
 
-// The chunk rule of linear_transform_bsgs.  A ciphertext holds max(1 + l, 2 n_baby) polynomials of hoisted rows or baby rotations
-// and (1 + l) hoisted rows per giant step; cts ciphertexts with all their giant steps fit the budget of chunk_polys(N).  Where one
-// ciphertext's giant rows alone exceed it (cts = 1), the giant steps go in groups of giants and the groups add up in the transform
-// domain.  A chunk that is not the whole batch is a multiple of the kernels' tile of CT ciphertexts.
-void bsgs_chunks(uint64_t n, size_t n_cts, size_t n_baby, size_t n_giant, size_t rows, size_t *cts, size_t *giants) {
-  *cts = chunk_cts(n, n_cts, std::max(rows, 2 * n_baby) + n_giant * rows);
-  if (*cts > CT && *cts < n_cts) *cts -= *cts % CT;   // whole ciphertext tiles, unless the chunk is the batch
-  *giants = std::min(n_giant, std::max<size_t>(1, chunk_polys(n) / (*cts * rows)));
+// both flat calls: diag == nullptr is apply_galois_many
+int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, size_t n_elems,
+                const uint64_t *g, const uint64_t *gk0, const uint64_t *gk1, int base_bits, const uint64_t *diag, uint64_t *out0,
+                uint64_t *out1, const char *fn) {
+  const KeyLists ks{n_elems, 0, g, gk0, gk1, nullptr, nullptr, nullptr};
+  zkfhe_bfv_plan p;
+  ZK_CK(prepare_head(ctx, params, ks, base_bits, false, diag != nullptr, fn, &p));
+  ZK_CK(check_cts(ctx, p, n_cts, c0, c1, fn));
+  ZK_CK(prepare_check(ctx, p, ks, diag, fn));
+  int *flag;
+  uint64_t *key_d, *diag_d;
+  LinearWork w;
+  Arena a;
+  add_prepared(a, p, flag, key_d, diag_d);
+  add_linear_work(a, p, n_cts, w);
+  ZK_CK(a.carve(ctx));
+  ZK_CK(prepare_device(ctx, p, ks, diag, key_d, diag_d, flag));
+  return linear_run(ctx, p, n_cts, c0, c1, out0, out1, w);
 }
 
 template <int GT, int CTI>
@@ -345,55 +461,31 @@ void launch_bsgs_inner(zkfhe_ctx *ctx, const uint32_t *baby, const uint32_t *dia
   k_bsgs_inner<GT, CTI><<<grid, ACC_THREADS, 0, ctx->stream>>>(baby, diag_hat, (int)n_baby, (int)n_giant, c, log_n, rc, out);
 }
 
-int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, size_t n_baby,
-              const uint64_t *g_baby, const uint64_t *bk0, const uint64_t *bk1, size_t n_giant, const uint64_t *g_giant, const uint64_t *hk0,
-              const uint64_t *hk1, int base_bits, const uint64_t *diag, uint64_t *out0, uint64_t *out1) {
-  const char *fn = "bfv_linear_transform_bsgs";
-  ZK_CK(check_params(ctx, params));
-  int l = 0;
-  ZK_CK(relin_rows(ctx, params, base_bits, fn, &l));
-  const uint64_t n = params->n, q = params->q;
-  if ((n_baby >> 20) || (n_giant >> 20)) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": more than 2^20 Galois elements");
-  const size_t n_elems = n_baby + n_giant;   // the baby elements, then the giant ones
-  const auto g_of = [&](size_t k) { return k < n_baby ? g_baby[k] : g_giant[k - n_baby]; };
-  for (size_t k = 0; k < n_elems; ++k)
-    if (!(g_of(k) & 1) || g_of(k) >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": every Galois element g must be odd and below 2N");
-  ZK_CK(check_range(ctx, params, n_baby, l, base_bits, fn));   // the inner sum; before any O(n) pass and any device work
-  const int log_n = bit_log2(n);
-  const size_t lw = (size_t)l * n;
-  ZK_CK(check_below_q(ctx, c0, n_cts * n, q, fn, "a ciphertext", c1));
-  std::vector<uint32_t> elem(2 * n_elems);
-  size_t slots = 0;
-  for (size_t k = 0; k < n_elems; ++k) {   // the key rows of g = 1 are neither read nor checked
-    const uint64_t *k0 = k < n_baby ? bk0 + k * lw : hk0 + (k - n_baby) * lw, *k1 = k < n_baby ? bk1 + k * lw : hk1 + (k - n_baby) * lw;
-    elem[2 * k] = (uint32_t)g_of(k);
-    elem[2 * k + 1] = g_of(k) == 1 ? NO_KEY : (uint32_t)slots++;
-    if (g_of(k) != 1) ZK_CK(check_below_q(ctx, k0, lw, q, fn, "a Galois-key", k1));
-  }
-  const size_t n_diag = n_giant * n_baby;
-  ZK_CK(check_plain(ctx, diag, n_diag * n, q, params->t, fn, "a diagonal"));
-
-  const size_t rows = (size_t)l + 1;
+// the work buffers of bsgs_run for n_cts ciphertexts
+struct BsgsWork {
   size_t chunk, group;
-  bsgs_chunks(n, n_cts, n_baby, n_giant, rows, &chunk, &group);
-  const size_t cw = chunk * n;
-  int *flag;
-  uint64_t *key_d, *diag_d, *x_d, *inner_q, *o_d;
-  uint32_t *key_hat, *diag_hat, *elem_d, *hst, *baby, *inner, *hst_in, *res;
-  ZK_CK(Arena().add(flag, 1).add(elem_d, 2 * n_elems).add(key_d, 2 * slots * lw).add(key_hat, 2 * slots * lw * NP).add(diag_d, n_diag * n)
-            .add(diag_hat, n_diag * n * NP).add(x_d, 2 * cw).add(hst, rows * cw * NP).add(baby, 2 * n_baby * cw * NP)
-            .add(inner, 2 * group * cw * NP).add(inner_q, 2 * group * cw).add(hst_in, group * rows * cw * NP).add(res, 2 * cw * NP)
-            .add(o_d, 2 * cw).carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, elem_d, elem.data(), elem.size() * 4));
-  for (size_t k = 0; k < n_elems; ++k) {   // key slot s: its gk0 rows, then its gk1 rows
-    if (elem[2 * k + 1] == NO_KEY) continue;
-    const uint64_t *k0 = k < n_baby ? bk0 + k * lw : hk0 + (k - n_baby) * lw, *k1 = k < n_baby ? bk1 + k * lw : hk1 + (k - n_baby) * lw;
-    ZK_CK(zkfhe_upload(ctx, key_d + (size_t)elem[2 * k + 1] * 2 * lw, k0, lw * 8));
-    ZK_CK(zkfhe_upload(ctx, key_d + ((size_t)elem[2 * k + 1] * 2 + 1) * lw, k1, lw * 8));
-  }
-  if (slots) ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * slots * l, log_n, nullptr, 0, key_hat, flag));
-  ZK_CK(zkfhe_upload(ctx, diag_d, diag, n_diag * n * 8));
-  ZK_CK(launch_rns_ntt<NP>(ctx, false, diag_d, LOAD_CENTRED, q, n_diag, log_n, nullptr, 0, diag_hat, flag));
+  uint64_t *x_d, *inner_q, *o_d;
+  uint32_t *hst, *baby, *inner, *hst_in, *res;
+};
+void add_bsgs_work(Arena &a, const zkfhe_bfv_plan &p, size_t n_cts, BsgsWork &w) {
+  const uint64_t n = p.params.n;
+  const size_t rows = (size_t)p.l + 1;
+  bsgs_chunks(n, n_cts, p.n_baby, p.n_giant, rows, &w.chunk, &w.group);
+  const size_t cw = w.chunk * n, group = w.group;
+  a.add(w.x_d, 2 * cw).add(w.hst, rows * cw * NP).add(w.baby, 2 * p.n_baby * cw * NP).add(w.inner, 2 * group * cw * NP)
+      .add(w.inner_q, 2 * group * cw).add(w.hst_in, group * rows * cw * NP).add(w.res, 2 * cw * NP).add(w.o_d, 2 * cw);
+}
+
+// The run half of linear_transform_bsgs: the chunk loop over the ciphertexts and, inside it, the groups of giant steps.
+int bsgs_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0, uint64_t *out1,
+             const BsgsWork &w) {
+  const uint64_t n = p.params.n, q = p.params.q;
+  const int l = p.l, log_n = p.log_n, base_bits = p.base_bits;
+  const size_t n_baby = p.n_baby, n_giant = p.n_giant, rows = (size_t)l + 1, chunk = w.chunk, group = w.group;
+  const std::vector<uint32_t> &elem = p.elem;
+  const uint32_t *elem_d = p.elem_d, *key_hat = p.key_hat, *diag_hat = p.diag_hat;
+  uint64_t *x_d = w.x_d, *inner_q = w.inner_q, *o_d = w.o_d;
+  uint32_t *hst = w.hst, *baby = w.baby, *inner = w.inner, *hst_in = w.hst_in, *res = w.res;
   const uint32_t *tw;
   ZK_CK(zk_rns_tables(ctx, &tw));
   int lds_h;
@@ -455,6 +547,83 @@ int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, cons
   return ZKFHE_OK;
 }
 
+int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, size_t n_baby,
+              const uint64_t *g_baby, const uint64_t *bk0, const uint64_t *bk1, size_t n_giant, const uint64_t *g_giant, const uint64_t *hk0,
+              const uint64_t *hk1, int base_bits, const uint64_t *diag, uint64_t *out0, uint64_t *out1) {
+  const char *fn = "bfv_linear_transform_bsgs";
+  const KeyLists ks{n_baby, n_giant, g_baby, bk0, bk1, g_giant, hk0, hk1};   // the baby elements, then the giant ones
+  zkfhe_bfv_plan p;
+  ZK_CK(prepare_head(ctx, params, ks, base_bits, true, true, fn, &p));
+  ZK_CK(check_cts(ctx, p, n_cts, c0, c1, fn));
+  ZK_CK(prepare_check(ctx, p, ks, diag, fn));
+  int *flag;
+  uint64_t *key_d, *diag_d;
+  BsgsWork w;
+  Arena a;
+  add_prepared(a, p, flag, key_d, diag_d);
+  add_bsgs_work(a, p, n_cts, w);
+  ZK_CK(a.carve(ctx));
+  ZK_CK(prepare_device(ctx, p, ks, diag, key_d, diag_d, flag));
+  return bsgs_run(ctx, p, n_cts, c0, c1, out0, out1, w);
+}
+
+// a plan's own buffers and the plan itself; hipFree waits for the device
+void plan_free(zkfhe_bfv_plan *p) {
+  if (!p) return;
+  if (p->owned) (void)hipFree(p->elem_d), (void)hipFree(p->key_hat), (void)hipFree(p->diag_hat);
+  delete p;
+}
+
+// words uint32_t of the plan's own (nullptr for none)
+int plan_alloc(zkfhe_ctx *ctx, uint32_t **out, unsigned __int128 words, const char *fn) {
+  if (!words) return ZKFHE_OK;
+  if (words >> 60) return zk_fail_msg(ctx, ZKFHE_ENOMEM, std::string(fn) + ": out of device memory");
+  const hipError_t e = hipMalloc(out, (size_t)words * 4);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return zk_fail_msg(ctx, ZKFHE_ENOMEM, std::string(fn) + ": out of device memory");
+  }
+  ZK_HIP(ctx, e);
+  return ZKFHE_OK;
+}
+
+// The prepare half into allocations of the plan's own: the staging copies alone come from the arena.  The plan is complete, and
+// readable from any stream of the device, when this returns.
+int plan_fill(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const KeyLists &ks, int base_bits, bool bsgs, const uint64_t *diag, const char *fn,
+              zkfhe_bfv_plan *p) {
+  ZK_CK(prepare_head(ctx, params, ks, base_bits, bsgs, true, fn, p));
+  ZK_CK(prepare_check(ctx, *p, ks, diag, fn));
+  const uint64_t n = params->n;
+  const size_t n_diag = p->n_diag;
+  p->owned = true;
+  unsigned __int128 total = 0;
+  uint32_t **bufs[3] = {&p->elem_d, &p->key_hat, &p->diag_hat};
+  for (int i = 0; i < 3; ++i) {
+    const unsigned __int128 words = plan_words(n, p->l, ks.count(), p->slots, n_diag, i);
+    ZK_CK(plan_alloc(ctx, bufs[i], words, fn));
+    total += 4 * words;
+  }
+  p->device_bytes = (uint64_t)total;
+  int *flag;
+  uint64_t *key_d, *diag_d;
+  ZK_CK(Arena().add(flag, 1).add(key_d, 2 * p->slots * p->l * n).add(diag_d, n_diag * n).carve(ctx));
+  ZK_CK(prepare_device(ctx, *p, ks, diag, key_d, diag_d, flag));
+  ZK_HIP(ctx, zk_wait(ctx));
+  return ZKFHE_OK;
+}
+
+int plan_create(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const KeyLists &ks, int base_bits, bool bsgs, const uint64_t *diag, const char *fn,
+                zkfhe_bfv_plan **out) {
+  zkfhe_bfv_plan *p = new zkfhe_bfv_plan;
+  const int rc = plan_fill(ctx, params, ks, base_bits, bsgs, diag, fn, p);
+  if (rc) {
+    plan_free(p);
+    return rc;
+  }
+  *out = p;
+  return ZKFHE_OK;
+}
+
 }  // namespace
 
 namespace zkrns {
@@ -498,6 +667,80 @@ int zkfhe_bfv_linear_transform_bsgs(zkfhe_ctx *ctx, const zkfhe_bfv_params *para
   ZK_ENTER(ctx);
   ZK_ARG(ctx, ctx && c0 && c1 && g_baby && bk0 && bk1 && g_giant && hk0 && hk1 && diag && out0 && out1 && n_cts > 0 && n_baby > 0 && n_giant > 0);
   return bsgs_call(ctx, params, n_cts, c0, c1, n_baby, g_baby, bk0, bk1, n_giant, g_giant, hk0, hk1, base_bits, diag, out0, out1);
+}
+
+int zkfhe_bfv_plan_create(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_elems, const uint64_t *g, const uint64_t *gk0,
+                          const uint64_t *gk1, int base_bits, const uint64_t *diag, zkfhe_bfv_plan **out) {
+  ZK_ENTER(ctx);
+  if (out) *out = nullptr;
+  if (!(ctx && g && gk0 && gk1 && diag && out && n_elems > 0))
+    return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_plan_create: a NULL argument or a zero count");
+  const KeyLists ks{n_elems, 0, g, gk0, gk1, nullptr, nullptr, nullptr};
+  return plan_create(ctx, params, ks, base_bits, false, diag, "bfv_plan_create", out);
+}
+
+int zkfhe_bfv_plan_create_bsgs(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_baby, const uint64_t *g_baby, const uint64_t *bk0,
+                               const uint64_t *bk1, size_t n_giant, const uint64_t *g_giant, const uint64_t *hk0, const uint64_t *hk1,
+                               int base_bits, const uint64_t *diag, zkfhe_bfv_plan **out) {
+  ZK_ENTER(ctx);
+  if (out) *out = nullptr;
+  if (!(ctx && g_baby && bk0 && bk1 && g_giant && hk0 && hk1 && diag && out && n_baby > 0 && n_giant > 0))
+    return zk_fail_msg(ctx, ZKFHE_EINVAL, "bfv_plan_create_bsgs: a NULL argument or a zero count");
+  const KeyLists ks{n_baby, n_giant, g_baby, bk0, bk1, g_giant, hk0, hk1};
+  return plan_create(ctx, params, ks, base_bits, true, diag, "bfv_plan_create_bsgs", out);
+}
+
+int zkfhe_bfv_plan_apply(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0,
+                         uint64_t *out1) {
+  ZK_ENTER(ctx);
+  const char *fn = "bfv_plan_apply";
+  if (!(ctx && plan && c0 && c1 && out0 && out1 && n_cts > 0)) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": a NULL argument or a zero count");
+  if (ctx->device != plan->device)
+    return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": the plan lives on device " + std::to_string(plan->device) + " and the context on device " +
+                                              std::to_string(ctx->device));
+  ZK_CK(check_cts(ctx, *plan, n_cts, c0, c1, fn));
+  Arena a;
+  if (plan->bsgs) {
+    BsgsWork w;
+    add_bsgs_work(a, *plan, n_cts, w);
+    ZK_CK(a.carve(ctx));
+    return bsgs_run(ctx, *plan, n_cts, c0, c1, out0, out1, w);
+  }
+  LinearWork w;
+  add_linear_work(a, *plan, n_cts, w);
+  ZK_CK(a.carve(ctx));
+  return linear_run(ctx, *plan, n_cts, c0, c1, out0, out1, w);
+}
+
+int zkfhe_bfv_plan_info(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int *base_bits, size_t counts[3], uint64_t *device_bytes) {
+  if (!plan) return zk_fail_msg(nullptr, ZKFHE_EINVAL, "bfv_plan_info: plan is NULL");
+  if (params) *params = plan->params;
+  if (base_bits) *base_bits = plan->base_bits;
+  if (counts) counts[0] = plan->n_baby, counts[1] = plan->n_giant, counts[2] = plan->slots;
+  if (device_bytes) *device_bytes = plan->device_bytes;
+  return ZKFHE_OK;
+}
+
+int zkfhe_bfv_plan_bytes(const zkfhe_bfv_params *params, int base_bits, size_t n_elems_total, size_t n_key_slots, size_t n_diagonals,
+                         uint64_t *bytes) {
+  if (!bytes) return zk_fail_msg(nullptr, ZKFHE_EINVAL, "bfv_plan_bytes: bytes is NULL");
+  ZK_CK(check_params(nullptr, params));
+  int l = 0;
+  ZK_CK(relin_rows(nullptr, params, base_bits, "bfv_plan_bytes", &l));
+  // every term is below 2^64 2^6 2^15 2^4: the sum fits 128 bits
+  unsigned __int128 total = 0;
+  for (int i = 0; i < 3; ++i) total += 4 * plan_words(params->n, l, n_elems_total, n_key_slots, n_diagonals, i);
+  if (total >> 64) return zk_fail_msg(nullptr, ZKFHE_EINVAL, "bfv_plan_bytes: the size does not fit 64 bits");
+  *bytes = (uint64_t)total;
+  return ZKFHE_OK;
+}
+
+int zkfhe_bfv_plan_destroy(zkfhe_ctx *ctx, zkfhe_bfv_plan *plan) {
+  ZK_ENTER(ctx);
+  if (!plan) return ZKFHE_OK;
+  if (ctx) ZK_HIP(ctx, zk_wait(ctx));   // what this context has queued against the plan
+  plan_free(plan);
+  return ZKFHE_OK;
 }
 
 }  // extern "C"
