@@ -84,7 +84,7 @@ struct zkfhe_basis {
   int c = 0;        // window bits
   int windows = 0;  // number of signed windows
   zk::G1Affine *table = nullptr;  // [windows][n] : 2^(c*w) * P_i
-  // digit-multiple table (msm.hip k_msm_table): mult[(i*mw + w) * 2^(mc-1) + j-1] = j * 2^(mc*w) * P_i, j = 1..2^(mc-1),
+  // digit-multiple table (msm_table.hip.hpp k_msm_table): mult[(i*mw + w) * 2^(mc-1) + j-1] = j * 2^(mc*w) * P_i, j = 1..2^(mc-1),
   // mw = ceil(255/mc) signed windows; mc is the widest width whose table fits the per-basis budget (23.6 GB at n = 2^13,
   // mc = 12).  nullptr: calls against this basis take the bucket pipeline over `table`.
   zk::G1Affine *mult = nullptr;

@@ -1,4 +1,5 @@
-// Wave- and workgroup-wide sums of G1X29 accumulators (shared by the MSM kernels of msm.hip and verify.hip).
+// Wave- and workgroup-wide sums of G1X29 accumulators (shared by the MSM kernels of msm_bucket.hip.hpp, msm_table.hip.hpp and
+// verify.hip).
 #pragma once
 #include "fq29.hip.hpp"
 
