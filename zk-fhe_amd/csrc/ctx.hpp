@@ -179,14 +179,18 @@ int zk_scratch(zkfhe_ctx *ctx, int slot, size_t bytes, void **out);
 int zk_basis_create_scaled(zkfhe_ctx *ctx, const zkfhe_g1_affine *bases_host, size_t n, int window_bits, double table_budget_scale, zkfhe_basis **out);
 // stream-ordered device-to-device copy (own kernel for large blocks)
 int zk_copy_d2d(zkfhe_ctx *ctx, void *dst, const void *src, size_t bytes);
+// the tables of the domain of 2^log_n points, built on first use and kept with the context (ntt.hip)
 int zk_domain(zkfhe_ctx *ctx, int log_n, const NttDomain **out);
+// the coset tables of the 2^13 tile, built once per (g, lef, rows, scaled) and kept with the context (ntt13.hip)
 int zk_pre13(zkfhe_ctx *ctx, const zk::Fr &g, int lef, int rows, bool scaled, const void **out);
-// Lagrange columns -> the first `rows` cosets of the extended domain (lagrange_to_coeff + coeff_to_extended in one call): tmp_dev
-// receives the coefficient form (at n = 2^13: times n, the n^-1 lives in the coset tables), column c at c * 2^log_n; out as
-// zk_coset_ntt_rows
-int zk_extend_lagrange(zkfhe_ctx *ctx, const zk::Fr *lagr_dev, zk::Fr *tmp_dev, zk::Fr *out_dev, size_t n_cols, int log_n, int lef, const zk::Fr &g, int rows);
-// forward coset extension of the first `rows` cosets (ntt.hip)
+// Forward coset extension of the first `rows` cosets g w_ext^k1 of the 2^(log_n + lef) domain (rows <= 2^lef; ntt.hip), written
+// densely: column c, coset k1 at out_dev + (c * rows + k1) * 2^log_n.  in_dev: the coefficients, column c at c * 2^log_n; in and out
+// must not overlap.  zkfhe_coset_ntt_batch (forward) is this call with rows = 2^lef.
 int zk_coset_ntt_rows(zkfhe_ctx *ctx, const zk::Fr *in_dev, zk::Fr *out_dev, size_t n_cols, int log_n, int lef, const zk::Fr &g, int rows);
+// Lagrange columns -> the first `rows` cosets of the extended domain (lagrange_to_coeff + coeff_to_extended in one call): tmp_dev
+// receives the coefficient form (at n = 2^13: times n, the n^-1 lives in the coset tables), column c at c * 2^log_n; out_dev in the
+// layout of zk_coset_ntt_rows
+int zk_extend_lagrange(zkfhe_ctx *ctx, const zk::Fr *lagr_dev, zk::Fr *tmp_dev, zk::Fr *out_dev, size_t n_cols, int log_n, int lef, const zk::Fr &g, int rows);
 
 // host-side Fr helpers (same code as the device, compiled for the host)
 zk::Fr zk_fr_from_u64(uint64_t v);

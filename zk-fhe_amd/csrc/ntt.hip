@@ -15,28 +15,18 @@
 // algorithmic minimum: every coefficient is read once and written once, both as full 2 KiB-per-wave
 // coalesced runs; twiddles come from an omega^j table that all columns share (L2 resident).
 //
-// Larger n: log2(n/2^13) radix-2 DIF stages over the whole vector (coalesced), then the tile kernel on
-// each contiguous 2^13 block with a strided scatter to natural order (round-1 implementation; the
-// prover itself never needs it, see zkfhe_coset_ntt_batch which keeps the extended domain coset-major).
+// Larger n: the log2(n/2^13) DIF stages above the tile in a few passes over the whole vector (coalesced), then the tile
+// kernel on each contiguous 2^13 block with a strided scatter to natural order.  Which passes, and through which buffers, is
+// the plan of ntt_plan.hpp (host only, checked on the CPU); ntt_long_rows below runs it.  The extended domain stays
+// coset-major (zkfhe_coset_ntt_batch), so the prover's longest transform has the length of a column.
 #include <cstring>
 
 #include "ctx.hpp"
+#include "ntt_plan.hpp"
 #include "ntt_tile.hip.hpp"
 #include "fr29.hip.hpp"
 
 using namespace zk;
-
-int zk_launch_tile_3(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_4(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_5(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_6(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_7(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_8(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_9(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_10(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_11(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_12(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
-int zk_launch_tile_13(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
 
 namespace {
 
@@ -107,8 +97,6 @@ __global__ void __launch_bounds__(256) k_dif_fused(const Fr *src, Fr *data, size
     }
 #pragma unroll
     for (int t = 0; t < S; ++t) {
-      constexpr int dummy = 0;
-      (void)dummy;
       const int h = R >> (t + 1);                // partner distance in units of q
       const int sh = log_n - 1 - (log_half - t); // twiddle exponent shift of this level
 #pragma unroll
@@ -274,20 +262,67 @@ __global__ void __launch_bounds__(256) k_ext_combine(const Fr *__restrict__ rows
 }
 
 int launch_tile_dyn(zkfhe_ctx *ctx, int log_tile, const TileArgs &a, unsigned tiles, unsigned cols) {
-  switch (log_tile) {
-    case 3: return zk_launch_tile_3(ctx, a, tiles, cols);
-    case 4: return zk_launch_tile_4(ctx, a, tiles, cols);
-    case 5: return zk_launch_tile_5(ctx, a, tiles, cols);
-    case 6: return zk_launch_tile_6(ctx, a, tiles, cols);
-    case 7: return zk_launch_tile_7(ctx, a, tiles, cols);
-    case 8: return zk_launch_tile_8(ctx, a, tiles, cols);
-    case 9: return zk_launch_tile_9(ctx, a, tiles, cols);
-    case 10: return zk_launch_tile_10(ctx, a, tiles, cols);
-    case 11: return zk_launch_tile_11(ctx, a, tiles, cols);
-    case 12: return zk_launch_tile_12(ctx, a, tiles, cols);
-    case 13: return zk_launch_tile_13(ctx, a, tiles, cols);
-  }
-  return zk_fail_msg(ctx, ZKFHE_EINVAL, "tile size out of range");
+#define ZK_TILE_LAUNCHER(k) zk_launch_tile_##k,
+  static int (*const launchers[])(zkfhe_ctx *, const TileArgs &, unsigned, unsigned) = {ZK_TILE_SIZES(ZK_TILE_LAUNCHER)};
+#undef ZK_TILE_LAUNCHER
+  if (log_tile < 3 || log_tile > NTT_TILE_LOG) return zk_fail_msg(ctx, ZKFHE_EINVAL, "tile size out of range");
+  return launchers[log_tile - 3](ctx, a, tiles, cols);
+}
+
+// The three shapes of a tile launch.  Each returns a TileArgs for columns of n = 2^log_n points cut into 2^log_tiles tiles; the
+// fields it does not name stay zero, which the tile kernels read as "absent".
+
+// Independent tiles, natural order: tile b of column c is the run of N = n points at (c 2^log_tiles + b) N, in and out.  No
+// multiplier at the load (pre, pre13 and pre_tile_stride zero); post: one multiplier at the store (n^-1), or nullptr.
+TileArgs tiles_independent(const Fr *in, Fr *out, int log_n, int log_tiles, const Fr *tw, const Fr *post) {
+  const size_t n = (size_t)1 << log_n;
+  TileArgs a{};
+  a.in = in;
+  a.out = out;
+  a.in_tile_stride = n;
+  a.col_stride_in = a.col_stride_out = n << log_tiles;
+  a.tw = tw;
+  a.post = post;
+  a.log_tiles = log_tiles;
+  a.in_len = (int)n;
+  a.out_natural_tiles = 1;
+  return a;
+}
+
+// One input fanned out to `rows` coset tiles: every tile of column c reads the same n coefficients at c n (in_tile_stride zero) and
+// tile k1 multiplies them by its row of coset powers as it loads; the rows of a column come out densely, (c rows + k1) n.  The
+// powers are either `pre` ([rows][n], 2^261 form) or, at n = 2^13, the tables of zk_pre13 (`pre13`; pre is then nullptr: that tile
+// never reads it).  No multiplier at the store (post zero).
+TileArgs tiles_fan_out(const Fr *in, Fr *out, int log_n, int lef, int rows, const Fr *tw, const Fr *pre, const void *pre13) {
+  const size_t n = (size_t)1 << log_n;
+  TileArgs a{};
+  a.in = in;
+  a.out = out;
+  a.col_stride_in = n;
+  a.col_stride_out = n * (size_t)rows;
+  a.tw = tw;
+  a.pre = pre;
+  a.pre13 = pre13;
+  a.pre_tile_stride = n;
+  a.log_tiles = lef;
+  a.in_len = (int)n;
+  a.out_natural_tiles = 1;
+  return a;
+}
+
+// The last stage of a long row: the 2^(log_n - 13) contiguous 2^13 blocks of a column, each transformed and scattered with stride
+// 2^log_tiles from the bit-reversed block number (out_natural_tiles zero).  No multiplier at the load; post as above.
+TileArgs tiles_scatter(const Fr *in, Fr *out, int log_n, const Fr *tw, const Fr *post) {
+  TileArgs a{};
+  a.in = in;
+  a.out = out;
+  a.in_tile_stride = (size_t)1 << NTT_TILE_LOG;
+  a.col_stride_in = a.col_stride_out = (size_t)1 << log_n;
+  a.tw = tw;
+  a.post = post;
+  a.log_tiles = log_n - NTT_TILE_LOG;
+  a.in_len = 1 << NTT_TILE_LOG;
+  return a;
 }
 
 }  // namespace
@@ -334,15 +369,193 @@ int zk_domain(zkfhe_ctx *ctx, int log_n, const NttDomain **out) {
   return ZKFHE_OK;
 }
 
-#define MAX_TILE_LOG 13
+namespace {
 
+// n = 2 and n = 4: log_n radix-2 stages in place on the destination, which leave n = 4 with outputs 1 and 2 exchanged.  The
+// exchange (two strided copies out of a snapshot in scratch slot 0) and the n^-1 of the inverse (zkfhe_fr_scale) follow; no tile
+// kernel exists below eight points.
+int ntt_tiny(zkfhe_ctx *ctx, const Fr *src, Fr *data, size_t n_cols, int log_n, int inverse, const NttDomain *dom) {
+  const size_t n = (size_t)1 << log_n, bytes = n_cols * n * sizeof(Fr);
+  if (src) ZK_CK(zk_copy_d2d(ctx, data, src, bytes));
+  const Fr *tw = inverse ? dom->inv29 : dom->fwd29;
+  for (int s = log_n - 1; s >= 0; --s) {
+    k_dif_stage<<<zk_blocks(n_cols * (n / 2), 256), 256, 0, ctx->stream>>>(data, data, n_cols, log_n, s, tw);
+    ZK_LAUNCH_CHECK(ctx);
+  }
+  if (log_n == 2 || inverse) {
+    void *p;
+    ZK_CK(zk_scratch(ctx, 0, bytes, &p));
+    Fr *tmp = (Fr *)p;
+    ZK_CK(zk_copy_d2d(ctx, tmp, data, bytes));   // the snapshot is taken for every inverse, n = 2 included, where nothing reads it
+    if (log_n == 2) {
+      ZK_HIP(ctx, hipMemcpy2DAsync(data + 1, 4 * sizeof(Fr), tmp + 2, 4 * sizeof(Fr), sizeof(Fr), n_cols, hipMemcpyDeviceToDevice, ctx->stream));
+      ZK_HIP(ctx, hipMemcpy2DAsync(data + 2, 4 * sizeof(Fr), tmp + 1, 4 * sizeof(Fr), sizeof(Fr), n_cols, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (inverse) ZK_CK(zkfhe_fr_scale(ctx, (const zkfhe_fr *)data, (const zkfhe_fr *)&dom->n_inv, (zkfhe_fr *)data, n_cols * n));
+  }
+  return ZKFHE_OK;
+}
+
+// 8 <= n <= 2^13: one tile per column
+int ntt_one_tile(zkfhe_ctx *ctx, const Fr *src, Fr *data, size_t n_cols, int log_n, int inverse, const NttDomain *dom) {
+  TileArgs a = tiles_independent(src ? src : data, data, log_n, 0, inverse ? dom->inv29 : dom->fwd29, inverse ? dom->n_inv29_dev : nullptr);
+  if (log_n == NTT_TILE_LOG && a.in == a.out) {
+    // the 2^13 tile cuts a column into two workgroups that both read all of it: in place it goes through scratch
+    const size_t bytes = (n_cols << log_n) * sizeof(Fr);
+    void *p;
+    ZK_CK(zk_scratch(ctx, 0, bytes, &p));
+    a.out = (Fr *)p;
+    ZK_CK(launch_tile_dyn(ctx, log_n, a, 1, (unsigned)n_cols));
+    return zk_copy_d2d(ctx, data, p, bytes);
+  }
+  return launch_tile_dyn(ctx, log_n, a, 1, (unsigned)n_cols);
+}
+
+// One pass of a plan (ntt_plan.hpp) over all rows.  pre: the coset powers, read by the pass that carries the multiplier.
+int ntt_run_pass(zkfhe_ctx *ctx, const NttPass &ps, const Fr *in, Fr *out, size_t n_cols, int log_n, int inverse, const Fr *tw, const Fr *pre, unsigned rows,
+                 const Fr *shifts_host) {
+  const size_t n = (size_t)1 << log_n;
+  if (!ps.coset) pre = nullptr;
+  if (ps.kind == NTT_FOUR_STEP) return zk_dif8_pass(ctx, in, out, n_cols, log_n, ps.S, inverse, ps.coset ? shifts_host : nullptr, ps.coset ? rows : 1u);
+  if (ps.kind == NTT_LDS) {
+    const size_t tiles = n_cols * (n >> 10);
+    unsigned grid = (unsigned)(tiles < (size_t)ctx->num_cu * 64 ? tiles : (size_t)ctx->num_cu * 64);
+    if (ps.S == 6) k_dif_lds<3><<<grid, 128, 0, ctx->stream>>>(in, out, n_cols, log_n, ps.log_half, tw, pre, rows);
+    else if (ps.S == 5) k_dif_lds<2><<<grid, 128, 0, ctx->stream>>>(in, out, n_cols, log_n, ps.log_half, tw, pre, rows);
+    else k_dif_lds<1><<<grid, 128, 0, ctx->stream>>>(in, out, n_cols, log_n, ps.log_half, tw, pre, rows);
+  } else {
+    unsigned grid = zk_blocks(n_cols * (n >> ps.S), 256);
+    unsigned cap = (unsigned)ctx->num_cu * 16;
+    if (grid > cap) grid = cap;
+    if (ps.S == 3) k_dif_fused<3><<<grid, 256, 0, ctx->stream>>>(in, out, n_cols, log_n, ps.log_half, tw, pre, rows);
+    else if (ps.S == 2) k_dif_fused<2><<<grid, 256, 0, ctx->stream>>>(in, out, n_cols, log_n, ps.log_half, tw, pre, rows);
+    else k_dif_stage<<<grid, 256, 0, ctx->stream>>>(in, out, n_cols, log_n, ps.log_half, tw, pre, rows);
+  }
+  ZK_LAUNCH_CHECK(ctx);
+  return ZKFHE_OK;
+}
+
+// 2^14 <= n <= 2^26: the plan's passes bring every row down to 2^13 blocks, the tile kernel transforms each block and scatters it
+// to natural order.  What runs, and through which buffers, is ntt_plan.hpp.
+int ntt_long_rows(zkfhe_ctx *ctx, const Fr *src, Fr *data, size_t n_cols, int log_n, int inverse, const NttDomain *dom, const Fr *pre, unsigned rows,
+                  const Fr *shifts_host) {
+  static const bool lds_pass = ntt_lds_pass_enabled(getenv("ZKFHE_NTT_LDS_PASS"));
+  const size_t bytes = (n_cols << log_n) * sizeof(Fr);
+  void *work;
+  ZK_CK(zk_scratch(ctx, 0, bytes, &work));
+  const NttPlan plan = ntt_plan(log_n, inverse != 0, src == nullptr, pre ? NTT_COSET_PRE : shifts_host ? NTT_COSET_SHIFTS : NTT_COSET_NONE, rows, lds_pass);
+  if (plan.refused) return zk_fail_msg(ctx, ZKFHE_EINVAL, "bad argument: coset shifts on the host take a four-step size (2^16, 2^19) and at most four rows");
+  const Fr *rd[3] = {src, data, (const Fr *)work};   // indexed by NttBuf
+  Fr *wr[3] = {nullptr, data, (Fr *)work};           // no pass writes the source
+  const Fr *tw = inverse ? dom->inv29 : dom->fwd29;
+  for (int i = 0; i < plan.n_passes; ++i) ZK_CK(ntt_run_pass(ctx, plan.pass[i], rd[plan.pass[i].in], wr[plan.pass[i].out], n_cols, log_n, inverse, tw, pre, rows, shifts_host));
+  const NttDomain *tdom;
+  ZK_CK(zk_domain(ctx, NTT_TILE_LOG, &tdom));
+  const TileArgs a = tiles_scatter(rd[plan.tile_in], wr[plan.tile_out], log_n, inverse ? tdom->inv29 : tdom->fwd29, inverse ? dom->n_inv29_dev : nullptr);
+  ZK_CK(launch_tile_dyn(ctx, NTT_TILE_LOG, a, 1u << a.log_tiles, (unsigned)n_cols));
+  if (plan.copy_back) ZK_CK(zk_copy_d2d(ctx, data, work, bytes));
+  return ZKFHE_OK;
+}
+
+// src == nullptr: in place on cols_dev.  pre / shifts_host (long rows, forward, out of place only): the n_cols transforms are
+// `rows` coset rows of the n_cols / rows vectors at src, each multiplied by the powers of its coset shift as the first pass loads it
+// -- pre holds the powers ([rows][n], 2^261 form), shifts_host the `rows` shifts themselves (2^16 and 2^19, up to four rows).
 int zk_ntt_impl(zkfhe_ctx *ctx, const zkfhe_fr *src_dev, zkfhe_fr *cols_dev, size_t n_cols, int log_n, int inverse, const Fr *pre = nullptr, unsigned rows = 1,
-                const Fr *shifts_host = nullptr);
+                const Fr *shifts_host = nullptr) {
+  ZK_ENTER(ctx);
+  ZK_ARG(ctx, (pre == nullptr && shifts_host == nullptr) || (src_dev != nullptr && !inverse && log_n > 13 && rows >= 1 && n_cols % rows == 0));
+  ZK_ARG(ctx, !(pre && shifts_host));
+  ZK_ARG(ctx, log_n >= 1 && log_n <= 26);
+  if (!n_cols) return ZKFHE_OK;
+  ZK_ARG(ctx, cols_dev != nullptr);
+  ZK_ARG(ctx, n_cols < 65536);
+  const NttDomain *dom;
+  ZK_CK(zk_domain(ctx, log_n, &dom));
+  if (log_n < 3) return ntt_tiny(ctx, (const Fr *)src_dev, (Fr *)cols_dev, n_cols, log_n, inverse, dom);
+  if (log_n <= NTT_TILE_LOG) return ntt_one_tile(ctx, (const Fr *)src_dev, (Fr *)cols_dev, n_cols, log_n, inverse, dom);
+  return ntt_long_rows(ctx, (const Fr *)src_dev, (Fr *)cols_dev, n_cols, log_n, inverse, dom, pre, rows, shifts_host);
+}
 
-// Rows of 2^16 and 2^19 (three / six stages above the 2^13 tile: BASELINE configs[3] and [4]) run those stages in four-step form
-// (ntt_dif8.hip): constants for the size-8 / size-64 part, one streaming table product per element.  Every other length takes the
-// radix-2 passes with gathered twiddles (k_dif_fused / k_dif_lds).
-static bool dif8_rows(int log_n) { return log_n - MAX_TILE_LOG == 3 || log_n - MAX_TILE_LOG == 6; }
+// the shifts g w_ext^k1 of the first `rows` cosets (rows <= 8: the extension factor is at most 2^3)
+void coset_shifts(const Fr &g, const Fr &w_ext, int rows, Fr (&out)[8]) {
+  Fr shift = g;
+  for (int k1 = 0; k1 < rows; ++k1) {
+    out[k1] = shift;
+    shift = shift * w_ext;
+  }
+}
+
+// The second half of extended_to_coeff: the scale table 2^-lef g^-j, j < n 2^lef, into scratch slot 1, then k_ext_combine over
+// the inverse-transformed coset rows.
+int ext_combine(zkfhe_ctx *ctx, const Fr *rows, Fr *out, size_t n_cols, int log_n, int lef, const Fr &g, const NttDomain *edom) {
+  const size_t n = (size_t)1 << log_n, ne = n << lef;
+  void *p;
+  ZK_CK(zk_scratch(ctx, 1, ne * sizeof(Fr), &p));
+  Fr *scale = (Fr *)p;
+  const Fr einv = fp_inv<FrP>(zk_fr_from_u64((uint64_t)1 << lef));
+  const Fr ginv = fp_inv<FrP>(g);
+  k_pow_table_scaled<<<zk_blocks(ne, 256), 256, 0, ctx->stream>>>(zk_fr_to_29(einv), ginv, scale, ne);
+  ZK_LAUNCH_CHECK(ctx);
+  const unsigned grid = zk_blocks(n_cols * n, 256);
+  if (lef == 1) k_ext_combine<1><<<grid, 256, 0, ctx->stream>>>(rows, out, n_cols, log_n, edom->inv29, scale);
+  else if (lef == 2) k_ext_combine<2><<<grid, 256, 0, ctx->stream>>>(rows, out, n_cols, log_n, edom->inv29, scale);
+  else k_ext_combine<3><<<grid, 256, 0, ctx->stream>>>(rows, out, n_cols, log_n, edom->inv29, scale);
+  ZK_LAUNCH_CHECK(ctx);
+  return ZKFHE_OK;
+}
+
+}  // namespace
+
+// Forward coset extension of the first `rows` cosets only (rows <= 2^lef; more are cut to 2^lef), written DENSELY: column c, coset
+// k1 at out + (c * rows + k1) * n.  The prover's quotient has degree < 3n, so three of the four cosets determine it.  Row k1 is
+// the transform of x[i] (g w_ext^k1)^i, and the powers reach the kernels in one of three ways:
+//   n = 2^13: the tile's own tables (powers times the first-stage twiddles), built once per (g, lef, rows) by zk_pre13;
+//   n = 2^16, 2^19 and up to four rows: the four-step pass folds them into its (cached) tables, from the shifts alone;
+//   otherwise: a table of powers per call in scratch slot 1, filled here -- the only writer of that slot on the forward path --
+//     and read by the first pass of the transform (long rows) or by the tile as it loads.
+int zk_coset_ntt_rows(zkfhe_ctx *ctx, const Fr *in_dev, Fr *out_dev, size_t n_cols, int log_n, int lef, const Fr &g, int rows) {
+  if (rows > (1 << lef)) rows = 1 << lef;
+  if (!n_cols) return ZKFHE_OK;
+  const size_t n = (size_t)1 << log_n, n_rows = n_cols * (size_t)rows;
+  const NttDomain *dom, *edom;
+  ZK_CK(zk_domain(ctx, log_n, &dom));
+  ZK_CK(zk_domain(ctx, log_n + lef, &edom));
+  if (log_n == NTT_TILE_LOG) {
+    const void *pre13;
+    ZK_CK(zk_pre13(ctx, g, lef, rows, false, &pre13));
+    return launch_tile_dyn(ctx, log_n, tiles_fan_out(in_dev, out_dev, log_n, lef, rows, dom->fwd29, nullptr, pre13), (unsigned)rows, (unsigned)n_cols);
+  }
+  Fr shifts[8];
+  coset_shifts(g, edom->omega, rows, shifts);
+  if (ntt_four_step_size(log_n) && rows <= 4) return zk_ntt_impl(ctx, (const zkfhe_fr *)in_dev, (zkfhe_fr *)out_dev, n_rows, log_n, 0, nullptr, (unsigned)rows, shifts);
+  void *p;
+  ZK_CK(zk_scratch(ctx, 1, (size_t)rows * n * sizeof(Fr), &p));
+  Fr *pre = (Fr *)p;
+  const Fr c32 = zk_fr_to_29(Fr::one());
+  for (int k1 = 0; k1 < rows; ++k1) {   // (g w_ext^k1)^i as constant operands of the nine-limb multiply (2^261 form)
+    k_pow_table_scaled<<<zk_blocks(n, 256), 256, 0, ctx->stream>>>(c32, shifts[k1], pre + (size_t)k1 * n, n);
+    ZK_LAUNCH_CHECK(ctx);
+  }
+  // long rows: one out-of-place transform of all (column, coset) rows into the destination, whose first pass multiplies by the powers
+  if (log_n > NTT_TILE_LOG) return zk_ntt_impl(ctx, (const zkfhe_fr *)in_dev, (zkfhe_fr *)out_dev, n_rows, log_n, 0, pre, (unsigned)rows);
+  return launch_tile_dyn(ctx, log_n, tiles_fan_out(in_dev, out_dev, log_n, lef, rows, dom->fwd29, pre, nullptr), (unsigned)rows, (unsigned)n_cols);
+}
+
+// lagrange_to_coeff followed by coeff_to_extended on `rows` cosets, for the prover's extend step.  At n = 2^13 the inverse
+// transform runs out of place WITHOUT its final n^-1 (one product per coefficient less) and the coset tables carry the factor.
+int zk_extend_lagrange(zkfhe_ctx *ctx, const Fr *lagr_dev, Fr *tmp_dev, Fr *out_dev, size_t n_cols, int log_n, int lef, const Fr &g, int rows) {
+  if (!n_cols) return ZKFHE_OK;
+  if (log_n != NTT_TILE_LOG || rows > (1 << lef)) {
+    ZK_CK(zk_ntt_impl(ctx, (const zkfhe_fr *)lagr_dev, (zkfhe_fr *)tmp_dev, n_cols, log_n, 1));   // out of place: no copy
+    return zk_coset_ntt_rows(ctx, tmp_dev, out_dev, n_cols, log_n, lef, g, rows);
+  }
+  const NttDomain *dom;
+  ZK_CK(zk_domain(ctx, log_n, &dom));
+  const void *pre13;
+  ZK_CK(zk_pre13(ctx, g, lef, rows, true, &pre13));
+  ZK_CK(launch_tile_dyn(ctx, log_n, tiles_independent(lagr_dev, tmp_dev, log_n, 0, dom->inv29, nullptr), 1, (unsigned)n_cols));
+  return launch_tile_dyn(ctx, log_n, tiles_fan_out(tmp_dev, out_dev, log_n, lef, rows, dom->fwd29, nullptr, pre13), (unsigned)rows, (unsigned)n_cols);
+}
 
 extern "C" {
 
@@ -361,256 +574,8 @@ int zkfhe_ntt_batch_to(zkfhe_ctx *ctx, const zkfhe_fr *in_dev, zkfhe_fr *out_dev
   return zk_ntt_impl(ctx, in_dev, out_dev, n_cols, log_n, inverse);
 }
 
-// src == nullptr: in place on cols_dev.  pre (long rows, forward, out of place only): the n_cols transforms are `rows` coset rows
-// of the n_cols / rows vectors at src, each multiplied by its row of pre (2^261 form) while the first pass loads it.
-extern "C++" int zk_ntt_impl(zkfhe_ctx *ctx, const zkfhe_fr *src_dev, zkfhe_fr *cols_dev, size_t n_cols, int log_n, int inverse, const Fr *pre, unsigned rows,
-                             const Fr *shifts_host) {
-  ZK_ENTER(ctx);
-  ZK_ARG(ctx, (pre == nullptr && shifts_host == nullptr) || (src_dev != nullptr && !inverse && log_n > 13 && rows >= 1 && n_cols % rows == 0));
-  ZK_ARG(ctx, !(pre && shifts_host));
-  ZK_ARG(ctx, log_n >= 1 && log_n <= 26);
-  if (!n_cols) return ZKFHE_OK;
-  ZK_ARG(ctx, cols_dev != nullptr);
-  ZK_ARG(ctx, n_cols < 65536);
-  Fr *data = (Fr *)cols_dev;
-  const Fr *src = (const Fr *)src_dev;
-  const size_t n = (size_t)1 << log_n;
-  const NttDomain *dom;
-  int rc = zk_domain(ctx, log_n, &dom);
-  if (rc) return rc;
-  // n^-1 lives in device memory next to nothing else: keep a tiny scratch copy per call
-  const Fr *ninv_dev = inverse ? dom->n_inv29_dev : nullptr;
-  if (log_n < 3 && src) {
-    rc = zk_copy_d2d(ctx, data, src, n_cols * n * sizeof(Fr));
-    if (rc) return rc;
-  }
-  if (log_n < 3) {
-    // tiny transforms: DIF stages then a bit-reversed gather is overkill; do log_n DIF stages and fix order on 2/4 points
-    // n = 2: one stage is the whole transform (bitrev of 1 bit is identity).  n = 4: outputs 1 and 2 swapped.
-    const Fr *tw = inverse ? dom->inv29 : dom->fwd29;
-    for (int s = log_n - 1; s >= 0; --s) {
-      k_dif_stage<<<zk_blocks(n_cols * (n / 2), 256), 256, 0, ctx->stream>>>(data, data, n_cols, log_n, s, tw);
-      ZK_LAUNCH_CHECK(ctx);
-    }
-    if (log_n == 2 || inverse) {
-      // finish on the host side of the stream with a trivial kernel-free path: reuse tile kernel is impossible (< 8);
-      // use the scale kernel for n^-1 and a swap through scratch.
-      void *p;
-      rc = zk_scratch(ctx, 0, n_cols * n * sizeof(Fr), &p);
-      if (rc) return rc;
-      Fr *tmp = (Fr *)p;
-      rc = zk_copy_d2d(ctx, tmp, data, n_cols * n * sizeof(Fr));
-      if (rc) return rc;
-      if (log_n == 2) {
-        // swap elements 1 and 2 of every column: strided 2D copies
-        ZK_HIP(ctx, hipMemcpy2DAsync(data + 1, 4 * sizeof(Fr), tmp + 2, 4 * sizeof(Fr), sizeof(Fr), n_cols, hipMemcpyDeviceToDevice, ctx->stream));
-        ZK_HIP(ctx, hipMemcpy2DAsync(data + 2, 4 * sizeof(Fr), tmp + 1, 4 * sizeof(Fr), sizeof(Fr), n_cols, hipMemcpyDeviceToDevice, ctx->stream));
-      }
-      if (inverse) {
-        rc = zkfhe_fr_scale(ctx, (const zkfhe_fr *)data, (const zkfhe_fr *)&dom->n_inv, (zkfhe_fr *)data, n_cols * n);
-        if (rc) return rc;
-      }
-    }
-    return ZKFHE_OK;
-  }
-  if (log_n <= MAX_TILE_LOG) {
-    TileArgs a{};
-    a.in = src ? src : data;
-    a.out = data;
-    a.in_tile_stride = n;
-    a.col_stride_in = a.col_stride_out = n;
-    a.tw = inverse ? dom->inv29 : dom->fwd29;
-    a.pre = nullptr;
-    a.post = ninv_dev;
-    a.log_tiles = 0;
-    a.in_len = (int)n;
-    a.out_natural_tiles = 1;
-    if (log_n == 13 && a.in == a.out) {
-      // the 2^13 tile cuts a column into two workgroups that both read all of it: in place it goes through scratch
-      void *p;
-      rc = zk_scratch(ctx, 0, n_cols * n * sizeof(Fr), &p);
-      if (rc) return rc;
-      a.out = (Fr *)p;
-      rc = launch_tile_dyn(ctx, log_n, a, 1, (unsigned)n_cols);
-      if (rc) return rc;
-      return zk_copy_d2d(ctx, data, p, n_cols * n * sizeof(Fr));
-    }
-    return launch_tile_dyn(ctx, log_n, a, 1, (unsigned)n_cols);
-  }
-  // large: DIF stages down to 2^13 blocks, then tile NTT per block with bit-reversed strided scatter.
-  // Out of place (src given): the first pass reads src and writes the scratch arena, the later passes run in place there and the
-  // tile kernel scatters into the destination -- no copy anywhere.  In place: passes on the data, tiles into scratch, one copy back.
-  void *p;
-  rc = zk_scratch(ctx, 0, n_cols * n * sizeof(Fr), &p);
-  if (rc) return rc;
-  Fr *work = src ? (Fr *)p : data;
-  const Fr *pass_in = src ? src : data;
-  const int log_tiles = log_n - MAX_TILE_LOG;
-  const Fr *tw = inverse ? dom->inv29 : dom->fwd29;
-  int s_top = log_n - 1;
-  if (dif8_rows(log_n) && !pre) {
-    // all stages above the tile in one four-step pass (the coset shifts, if any, are folded into its tables)
-    rc = zk_dif8_pass(ctx, pass_in, work, n_cols, log_n, log_n - MAX_TILE_LOG, inverse, shifts_host, shifts_host ? rows : 1u);
-    if (rc) return rc;
-    pass_in = work;
-    s_top = MAX_TILE_LOG - 1;
-  } else {
-    ZK_ARG(ctx, shifts_host == nullptr);   // the radix-2 passes take the coset powers as a device table (pre)
-  }
-  for (int s = s_top; s >= MAX_TILE_LOG;) {
-    const int left = s - MAX_TILE_LOG + 1;
-    static const bool lds_pass = !(getenv("ZKFHE_NTT_LDS_PASS") && getenv("ZKFHE_NTT_LDS_PASS")[0] == '0');
-    if (left >= 4 && lds_pass) {   // four to six stages in one pass through LDS (seven: four, then three in registers)
-      const int S = left == 7 ? 4 : (left > 6 ? 6 : left);
-      const size_t tiles = n_cols * (n >> 10);
-      unsigned grid = (unsigned)(tiles < (size_t)ctx->num_cu * 64 ? tiles : (size_t)ctx->num_cu * 64);
-      if (S == 6) k_dif_lds<3><<<grid, 128, 0, ctx->stream>>>(pass_in, work, n_cols, log_n, s, tw, pre, rows);
-      else if (S == 5) k_dif_lds<2><<<grid, 128, 0, ctx->stream>>>(pass_in, work, n_cols, log_n, s, tw, pre, rows);
-      else k_dif_lds<1><<<grid, 128, 0, ctx->stream>>>(pass_in, work, n_cols, log_n, s, tw, pre, rows);
-      ZK_LAUNCH_CHECK(ctx);
-      pre = nullptr;
-      pass_in = work;
-      s -= S;
-      continue;
-    }
-    const int S = left >= 3 ? 3 : left;       // fuse up to three stages per pass over memory
-    size_t wk = n_cols * (n >> S);
-    unsigned grid = zk_blocks(wk, 256);
-    unsigned cap = (unsigned)ctx->num_cu * 16;
-    if (grid > cap) grid = cap;
-    if (S == 3) k_dif_fused<3><<<grid, 256, 0, ctx->stream>>>(pass_in, work, n_cols, log_n, s, tw, pre, rows);
-    else if (S == 2) k_dif_fused<2><<<grid, 256, 0, ctx->stream>>>(pass_in, work, n_cols, log_n, s, tw, pre, rows);
-    else k_dif_stage<<<grid, 256, 0, ctx->stream>>>(pass_in, work, n_cols, log_n, s, tw, pre, rows);
-    ZK_LAUNCH_CHECK(ctx);
-    pre = nullptr;   // only the first pass reads the unscaled input
-    pass_in = work;
-    s -= S;
-  }
-  const NttDomain *tdom;
-  rc = zk_domain(ctx, MAX_TILE_LOG, &tdom);
-  if (rc) return rc;
-  TileArgs a{};
-  a.in = work;
-  a.out = src ? data : (Fr *)p;
-  a.in_tile_stride = (size_t)1 << MAX_TILE_LOG;
-  a.col_stride_in = a.col_stride_out = n;
-  a.tw = inverse ? tdom->inv29 : tdom->fwd29;
-  a.post = ninv_dev;
-  a.log_tiles = log_tiles;
-  a.in_len = 1 << MAX_TILE_LOG;
-  a.out_natural_tiles = 0;
-  rc = launch_tile_dyn(ctx, MAX_TILE_LOG, a, 1u << log_tiles, (unsigned)n_cols);
-  if (rc) return rc;
-  if (!src) {
-    rc = zk_copy_d2d(ctx, data, p, n_cols * n * sizeof(Fr));
-    if (rc) return rc;
-  }
-  return ZKFHE_OK;
-}
-
-// Forward coset extension of the first `rows` cosets only (rows <= 2^lef), written DENSELY: column c, coset k1 at
-// out + (c * rows + k1) * n.  The prover's quotient has degree < 3n, so three of the four cosets determine it.
-extern "C++" int zk_coset_ntt_rows(zkfhe_ctx *ctx, const Fr *in_dev, Fr *out_dev, size_t n_cols, int log_n, int lef, const Fr &g, int rows) {
-  const int E = 1 << lef;
-  if (rows >= E) return zkfhe_coset_ntt_batch(ctx, (const zkfhe_fr *)in_dev, (zkfhe_fr *)out_dev, n_cols, log_n, lef, (const zkfhe_fr *)&g, 0);
-  if (!n_cols) return ZKFHE_OK;
-  const size_t n = (size_t)1 << log_n, nr = n * (size_t)rows;
-  const NttDomain *dom, *edom;
-  int rc = zk_domain(ctx, log_n, &dom);
-  if (rc) return rc;
-  rc = zk_domain(ctx, log_n + lef, &edom);
-  if (rc) return rc;
-  void *p;
-  rc = zk_scratch(ctx, 1, nr * sizeof(Fr), &p);
-  if (rc) return rc;
-  Fr *pre = (Fr *)p;
-  const void *pre13 = nullptr;
-  if (log_n == 13) {   // the 2^13 tile keeps its own tables (coset powers times the first-stage twiddles), built once
-    rc = zk_pre13(ctx, g, lef, rows, false, &pre13);
-    if (rc) return rc;
-  } else if (dif8_rows(log_n) && rows <= 4) {
-    // the four-step pass folds the coset powers into its own (cached) tables: no table of powers per call
-    Fr shifts[4];
-    Fr shift = g;
-    for (int k1 = 0; k1 < rows; ++k1) {
-      shifts[k1] = shift;
-      shift = shift * edom->omega;
-    }
-    return zk_ntt_impl(ctx, (const zkfhe_fr *)in_dev, (zkfhe_fr *)out_dev, n_cols * (size_t)rows, log_n, 0, nullptr, (unsigned)rows, shifts);
-  } else {
-    Fr shift = g;
-    const Fr c32 = zk_fr_to_29(Fr::one());
-    for (int k1 = 0; k1 < rows; ++k1) {   // (g w_ext^k1)^i as constant operands of the nine-limb multiply (2^261 form)
-      k_pow_table_scaled<<<zk_blocks(n, 256), 256, 0, ctx->stream>>>(c32, shift, pre + (size_t)k1 * n, n);
-      ZK_LAUNCH_CHECK(ctx);
-      shift = shift * edom->omega;
-    }
-  }
-  if (log_n > MAX_TILE_LOG) {
-    // one out-of-place transform of all (column, coset) rows into the destination; its first pass multiplies by the coset powers
-    // as it loads (it used to be a separate pre-scaling pass through a scratch arena: one more read and write of every row)
-    return zk_ntt_impl(ctx, (const zkfhe_fr *)in_dev, (zkfhe_fr *)out_dev, n_cols * (size_t)rows, log_n, 0, pre, (unsigned)rows);
-  }
-  TileArgs a{};
-  a.in = in_dev;
-  a.out = out_dev;
-  a.in_tile_stride = 0;
-  a.col_stride_in = n;
-  a.col_stride_out = nr;
-  a.tw = dom->fwd29;
-  a.pre = pre;
-  a.pre13 = pre13;
-  a.pre_tile_stride = n;
-  a.post = nullptr;
-  a.log_tiles = lef;
-  a.in_len = (int)n;
-  a.out_natural_tiles = 1;
-  return launch_tile_dyn(ctx, log_n, a, (unsigned)rows, (unsigned)n_cols);
-}
-
-// lagrange_to_coeff followed by coeff_to_extended on `rows` cosets, for the prover's extend step.  At n = 2^13 the inverse
-// transform runs out of place WITHOUT its final n^-1 (one product per coefficient less) and the coset tables carry the factor.
-extern "C++" int zk_extend_lagrange(zkfhe_ctx *ctx, const Fr *lagr_dev, Fr *tmp_dev, Fr *out_dev, size_t n_cols, int log_n, int lef, const Fr &g, int rows) {
-  if (!n_cols) return ZKFHE_OK;
-  const size_t n = (size_t)1 << log_n;
-  if (log_n != 13 || rows > (1 << lef)) {
-    int rc = zk_ntt_impl(ctx, (const zkfhe_fr *)lagr_dev, (zkfhe_fr *)tmp_dev, n_cols, log_n, 1);   // out of place: no copy
-    if (rc) return rc;
-    return zk_coset_ntt_rows(ctx, tmp_dev, out_dev, n_cols, log_n, lef, g, rows);
-  }
-  const NttDomain *dom;
-  int rc = zk_domain(ctx, log_n, &dom);
-  if (rc) return rc;
-  const void *pre13 = nullptr;
-  rc = zk_pre13(ctx, g, lef, rows, true, &pre13);
-  if (rc) return rc;
-  TileArgs a{};
-  a.in = lagr_dev;
-  a.out = tmp_dev;
-  a.in_tile_stride = n;
-  a.col_stride_in = a.col_stride_out = n;
-  a.tw = dom->inv29;
-  a.log_tiles = 0;
-  a.in_len = (int)n;
-  a.out_natural_tiles = 1;
-  rc = launch_tile_dyn(ctx, log_n, a, 1, (unsigned)n_cols);
-  if (rc) return rc;
-  TileArgs b{};
-  b.in = tmp_dev;
-  b.out = out_dev;
-  b.in_tile_stride = 0;
-  b.col_stride_in = n;
-  b.col_stride_out = n * (size_t)rows;
-  b.tw = dom->fwd29;
-  b.pre = tmp_dev;   // not read: the tile takes its multipliers from pre13
-  b.pre13 = pre13;
-  b.pre_tile_stride = n;
-  b.log_tiles = lef;
-  b.in_len = (int)n;
-  b.out_natural_tiles = 1;
-  return launch_tile_dyn(ctx, log_n, b, (unsigned)rows, (unsigned)n_cols);
-}
-
+// forward: coeff_to_extended, row k1 of a column = NTT_n of x[i] (g w_ext^k1)^i (zk_coset_ntt_rows with every coset);
+// inverse: extended_to_coeff, the row iNTTs (size n, scaled by n^-1) into scratch, then k_ext_combine across k1
 int zkfhe_coset_ntt_batch(zkfhe_ctx *ctx, const zkfhe_fr *in_dev, zkfhe_fr *out_dev, size_t n_cols, int log_n,
                           int log_ext_factor, const zkfhe_fr *g_host, int inverse) {
   ZK_ENTER(ctx);
@@ -620,114 +585,23 @@ int zkfhe_coset_ntt_batch(zkfhe_ctx *ctx, const zkfhe_fr *in_dev, zkfhe_fr *out_
   if (!n_cols) return ZKFHE_OK;
   ZK_ARG(ctx, in_dev != nullptr && out_dev != nullptr && n_cols < 65536);
   const int lef = log_ext_factor, E = 1 << lef;
-  const size_t n = (size_t)1 << log_n, ne = n * E;
   Fr g;
   memcpy(&g, g_host, 32);
+  if (!inverse) return zk_coset_ntt_rows(ctx, (const Fr *)in_dev, (Fr *)out_dev, n_cols, log_n, lef, g, E);
   const NttDomain *dom, *edom;
-  int rc = zk_domain(ctx, log_n, &dom);
-  if (rc) return rc;
-  rc = zk_domain(ctx, log_n + lef, &edom);
-  if (rc) return rc;
+  ZK_CK(zk_domain(ctx, log_n, &dom));
+  ZK_CK(zk_domain(ctx, log_n + lef, &edom));
+  const size_t bytes = ((n_cols << lef) << log_n) * sizeof(Fr);
   void *p;
-  if (!inverse) {
-    // row k1: NTT_n of x[i] * (g * w_ext^k1)^i.  pre table: [k1][i]
-    rc = zk_scratch(ctx, 1, ne * sizeof(Fr), &p);
-    if (rc) return rc;
-    Fr *pre = (Fr *)p;
-    const void *pre13 = nullptr;
-    if (log_n == 13) {
-      rc = zk_pre13(ctx, g, lef, E, false, &pre13);
-      if (rc) return rc;
-    } else if (dif8_rows(log_n) && E <= 4) {
-      Fr shifts[4];
-      Fr shift = g;
-      for (int k1 = 0; k1 < E; ++k1) {
-        shifts[k1] = shift;
-        shift = shift * edom->omega;
-      }
-      return zk_ntt_impl(ctx, in_dev, out_dev, n_cols * E, log_n, 0, nullptr, (unsigned)E, shifts);
-    } else {
-      Fr shift = g;
-      const Fr c32 = zk_fr_to_29(Fr::one());
-      for (int k1 = 0; k1 < E; ++k1) {
-        k_pow_table_scaled<<<zk_blocks(n, 256), 256, 0, ctx->stream>>>(c32, shift, pre + (size_t)k1 * n, n);
-        ZK_LAUNCH_CHECK(ctx);
-        shift = shift * edom->omega;
-      }
-    }
-    if (log_n > MAX_TILE_LOG) {
-      // rows longer than one tile: pre-scale into the output rows, then a batched size-n NTT over all (column, k1) rows
-      return zk_ntt_impl(ctx, in_dev, out_dev, n_cols * E, log_n, 0, pre, (unsigned)E);
-    }
-    TileArgs a{};
-    a.in = (const Fr *)in_dev;
-    a.out = (Fr *)out_dev;
-    a.in_tile_stride = 0;  // every coset row of a column starts from the same n coefficients
-    a.col_stride_in = n;
-    a.col_stride_out = ne;
-    a.tw = dom->fwd29;
-    a.pre = pre;
-    a.pre13 = pre13;
-    a.pre_tile_stride = n;
-    a.post = nullptr;
-    a.log_tiles = lef;
-    a.in_len = (int)n;
-    a.out_natural_tiles = 1;
-    return launch_tile_dyn(ctx, log_n, a, (unsigned)E, (unsigned)n_cols);
+  if (log_n > NTT_TILE_LOG) {
+    // slot 2, not slot 0: the long-row transform takes slot 0 as its own work arena while it writes these rows
+    ZK_CK(zk_scratch(ctx, 2, bytes, &p));
+    ZK_CK(zk_ntt_impl(ctx, in_dev, (zkfhe_fr *)p, n_cols * E, log_n, 1));
+  } else {
+    ZK_CK(zk_scratch(ctx, 0, bytes, &p));   // a tile launch needs no arena of its own
+    ZK_CK(launch_tile_dyn(ctx, log_n, tiles_independent((const Fr *)in_dev, (Fr *)p, log_n, lef, dom->inv29, dom->n_inv29_dev), (unsigned)E, (unsigned)n_cols));
   }
-  // inverse: rows iNTT (size n, scaled by n^-1) into scratch, then combine across k1
-  if (log_n > MAX_TILE_LOG) {
-    // rows transformed out of place straight into scratch slot 2 (the transform's own work arena is slot 0), combined from there
-    rc = zk_scratch(ctx, 2, n_cols * ne * sizeof(Fr), &p);
-    if (rc) return rc;
-    Fr *rows2 = (Fr *)p;
-    rc = zk_ntt_impl(ctx, in_dev, (zkfhe_fr *)rows2, n_cols * E, log_n, 1);
-    if (rc) return rc;
-    rc = zk_scratch(ctx, 1, ne * sizeof(Fr), &p);
-    if (rc) return rc;
-    Fr *scale2 = (Fr *)p;
-    const Fr einv2 = fp_inv<FrP>(zk_fr_from_u64((uint64_t)E));
-    const Fr ginv2 = fp_inv<FrP>(g);
-    k_pow_table_scaled<<<zk_blocks(ne, 256), 256, 0, ctx->stream>>>(zk_fr_to_29(einv2), ginv2, scale2, ne);
-    ZK_LAUNCH_CHECK(ctx);
-    unsigned grid2 = zk_blocks(n_cols * n, 256);
-    if (lef == 1) k_ext_combine<1><<<grid2, 256, 0, ctx->stream>>>(rows2, (Fr *)out_dev, n_cols, log_n, edom->inv29, scale2);
-    else if (lef == 2) k_ext_combine<2><<<grid2, 256, 0, ctx->stream>>>(rows2, (Fr *)out_dev, n_cols, log_n, edom->inv29, scale2);
-    else k_ext_combine<3><<<grid2, 256, 0, ctx->stream>>>(rows2, (Fr *)out_dev, n_cols, log_n, edom->inv29, scale2);
-    ZK_LAUNCH_CHECK(ctx);
-    return ZKFHE_OK;
-  }
-  rc = zk_scratch(ctx, 0, n_cols * ne * sizeof(Fr), &p);
-  if (rc) return rc;
-  Fr *rows = (Fr *)p;
-  const void *q = dom->n_inv29_dev;
-  TileArgs a{};
-  a.in = (const Fr *)in_dev;
-  a.out = rows;
-  a.in_tile_stride = n;
-  a.col_stride_in = ne;
-  a.col_stride_out = ne;
-  a.tw = dom->inv29;
-  a.post = (const Fr *)q;
-  a.log_tiles = lef;
-  a.in_len = (int)n;
-  a.out_natural_tiles = 1;
-  rc = launch_tile_dyn(ctx, log_n, a, (unsigned)E, (unsigned)n_cols);
-  if (rc) return rc;
-  // scale[j] = 2^-lef * g^-j
-  rc = zk_scratch(ctx, 1, ne * sizeof(Fr), &p);
-  if (rc) return rc;
-  Fr *scale = (Fr *)p;
-  Fr einv = fp_inv<FrP>(zk_fr_from_u64((uint64_t)E));
-  Fr ginv = fp_inv<FrP>(g);
-  k_pow_table_scaled<<<zk_blocks(ne, 256), 256, 0, ctx->stream>>>(zk_fr_to_29(einv), ginv, scale, ne);
-  ZK_LAUNCH_CHECK(ctx);
-  unsigned grid = zk_blocks(n_cols * n, 256);
-  if (lef == 1) k_ext_combine<1><<<grid, 256, 0, ctx->stream>>>(rows, (Fr *)out_dev, n_cols, log_n, edom->inv29, scale);
-  else if (lef == 2) k_ext_combine<2><<<grid, 256, 0, ctx->stream>>>(rows, (Fr *)out_dev, n_cols, log_n, edom->inv29, scale);
-  else k_ext_combine<3><<<grid, 256, 0, ctx->stream>>>(rows, (Fr *)out_dev, n_cols, log_n, edom->inv29, scale);
-  ZK_LAUNCH_CHECK(ctx);
-  return ZKFHE_OK;
+  return ext_combine(ctx, (const Fr *)p, (Fr *)out_dev, n_cols, log_n, lef, g, edom);
 }
 
 }  // extern "C"

@@ -206,6 +206,48 @@ Fr fr_pow_u64(Fr b, uint64_t e) {
   return r;
 }
 
+// The context's cache of device tables (ctx->dif8).  A bounded cache: the prover uses one entry of constants and one plain table
+// per direction, and one table per coset row; a caller that sweeps the coset generator must not grow device memory for the life
+// of the context.
+using Dif8Key = std::array<uint64_t, 8>;
+constexpr size_t DIF8_CACHE_MAX = 24;
+
+Dif8Key dif8_key(int log_n, int S, int inverse, const Fr *h /* nullptr: the butterfly constants */) {
+  Dif8Key key{};
+  key[0] = (uint64_t)log_n | ((uint64_t)S << 8) | ((uint64_t)(inverse ? 1 : 0) << 16) | ((uint64_t)(h ? 0 : 1) << 32);
+  if (h)
+    for (int i = 0; i < 4; ++i) key[1 + i] = (uint64_t)h->l[2 * i] | ((uint64_t)h->l[2 * i + 1] << 32);
+  return key;
+}
+
+// blocking copy + a wait on the null stream it ran on: the kernels that read the table run on ctx->stream, which is
+// hipStreamNonBlocking and would not order itself behind the copy (once per table: they are cached with the context)
+int dif8_upload(zkfhe_ctx *ctx, void *dst, const void *src, size_t bytes) {
+  if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+    return zk_fail_msg(ctx, ZKFHE_EHIP, "zk_dif8_pass: constant upload failed");
+  return ZKFHE_OK;
+}
+
+// the cached entry of `key`; on a miss, `bytes` of device memory that fill(pointer) has filled -- released again if it fails
+template <class Fill>
+int dif8_cached(zkfhe_ctx *ctx, const Dif8Key &key, size_t bytes, Fill fill, const void **out) {
+  auto it = ctx->dif8.find(key);
+  if (it == ctx->dif8.end()) {
+    struct Owned {   // released unless handed to the cache
+      void *p = nullptr;
+      ~Owned() {
+        if (p) (void)hipFree(p);
+      }
+    } own;
+    ZK_HIP(ctx, hipMalloc(&own.p, bytes));
+    ZK_CK(fill(own.p));
+    it = ctx->dif8.emplace(key, own.p).first;
+    own.p = nullptr;
+  }
+  *out = it->second;
+  return ZKFHE_OK;
+}
+
 }  // namespace
 
 // The top S (3 or 6) DIF stages of `n_cols` transforms of 2^log_n points, src -> dst (out of place or in place: a workgroup reads
@@ -217,6 +259,17 @@ int zk_dif8_pass(zkfhe_ctx *ctx, const Fr *src, Fr *dst, size_t n_cols, int log_
   const size_t n = (size_t)1 << log_n, q = n >> S;
   const Fr w = inverse ? fp_inv<FrP>(zk_fr_root_of_unity(log_n)) : zk_fr_root_of_unity(log_n);
   const Fr c32 = zk_fr_to_29(Fr::one());
+  Fr h[4];   // the shift of each row; one: no coset
+  for (unsigned k1 = 0; k1 < rows; ++k1) h[k1] = shifts_host ? shifts_host[k1] : Fr::one();
+  // Room for what this call is missing, made before any entry is looked up: on overflow everything goes, and the stream is drained
+  // first -- queued passes may still be reading the tables.
+  size_t missing = ctx->dif8.count(dif8_key(log_n, S, inverse, nullptr)) ? 0 : 1;
+  for (unsigned k1 = 0; k1 < rows; ++k1) missing += ctx->dif8.count(dif8_key(log_n, S, inverse, &h[k1])) ? 0 : 1;
+  if (missing && ctx->dif8.size() + missing > DIF8_CACHE_MAX) {
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (auto &kv : ctx->dif8) (void)hipFree(kv.second);
+    ctx->dif8.clear();
+  }
   Dif8Args A{};
   A.src = src;
   A.dst = dst;
@@ -224,69 +277,37 @@ int zk_dif8_pass(zkfhe_ctx *ctx, const Fr *src, Fr *dst, size_t n_cols, int log_
   A.log_n = log_n;
   A.rows = rows;
   A.coset = shifts_host != nullptr;
+  const void *entry;
   // constants of the butterflies: w8, w4, w8^3 and w64^(g s)
-  {
-    std::array<uint64_t, 8> key{};
-    key[0] = (uint64_t)log_n | ((uint64_t)S << 8) | ((uint64_t)(inverse ? 1 : 0) << 16) | ((uint64_t)1 << 32);
-    auto it = ctx->dif8.find(key);
-    if (it == ctx->dif8.end()) {
-      std::vector<LwMem> h(3 + 7 * 8);
-      const Fr w8 = fr_pow_u64(w, n >> 3), w64 = fr_pow_u64(w, n >> 6);
-      h[0] = lw_from_packed(zk_fr_to_29(w8));
-      h[1] = lw_from_packed(zk_fr_to_29(w8 * w8));
-      h[2] = lw_from_packed(zk_fr_to_29(w8 * w8 * w8));
-      for (unsigned g = 0; g < 8; ++g)
-        for (unsigned s = 1; s < 8; ++s) h[3 + 7 * g + (s - 1)] = lw_from_packed(zk_fr_to_29(fr_pow_u64(w64, (uint64_t)g * s)));
-      void *d = nullptr;
-      ZK_HIP(ctx, hipMalloc(&d, h.size() * sizeof(LwMem)));
-      // blocking copy + a wait on the null stream it ran on: the kernels that read the table run on ctx->stream, which is
-      // hipStreamNonBlocking and would not order itself behind the copy (once per table: they are cached with the context)
-      if (hipMemcpy(d, h.data(), h.size() * sizeof(LwMem), hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-        (void)hipFree(d);
-        return zk_fail_msg(ctx, ZKFHE_EHIP, "zk_dif8_pass: constant upload failed");
-      }
-      it = ctx->dif8.emplace(key, d).first;
-    }
-    A.consts = (const LwMem *)it->second;
-  }
+  ZK_CK(dif8_cached(ctx, dif8_key(log_n, S, inverse, nullptr), (3 + 7 * 8) * sizeof(LwMem), [&](void *d) {
+    std::vector<LwMem> c(3 + 7 * 8);
+    const Fr w8 = fr_pow_u64(w, n >> 3), w64 = fr_pow_u64(w, n >> 6);
+    c[0] = lw_from_packed(zk_fr_to_29(w8));
+    c[1] = lw_from_packed(zk_fr_to_29(w8 * w8));
+    c[2] = lw_from_packed(zk_fr_to_29(w8 * w8 * w8));
+    for (unsigned g = 0; g < 8; ++g)
+      for (unsigned s = 1; s < 8; ++s) c[3 + 7 * g + (s - 1)] = lw_from_packed(zk_fr_to_29(fr_pow_u64(w64, (uint64_t)g * s)));
+    return dif8_upload(ctx, d, c.data(), c.size() * sizeof(LwMem));
+  }, &entry));
+  A.consts = (const LwMem *)entry;
+  // per coset row: the M constants (h^q)^m, then the n entries of T
   for (unsigned k1 = 0; k1 < rows; ++k1) {
-    const Fr h = shifts_host ? shifts_host[k1] : Fr::one();
-    std::array<uint64_t, 8> key{};
-    key[0] = (uint64_t)log_n | ((uint64_t)S << 8) | ((uint64_t)(inverse ? 1 : 0) << 16);
-    for (int i = 0; i < 4; ++i) key[1 + i] = (uint64_t)h.l[2 * i] | ((uint64_t)h.l[2 * i + 1] << 32);
-    auto it = ctx->dif8.find(key);
-    if (it == ctx->dif8.end()) {
-      // a bounded cache: the prover uses one plain table per direction and one per coset row; a caller that sweeps the coset
-      // generator must not grow device memory for the life of the context
-      if (ctx->dif8.size() >= 24) {
-        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (auto &kv : ctx->dif8) (void)hipFree(kv.second);
-        ctx->dif8.clear();
-        return zk_dif8_pass(ctx, src, dst, n_cols, log_n, S, inverse, shifts_host, rows);   // rebuild what this call needs
-      }
-      Fr *d = nullptr;
-      ZK_HIP(ctx, hipMalloc((void **)&d, ((size_t)M + n) * sizeof(Fr)));
+    ZK_CK(dif8_cached(ctx, dif8_key(log_n, S, inverse, &h[k1]), ((size_t)M + n) * sizeof(Fr), [&](void *d) {
       std::vector<Fr> cp(M);
-      const Fr hq = fr_pow_u64(h, q);
+      const Fr hq = fr_pow_u64(h[k1], q);
       Fr cur = c32;
       for (int m = 0; m < M; ++m) {
         cp[m] = cur;
         cur = cur * hq;
       }
-      if (hipMemcpy(d, cp.data(), M * sizeof(Fr), hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-        (void)hipFree(d);
-        return zk_fail_msg(ctx, ZKFHE_EHIP, "zk_dif8_pass: constant upload failed");
-      }
+      ZK_CK(dif8_upload(ctx, d, cp.data(), M * sizeof(Fr)));
       unsigned grid = zk_blocks(n, 256);
       if (grid > 4096) grid = 4096;
-      k_dif8_table<<<grid, 256, 0, ctx->stream>>>(c32, h, w, log_n, S, d + M);
-      if (hipGetLastError() != hipSuccess) {
-        (void)hipFree(d);
-        return zk_fail_msg(ctx, ZKFHE_EHIP, "zk_dif8_pass: table launch failed");
-      }
-      it = ctx->dif8.emplace(key, (void *)d).first;
-    }
-    A.tab[k1] = (const Fr *)it->second;
+      k_dif8_table<<<grid, 256, 0, ctx->stream>>>(c32, h[k1], w, log_n, S, (Fr *)d + M);
+      if (hipGetLastError() != hipSuccess) return zk_fail_msg(ctx, ZKFHE_EHIP, "zk_dif8_pass: table launch failed");
+      return (int)ZKFHE_OK;
+    }, &entry));
+    A.tab[k1] = (const Fr *)entry;
   }
   if (S == 3) {
     const size_t total = n_cols * (q >> 8);

@@ -264,3 +264,9 @@ inline int launch_tile(zkfhe_ctx *ctx, const TileArgs &a, unsigned tiles, unsign
 
 
 }  // namespace zk
+
+// The launchers, one per tile size: zk_launch_tile_3 .. _12 are the instances of ntt_tile_inst.hip, zk_launch_tile_13 is ntt13.hip.
+#define ZK_TILE_SIZES(X) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
+#define ZK_DECLARE_TILE_LAUNCHER(k) int zk_launch_tile_##k(zkfhe_ctx *ctx, const zk::TileArgs &a, unsigned tiles, unsigned cols);
+ZK_TILE_SIZES(ZK_DECLARE_TILE_LAUNCHER)
+#undef ZK_DECLARE_TILE_LAUNCHER
