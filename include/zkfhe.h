@@ -8,6 +8,7 @@
  *   zkfhe_ntt_batch        <- halo2_proofs::arithmetic::best_fft(&mut [Fr], omega, log_n) and
  *                             poly::EvaluationDomain::{lagrange_to_coeff, coeff_to_lagrange}
  *   zkfhe_coset_ntt_batch  <- EvaluationDomain::{coeff_to_extended, extended_to_coeff}
+ *   zkfhe_g1_fft           <- best_fft::<G1> as g_to_lagrange uses it (ParamsKZG::downsize: zkfhe_srs_load_downsized)
  *   zkfhe_basis_create     <- poly::kzg::commitment::ParamsKZG {g, g_lagrange} (the SRS halves)
  *   zkfhe_msm_batch        <- arithmetic::best_multiexp(&[Fr], &[G1Affine]) as used by
  *                             ParamsKZG::{commit, commit_lagrange}
@@ -229,6 +230,14 @@ int zkfhe_g1_add(zkfhe_ctx *ctx, const zkfhe_g1_affine *a_dev, const zkfhe_g1_af
 /* out[i] = k[i] * p[i] */
 int zkfhe_g1_mul(zkfhe_ctx *ctx, const zkfhe_g1_affine *p_dev, const zkfhe_fr *k_dev,
                  zkfhe_g1_affine *out_dev, size_t n);
+/* halo2 best_fft::<G1> / g_to_lagrange.  points_dev: 2^log_n affine points, Montgomery limbs, identity = (0, 0); in place,
+ * natural order in and out.  inverse == 0: out[i] = sum_j w^(ij) P_j.  inverse != 0: out[i] = n^-1 sum_j w^(-ij) P_j.
+ * w = the 2^log_n-th root of zkfhe_ntt_batch.  1 <= log_n <= 20.  Waits.
+ * Any points on the curve are taken: equal, opposite and identity summands go through the complete addition.  Between the stages
+ * the points stay in the accumulator form in the context's scratch (128 B x 2^log_n, and 256 B x 2^log_n of window tables); one
+ * field inversion per point at the end. */
+int zkfhe_g1_fft(zkfhe_ctx *ctx, zkfhe_g1_affine *points_dev, int log_n, int inverse);
+#define ZKFHE_PROF_G1_FFT 23   /* k_g1_fft_shared, k_g1_fft_window: 256 B per point and stage; ops = scalar multiplications */
 /* Decompression of n 32-byte compressed G1 points (the proof byte stream's form: x little-endian, the sign and identity bits of
  * byte 31 as ZKFHE_POINT_ENCODING selects) into Montgomery affine points, identity = (0, 0), with one status per point.  Any bytes
  * are accepted; a point whose status is not ZKFHE_PT_OK is written as (0, 0).  The same checks, in the same order, as the host
@@ -374,8 +383,33 @@ int zkfhe_srs_file_g2(const char *path, uint32_t *k_out, uint8_t g2_le[128], uin
 int zkfhe_chacha20_block(const uint8_t key[32], const uint32_t counter_nonce[4], uint8_t out[64]);
 /* An SRS from outside (a ceremony file such as the reference's params/kzg_bn254_<k>.srs, README.md:34-38, read by the
  * caller): 2^k points g[i] = s^i G and g_lagrange[i] = L_i(s) G, host memory, affine, Montgomery limbs (halo2curves'
- * in-memory G1Affine).  The library only builds its MSM tables from them; nothing is checked about the ceremony. */
+ * in-memory G1Affine).  The library only builds its MSM tables from them; nothing is checked about the ceremony here:
+ * zkfhe_srs_check (below) checks the structure of an SRS that has its G2 half, and zkfhe_srs_from_monomial /
+ * zkfhe_srs_load_downsized compute g_lagrange themselves for a caller who holds the monomial powers only. */
 int zkfhe_srs_from_points(zkfhe_ctx *ctx, uint32_t k, const zkfhe_g1_affine *g_host, const zkfhe_g1_affine *g_lagrange_host, zkfhe_srs **out);
+/* An SRS from a ceremony's monomial powers alone: g[i] = s^i G for i < n_g, n_g >= 2^k (a longer list is cut: halo2's
+ * ParamsKZG::downsize).  g_lagrange is computed here (zkfhe_g1_fft, inverse).  g2_le / s_g2_le as zkfhe_srs_set_g2, or both NULL.
+ * Unsharded.  ZKFHE_EINVAL, message prefixed "srs_from_monomial:", for a NULL argument or exactly one G2 argument, k outside
+ * 3..20, n_g < 2^k, a coordinate >= p, a point off its curve, or the identity among the 2^k powers. */
+int zkfhe_srs_from_monomial(zkfhe_ctx *ctx, uint32_t k, const zkfhe_g1_affine *g_host, size_t n_g,
+                            const uint8_t g2_le[128], const uint8_t s_g2_le[128], zkfhe_srs **out);
+/* The same from a halo2 RawBytes params file of k_file >= k: reads the header, the first 2^k points of g and the G2 tail, never the
+ * file's g_lagrange.  Refusals as above, prefixed "srs_load_downsized:", and for k_file < k or a short or misframed file. */
+int zkfhe_srs_load_downsized(zkfhe_ctx *ctx, const char *path, uint32_t k, zkfhe_srs **out);
+/* Checks that an unsharded SRS with its G2 half (g2, s_g2) has the structure of one; *failed = 0 means every check passed.
+ *  - powers: with scalars r_i drawn from the seed, A = sum r_i g[i] and B = sum r_i g[i+1] (i < 2^k - 1; one MSM call of two
+ *    columns) must satisfy e(A, s_g2) e(-B, g2) = 1 (host pairing): g[i+1] = s g[i] for the s of (g2, s_g2), up to 2^-250.
+ *  - Lagrange: for a coefficient column c drawn from the seed, MSM(g, c) = MSM(g_lagrange, NTT(c)): a g_lagrange that is not the
+ *    Lagrange form of g passes with probability 1/r.
+ *  - generator: g[0] = (1, 2) and both G2 points on the twist curve.
+ * seed: 32 bytes the SRS's maker could not predict (NULL: the OS's entropy); a maker who knows the seed can pass a bad SRS.
+ * What this does NOT check: that anyone forgot s -- no computation on the points can; and that g2 / s_g2 lie in the prime-order
+ * subgroup of the twist: only the curve equation is tested, as halo2's RawBytes read does.
+ * ZKFHE_EINVAL with a message for an SRS without G2 (zkfhe_srs_set_g2) and for a sharded SRS. */
+#define ZKFHE_SRS_BAD_POWERS 1     /* g is not (g[0], s g[0], s^2 g[0], ...) for the s of (g2, s_g2) */
+#define ZKFHE_SRS_BAD_LAGRANGE 2   /* g_lagrange is not the Lagrange form of g */
+#define ZKFHE_SRS_BAD_GENERATOR 4  /* g[0] is not the generator (1, 2), or g2 / s_g2 is not on the twist curve */
+int zkfhe_srs_check(zkfhe_ctx *ctx, const zkfhe_srs *srs, const uint8_t seed[32], uint32_t *failed);
 /* The same seeded setup, but only this rank's point range of both halves (1 / world of the table memory); keygen and prove
  * called with it shard every commitment over `comm` (see "intra-proof multi-GPU").  comm must outlive the SRS. */
 int zkfhe_srs_create_sharded(zkfhe_ctx *ctx, zkfhe_comm *comm, uint32_t k, const uint8_t *seed, size_t seed_len, zkfhe_srs **out);

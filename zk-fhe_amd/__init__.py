@@ -25,6 +25,8 @@ PROF_BFV_HOIST, PROF_BFV_LINEAR = 16, 17   # ... and of the hoisted rotations an
 PROF_BFV_BSGS_INNER, PROF_BFV_BSGS_GIANT = 18, 19   # ... and of the baby-step/giant-step transform's own kernels
 PROF_BFV_DOT = 20   # ... and of the fused inner product's accumulation
 PROF_BFV_PCKS_COMBINE, PROF_BFV_REFRESH_COMBINE = 21, 22   # ... and of the key-switch and refresh combines
+PROF_G1_FFT = 23   # ... and of the G1 FFT's butterfly kernels
+SRS_BAD_POWERS, SRS_BAD_LAGRANGE, SRS_BAD_GENERATOR = 1, 2, 4   # the bits of Srs.check (zkfhe_srs_check)
 
 EXPORTS = [
     "zkfhe_ctx_create", "zkfhe_ctx_destroy", "zkfhe_last_error", "zkfhe_sync", "zkfhe_stream", "zkfhe_device_info",
@@ -34,7 +36,7 @@ EXPORTS = [
     "zkfhe_fr_batch_invert", "zkfhe_fr_batch_invert_mul", "zkfhe_fr9_op", "zkfhe_fr_sqr_chain", "zkfhe_fq29_sqr_chain",
     "zkfhe_ntt_batch", "zkfhe_ntt_batch_to", "zkfhe_coset_ntt_batch",
     "zkfhe_basis_create", "zkfhe_basis_destroy", "zkfhe_basis_len", "zkfhe_msm_batch",
-    "zkfhe_g1_add", "zkfhe_g1_mul", "zkfhe_msm_sparse", "zkfhe_msm_batch_xyzz", "zkfhe_msm_sparse_xyzz", "zkfhe_g1_xyzz_to_affine", "zkfhe_basis_has_multiples", "zkfhe_basis_table_bits", "zkfhe_basis_table_bytes", "zkfhe_srs_table_bits", "zkfhe_srs_table_info",
+    "zkfhe_g1_add", "zkfhe_g1_mul", "zkfhe_g1_fft", "zkfhe_msm_sparse", "zkfhe_msm_batch_xyzz", "zkfhe_msm_sparse_xyzz", "zkfhe_g1_xyzz_to_affine", "zkfhe_basis_has_multiples", "zkfhe_basis_table_bits", "zkfhe_basis_table_bytes", "zkfhe_srs_table_bits", "zkfhe_srs_table_info",
     "zkfhe_comm_unique_id", "zkfhe_comm_create", "zkfhe_comm_create_with_transport", "zkfhe_comm_destroy", "zkfhe_comm_rank", "zkfhe_comm_world", "zkfhe_comm_active",
     "zkfhe_comm_point_range", "zkfhe_comm_all_gather", "zkfhe_comm_all_gather_async", "zkfhe_msm_batch_sharded", "zkfhe_msm_batch_sharded_async", "zkfhe_comm_join", "zkfhe_comm_record_event", "zkfhe_srs_create_sharded",
     "zkfhe_witness_poly_mul_u64", "zkfhe_host_poly_mul_u32", "zkfhe_witness_div_mod",
@@ -42,6 +44,7 @@ EXPORTS = [
     "zkfhe_bfv_tables_copy_fixed", "zkfhe_bfv_tables_copy_instance", "zkfhe_bfv_tables_copy_copies",
     "zkfhe_bfv_tables_copy_break_points", "zkfhe_bfv_mock_check", "zkfhe_bfv_tables_poke_advice",
     "zkfhe_srs_create", "zkfhe_srs_from_points", "zkfhe_srs_destroy", "zkfhe_srs_save", "zkfhe_srs_drop_host_copy", "zkfhe_srs_load", "zkfhe_srs_g2", "zkfhe_srs_set_g2", "zkfhe_srs_file_g2",
+    "zkfhe_srs_from_monomial", "zkfhe_srs_load_downsized", "zkfhe_srs_check",
     "zkfhe_chacha20_block", "zkfhe_snark_encode", "zkfhe_snark_decode", "zkfhe_bfv_keygen", "zkfhe_bfv_pk_destroy", "zkfhe_bfv_pk_release_ctx", "zkfhe_bfv_pk_info", "zkfhe_bfv_pk_prefix_cache",
     "zkfhe_bfv_pk_commitments", "zkfhe_bfv_pk_break_points", "zkfhe_bfv_pk_prehash", "zkfhe_bfv_prove", "zkfhe_bfv_pk_export_vk", "zkfhe_bfv_pk_save", "zkfhe_bfv_pk_load", "zkfhe_bfv_witness_stream", "zkfhe_lookup_permute", "zkfhe_bfv_verify", "zkfhe_bfv_verify_g2",
     "zkfhe_g1_decompress", "zkfhe_msm_segmented", "zkfhe_bfv_verify_batch",
@@ -116,6 +119,7 @@ def load_library():
     lib.zkfhe_msm_batch.argtypes = [vp, vp, vp, sz, vp]
     lib.zkfhe_g1_add.argtypes = [vp, vp, vp, vp, sz]
     lib.zkfhe_g1_mul.argtypes = [vp, vp, vp, vp, sz]
+    lib.zkfhe_g1_fft.argtypes = [vp, vp, ci, ci]
     lib.zkfhe_witness_poly_mul_u64.argtypes = [vp, vp, vp, sz, vp]
     lib.zkfhe_witness_div_mod.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, sz]
     _lib = lib
@@ -412,6 +416,20 @@ class Context:
         out = dp.download(shape=p.shape)
         dp.free(), dk.free()
         return out
+
+    def g1_fft(self, points, inverse=False):
+        """zkfhe_g1_fft: the FFT over 2^log_n G1 points ((n, 8) uint64, affine Montgomery limbs, identity = (0, 0)) with the root of
+        unity of ntt(); inverse=True is halo2's g_to_lagrange (w^-1 and n^-1).  Natural order in and out."""
+        p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        n = p.shape[0]
+        if n < 2 or n & (n - 1):
+            raise ValueError("g1_fft needs 2^log_n points, log_n >= 1")
+        dp = self.to_device(p)
+        try:
+            self._check(self.lib.zkfhe_g1_fft(self.h, self._p(dp), n.bit_length() - 1, 1 if inverse else 0))
+            return dp.download(shape=p.shape)
+        finally:
+            dp.free()
 
     def g1_decompress(self, data):
         """32-byte compressed G1 points (bytes, a multiple of 32 long) -> (points (n, 8) uint64 Montgomery affine, status (n,) int32:
@@ -1591,6 +1609,49 @@ class Srs:
         self.ctx, self.h, self.comm = ctx, h, None
         self.k = int.from_bytes(open(path, "rb").read(4), "little")
         return self
+
+    @staticmethod
+    def _g2_bytes(p):
+        return b"".join(int(v).to_bytes(32, "little") for v in (p[0][0], p[0][1], p[1][0], p[1][1]))
+
+    @classmethod
+    def from_monomial(cls, ctx, k, g, g2=None, s_g2=None):
+        """zkfhe_srs_from_monomial: an SRS from a ceremony's powers g[i] = s^i G alone ((n_g, 8) uint64, n_g >= 2^k: a longer list is
+        cut, halo2's downsize); g_lagrange is computed on the GPU.  g2, s_g2: as set_g2 takes them, or neither."""
+        lib = ctx.lib
+        lib.zkfhe_srs_from_monomial.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        lib.zkfhe_srs_destroy.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        a = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+        self = cls.__new__(cls)
+        h = ctypes.c_void_p()
+        ctx._check(lib.zkfhe_srs_from_monomial(ctx.h, k, a.ctypes.data_as(ctypes.c_void_p), a.shape[0], None if g2 is None else cls._g2_bytes(g2),
+                                               None if s_g2 is None else cls._g2_bytes(s_g2), ctypes.byref(h)))
+        self.ctx, self.h, self.comm, self.k = ctx, h, None, k
+        return self
+
+    @classmethod
+    def load_downsized(cls, ctx, path, k):
+        """zkfhe_srs_load_downsized: the SRS of 2^k points from a params file of k_file >= k (halo2's ParamsKZG::downsize): the first
+        2^k powers and the G2 half are read, g_lagrange is computed on the GPU."""
+        lib = ctx.lib
+        lib.zkfhe_srs_load_downsized.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+        lib.zkfhe_srs_destroy.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self = cls.__new__(cls)
+        h = ctypes.c_void_p()
+        ctx._check(lib.zkfhe_srs_load_downsized(ctx.h, os.fsencode(path), k, ctypes.byref(h)))
+        self.ctx, self.h, self.comm, self.k = ctx, h, None, k
+        return self
+
+    def check(self, seed=None):
+        """zkfhe_srs_check: 0, or the SRS_BAD_* bits of the checks that failed.  seed: 32 bytes the SRS's maker could not predict
+        (None: the OS's entropy).  Says nothing about whether anyone forgot s."""
+        lib = self.ctx.lib
+        lib.zkfhe_srs_check.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)]
+        if seed is not None and len(bytes(seed)) != 32:
+            raise ValueError("the seed of Srs.check is 32 bytes")
+        failed = ctypes.c_uint32()
+        self.ctx._check(lib.zkfhe_srs_check(self.ctx.h, self.h, None if seed is None else bytes(seed), ctypes.byref(failed)))
+        return int(failed.value)
 
     def save(self, path):
         lib = self.ctx.lib

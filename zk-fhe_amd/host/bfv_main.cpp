@@ -125,8 +125,46 @@ static void write_pinning(const std::string &path, const zkfhe_bfv_config &c, co
     }                                                                     \
   } while (0)
 
+// bfv -k <k> srs --from <file>: $PARAMS_DIR/kzg_bn254_<k>.srs out of a larger params file (halo2 ParamsKZG::downsize): the first 2^k
+// powers and the G2 half are read, g_lagrange is recomputed on the GPU, the result is checked (zkfhe_srs_check) and only then written
+static int srs_command(unsigned k, const std::string &from) {
+  if (from.empty()) {
+    fprintf(stderr, "srs needs --from <params file of k_file >= %u>\n", k);
+    return 2;
+  }
+  const char *pdir = getenv("PARAMS_DIR");
+  const std::string params_dir = pdir && pdir[0] ? pdir : "params";
+  const std::string srs_path = params_dir + "/kzg_bn254_" + std::to_string(k) + ".srs";
+  struct stat sb;
+  if (stat(srs_path.c_str(), &sb) == 0) {
+    fprintf(stderr, "srs: %s exists; not overwritten\n", srs_path.c_str());
+    return 1;
+  }
+  setenv("ZKFHE_TABLE_GB", "2", 0);   // one check and one save: no wide tables
+  zkfhe_ctx *ctx = nullptr;
+  if (zkfhe_ctx_create(0, nullptr, &ctx)) {
+    fprintf(stderr, "no gfx950 device: %s\n", zkfhe_last_error(nullptr));
+    return 1;
+  }
+  zkfhe_srs *srs = nullptr;
+  CHECK(zkfhe_srs_load_downsized(ctx, from.c_str(), k, &srs));
+  uint32_t failed = 0;
+  CHECK(zkfhe_srs_check(ctx, srs, nullptr, &failed));
+  if (failed) {
+    fprintf(stderr, "srs: %s does not have the structure of an SRS:%s%s%s\n", from.c_str(), failed & ZKFHE_SRS_BAD_POWERS ? " powers (g[i+1] = s g[i] for the s of the G2 half)" : "",
+            failed & ZKFHE_SRS_BAD_LAGRANGE ? " lagrange" : "", failed & ZKFHE_SRS_BAD_GENERATOR ? " generator (g[0] = (1, 2), G2 points on the twist)" : "");
+    return 1;
+  }
+  mkdir(params_dir.c_str(), 0755);
+  CHECK(zkfhe_srs_save(ctx, srs, srs_path.c_str()));
+  printf("wrote %s (2^%u powers of %s, g_lagrange recomputed; powers, Lagrange form and generator checked)\n", srs_path.c_str(), k, from.c_str());
+  zkfhe_srs_destroy(ctx, srs);
+  zkfhe_ctx_destroy(ctx);
+  return 0;
+}
+
 int main(int argc, char **argv) {
-  std::string name = "bfv", input, cmd, config_path = "configs", data_path = "data";
+  std::string name = "bfv", input, cmd, config_path = "configs", data_path = "data", srs_from;
   unsigned k = 13;
   uint32_t transcript = ZKFHE_TRANSCRIPT_POSEIDON;
   zkfhe_bfv_params prm = {1024, 536870909ULL, 7, 19};  // examples/bfv.rs:27-30
@@ -149,16 +187,19 @@ int main(int argc, char **argv) {
         return 2;
       }
     }
-    else if (a == "mock" || a == "keygen" || a == "prove" || a == "verify") cmd = a;
+    else if (a == "mock" || a == "keygen" || a == "prove" || a == "verify" || a == "srs") cmd = a;
+    else if (a == "--from") srs_from = next();
     else if (a == "--") continue;
     else {
       fprintf(stderr, "usage: bfv --name <n> -k <degree> --input <file under data/> {mock|keygen|prove|verify}\n");
+      fprintf(stderr, "       bfv -k <degree> srs --from <params file of k_file >= degree>\n");
       return 2;
     }
   }
+  if (cmd == "srs") return srs_command(k, srs_from);
   if (input.empty()) input = name + ".in";
   if (cmd.empty()) {
-    fprintf(stderr, "missing command: mock | keygen | prove | verify\n");
+    fprintf(stderr, "missing command: mock | keygen | prove | verify | srs\n");
     return 2;
   }
   const std::string text = slurp(data_path + "/" + input);

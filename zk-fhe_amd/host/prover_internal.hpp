@@ -164,6 +164,8 @@ int alloc_witness_buffers(zkfhe_ctx *ctx, const zkfhe_bfv_pk *pk, Workspace *ws)
 void zk_srs_g2_from_secret(const U256 &s, uint8_t g2_raw[128], uint8_t sg2_raw[128]);
 bool zk_g2_raw_to_canon(const uint8_t raw[128], uint8_t canon[128]);   // false: a coordinate is not reduced or the point is off the twist
 bool zk_g2_canon_to_raw(const uint8_t canon[128], uint8_t raw[128]);
+// e(A, s_g2) e(-B, g2) = 1 on the host (affine Montgomery G1 points, raw G2 coordinates): the powers check of zkfhe_srs_check
+bool zk_srs_pairing_powers(const zk::G1Affine &A, const zk::G1Affine &B, const uint8_t g2_raw[128], const uint8_t sg2_raw[128]);
 
 static inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

@@ -1,5 +1,6 @@
 // The structured reference string on one MI355X (include/zkfhe.h "SRS"): replaces halo2-scaffold `gen_srs` /
 // ParamsKZG::setup (third-party, reached from reference examples/bfv.rs:311; README.md:34 "unsafe" seeded setup).
+#include <sys/random.h>
 #include <unistd.h>
 
 #include "prover_internal.hpp"
@@ -196,6 +197,171 @@ int zkfhe_srs_load(zkfhe_ctx *ctx, const char *path, zkfhe_srs **out) {
   memcpy(srs->sg2_raw, raw + 128, 128);
   srs->have_g2 = true;
   *out = srs;
+  return ZKFHE_OK;
+}
+
+// ---- an SRS from a ceremony's monomial powers (include/zkfhe.h) ------------------------------------------------------------------
+
+// what zkfhe_srs_load asks of a G1 point: reduced coordinates, y^2 = x^3 + 3
+static bool srs_g1_on_curve(const G1Affine &p) {
+  static const U256 QM = {{0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
+  static const zk::Fq three = zk::fp_to_mont<zk::FqP>([] { zk::Fq t = zk::Fq::zero(); t.l[0] = 3; return t; }());
+  U256 x, y;
+  memcpy(x.l, p.x.l, 32);
+  memcpy(y.l, p.y.l, 32);
+  return x < QM && y < QM && p.y * p.y == p.x * p.x * p.x + three;
+}
+
+// g_host: at least 2^k points, checked here; g2_raw / sg2_raw: raw coordinates already checked, or both NULL.  `who` prefixes
+// every refusal.  Everything the arguments alone decide is refused before the first device call.
+static int srs_from_monomial_impl(zkfhe_ctx *ctx, const char *who, uint32_t k, const G1Affine *g_host, const uint8_t *g2_raw, const uint8_t *sg2_raw, zkfhe_srs **out) {
+  const std::string pre = std::string(who) + ": ";
+  const size_t n = (size_t)1 << k;
+  for (size_t i = 0; i < n; ++i) {
+    if (g_host[i].is_identity()) return zk_fail_msg(ctx, ZKFHE_EINVAL, pre + "g[" + std::to_string(i) + "] is the identity, which no power of s is");
+    if (!srs_g1_on_curve(g_host[i])) return zk_fail_msg(ctx, ZKFHE_EINVAL, pre + "g[" + std::to_string(i) + "] has a coordinate >= p or is not on the curve");
+  }
+  // g_lagrange[i] = L_i(s) G = n^-1 sum_j w^(-ij) g[j]: halo2's g_to_lagrange, an inverse FFT over the points
+  std::vector<G1Affine> gl(n);
+  {
+    struct Guard {
+      DevBuf pts;
+      ~Guard() { pts.release(); }
+    } guard;
+    CK(guard.pts.alloc(ctx, n * sizeof(G1Affine)));
+    CK(zkfhe_upload(ctx, guard.pts.p, g_host, n * sizeof(G1Affine)));
+    CK(zkfhe_g1_fft(ctx, (zkfhe_g1_affine *)guard.pts.p, (int)k, 1));
+    CK(zkfhe_download(ctx, gl.data(), guard.pts.p, n * sizeof(G1Affine)));
+  }
+  zkfhe_srs *srs = nullptr;
+  CK(zkfhe_srs_from_points(ctx, k, (const zkfhe_g1_affine *)g_host, (const zkfhe_g1_affine *)gl.data(), &srs));
+  if (g2_raw) {
+    memcpy(srs->g2_raw, g2_raw, 128);
+    memcpy(srs->sg2_raw, sg2_raw, 128);
+    srs->have_g2 = true;
+  }
+  *out = srs;
+  return ZKFHE_OK;
+}
+
+int zkfhe_srs_from_monomial(zkfhe_ctx *ctx, uint32_t k, const zkfhe_g1_affine *g_host, size_t n_g, const uint8_t g2_le[128], const uint8_t s_g2_le[128], zkfhe_srs **out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return ZKFHE_EINVAL;
+  if (!out || !g_host) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_from_monomial: a NULL argument");
+  *out = nullptr;
+  if ((g2_le == nullptr) != (s_g2_le == nullptr)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_from_monomial: g2 and s_g2 come together or not at all");
+  if (k < 3 || k > 20) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_from_monomial: k outside 3..20");
+  if (n_g < ((size_t)1 << k)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_from_monomial: " + std::to_string(n_g) + " powers are fewer than 2^k");
+  uint8_t a[128], b[128];
+  if (g2_le && (!zk_g2_canon_to_raw(g2_le, a) || !zk_g2_canon_to_raw(s_g2_le, b)))
+    return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_from_monomial: a G2 point has a coordinate >= p or is not on the twist curve");
+  return srs_from_monomial_impl(ctx, "srs_from_monomial", k, (const G1Affine *)g_host, g2_le ? a : nullptr, g2_le ? b : nullptr, out);
+}
+
+int zkfhe_srs_load_downsized(zkfhe_ctx *ctx, const char *path, uint32_t k, zkfhe_srs **out) {
+  ZK_ENTER(ctx);
+  if (!ctx) return ZKFHE_EINVAL;
+  if (!out || !path) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_load_downsized: a NULL argument");
+  *out = nullptr;
+  if (k < 3 || k > 20) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_load_downsized: k outside 3..20");
+  FILE *f = fopen(path, "rb");
+  if (!f) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string("srs_load_downsized: cannot open ") + path);
+  // u32 k_file | g[2^k_file] | g_lagrange[2^k_file] | g2 | s_g2: the head of g and the 256-byte tail are read, the rest is skipped
+  uint32_t kf = 0;
+  const size_t n = (size_t)1 << k;
+  std::vector<G1Affine> g;
+  uint8_t raw[256], canon[128];
+  bool framed = fread(&kf, 4, 1, f) == 1 && kf >= 1 && kf <= 28;
+  const long long want = framed ? 4 + 2 * 64 * ((long long)1 << kf) + 256 : 0;
+  framed = framed && fseeko(f, 0, SEEK_END) == 0 && (long long)ftello(f) == want;
+  const bool large_enough = framed && kf >= k;
+  bool ok = large_enough;
+  if (ok) {
+    g.resize(n);
+    ok = fseeko(f, 4, SEEK_SET) == 0 && fread(g.data(), 64, n, f) == n && fseeko(f, (off_t)(want - 256), SEEK_SET) == 0 && fread(raw, 256, 1, f) == 1;
+  }
+  fclose(f);
+  if (!framed) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string("srs_load_downsized: ") + path + " is not a params file (u32 k | 2^k g | 2^k g_lagrange | g2 | s_g2, RawBytes): short or misframed");
+  if (!large_enough) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string("srs_load_downsized: ") + path + " holds k = " + std::to_string(kf) + ", fewer powers than 2^" + std::to_string(k));
+  if (!ok) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string("srs_load_downsized: reading ") + path + " failed");
+  if (!zk_g2_raw_to_canon(raw, canon) || !zk_g2_raw_to_canon(raw + 128, canon))
+    return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string("srs_load_downsized: ") + path + ": a G2 point has a coordinate >= p or is not on the twist curve");
+  return srs_from_monomial_impl(ctx, "srs_load_downsized", k, g.data(), raw, raw + 128, out);
+}
+
+// ---- zkfhe_srs_check ---------------------------------------------------------------------------------------------------------------
+
+// count scalars below 2^253 (< r) from the ChaCha20 keystream of the seed, canonical; `stream` separates the draws of one check
+static void srs_check_scalars(const uint8_t seed[32], uint32_t stream, U256 *out, size_t count) {
+  uint8_t block[64];
+  for (size_t i = 0; i < count; i += 2) {
+    const uint64_t ctr = i / 2;
+    const uint32_t cn[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), stream, 0};
+    chacha20_block(seed, cn, block);
+    block[31] &= 0x1f, block[63] &= 0x1f;
+    memcpy(out[i].l, block, 32);
+    if (i + 1 < count) memcpy(out[i + 1].l, block + 32, 32);
+  }
+}
+
+int zkfhe_srs_check(zkfhe_ctx *ctx, const zkfhe_srs *srs, const uint8_t seed[32], uint32_t *failed) {
+  ZK_ENTER(ctx);
+  if (!ctx) return ZKFHE_EINVAL;
+  if (!srs || !failed) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_check: a NULL argument");
+  *failed = 0;
+  if (srs->sharded()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_check: a sharded SRS holds only a slice of the points");
+  if (!srs->have_g2) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_check: the SRS has no G2 half (zkfhe_srs_set_g2)");
+  uint8_t own[32];
+  if (!seed) {
+    if (getrandom(own, 32, 0) != 32) return zk_fail_msg(ctx, ZKFHE_EINVAL, "srs_check: no seed given and the operating system gave no randomness (getrandom)");
+    seed = own;
+  }
+  const uint32_t k = srs->k;
+  const size_t n = (size_t)1 << k;
+  uint32_t bad = 0;
+  struct Guard {
+    DevBuf cols, evals, pts;
+    ~Guard() { cols.release(), evals.release(), pts.release(); }
+  } guard;
+  CK(guard.cols.alloc(ctx, 2 * n * 32));
+  CK(guard.evals.alloc(ctx, n * 32));
+  CK(guard.pts.alloc(ctx, 4 * sizeof(G1Affine)));
+  G1Affine *pts = (G1Affine *)guard.pts.p;
+  std::vector<U256> h(2 * n);
+  G1Affine res[4];
+  // powers: columns (r, 0) and (0, r) over g give A = sum r_i g[i] and B = sum r_i g[i + 1] = s A
+  srs_check_scalars(seed, 0, h.data(), n - 1);
+  h[n - 1] = h[n] = fe::zero();
+  memcpy(h[n + 1].l, h[0].l, (n - 1) * 32);
+  CK(upload_canon(ctx, guard.cols.fr(), h.data(), 2 * n));
+  CK(zkfhe_msm_batch(ctx, srs->g, (const zkfhe_fr *)guard.cols.p, 2, (zkfhe_g1_affine *)pts));
+  // Lagrange: the commitment of the coefficients c under g is the commitment of the evaluations NTT(c) under g_lagrange
+  ZK_HIP(ctx, zk_wait(ctx));   // h is read by the copy above until here
+  srs_check_scalars(seed, 1, h.data(), n);
+  CK(upload_canon(ctx, guard.cols.fr(), h.data(), n));
+  CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)guard.cols.p, (zkfhe_fr *)guard.evals.p, 1, (int)k, 0));
+  CK(zkfhe_msm_batch(ctx, srs->g, (const zkfhe_fr *)guard.cols.p, 1, (zkfhe_g1_affine *)(pts + 2)));
+  CK(zkfhe_msm_batch(ctx, srs->g_lagrange, (const zkfhe_fr *)guard.evals.p, 1, (zkfhe_g1_affine *)(pts + 3)));
+  CK(zkfhe_download(ctx, res, pts, sizeof(res)));
+  if (memcmp(&res[2], &res[3], sizeof(G1Affine)) != 0) bad |= ZKFHE_SRS_BAD_LAGRANGE;
+  uint8_t canon[128];
+  const bool g2_ok = zk_g2_raw_to_canon(srs->g2_raw, canon) && zk_g2_raw_to_canon(srs->sg2_raw, canon);
+  if (!g2_ok || !zk_srs_pairing_powers(res[0], res[1], srs->g2_raw, srs->sg2_raw)) bad |= ZKFHE_SRS_BAD_POWERS;
+  // g[0]: the first column of the powers check with every scalar but the first zero would do; the host copy is at hand more often
+  G1Affine gen, g0;
+  gen.x = zk::fp_to_mont<zk::FqP>([] { zk::Fq t = zk::Fq::zero(); t.l[0] = 1; return t; }());
+  gen.y = zk::fp_to_mont<zk::FqP>([] { zk::Fq t = zk::Fq::zero(); t.l[0] = 2; return t; }());
+  if (!srs->g_host.empty()) {
+    g0 = srs->g_host[0];
+  } else {
+    CK(zkfhe_memset_dev(ctx, guard.cols.p, 0, n * 32));
+    const Fr one = Fr::one();
+    CK(zkfhe_upload(ctx, guard.cols.p, &one, 32));
+    CK(zkfhe_msm_batch(ctx, srs->g, (const zkfhe_fr *)guard.cols.p, 1, (zkfhe_g1_affine *)pts));
+    CK(zkfhe_download(ctx, &g0, pts, sizeof(G1Affine)));
+  }
+  if (!g2_ok || memcmp(&g0, &gen, sizeof(G1Affine)) != 0) bad |= ZKFHE_SRS_BAD_GENERATOR;
+  *failed = bad;
   return ZKFHE_OK;
 }
 

@@ -822,6 +822,16 @@ int verify_batch(zkfhe_ctx *ctx, const Vk &vk, const SrsG2 &srs, std::vector<Bat
 
 }  // namespace
 
+// zkfhe_srs_check (srs.hip): e(A, s_g2) e(-B, g2) = 1 for affine Montgomery points A, B and raw G2 coordinates -- the final check
+// of a proof with F = B, W = A (the inverse of that product).  false as well when a G2 point is not on the twist.
+bool zk_srs_pairing_powers(const zk::G1Affine &A, const zk::G1Affine &B, const uint8_t g2_raw[128], const uint8_t sg2_raw[128]) {
+  uint8_t canon[128];
+  SrsG2 srs;
+  if (!zk_g2_raw_to_canon(g2_raw, canon) || !g2_from_canon(canon, srs.g2)) return false;
+  if (!zk_g2_raw_to_canon(sg2_raw, canon) || !g2_from_canon(canon, srs.sg2)) return false;
+  return final_check(canon_of(B), canon_of(A), srs);
+}
+
 extern "C" {
 
 int zkfhe_srs_file_g2(const char *path, uint32_t *k_out, uint8_t g2_le[128], uint8_t s_g2_le[128]) {
