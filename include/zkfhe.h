@@ -942,6 +942,84 @@ int zkfhe_bfv_plan_bytes(const zkfhe_bfv_params *params, int base_bits, size_t n
 /* waits for ctx (a context of the plan's device), then frees the plan; a NULL plan is not an error */
 int zkfhe_bfv_plan_destroy(zkfhe_ctx *ctx, zkfhe_bfv_plan *plan);
 
+/* ---- The ballot box: from verified proofs to a tally (bfv_ballot.hip) ----
+ * The joint between zkfhe_bfv_verify_batch and zkfhe_bfv_sum.  A proof's public inputs ("instances") are 5 N + 1 canonical 32-byte
+ * little-endian scalars pk0 | pk1 | c0 | c1 | cyclo; position p of a polynomial's N scalars is word p of its N uint64_t in
+ * CircuitInput order, so the low limb of scalar 2 N + p is c0[p] and that of scalar 3 N + p is c1[p].
+ * An item IS A CIPHERTEXT only if all three hold: it has exactly 5 N + 1 scalars; each of the 2 N scalars of c0 | c1 (positions
+ * 2 N ... 4 N - 1) has limbs 1 to 3 zero and limb 0 below Q; the last N + 1 scalars spell x^N + 1 highest degree first, that is
+ * 1, 0, ..., 0, 1.  Per-item statuses (int32_t; one total per status, ZKFHE_BALLOT_STATUSES of them, in zkfhe_bfv_box_info): */
+#define ZKFHE_BALLOT_COUNTED 0            /* summed into its group */
+#define ZKFHE_BALLOT_SKIPPED 1            /* zkfhe_bfv_sum_instances: group < 0 */
+#define ZKFHE_BALLOT_BAD_GROUP 2          /* group >= n_groups (the box: also group < 0) */
+#define ZKFHE_BALLOT_NOT_A_CIPHERTEXT 3   /* one of the three conditions above fails */
+#define ZKFHE_BALLOT_WRONG_KEY 4          /* the box: pk0 | pk1 is not the box's key */
+#define ZKFHE_BALLOT_REJECTED 5           /* the box: zkfhe_bfv_verify_batch rejects the proof */
+#define ZKFHE_BALLOT_REPEATED 6           /* the box: c0 | c1 equals that of a ballot already counted */
+#define ZKFHE_BALLOT_STATUSES 7
+/* Host only.  The four polynomials of one item: the three conditions, with the second one applied to all 4 N scalars of
+ * pk0 | pk1 | c0 | c1.  *status = ZKFHE_BALLOT_COUNTED and the low limbs written to pk0, pk1, c0, c1 (N words each; any may be NULL),
+ * or *status = ZKFHE_BALLOT_NOT_A_CIPHERTEXT and nothing written; both return ZKFHE_OK.  With status == NULL an item that is not a
+ * ciphertext is ZKFHE_EINVAL.  Refused with ZKFHE_EINVAL and a message "bfv_instances_unpack: ...": NULL params or instances; bad
+ * parameters (the text of every BFV call).  What it returns feeds zkfhe_bfv_mul, zkfhe_bfv_dot and the plans. */
+int zkfhe_bfv_instances_unpack(const zkfhe_bfv_params *params, const uint8_t *instances, size_t n_instances, uint64_t *pk0, uint64_t *pk1,
+                               uint64_t *c0, uint64_t *c1, int32_t *status);
+/* Sums straight from instance scalars, WITHOUT verification: item j has n_instances[j] scalars at instances[j] and belongs to group
+ * group[j] (group == NULL: every item to group 0).  Defined exactly: out0[g], out1[g] (N words each, [n_groups][N]) are the sums mod Q,
+ * coefficient-wise, of the c0 / c1 words of the items with group[j] == g that are ciphertexts; an empty group is all zeros;
+ * counted[g] is the number of items summed into group g.  status[j], decided in this order: ZKFHE_BALLOT_SKIPPED (group[j] < 0),
+ * ZKFHE_BALLOT_BAD_GROUP (group[j] >= n_groups), ZKFHE_BALLOT_NOT_A_CIPHERTEXT, ZKFHE_BALLOT_COUNTED.  A malformed item never
+ * contributes and never fails the call.  Only the c0 | c1 span of an item goes to the device, in chunks (k_ballot_unpack checks and
+ * unpacks it, k_ballot_sum adds it to its group); the count and the cyclotomic tail are compared on the host.
+ * Refused with ZKFHE_EINVAL and a message "bfv_sum_instances: ...", in this order and before any device work: a NULL argument other
+ * than ctx and group (an instances[j] with n_instances[j] > 0 included) or n_items = 0; n_groups outside [1, 4096]; bad parameters
+ * (the text of every BFV call); a NULL ctx.  Waits for its result. */
+int zkfhe_bfv_sum_instances(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_items, const uint8_t *const *instances,
+                            const size_t *n_instances, const int32_t *group, size_t n_groups, uint64_t *out0, uint64_t *out1,
+                            uint64_t *counted, int32_t *status);
+/* The box: a device-resident tally that takes (instances, proof) pairs and counts exactly the ones that deserve it.  It owns a copy
+ * of the vk bytes, of the verifier's half of the SRS (srs_seed, or g2 and s_g2: the convention of zkfhe_bfv_verify_batch), of the
+ * election's public key pk0 | pk1 (N words each, below Q) and of the parameters.  On the device, from create to destroy: the
+ * accumulator [n_groups][2][N], the counts per group and the totals per status.  On the host: the set of the Blake2b-256 digests
+ * (no personalisation) of the 2 N little-endian words c0 | c1 of every ballot counted so far.
+ * zkfhe_bfv_box_add decides the fate of proof j in this fixed order (group == NULL: every proof to group 0):
+ *   1. ZKFHE_BALLOT_BAD_GROUP         group[j] outside [0, n_groups): a negative group is bad here, not skipped
+ *   2. ZKFHE_BALLOT_NOT_A_CIPHERTEXT  n_instances[j] != 5 N + 1, or a wrong cyclotomic tail
+ *   3. ZKFHE_BALLOT_WRONG_KEY         the first 2 N scalars are not the box's pk0 | pk1
+ *   4. ZKFHE_BALLOT_REJECTED          the remaining proofs, and only those, go through zkfhe_bfv_verify_batch in one call; for a
+ *                                     proof it rejects, errs + j * err_stride holds the reason exactly as zkfhe_bfv_verify words it
+ *   5. ZKFHE_BALLOT_NOT_A_CIPHERTEXT  an accepted proof whose c0 | c1 is not made of residues below Q (the device check)
+ *   6. ZKFHE_BALLOT_REPEATED          c0 | c1 equals that of a ballot counted earlier in this box, in an earlier call or earlier in
+ *                                     this one; the group plays no part
+ *   7. ZKFHE_BALLOT_COUNTED           the ciphertext is summed into its group
+ * Only ACCEPTED proofs enter the digest set, so a forged proof that carries a copied ciphertext can never shut out the genuine
+ * ballot; within a call the first accepted occurrence wins.  The tally does not depend on how the ballots were split into calls or on
+ * their order; only WHICH copy of a repeat is flagged does.  errs may be NULL; every other reason is the empty string.
+ * zkfhe_bfv_box_tally downloads the accumulator (out0, out1: [n_groups][N]) and the counts ([n_groups]); it does not change the box
+ * and may be called between adds.  zkfhe_bfv_box_info is host only (it reports the box's host mirror of the device totals and touches
+ * no device); any output may be NULL; totals[s] is the number of proofs that ended with status s over all completed adds.
+ * Refused with ZKFHE_EINVAL and a message "bfv_box: ...": create: a NULL argument other than ctx, srs_seed, g2 and s_g2, or vk_len = 0;
+ * n_groups outside [1, 4096]; bad parameters (the text of every BFV call); only one of g2 and s_g2, or a NULL srs_seed with a length;
+ * a NULL ctx; a public-key coefficient >= Q.  add: a NULL argument other than group and errs (a proofs[j] or instances[j] with a
+ * non-zero length included) or n_proofs = 0.  tally: a NULL argument.  add and tally: a context of another device than the box's.
+ * If an error interrupts the summing of an add once its first device command is issued, the call returns it and the box refuses every
+ * later add and tally with a message that says so: a tally that may be half-applied is never handed out.  A failure before that (the
+ * verifier's, or no room for the work buffers) leaves the box as it was.  One add at a time per box is the caller's duty, as for
+ * contexts; any context of the box's device may add, tally and destroy.  zkfhe_bfv_box_destroy waits for ctx, then frees; a NULL box is
+ * not an error. */
+typedef struct zkfhe_bfv_box zkfhe_bfv_box;
+int zkfhe_bfv_box_create(zkfhe_ctx *ctx, const uint8_t *vk_bytes, size_t vk_len, const zkfhe_bfv_params *params, const uint64_t *pk0,
+                         const uint64_t *pk1, size_t n_groups, const uint8_t *srs_seed, size_t seed_len, const uint8_t *g2,
+                         const uint8_t *s_g2, zkfhe_bfv_box **out);
+int zkfhe_bfv_box_add(zkfhe_ctx *ctx, zkfhe_bfv_box *box, size_t n_proofs, const uint8_t *const *instances, const size_t *n_instances,
+                      const uint8_t *const *proofs, const size_t *proof_lens, const int32_t *group, int32_t *status, char *errs,
+                      size_t err_stride);
+int zkfhe_bfv_box_tally(zkfhe_ctx *ctx, const zkfhe_bfv_box *box, uint64_t *out0, uint64_t *out1, uint64_t *counted);
+int zkfhe_bfv_box_info(const zkfhe_bfv_box *box, zkfhe_bfv_params *params, size_t *n_groups, uint64_t totals[ZKFHE_BALLOT_STATUSES]);
+int zkfhe_bfv_box_destroy(zkfhe_ctx *ctx, zkfhe_bfv_box *box);
+/* zkfhe_prof_read slot of the ballot kernels */
+#define ZKFHE_PROF_BFV_BALLOT 24   /* k_ballot_unpack, k_ballot_sum (and the few-thread k_ballot_totals of the box) */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

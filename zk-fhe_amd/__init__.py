@@ -26,6 +26,11 @@ PROF_BFV_BSGS_INNER, PROF_BFV_BSGS_GIANT = 18, 19   # ... and of the baby-step/g
 PROF_BFV_DOT = 20   # ... and of the fused inner product's accumulation
 PROF_BFV_PCKS_COMBINE, PROF_BFV_REFRESH_COMBINE = 21, 22   # ... and of the key-switch and refresh combines
 PROF_G1_FFT = 23   # ... and of the G1 FFT's butterfly kernels
+PROF_BFV_BALLOT = 24   # ... and of the ballot box's unpack and sum kernels
+# per-item statuses of Context.bfv_sum_instances and BallotBox.add (ZKFHE_BALLOT_* of zkfhe.h)
+BALLOT_COUNTED, BALLOT_SKIPPED, BALLOT_BAD_GROUP, BALLOT_NOT_A_CIPHERTEXT, BALLOT_WRONG_KEY, BALLOT_REJECTED, BALLOT_REPEATED = range(7)
+BALLOT_STATUSES = 7
+BALLOT_STATUS_NAMES = ("counted", "skipped", "bad_group", "not_a_ciphertext", "wrong_key", "rejected", "repeated")
 SRS_BAD_POWERS, SRS_BAD_LAGRANGE, SRS_BAD_GENERATOR = 1, 2, 4   # the bits of Srs.check (zkfhe_srs_check)
 
 EXPORTS = [
@@ -58,6 +63,8 @@ EXPORTS = [
     "zkfhe_bfv_galois_keygen", "zkfhe_bfv_apply_galois", "zkfhe_bfv_slot_sum", "zkfhe_bfv_galois_share",
     "zkfhe_bfv_apply_galois_many", "zkfhe_bfv_linear_transform", "zkfhe_bfv_linear_transform_bsgs",
     "zkfhe_bfv_plan_create", "zkfhe_bfv_plan_create_bsgs", "zkfhe_bfv_plan_apply", "zkfhe_bfv_plan_info", "zkfhe_bfv_plan_bytes", "zkfhe_bfv_plan_destroy",
+    "zkfhe_bfv_instances_unpack", "zkfhe_bfv_sum_instances",
+    "zkfhe_bfv_box_create", "zkfhe_bfv_box_add", "zkfhe_bfv_box_tally", "zkfhe_bfv_box_info", "zkfhe_bfv_box_destroy",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -605,6 +612,28 @@ class Context:
         out = [np.empty(c0.shape[1], dtype=np.uint64) for _ in range(2)]
         self._bfv("zkfhe_bfv_sum", "npppp", params, c0.shape[0], c0, c1, *out)
         return tuple(out)
+
+    def bfv_sum_instances(self, params, items, groups=None, n_groups=1):
+        """zkfhe_bfv_sum_instances: sums straight from the public inputs of proofs, WITHOUT verification.  items: one Instances,
+        bytes or list of ints each; groups: one int per item (None: all 0; negative: skip).  -> (out0, out1) of shape (n_groups, N),
+        counted (n_groups,) uint64 and status (n_items,) int32 (BALLOT_*).  An item that is not a ciphertext never contributes."""
+        n = int(params[0])
+        arr, n_inst, keep = _instance_arrays(items)   # keep: what arr points into
+        k, ng = len(keep), int(n_groups)
+        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        if grp is not None and grp.shape != (k,):
+            raise ValueError("groups must hold one integer per item")
+        rows = ng if 1 <= ng <= 4096 else 1   # else the call refuses n_groups
+        out0, out1 = (np.zeros((rows, n), dtype=np.uint64) for _ in range(2))
+        counted, status = np.zeros(rows, dtype=np.uint64), np.zeros(max(k, 1), dtype=np.int32)
+        f = self.lib.zkfhe_bfv_sum_instances
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_size_t, _U64P, _U64P, _U64P, ctypes.c_void_p]
+        prm = BfvParamsC(*[int(x) for x in params])
+        self._check(f(self.h, ctypes.byref(prm), k, arr, n_inst, grp.ctypes.data_as(ctypes.c_void_p) if grp is not None else None, ng,
+                      out0.ctypes.data_as(_U64P), out1.ctypes.data_as(_U64P), counted.ctypes.data_as(_U64P),
+                      status.ctypes.data_as(ctypes.c_void_p)))
+        return out0, out1, counted, status[:k]
 
     def _plain_op(self, fn, params, c0, c1, m):
         c0, c1 = self._eval_arrays(params, c0, c1)
@@ -2017,3 +2046,144 @@ def bfv_verify_batch(ctx, vk_bytes, items, srs_seed=b"zkfhe-unsafe-srs", g2=None
     if rc != 0:
         raise ZkfheError("zkfhe_bfv_verify_batch failed (%d): %s" % (rc, lib.zkfhe_last_error(ctx.h).decode()))
     return [(bool(ok[j]), errs.raw[j * stride:(j + 1) * stride].split(b"\0", 1)[0].decode()) for j in range(n)]
+
+
+# ---------------------------------------------------------------------- the ballot box (zkfhe.h, bfv_ballot.hip)
+
+def _instance_bytes(v):
+    """the public inputs of one proof as canonical 32-byte little-endian scalars: Instances, bytes, or a sequence of ints"""
+    if isinstance(v, Instances):
+        return v.raw
+    if isinstance(v, (bytes, bytearray, memoryview)):
+        b = bytes(v)
+        if len(b) % 32:
+            raise ValueError("instances given as bytes are a multiple of 32 long")
+        return b
+    return b"".join(int(x).to_bytes(32, "little") for x in v)
+
+
+def _byte_arrays(blobs):
+    """-> (an array of pointers to the blobs, the blobs): keep the second alive while the first is in use"""
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    blobs = [bytes(b) for b in blobs]
+    return (u8p * max(len(blobs), 1))(*[ctypes.cast(ctypes.c_char_p(b), u8p) for b in blobs]), blobs
+
+
+def _instance_arrays(items):
+    """-> (pointers, scalar counts, the buffers they point into)"""
+    arr, keep = _byte_arrays([_instance_bytes(v) for v in items])
+    return arr, (ctypes.c_size_t * max(len(keep), 1))(*[len(b) // 32 for b in keep]), keep
+
+
+def bfv_instance_words(params, instances):
+    """zkfhe_bfv_instances_unpack (host only): the public inputs of one proof (Instances, bytes or a list of ints) -> (pk0, pk1, c0, c1),
+    four uint64 arrays of N residues in CircuitInput order, ready for the evaluator.  Raises ZkfheError unless the item is a
+    ciphertext: 5 N + 1 scalars, every one of the first 4 N a residue below Q, the rest spelling x^N + 1."""
+    raw = _instance_bytes(instances)
+    out = [np.empty(int(params[0]), dtype=np.uint64) for _ in range(4)]
+    st = ctypes.c_int32(-1)
+    _host_bfv("zkfhe_bfv_instances_unpack", [ctypes.c_char_p, ctypes.c_size_t] + [_U64P] * 4 + [ctypes.POINTER(ctypes.c_int32)], params,
+              raw, len(raw) // 32, *[a.ctypes.data_as(_U64P) for a in out], ctypes.byref(st))
+    if st.value != BALLOT_COUNTED:
+        raise ZkfheError("bfv_instance_words: the item is not a ciphertext")
+    return tuple(out)
+
+
+class BallotBox:
+    """zkfhe_bfv_box: a tally resident on ctx's device.  add() takes (instances, proof) pairs and counts exactly the proofs that were
+    made for this election's public key (pk0, pk1), verify under vk_bytes, carry residues below Q and do not repeat the ciphertext
+    of a ballot counted before; tally() reads the sums per group.  srs_seed / g2 / s_g2 as bfv_verify_batch."""
+
+    def __init__(self, ctx, vk_bytes, params, pk0, pk1, n_groups=1, srs_seed=b"zkfhe-unsafe-srs", g2=None, s_g2=None):
+        if (g2 is None) != (s_g2 is None):
+            raise ValueError("BallotBox: give both g2 and s_g2, or neither")
+        self.ctx, self.h = ctx, None
+        self.params = tuple(int(x) for x in params)
+        self.n_groups = int(n_groups)
+        n = self.params[0]
+        pk0 = np.ascontiguousarray(pk0, dtype=np.uint64)
+        pk1 = np.ascontiguousarray(pk1, dtype=np.uint64)
+        if pk0.shape != (n,) or pk1.shape != (n,):
+            raise ValueError("pk0 / pk1 must hold N coefficients")
+        enc = lambda p: b"".join(int(v).to_bytes(32, "little") for pair in p for v in pair)  # noqa: E731
+        seed = bytes(srs_seed) if (srs_seed is not None and g2 is None) else None
+        f = ctx.lib.zkfhe_bfv_box_create
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(BfvParamsC), _U64P, _U64P, ctypes.c_size_t,
+                      ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        h = ctypes.c_void_p()
+        vk_bytes = bytes(vk_bytes)
+        ctx._check(f(ctx.h, vk_bytes, len(vk_bytes), ctypes.byref(BfvParamsC(*self.params)), pk0.ctypes.data_as(_U64P), pk1.ctypes.data_as(_U64P),
+                     self.n_groups, seed, len(seed) if seed else 0, enc(g2) if g2 is not None else None, enc(s_g2) if s_g2 is not None else None,
+                     ctypes.byref(h)))
+        self.h = h
+
+    def _handle(self):
+        if not self.h:
+            raise ZkfheError("the ballot box is closed")
+        return self.h
+
+    def add(self, items, groups=None, ctx=None):
+        """zkfhe_bfv_box_add: items = [(instances, proof), ...], groups one int per item (None: all 0) -> [(status, why), ...] with
+        status one of BALLOT_* and why the verifier's reason for a BALLOT_REJECTED proof.  ctx: any context of the box's device."""
+        ctx = ctx or self.ctx
+        box = self._handle()
+        items = list(items)
+        k = len(items)
+        inst, n_inst, keep_i = _instance_arrays([i for i, _ in items])
+        proofs, keep_p = _byte_arrays([p for _, p in items])
+        lens = (ctypes.c_size_t * max(k, 1))(*[len(b) for b in keep_p])
+        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        if grp is not None and grp.shape != (k,):
+            raise ValueError("groups must hold one integer per item")
+        status = np.zeros(max(k, 1), dtype=np.int32)
+        stride = 256
+        errs = ctypes.create_string_buffer(stride * max(k, 1))
+        f = ctx.lib.zkfhe_bfv_box_add
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        ctx._check(f(ctx.h, box, k, inst, n_inst, proofs, lens, grp.ctypes.data_as(ctypes.c_void_p) if grp is not None else None,
+                     status.ctypes.data_as(ctypes.c_void_p), errs, stride))
+        del keep_i, keep_p
+        return [(int(status[j]), errs.raw[j * stride:(j + 1) * stride].split(b"\0", 1)[0].decode()) for j in range(k)]
+
+    def tally(self, ctx=None):
+        """zkfhe_bfv_box_tally -> (c0, c1) of shape (n_groups, N) and counted (n_groups,): the sums so far; the box is unchanged"""
+        ctx = ctx or self.ctx
+        n = self.params[0]
+        c0, c1 = (np.empty((self.n_groups, n), dtype=np.uint64) for _ in range(2))
+        counted = np.empty(self.n_groups, dtype=np.uint64)
+        f = ctx.lib.zkfhe_bfv_box_tally
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [_U64P] * 3
+        ctx._check(f(ctx.h, self._handle(), *[a.ctypes.data_as(_U64P) for a in (c0, c1, counted)]))
+        return c0, c1, counted
+
+    @property
+    def totals(self):
+        """zkfhe_bfv_box_info: the number of proofs per final status over every completed add, keyed by BALLOT_STATUS_NAMES"""
+        f = self.ctx.lib.zkfhe_bfv_box_info
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.POINTER(ctypes.c_size_t), _U64P]
+        t = (ctypes.c_uint64 * BALLOT_STATUSES)()
+        rc = f(self._handle(), None, None, t)
+        if rc != 0:
+            raise ZkfheError("zkfhe_bfv_box_info failed (%d): %s" % (rc, self.ctx.lib.zkfhe_last_error(None).decode()))
+        return {name: int(t[i]) for i, name in enumerate(BALLOT_STATUS_NAMES)}
+
+    def close(self):
+        if self.h:
+            f = self.ctx.lib.zkfhe_bfv_box_destroy
+            f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            h, self.h = self.h, None
+            self.ctx._check(f(self.ctx.h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
