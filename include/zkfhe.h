@@ -1020,6 +1020,89 @@ int zkfhe_bfv_box_destroy(zkfhe_ctx *ctx, zkfhe_bfv_box *box);
 /* zkfhe_prof_read slot of the ballot kernels */
 #define ZKFHE_PROF_BFV_BALLOT 24   /* k_ballot_unpack, k_ballot_sum (and the few-thread k_ballot_totals of the box) */
 
+/* ---- Resident ciphertext batches: chaining evaluation calls on the device (bfv_resident.hip) ----
+ * Every evaluation call above takes host arrays: it checks them on the host, uploads them, runs a few kernels, downloads the result
+ * and waits.  A batch keeps ciphertexts on the device between calls: it is opaque and holds n ciphertexts as two planes c0[n][N]
+ * and c1[n][N] (N uint64_t per polynomial, CircuitInput order) in one device allocation of its own, with its parameters and its
+ * device.  The calls below are the evaluation calls on batches.  No new arithmetic is defined, there is no new randomness and no new
+ * ChaCha20 domain.
+ * INVARIANT: every word of a batch is a residue below Q, from creation to destruction.  Every way in either checks this or preserves
+ * it: zkfhe_bfv_cts_alloc writes zeros; zkfhe_bfv_cts_upload and zkfhe_bfv_cts_store check on the device (k_cts_check, one pass,
+ * one flag word read once) before a word becomes part of a batch; every other call writes residues that a kernel computed mod Q from
+ * residues.  Calls on batches therefore run no range pass over ciphertexts; the host arrays of a call (plaintexts, keys, indices,
+ * groups) are checked on the host as in the host-array call.
+ * Ownership: the allocation is the batch's own, not part of a context's workspace (which the next call reuses), and lives until
+ * zkfhe_bfv_cts_destroy.  Any context of the same device may use a batch; a context of another device is refused ("...: the batch
+ * lives on device D and the context on device E").  Every call waits for its result, like every evaluation call, so a batch used by
+ * two contexts needs no stream bookkeeping; two calls at once on one batch, one of them writing, are the caller's error.
+ * zkfhe_bfv_cts_destroy waits for the context it is given and then frees.
+ * Evaluation: every call writes into a caller-provided destination batch dst of the right count and allocates no device memory
+ * (freeing it would synchronise the device and stall a prover running beside it).  Sources and dst share parameters and device.
+ *   call                                                      definition (bit for bit)                       dst may be a source
+ *   zkfhe_bfv_cts_add(ctx, a, b, subtract, dst)               zkfhe_bfv_add                                  yes
+ *   zkfhe_bfv_cts_add_plain(ctx, a, m_count, m, dst)          zkfhe_bfv_add_plain; m a host array            yes
+ *   zkfhe_bfv_cts_mul_plain(ctx, a, m_count, m, dst)          zkfhe_bfv_mul_plain; m a host array            yes
+ *   zkfhe_bfv_cts_mul(ctx, a, b, rlk0, rlk1, base_bits, dst)  zkfhe_bfv_mul; the key host arrays, checked    yes
+ *                                                             and transformed once per call
+ *   zkfhe_bfv_cts_apply_galois(ctx, a, g, gk0, gk1,           zkfhe_bfv_apply_galois; the key host arrays    yes
+ *                              base_bits, dst)
+ *   zkfhe_bfv_cts_plan_apply(ctx, plan, a, dst)               zkfhe_bfv_plan_apply; the plan's parameters    yes
+ *                                                             equal the batch's
+ *   zkfhe_bfv_cts_select(ctx, a, n_idx, idx, dst)             dst[j] = a[idx[j]], j < n_idx = dst's count;   no (refused)
+ *                                                             idx a host array, repeats allowed: slice,
+ *                                                             reorder, broadcast (k_cts_gather)
+ *   zkfhe_bfv_cts_sum(ctx, a, group, n_groups, dst)           dst[g] = zkfhe_bfv_sum of the members with     no (refused)
+ *                                                             group[j] == g (k_cts_group_sum)
+ * "Bit for bit": downloading dst gives exactly what the host-array call returns on the downloaded sources, for every n, across
+ * ciphertext chunks, and with the same kernels: each host-array call is a wrapper (host checks, uploads, downloads) around a device
+ * core on device pointers, and the batch call drives the same core from resident memory, so the zkfhe_prof_read slots of a batch
+ * call are those of the host-array call.
+ * Alias rules: where the table says yes, dst may be a or b (or both).  A chunk's result goes to the context's workspace and is copied
+ * into dst after the kernels that read the chunk, on the same stream, so a chunk is read completely before it is written.
+ * zkfhe_bfv_cts_sum: group is a host array of a's count (NULL: everything to group 0); group[j] < 0 is skipped; an empty group is all
+ * zeros; n_groups is in [1, 4096] and dst holds n_groups ciphertexts.  The member lists are built on the host; every thread owns
+ * output coefficients and adds its group's members in the order of the batch.  Addition mod Q is exact, so the result equals any
+ * order of zkfhe_bfv_add; no atomics and no floating point are involved.
+ * Refusals: ZKFHE_EINVAL with a message "bfv_cts_<name>: ..." (zkfhe_bfv_box_tally_cts: "bfv_cts_box_tally: ...", and the box's own
+ * refusals under "bfv_box: ..."), in this order and all before any device work on ciphertexts: a NULL argument, a zero count or bad
+ * parameters (the text of every BFV call); a batch (or plan) on another device than the context's; batches of different parameters,
+ * or a count that does not match (b and dst hold a's count; dst of select holds n_idx, dst of sum n_groups); dst among the sources
+ * where the table says no; an index >= a's count, a group >= n_groups, a range of store / download outside the batch; then the key
+ * and plaintext checks of the host-array call with its texts (base_bits outside [1, 32], g even or >= 2N, m_count neither 1 nor the
+ * count, a key coefficient >= Q, a plaintext out of range).  A refused call leaves dst as it was.
+ * zkfhe_bfv_cts_upload: allocates, uploads in chunks, checks; on a coefficient >= Q ("bfv_cts_upload: a ciphertext coefficient >= Q")
+ * or any other failure (ZKFHE_ENOMEM included) everything is freed and *out is NULL.  zkfhe_bfv_cts_store is the same checked upload
+ * into ciphertexts first ... first + count - 1 of an existing batch: every chunk is staged and checked before the batch is touched,
+ * so a refused store leaves the batch as it was.  zkfhe_bfv_cts_info is host only; any output may be NULL; device_bytes = 16 n N.
+ * zkfhe_bfv_box_tally_cts copies the box's accumulator into dst (n_groups ciphertexts with the box's parameters) without touching
+ * the host; counted is as in zkfhe_bfv_box_tally, and the box is unchanged. */
+typedef struct zkfhe_bfv_cts zkfhe_bfv_cts;
+/* n ciphertexts of zero */
+int zkfhe_bfv_cts_alloc(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, zkfhe_bfv_cts **out);
+/* c0, c1: host arrays n x N */
+int zkfhe_bfv_cts_upload(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1,
+                         zkfhe_bfv_cts **out);
+int zkfhe_bfv_cts_store(zkfhe_ctx *ctx, zkfhe_bfv_cts *cts, size_t first, size_t count, const uint64_t *c0, const uint64_t *c1);
+/* out0, out1: host arrays count x N */
+int zkfhe_bfv_cts_download(zkfhe_ctx *ctx, const zkfhe_bfv_cts *cts, size_t first, size_t count, uint64_t *out0, uint64_t *out1);
+int zkfhe_bfv_cts_info(const zkfhe_bfv_cts *cts, zkfhe_bfv_params *params, size_t *n, uint64_t *device_bytes);
+/* waits for ctx (a context of the batch's device; may be NULL), then frees the batch; a NULL batch is not an error */
+int zkfhe_bfv_cts_destroy(zkfhe_ctx *ctx, zkfhe_bfv_cts *cts);
+int zkfhe_bfv_box_tally_cts(zkfhe_ctx *ctx, const zkfhe_bfv_box *box, zkfhe_bfv_cts *dst, uint64_t *counted);
+int zkfhe_bfv_cts_add(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, int subtract, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_add_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t m_count, const uint64_t *m, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t m_count, const uint64_t *m, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_mul(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, const uint64_t *rlk0, const uint64_t *rlk1,
+                      int base_bits, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_apply_galois(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t g, const uint64_t *gk0, const uint64_t *gk1, int base_bits,
+                               zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_plan_apply(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, const zkfhe_bfv_cts *a, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_select(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_idx, const uint64_t *idx, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const int32_t *group, size_t n_groups, zkfhe_bfv_cts *dst);
+/* zkfhe_prof_read slot of the batches' own kernels: algorithmic bytes = the words read and written.  The evaluation calls on batches
+ * count in the slots of their host-array calls. */
+#define ZKFHE_PROF_BFV_RESIDENT 25   /* k_cts_check, k_cts_gather, k_cts_group_sum */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

@@ -27,6 +27,7 @@ PROF_BFV_DOT = 20   # ... and of the fused inner product's accumulation
 PROF_BFV_PCKS_COMBINE, PROF_BFV_REFRESH_COMBINE = 21, 22   # ... and of the key-switch and refresh combines
 PROF_G1_FFT = 23   # ... and of the G1 FFT's butterfly kernels
 PROF_BFV_BALLOT = 24   # ... and of the ballot box's unpack and sum kernels
+PROF_BFV_RESIDENT = 25   # ... and of the resident batches' check, gather and group-sum kernels
 # per-item statuses of Context.bfv_sum_instances and BallotBox.add (ZKFHE_BALLOT_* of zkfhe.h)
 BALLOT_COUNTED, BALLOT_SKIPPED, BALLOT_BAD_GROUP, BALLOT_NOT_A_CIPHERTEXT, BALLOT_WRONG_KEY, BALLOT_REJECTED, BALLOT_REPEATED = range(7)
 BALLOT_STATUSES = 7
@@ -65,6 +66,9 @@ EXPORTS = [
     "zkfhe_bfv_plan_create", "zkfhe_bfv_plan_create_bsgs", "zkfhe_bfv_plan_apply", "zkfhe_bfv_plan_info", "zkfhe_bfv_plan_bytes", "zkfhe_bfv_plan_destroy",
     "zkfhe_bfv_instances_unpack", "zkfhe_bfv_sum_instances",
     "zkfhe_bfv_box_create", "zkfhe_bfv_box_add", "zkfhe_bfv_box_tally", "zkfhe_bfv_box_info", "zkfhe_bfv_box_destroy",
+    "zkfhe_bfv_cts_alloc", "zkfhe_bfv_cts_upload", "zkfhe_bfv_cts_store", "zkfhe_bfv_cts_download", "zkfhe_bfv_cts_info", "zkfhe_bfv_cts_destroy",
+    "zkfhe_bfv_box_tally_cts", "zkfhe_bfv_cts_add", "zkfhe_bfv_cts_add_plain", "zkfhe_bfv_cts_mul_plain", "zkfhe_bfv_cts_mul",
+    "zkfhe_bfv_cts_apply_galois", "zkfhe_bfv_cts_plan_apply", "zkfhe_bfv_cts_select", "zkfhe_bfv_cts_sum",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -983,6 +987,162 @@ class Context:
                   ctypes.byref(h))
         return BfvLinearPlan(self, h)
 
+    # ---- resident batches: ciphertexts kept on the device between calls (zkfhe.h, bfv_resident.hip)
+
+    def bfv_cts(self, params, c0, c1):
+        """zkfhe_bfv_cts_upload: n ciphertexts (n, N) -> a BfvCiphertexts on this context's device; every coefficient is checked
+        below Q on the device, and a batch is never created from anything else."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        h = ctypes.c_void_p()
+        self._bfv("zkfhe_bfv_cts_upload", "nppP", params, c0.shape[0], c0, c1, ctypes.byref(h))
+        return BfvCiphertexts(self, h)
+
+    def bfv_cts_zeros(self, params, n):
+        """zkfhe_bfv_cts_alloc: a BfvCiphertexts of n ciphertexts of zero (a destination for the calls on batches)"""
+        h = ctypes.c_void_p()
+        self._bfv("zkfhe_bfv_cts_alloc", "nP", params, int(n), ctypes.byref(h))
+        return BfvCiphertexts(self, h)
+
+
+class BfvCiphertexts:
+    """A resident batch (zkfhe_bfv_cts): n ciphertexts on the device, every word a residue below Q.  The methods are the evaluation
+    calls on batches, bit for bit the host-array calls of Context; each takes out=None (a fresh batch is allocated) or a batch of the
+    right count to write into, which may be self or the other operand except for select and sum, and ctx=None (the creating context)
+    or any context of the same device.  close() (or leaving the with block) frees it."""
+
+    def __init__(self, ctx, handle=None):
+        if not isinstance(ctx, Context):
+            raise ZkfheError("BfvCiphertexts needs a Context: use Context.bfv_cts or Context.bfv_cts_zeros")
+        if not handle:
+            raise ZkfheError("BfvCiphertexts wraps a batch made by Context.bfv_cts or Context.bfv_cts_zeros")
+        self.ctx = ctx
+        self.h = handle
+        info = self.info()
+        self.params, self.n = info["params"], info["n"]
+
+    def _handle(self):
+        if not self.h:
+            raise ZkfheError("the batch is closed")
+        return self.h
+
+    def __len__(self):
+        return self.n
+
+    def info(self):
+        """zkfhe_bfv_cts_info -> params (N, Q, T, B), n and device_bytes (16 n N)"""
+        f = self.ctx.lib.zkfhe_bfv_cts_info
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_uint64)]
+        prm, n, nbytes = BfvParamsC(), ctypes.c_size_t(), ctypes.c_uint64()
+        rc = f(self._handle(), ctypes.byref(prm), ctypes.byref(n), ctypes.byref(nbytes))
+        if rc != 0:
+            raise ZkfheError("zkfhe_bfv_cts_info failed (%d): %s" % (rc, self.ctx.lib.zkfhe_last_error(None).decode()))
+        return {"params": tuple(int(getattr(prm, name)) for name, _ in BfvParamsC._fields_), "n": n.value, "device_bytes": nbytes.value}
+
+    def _call(self, fn, argtypes, ctx, *args):
+        ctx = ctx or self.ctx
+        f = getattr(ctx.lib, fn)
+        f.argtypes = [ctypes.c_void_p] + argtypes
+        ctx._check(f(ctx.h, *args))
+
+    def _out(self, out, ctx, n=None):
+        """the destination of a call: out, or a fresh batch of n ciphertexts (default: as many as self)"""
+        return out if out is not None else (ctx or self.ctx).bfv_cts_zeros(self.params, self.n if n is None else n)
+
+    def _into(self, out, ctx, n, fn, argtypes, *args):
+        """fn(ctx, *args, dst) into out or a fresh batch, which is closed again if the call is refused"""
+        dst = self._out(out, ctx, n)
+        try:
+            self._call(fn, argtypes + [ctypes.c_void_p], ctx, *args, dst._handle())
+        except Exception:
+            if out is None:
+                dst.close()
+            raise
+        return dst
+
+    def download(self, first=0, count=None, ctx=None):
+        """zkfhe_bfv_cts_download -> (c0, c1) of shape (count, N): ciphertexts first ... first + count - 1 (default: to the end)"""
+        count = self.n - int(first) if count is None else int(count)
+        out = [np.empty((max(count, 0), self.params[0]), dtype=np.uint64) for _ in range(2)]
+        self._call("zkfhe_bfv_cts_download", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _U64P, _U64P], ctx, self._handle(), int(first),
+                   count, *[a.ctypes.data_as(_U64P) for a in out])
+        return tuple(out)
+
+    def store(self, c0, c1, first=0, ctx=None):
+        """zkfhe_bfv_cts_store: ciphertexts (count, N) over ciphertexts first ... first + count - 1, checked below Q on the device
+        first; a refused store leaves the batch as it was"""
+        c0, c1 = self.ctx._eval_arrays(self.params, c0, c1)
+        self._call("zkfhe_bfv_cts_store", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _U64P, _U64P], ctx, self._handle(), int(first),
+                   c0.shape[0], c0.ctypes.data_as(_U64P), c1.ctypes.data_as(_U64P))
+
+    def add(self, other, out=None, ctx=None, subtract=False):
+        """zkfhe_bfv_cts_add: self + other (or self - other)"""
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_add", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int], self._handle(), other._handle(),
+                          int(bool(subtract)))
+
+    def sub(self, other, out=None, ctx=None):
+        """zkfhe_bfv_cts_add with subtract: self - other"""
+        return self.add(other, out=out, ctx=ctx, subtract=True)
+
+    def _plain_op(self, fn, m, out, ctx):
+        m = self.ctx._plain(self.params, m, self.n)
+        return self._into(out, ctx, None, fn, [ctypes.c_void_p, ctypes.c_size_t, _U64P], self._handle(), m.shape[0], m.ctypes.data_as(_U64P))
+
+    def add_plain(self, m, out=None, ctx=None):
+        """zkfhe_bfv_cts_add_plain; m is one plaintext (N,) for every ciphertext or one per ciphertext (n, N)"""
+        return self._plain_op("zkfhe_bfv_cts_add_plain", m, out, ctx)
+
+    def mul_plain(self, m, out=None, ctx=None):
+        """zkfhe_bfv_cts_mul_plain; m as for add_plain"""
+        return self._plain_op("zkfhe_bfv_cts_mul_plain", m, out, ctx)
+
+    def mul(self, other, rlk0, rlk1, base_bits=16, out=None, ctx=None):
+        """zkfhe_bfv_cts_mul: the relinearized products self * other under the key (rlk0, rlk1) of shape (l, N)"""
+        rlk0, rlk1 = self.ctx._galois_keys(self.params, rlk0, rlk1, base_bits, ())
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_mul", [ctypes.c_void_p, ctypes.c_void_p, _U64P, _U64P, ctypes.c_int], self._handle(),
+                          other._handle(), rlk0.ctypes.data_as(_U64P), rlk1.ctypes.data_as(_U64P), int(base_bits))
+
+    def apply_galois(self, g, gk0, gk1, base_bits=16, out=None, ctx=None):
+        """zkfhe_bfv_cts_apply_galois: sigma_g of every ciphertext, key-switched back with (gk0, gk1) of shape (l, N)"""
+        gk0, gk1 = self.ctx._galois_keys(self.params, gk0, gk1, base_bits, ())
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_apply_galois", [ctypes.c_void_p, ctypes.c_uint64, _U64P, _U64P, ctypes.c_int],
+                          self._handle(), int(g), gk0.ctypes.data_as(_U64P), gk1.ctypes.data_as(_U64P), int(base_bits))
+
+    def select(self, indices, out=None, ctx=None):
+        """zkfhe_bfv_cts_select: out[j] = self[indices[j]] (repeats allowed): slice, reorder, broadcast.  out must not be self."""
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64).reshape(-1)
+        return self._into(out, ctx, idx.shape[0], "zkfhe_bfv_cts_select", [ctypes.c_void_p, ctypes.c_size_t, _U64P], self._handle(), idx.shape[0],
+                          idx.ctypes.data_as(_U64P))
+
+    def sum(self, groups=None, n_groups=1, out=None, ctx=None):
+        """zkfhe_bfv_cts_sum: out[g] = the sum of the ciphertexts with groups[j] == g (None: all to group 0; negative: skipped); a
+        batch of n_groups ciphertexts.  out must not be self."""
+        grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        if grp is not None and grp.shape != (self.n,):
+            raise ValueError("groups must hold one integer per ciphertext")
+        ng = int(n_groups)
+        return self._into(out, ctx, ng if 1 <= ng <= 4096 else 1, "zkfhe_bfv_cts_sum", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
+                          self._handle(), grp.ctypes.data_as(ctypes.c_void_p) if grp is not None else None, ng)
+
+    def close(self):
+        if self.h:
+            f = self.ctx.lib.zkfhe_bfv_cts_destroy
+            f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            h, self.h = self.h, None
+            self.ctx._check(f(self.ctx.h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class BfvLinearPlan:
     """A prepared linear transform (zkfhe_bfv_plan): the element table, the transformed Galois keys and the transformed diagonals
@@ -1009,6 +1169,12 @@ class BfvLinearPlan:
         f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [_U64P] * 4
         ctx._check(f(ctx.h, plan, c0.shape[0], *[a.ctypes.data_as(_U64P) for a in (c0, c1, *out)]))
         return tuple(out)
+
+    def apply_cts(self, ctx, cts, out=None):
+        """zkfhe_bfv_cts_plan_apply: a resident batch through the plan, on ctx (None: the creating context) -> a BfvCiphertexts
+        (out, which may be cts, or a fresh batch); bit for bit apply() on the downloaded batch"""
+        ctx = ctx or self.ctx
+        return cts._into(out, ctx, None, "zkfhe_bfv_cts_plan_apply", [ctypes.c_void_p, ctypes.c_void_p], self._handle(), cts._handle())
 
     def info(self):
         """zkfhe_bfv_plan_info -> params (N, Q, T, B), base_bits, n_elems (n_baby of a two-level plan), n_giant (0: a flat plan),
@@ -2156,6 +2322,23 @@ class BallotBox:
         f.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [_U64P] * 3
         ctx._check(f(ctx.h, self._handle(), *[a.ctypes.data_as(_U64P) for a in (c0, c1, counted)]))
         return c0, c1, counted
+
+    def tally_cts(self, ctx=None, out=None):
+        """zkfhe_bfv_box_tally_cts -> (cts, counted): the sums so far as a resident batch of n_groups ciphertexts (out, or a fresh
+        batch), copied on the device, and counted (n_groups,); the box is unchanged"""
+        ctx = ctx or self.ctx
+        box = self._handle()
+        dst = out if out is not None else ctx.bfv_cts_zeros(self.params, self.n_groups)
+        counted = np.empty(self.n_groups, dtype=np.uint64)
+        f = ctx.lib.zkfhe_bfv_box_tally_cts
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _U64P]
+        try:
+            ctx._check(f(ctx.h, box, dst._handle(), counted.ctypes.data_as(_U64P)))
+        except Exception:
+            if out is None:
+                dst.close()
+            raise
+        return dst, counted
 
     @property
     def totals(self):

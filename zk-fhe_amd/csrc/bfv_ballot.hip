@@ -256,6 +256,17 @@ int box_sum(zkfhe_ctx *ctx, zkfhe_bfv_box *box, const std::vector<Cand> &cands, 
 
 }  // namespace
 
+namespace zkrns {
+
+int zk_bfv_box_view(zkfhe_ctx *ctx, const zkfhe_bfv_box *box, zkfhe_bfv_params *params, size_t *n_groups, const uint64_t **acc,
+                    const unsigned long long **counts) {
+  ZK_CK(box_usable(ctx, box));
+  *params = box->params, *n_groups = box->n_groups, *acc = box->acc, *counts = box->counts;
+  return ZKFHE_OK;
+}
+
+}  // namespace zkrns
+
 extern "C" {
 
 int zkfhe_bfv_instances_unpack(const zkfhe_bfv_params *params, const uint8_t *instances, size_t n_instances, uint64_t *pk0, uint64_t *pk1,

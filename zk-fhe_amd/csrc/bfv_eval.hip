@@ -13,6 +13,8 @@
 //   5. k_eval_epilogue (EV_ADD): out_j = c^_j + sum mod Q.
 // The relinearization key is transformed once per call.  No step branches on or addresses by a coefficient's value.
 // k_eval_epilogue and k_key_switch also serve the Galois key switch of bfv_galois.hip (EV_GALOIS, k_key_switch<true>).
+// Each entry point is a wrapper (host checks, uploads, downloads) around a device core on device pointers (zk_bfv_add_core,
+// zk_bfv_mul_plain_core, zk_bfv_mul_core: the body of its chunk loop), which bfv_resident.hip drives from resident memory.
 #include <cstring>
 
 #include "rns_ntt.hip.hpp"
@@ -185,18 +187,18 @@ int launch_tensor(zkfhe_ctx *ctx, const uint32_t *hat, size_t c, int log_n, uint
   return ZKFHE_OK;
 }
 
-int launch_add(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtract, const uint64_t *m, int m_shared, uint64_t delta,
-               size_t total, int log_n, uint64_t q, uint64_t *out) {
+}  // namespace
+
+namespace zkrns {
+
+int zk_bfv_add_core(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtract, const uint64_t *m, int m_shared, uint64_t delta,
+                    size_t total, int log_n, uint64_t q, uint64_t *out) {
   zk_prof_begin(ctx);
   k_bfv_add<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(a, b, subtract, m, m_shared, delta, total, log_n, q, out);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_ELEMENTWISE, (double)total * 24);
   return ZKFHE_OK;
 }
-
-}  // namespace
-
-namespace zkrns {
 
 int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out) {
   const size_t total = n_polys << log_n;
@@ -226,6 +228,33 @@ int zk_bfv_key_switch(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64
   return ZKFHE_OK;
 }
 
+int zk_bfv_hat(zkfhe_ctx *ctx, const uint64_t *src, int mode, uint64_t q, size_t rows, int log_n, uint32_t *hat, int *flag) {
+  return launch_rns_ntt<NP>(ctx, false, src, mode, q, rows, log_n, nullptr, 0, hat, flag);
+}
+
+int zk_bfv_mul_plain_core(zkfhe_ctx *ctx, const uint64_t *x, size_t c, int log_n, uint64_t q, const uint32_t *m_hat, size_t hat_stride,
+                          uint32_t *res, int *flag, uint64_t *out) {
+  ZK_CK(launch_rns_ntt<NP>(ctx, true, x, LOAD_CENTRED, q, c, log_n, m_hat, hat_stride, res, flag));
+  return zk_bfv_eval_epilogue(ctx, res, c, log_n, q, EvEpi{}, out);
+}
+
+void add_mul_work(Arena &a, uint64_t n, int l, size_t n_pairs, MulWork &w) {
+  w.chunk = std::min<size_t>(n_pairs, chunk_polys(n));
+  const size_t cw = w.chunk * n, lw = (size_t)l * n;
+  a.add(w.flag, 1).add(w.rlk_d, 2 * lw).add(w.rlk_hat, 2 * lw * NP).add(w.in_d, 4 * cw).add(w.hat, 4 * cw * NP).add(w.res, 3 * cw * NP)
+      .add(w.chat, 3 * cw).add(w.o_d, 2 * cw);
+}
+
+int zk_bfv_mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l, int base_bits, const MulWork &w) {
+  const uint64_t n = prm->n, q = prm->q;
+  const int log_n = bit_log2(n);
+  ZK_CK(zk_bfv_hat(ctx, w.in_d, LOAD_CENTRED, q, 4 * c, log_n, w.hat, w.flag));
+  ZK_CK(launch_tensor(ctx, w.hat, c, log_n, w.res));
+  ZK_CK(zk_bfv_eval_epilogue(ctx, w.res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = prm->t}, w.chat));
+  ZK_CK(zk_bfv_key_switch(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, w.rlk_hat, c, log_n, w.res));
+  return zk_bfv_eval_epilogue(ctx, w.res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = w.chat}, w.o_d);
+}
+
 }  // namespace zkrns
 
 extern "C" {
@@ -249,7 +278,7 @@ int zkfhe_bfv_add(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, 
       const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
       ZK_CK(zkfhe_upload(ctx, a_d, a + lo * n, bytes));
       ZK_CK(zkfhe_upload(ctx, b_d, b + lo * n, bytes));
-      ZK_CK(launch_add(ctx, a_d, b_d, subtract, nullptr, 0, 0, c * n, log_n, q, o_d));
+      ZK_CK(zk_bfv_add_core(ctx, a_d, b_d, subtract, nullptr, 0, 0, c * n, log_n, q, o_d));
       ZK_CK(zkfhe_download(ctx, out + lo * n, o_d, bytes));
     }
   }
@@ -300,7 +329,7 @@ int zkfhe_bfv_add_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
     ZK_CK(zkfhe_upload(ctx, c_d, c0 + lo * n, bytes));
     if (!shared) ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, bytes));
-    ZK_CK(launch_add(ctx, c_d, nullptr, 0, m_d, shared, q / params->t, c * n, log_n, q, o_d));
+    ZK_CK(zk_bfv_add_core(ctx, c_d, nullptr, 0, m_d, shared, q / params->t, c * n, log_n, q, o_d));
     ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
   }
   if (out1 != c1) memcpy(out1, c1, n_cts * n * 8);
@@ -325,18 +354,17 @@ int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
   const bool shared = m_count == 1;
   if (shared) {
     ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
-    ZK_CK(launch_rns_ntt<NP>(ctx, false, m_d, LOAD_CENTRED, q, 1, log_n, nullptr, 0, hat, flag));
+    ZK_CK(zk_bfv_hat(ctx, m_d, LOAD_CENTRED, q, 1, log_n, hat, flag));
   }
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
     if (!shared) {
       ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, bytes));
-      ZK_CK(launch_rns_ntt<NP>(ctx, false, m_d, LOAD_CENTRED, q, c, log_n, nullptr, 0, hat, flag));
+      ZK_CK(zk_bfv_hat(ctx, m_d, LOAD_CENTRED, q, c, log_n, hat, flag));
     }
     for (int comp = 0; comp < 2; ++comp) {
       ZK_CK(zkfhe_upload(ctx, c_d, (comp ? c1 : c0) + lo * n, bytes));
-      ZK_CK(launch_rns_ntt<NP>(ctx, true, c_d, LOAD_CENTRED, q, c, log_n, hat, shared ? 0 : (size_t)NP * n, res, flag));
-      ZK_CK(zk_bfv_eval_epilogue(ctx, res, c, log_n, q, EvEpi{}, o_d));
+      ZK_CK(zk_bfv_mul_plain_core(ctx, c_d, c, log_n, q, hat, shared ? 0 : (size_t)NP * n, res, flag, o_d));
       ZK_CK(zkfhe_download(ctx, (comp ? out1 : out0) + lo * n, o_d, bytes));
     }
   }
@@ -394,26 +422,20 @@ int zkfhe_bfv_mul(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_pairs
   ZK_CK(check_below_q(ctx, a0, n_pairs * n, q, "bfv_mul", "a ciphertext", a1));
   ZK_CK(check_below_q(ctx, b0, n_pairs * n, q, "bfv_mul", "a ciphertext", b1));
   ZK_CK(check_below_q(ctx, rlk0, lw, q, "bfv_mul", "a relinearization-key", rlk1));
-  const size_t chunk = std::min<size_t>(n_pairs, chunk_polys(n)), cw = chunk * n;
-  int *flag;
-  uint64_t *rlk_d, *in_d, *chat, *o_d;
-  uint32_t *rlk_hat, *hat, *res;
-  ZK_CK(Arena().add(flag, 1).add(rlk_d, 2 * lw).add(rlk_hat, 2 * lw * NP).add(in_d, 4 * cw).add(hat, 4 * cw * NP).add(res, 3 * cw * NP)
-            .add(chat, 3 * cw).add(o_d, 2 * cw).carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, rlk_d, rlk0, lw * 8));
-  ZK_CK(zkfhe_upload(ctx, rlk_d + lw, rlk1, lw * 8));
-  ZK_CK(launch_rns_ntt<NP>(ctx, false, rlk_d, LOAD_RESIDUE, q, 2 * l, log_n, nullptr, 0, rlk_hat, flag));
+  MulWork w;
+  Arena a;
+  add_mul_work(a, n, l, n_pairs, w);
+  ZK_CK(a.carve(ctx));
+  ZK_CK(zkfhe_upload(ctx, w.rlk_d, rlk0, lw * 8));
+  ZK_CK(zkfhe_upload(ctx, w.rlk_d + lw, rlk1, lw * 8));
+  ZK_CK(zk_bfv_hat(ctx, w.rlk_d, LOAD_RESIDUE, q, 2 * l, log_n, w.rlk_hat, w.flag));
   const uint64_t *src[4] = {a0, a1, b0, b1};
-  for (size_t lo = 0; lo < n_pairs; lo += chunk) {
-    const size_t c = std::min(chunk, n_pairs - lo), bytes = c * n * 8;
-    for (int i = 0; i < 4; ++i) ZK_CK(zkfhe_upload(ctx, in_d + i * c * n, src[i] + lo * n, bytes));
-    ZK_CK(launch_rns_ntt<NP>(ctx, false, in_d, LOAD_CENTRED, q, 4 * c, log_n, nullptr, 0, hat, flag));
-    ZK_CK(launch_tensor(ctx, hat, c, log_n, res));
-    ZK_CK(zk_bfv_eval_epilogue(ctx, res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = params->t}, chat));
-    ZK_CK(zk_bfv_key_switch(ctx, chat + 2 * c * n, 0, q, l, base_bits, rlk_hat, c, log_n, res));
-    ZK_CK(zk_bfv_eval_epilogue(ctx, res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = chat}, o_d));
-    ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
-    ZK_CK(zkfhe_download(ctx, out1 + lo * n, o_d + c * n, bytes));
+  for (size_t lo = 0; lo < n_pairs; lo += w.chunk) {
+    const size_t c = std::min(w.chunk, n_pairs - lo), bytes = c * n * 8;
+    for (int i = 0; i < 4; ++i) ZK_CK(zkfhe_upload(ctx, w.in_d + i * c * n, src[i] + lo * n, bytes));
+    ZK_CK(zk_bfv_mul_core(ctx, params, c, l, base_bits, w));
+    ZK_CK(zkfhe_download(ctx, out0 + lo * n, w.o_d, bytes));
+    ZK_CK(zkfhe_download(ctx, out1 + lo * n, w.o_d + c * n, bytes));
   }
   return ZKFHE_OK;
 }

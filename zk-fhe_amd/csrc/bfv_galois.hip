@@ -77,11 +77,6 @@ int check_batching(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const char *f
   return ZKFHE_OK;
 }
 
-int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn) {
-  if (!(g & 1) || g >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": the Galois element g must be odd and below 2N");
-  return ZKFHE_OK;
-}
-
 // g^-1 mod 2N: the units mod 2N form a group of order N
 unsigned galois_inv(uint64_t g, uint64_t n) { return (unsigned)pow_mod(g, n - 1, 2 * n); }
 
@@ -164,15 +159,6 @@ int slot_transform(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_poly
   return ZKFHE_OK;
 }
 
-// one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][NP][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
-int launch_galois(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
-                  bool accumulate, uint32_t *acc, uint64_t *out_d) {
-  const unsigned ginv = galois_inv(g, (uint64_t)1 << log_n);
-  ZK_CK(zk_bfv_key_switch(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, acc));
-  const EvEpi epi{.mode = EV_GALOIS, .add = accumulate ? x_d : nullptr, .poly = x_d, .ginv = ginv, .c = c};
-  return zk_bfv_eval_epilogue(ctx, acc, 2 * c, log_n, q, epi, out_d);
-}
-
 // r_j = 2^(j w) sigma_g(s) - (a_j s + e_j) mod Q, j < l: a_j uniform from (crs_seed, 14, g 64 + j), e_j an error sample from
 // (party_seed, 15, g 64 + j)
 int galois_key(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk, const uint8_t crs_seed[32], const uint8_t party_seed[32],
@@ -202,6 +188,23 @@ int galois_key(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *s
 }
 
 }  // namespace
+
+namespace zkrns {
+
+int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn) {
+  if (!(g & 1) || g >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": the Galois element g must be odd and below 2N");
+  return ZKFHE_OK;
+}
+
+int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
+                       bool accumulate, uint32_t *acc, uint64_t *out_d) {
+  const unsigned ginv = galois_inv(g, (uint64_t)1 << log_n);
+  ZK_CK(zk_bfv_key_switch(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, acc));
+  const EvEpi epi{.mode = EV_GALOIS, .add = accumulate ? x_d : nullptr, .poly = x_d, .ginv = ginv, .c = c};
+  return zk_bfv_eval_epilogue(ctx, acc, 2 * c, log_n, q, epi, out_d);
+}
+
+}  // namespace zkrns
 
 extern "C" {
 
@@ -295,7 +298,7 @@ int zkfhe_bfv_apply_galois(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
     ZK_CK(zkfhe_upload(ctx, x_d, c0 + lo * n, bytes));
     ZK_CK(zkfhe_upload(ctx, x_d + c * n, c1 + lo * n, bytes));
-    ZK_CK(launch_galois(ctx, x_d, c, log_n, q, g, l, base_bits, key_hat, false, acc, o_d));
+    ZK_CK(zk_bfv_galois_core(ctx, x_d, c, log_n, q, g, l, base_bits, key_hat, false, acc, o_d));
     ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
     ZK_CK(zkfhe_download(ctx, out1 + lo * n, o_d + c * n, bytes));
   }
@@ -335,7 +338,7 @@ int zkfhe_bfv_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_
     ZK_CK(zkfhe_upload(ctx, x, c0 + lo * n, bytes));
     ZK_CK(zkfhe_upload(ctx, x + c * n, c1 + lo * n, bytes));
     for (size_t k = 0; k < steps; ++k) {   // x <- x + apply_galois(x, g_k), on the device
-      ZK_CK(launch_galois(ctx, x, c, log_n, q, gs[k], l, base_bits, key_hat + 2 * k * kw * NP, true, acc, y));
+      ZK_CK(zk_bfv_galois_core(ctx, x, c, log_n, q, gs[k], l, base_bits, key_hat + 2 * k * kw * NP, true, acc, y));
       std::swap(x, y);
     }
     ZK_CK(zkfhe_download(ctx, out0 + lo * n, x, bytes));

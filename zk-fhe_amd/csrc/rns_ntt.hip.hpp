@@ -460,6 +460,48 @@ int launch_rns_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, int mode, uint
   return ZKFHE_OK;
 }
 
+// ---- The device cores of the evaluation calls: the body of a call's chunk loop, on device pointers.  The host-array calls drive
+// them between their uploads and downloads; the batch calls of bfv_resident.hip drive the same cores from resident memory, so a
+// batch call runs the kernels of the host-array call, in its order and its profiling slots.  No core checks a range: its caller has.
+// ---- defined in bfv_eval.hip
+// k_bfv_add over total words: out = a +/- b (b set) or a + delta m (m set; m_shared: one plaintext of N words for every polynomial)
+int zk_bfv_add_core(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtract, const uint64_t *m, int m_shared, uint64_t delta,
+                    size_t total, int log_n, uint64_t q, uint64_t *out);
+// rows polynomials of src ([rows][N]) read in `mode` and transformed with the five primes into hat ([rows][5][N]): the keys
+// (LOAD_RESIDUE) and the plaintexts (LOAD_CENTRED) of a call
+int zk_bfv_hat(zkfhe_ctx *ctx, const uint64_t *src, int mode, uint64_t q, size_t rows, int log_n, uint32_t *hat, int *flag);
+// one component of mul_plain: out = x m mod (x^N + 1, Q) for the c polynomials of x against m_hat (hat_stride 0: one plaintext)
+int zk_bfv_mul_plain_core(zkfhe_ctx *ctx, const uint64_t *x, size_t c, int log_n, uint64_t q, const uint32_t *m_hat, size_t hat_stride,
+                          uint32_t *res, int *flag, uint64_t *out);
+// the work buffers of bfv_mul for n_pairs pairs and a key of l rows, in the order the call has always carved them
+struct MulWork {
+  size_t chunk;
+  int *flag;
+  uint64_t *rlk_d, *in_d, *chat, *o_d;
+  uint32_t *rlk_hat, *hat, *res;
+};
+void add_mul_work(Arena &a, uint64_t n, int l, size_t n_pairs, MulWork &w);
+// steps 1 to 5 of bfv_eval.hip for c pairs: w.in_d = [a0 | a1 | b0 | b1] ([4 c][N]), w.rlk_hat the transformed key; w.o_d = [out0 | out1]
+int zk_bfv_mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l, int base_bits, const MulWork &w);
+// ---- defined in bfv_galois.hip
+// "fn: ..." unless g is odd and below 2N
+int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn);
+// one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
+int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
+                       bool accumulate, uint32_t *acc, uint64_t *out_d);
+// ---- defined in bfv_linear.hip
+// the parameters and the device of a plan
+void zk_bfv_plan_view(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int *device);
+// the run half of zkfhe_bfv_plan_apply on device arrays: c0, c1, out0, out1 are [n_cts][N] each on the plan's device.  A chunk is
+// copied into the work arena before its kernels run and its result copied out after them, so out may be c0, c1
+int zk_bfv_plan_run_dev(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0,
+                        uint64_t *out1);
+// ---- defined in bfv_ballot.hip
+// the box's refusals (another device, a box closed by an interrupted add), then its parameters, its groups, its accumulator
+// ([n_groups][2][N]) and its counts ([n_groups]) on the device
+int zk_bfv_box_view(zkfhe_ctx *ctx, const zkfhe_bfv_box *box, zkfhe_bfv_params *params, size_t *n_groups, const uint64_t **acc,
+                    const unsigned long long **counts);
+
 // the secret key uploaded to sk_d and transformed with the first NP primes into hat; refuses a non-ternary key (zeroes flag first)
 template <int NP>
 int secret_hat(zkfhe_ctx *ctx, const uint64_t *sk, uint64_t n, uint64_t q, uint64_t *sk_d, uint32_t *hat, int *flag, const char *fn) {
