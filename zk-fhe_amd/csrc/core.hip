@@ -123,6 +123,8 @@ int zkfhe_ctx_create(int device_id, void *hip_stream, zkfhe_ctx **out) {
   ctx->uid = next_uid.fetch_add(1);
   ctx->device = device_id;
   ctx->num_cu = prop.multiProcessorCount;
+  const char *chain_env = getenv("ZKFHE_CHAIN");
+  ctx->chain_serial = chain_env && !strcmp(chain_env, "serial");
   if (hip_stream) {
     ctx->stream = (hipStream_t)hip_stream;
   } else {
@@ -457,7 +459,9 @@ int zkfhe_fr_from_mont(zkfhe_ctx *ctx, const zkfhe_fr *a, zkfhe_fr *out, size_t 
   ZK_LAUNCH_CHECK(ctx);
   return ZKFHE_OK;
 }
-static int batch_invert(zkfhe_ctx *ctx, Fr *a, Fr *num, size_t n) {
+// joined: the array is several shorter ones put behind each other to save launches (zk_fr_batch_invert_mul_joined): BI_LONG's floor of
+// 16 per inversion does not apply, every part keeps the group size it would have alone
+static int batch_invert(zkfhe_ctx *ctx, Fr *a, Fr *num, size_t n, bool joined = false) {
   if (!n) return ZKFHE_OK;
   void *tmp;
   int rc = zk_scratch(ctx, 0, n * sizeof(Fr), &tmp);
@@ -467,7 +471,7 @@ static int batch_invert(zkfhe_ctx *ctx, Fr *a, Fr *num, size_t n) {
   static const int forced = getenv("ZKFHE_BI_CHUNK") ? atoi(getenv("ZKFHE_BI_CHUNK")) : 0;
   size_t chunk = forced > 0 ? (size_t)forced : n / ((size_t)ctx->num_cu * 1024);
   if (forced <= 0) chunk = chunk < BI_CHUNK ? BI_CHUNK : (chunk > 32 ? 32 : chunk);
-  if (forced <= 0 && n >= BI_LONG && chunk < 16) chunk = 16;
+  if (forced <= 0 && n >= BI_LONG && chunk < 16 && !joined) chunk = 16;
   size_t T = (n + chunk - 1) / chunk;
   if (num)
     k_fr_batch_invert<true><<<zk_blocks(T, 256), 256, 0, ctx->stream>>>(a, num, (Fr *)tmp, n, T);
@@ -485,6 +489,13 @@ int zkfhe_fr_batch_invert_mul(zkfhe_ctx *ctx, const zkfhe_fr *den, zkfhe_fr *num
   ZK_ARG(ctx, n == 0 || (den != nullptr && num != nullptr && (const void *)den != (const void *)num));
   return batch_invert(ctx, (Fr *)den, (Fr *)num, n);
 }
+}   // extern "C"
+int zk_fr_batch_invert_mul_joined(zkfhe_ctx *ctx, const zk::Fr *den, zk::Fr *num, size_t n) {
+  ZK_ENTER(ctx);
+  ZK_ARG(ctx, n == 0 || (den != nullptr && num != nullptr && (const void *)den != (const void *)num));
+  return batch_invert(ctx, (Fr *)den, num, n, true);
+}
+extern "C" {
 int zkfhe_fr9_op(zkfhe_ctx *ctx, int op, const zkfhe_fr *in, zkfhe_fr *out, size_t n) {
   ZK_ENTER(ctx);
   ZK_ARG(ctx, op >= 0 && op < FR9_OPS);

@@ -68,6 +68,9 @@ struct zkfhe_ctx {
   // auxiliary context counts into the context of the proof (cmd_owner, set by the proof; both are driven by one host thread).
   uint64_t cmd_count[3] = {0, 0, 0};
   zkfhe_ctx *cmd_owner = nullptr;
+  // ZKFHE_CHAIN=serial, read when the context is created: a proof's independent thin launches (grand products, SHPLONK sets, H(X) and
+  // the barycentric denominators) go out one after the other as they did before they were merged -- the reference of the side-by-side tests
+  bool chain_serial = false;
   unsigned *tickets = nullptr;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
   // the BFV calls (rns_ntt.hip.hpp): the RNS twiddle tables (built on first use) and a grow-only work arena
   uint32_t *bfv_tw = nullptr;
@@ -179,6 +182,9 @@ int zk_func_max_lds(zkfhe_ctx *ctx, const void *kernel, int bytes);
 int zk_scratch(zkfhe_ctx *ctx, int slot, size_t bytes, void **out);
 // zkfhe_basis_create with a share of the digit-multiple table budget (msm.hip)
 int zk_basis_create_scaled(zkfhe_ctx *ctx, const zkfhe_g1_affine *bases_host, size_t n, int window_bits, double table_budget_scale, zkfhe_basis **out);
+// zkfhe_fr_batch_invert_mul over several arrays of fewer than 2^20 elements that lie behind each other: one launch, and the 8
+// elements per inversion each of them has alone (core.hip)
+int zk_fr_batch_invert_mul_joined(zkfhe_ctx *ctx, const zk::Fr *den, zk::Fr *num, size_t n);
 // stream-ordered device-to-device copy (own kernel for large blocks)
 int zk_copy_d2d(zkfhe_ctx *ctx, void *dst, const void *src, size_t bytes);
 // the tables of the domain of 2^log_n points, built on first use and kept with the context (ntt.hip)

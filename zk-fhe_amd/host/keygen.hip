@@ -79,8 +79,9 @@ int alloc_workspace(zkfhe_ctx *ctx, const CircuitConfig &c, Workspace *ws, int e
   CK(ws->h_c.alloc(ctx, 4 * col));
   CK(ws->misc.alloc(ctx, 32 * col));
   CK(ws->points.alloc(ctx, std::max<size_t>(n_all, c.n_perm()) * 64 + 64));
-  CK(ws->num.alloc(ctx, std::max<size_t>(c.n_chunks(), c.n_lookup) * col));
-  CK(ws->den.alloc(ctx, std::max<size_t>(c.n_chunks(), c.n_lookup) * col));
+  // the factors of the permutation products' ratios and, behind them, the lookup products': inverted and multiplied up together
+  CK(ws->num.alloc(ctx, ((size_t)c.n_chunks() + c.n_lookup) * col));
+  CK(ws->den.alloc(ctx, ((size_t)c.n_chunks() + c.n_lookup) * col));
   // ws->small is carved up at fixed offsets (prove.hip): [0, 128 K) beta * delta^i per permutation column, [128 K, 256 K) chunk /
   // lookup totals, 128 KB each for the quotient groups, y powers and inverses, then pointer / scalar / point lists, the SHPLONK
   // sets (700 K), gadget arguments (768 K) and the early-commitment patch lists (900 K, 920 K): the widest lists must fit

@@ -940,9 +940,10 @@ struct Proof {
     U256 dcan;
     memcpy(dcan.l, DELTA_CANON, 32);
     beta_delta_dev = (Fr *)ws->small.p;
+    const size_t nch = cfg.n_chunks(), nb_z = nbl - 1;
+    if (n <= 65536 && !ctx->chain_serial) return grand_products_side_by_side(mont(dcan));
     zkp::k_powers<<<1, 256, 0, ctx->stream>>>(beta, mont(dcan), beta_delta_dev, cfg.n_perm());
     ZK_LAUNCH_CHECK(ctx);
-    const size_t nch = cfg.n_chunks(), nb_z = nbl - 1;
     zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(perm_args(), ws->num.fr(), ws->den.fr());
     ZK_LAUNCH_CHECK(ctx);
     CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nch * n));   // num <- num / den: the ratios, in one kernel
@@ -967,6 +968,36 @@ struct Proof {
       zkp::k_chunk_carry<<<1, 1024, 0, ctx->stream>>>(totals_dev, (unsigned)nl, 1, closes + 1);
       ZK_LAUNCH_CHECK(ctx);
     }
+    return commit_products();
+  }
+  // Short rows (every launch here is thin): the lookup products do not read what the permutation products write, so the two run as
+  // columns of the same launches -- six launches instead of ten.  The lookup columns lie behind the permutation's in num / den, in the
+  // product columns (pz | lz) and in the totals, and their blinding counters follow the permutation's (ctr_lz = ctr_pz + n_chunks *
+  // (nbl - 1)): every buffer and every draw is the one of the sequence above.
+  int grand_products_side_by_side(const Fr &delta) {
+    const size_t nch = cfg.n_chunks(), nl = cfg.n_lookup, nb_z = nbl - 1;
+    if ((nch + nl) * n * 32 > ws->num.bytes || (nch + nl) * n * 32 > ws->den.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "grand products: ratio buffers too small");
+    Fr *const num_lk = ws->num.fr() + nch * n, *const den_lk = ws->den.fr() + nch * n;
+    zkp::k_lookup_num_den_powers<<<(nl ? grid_for(ctx, nl * n) : 0u) + 1u, 256, 0, ctx->stream>>>(
+        ws->adv_l.fr() + (size_t)cfg.adv_lookup0() * n, pk->fixed_l.fr() + (size_t)cfg.fix_table() * n, ws->la_l.fr(), ws->ls_l.fr(), beta, gamma, (unsigned)nl, n, num_lk, den_lk,
+        beta, delta, beta_delta_dev, cfg.n_perm());
+    ZK_LAUNCH_CHECK(ctx);
+    zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(perm_args(), ws->num.fr(), ws->den.fr());
+    ZK_LAUNCH_CHECK(ctx);
+    CK(zk_fr_batch_invert_mul_joined(ctx, ws->den.fr(), ws->num.fr(), (nch + nl) * n));   // every ratio of both arguments
+    Fr *totals_dev = (Fr *)ws->small.p + 4096;   // [n_chunks | n_lookup]
+    CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch + nl, blind_rows(ctr_pz, nb_z), totals_dev));   // pz | lz contiguous
+    int *const closes = ws->out_flags();
+    closes[0] = closes[1] = 1;
+    zkp::k_chunk_carry_both<<<nl ? 2 : 1, 1024, 0, ctx->stream>>>(totals_dev, (unsigned)nch, (unsigned)nl, closes);
+    ZK_LAUNCH_CHECK(ctx);
+    zkp::k_scale_rows<<<grid_for(ctx, nch * (u + 1)), 256, 0, ctx->stream>>>(ws->pz_l.fr(), totals_dev, n, (unsigned)(u + 1), (unsigned)nch);
+    ZK_LAUNCH_CHECK(ctx);
+    return commit_products();
+  }
+  int commit_products() {
+    const size_t nch = cfg.n_chunks();
+    int *const closes = ws->out_flags();
     std::vector<AffinePoint> pz_commit;
     CK(commit_cols_out(ctx, srs, srs->g_lagrange, ws->pz_l.fr(), nch + cfg.n_lookup, ws, pz_commit));  // pz | lz contiguous
     if (!closes[0]) return zk_fail_msg(ctx, ZKFHE_EINVAL, "permutation argument does not close: a copy constraint is violated");
@@ -1239,13 +1270,25 @@ struct Proof {
     STAGE(sc_dev, Fr, ws, sc, sizeof(sc));
     STAGE(pts_dev, Fr, ws, pts_rot, sizeof(pts_rot));   // the six evaluation points go up with the same flush
     STAGE(jobs_dev, zkp::EvalJob, ws, jobs.data(), jobs.size() * sizeof(zkp::EvalJob));   // ... and so does the evaluation job list
-    CK(flush_staged(ctx, ws));
-    CK(lincomb(ptrs_dev, sc_dev, 3, H_c));
+    Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
+    const bool side_by_side = n <= 65536 && !ctx->chain_serial;   // short rows: H(X) and the weights' denominators (which depend on x alone) in one launch
+    if (side_by_side) {
+      const chain::Job hjob{0, 3, 0, -1};
+      STAGE(hjob_dev, chain::Job, ws, &hjob, sizeof(hjob));
+      CK(flush_staged(ctx, ws));
+      const unsigned gx = grid_for(ctx, n), tail_rows = (grid_for(ctx, 6 * n) + gx - 1) / gx;
+      zkp::k_chain_jobs<zkp::TAIL_BARY><<<dim3(gx, 1 + tail_rows), 256, 0, ctx->stream>>>(hjob_dev, 1, ptrs_dev, sc_dev, n, H_c, nullptr, pts_dev, 6, dom->fwd, bw);
+      ZK_LAUNCH_CHECK(ctx);
+    } else {
+      CK(flush_staged(ctx, ws));
+      CK(lincomb(ptrs_dev, sc_dev, 3, H_c));
+    }
     CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)H_c, (zkfhe_fr *)H_l, 1, (int)k, 0));
     if (!early_rand) CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)rand_c, (zkfhe_fr *)rand_l, 1, (int)k, 0));   // early: transformed on the auxiliary stream at the start
-    Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
-    zkp::k_bary_den<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, pts_dev, 6, n, bw);
-    ZK_LAUNCH_CHECK(ctx);
+    if (!side_by_side) {
+      zkp::k_bary_den<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, pts_dev, 6, n, bw);
+      ZK_LAUNCH_CHECK(ctx);
+    }
     CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)bw, 6 * n));
     const Fr c = zk::zk_fr_to_29((xn - Fr::one()) * dom->n_inv);   // the weights in the 2^261 form: the constant operand of k_eval_jobs' nine-limb products
     zkp::k_bary_weights<<<grid_for(ctx, 6 * n), 256, 0, ctx->stream>>>(dom->fwd, c, 6 * n, n, bw);
@@ -1307,6 +1350,15 @@ struct Proof {
     // pointer and scalar tables of every set are staged first and go up with one flush; then the launches
     std::vector<const Fr *const *> set_ptrs(ns);
     std::vector<const Fr *> set_pw(ns);
+    // short rows, one GPU: the sets' lists lie behind each other and every chunk of every set is a job of one launch (chain_jobs.hpp)
+    const bool side_by_side = n <= 65536 && !ctx->chain_serial && !(W_sh > 1 && k >= 14);
+    std::vector<size_t> set_sizes(ns);
+    for (size_t j = 0; j < ns; ++j) set_sizes[j] = sets[j].members.size();
+    const chain::Plan plan = chain::plan(set_sizes);
+    std::vector<const Fr *> all_ptrs;
+    std::vector<Fr> all_pw;
+    all_ptrs.reserve(plan.members);
+    all_pw.reserve(plan.members);
     for (size_t j = 0; j < ns; ++j) {
       const auto &mem = sets[j].members;
       std::vector<const Fr *> ptrs(mem.size());
@@ -1321,10 +1373,15 @@ struct Proof {
         for (size_t t = 0; t < np; ++t) comb[t] = comb[t] + cur * mont(items[mem[m]].ev[layout.eval_slot(mem[m], sets[j].rots[t])]);
         cur = cur * yq;
       }
-      STAGE(pd, const Fr *, ws, ptrs.data(), mem.size() * sizeof(void *));
-      STAGE(sd, Fr, ws, pw.data(), mem.size() * 32);
-      set_ptrs[j] = pd;
-      set_pw[j] = sd;
+      if (side_by_side) {
+        all_ptrs.insert(all_ptrs.end(), ptrs.begin(), ptrs.end());
+        all_pw.insert(all_pw.end(), pw.begin(), pw.end());
+      } else {
+        STAGE(pd, const Fr *, ws, ptrs.data(), mem.size() * sizeof(void *));
+        STAGE(sd, Fr, ws, pw.data(), mem.size() * 32);
+        set_ptrs[j] = pd;
+        set_pw[j] = sd;
+      }
       // r_j: interpolation through (pts, comb), ascending coefficients
       zkp::ShSet &S = shsets[j];
       S.n_pts = (int)np;
@@ -1341,26 +1398,52 @@ struct Proof {
       vj = vj * v;
     }
     STAGE(sets_dev, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
-    CK(flush_staged(ctx, ws));
-    // One proof over several GPUs, long rows: every rank sums its share of a set's members (a k_lincomb_ptrs over zero members
-    // writes zeros), the W partial combinations of all sets are all-gathered (ns n values per rank) and added up.
-    const bool shard_sets = W_sh > 1 && k >= 14;
-    if (shard_sets) CK(grow_qgather((size_t)W_sh * ns * n * 32));   // [set][rank][n]: the buffer of the quotient shares, grown if there are more sets than coset rows
-    for (size_t j = 0; j < ns; ++j) {
-      const size_t all = sets[j].members.size();
-      const size_t m_lo = shard_sets ? all * r_sh / W_sh : 0, m_hi = shard_sets ? all * (r_sh + 1) / W_sh : all;
-      CK(lincomb(set_ptrs[j] + m_lo, set_pw[j] + m_lo, (unsigned)(m_hi - m_lo), F + j * n));
-      // set j's share goes onto the communicator's stream as soon as it is formed (16 MB per rank at k = 19) and travels while the
-      // next set is combined; the sums wait for the join below
-      if (shard_sets) CK(zkfhe_comm_all_gather_async(ctx, srs->comm, F + j * n, ws->qgather.fr() + j * (size_t)W_sh * n, n * 32));
-    }
-    if (shard_sets) CK(sum_shares(ns, F));
     Fr *zs = ws->misc.fr() + 20 * n;   // [ns][n]
     Fr *hq = ws->misc.fr() + 28 * n;   // [n]
     Fr *Wq = ws->misc.fr() + 29 * n;   // [n]
     Fr *dinv = ws->misc.fr() + 30 * n; // [n]
-    zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
-    ZK_LAUNCH_CHECK(ctx);
+    if (side_by_side) {
+      if ((size_t)plan.slots * n * 32 > ws->partials.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "SHPLONK: partial sums do not fit the quotient buffer");
+      STAGE(ptrs_dev, const Fr *, ws, all_ptrs.data(), all_ptrs.size() * sizeof(void *));
+      STAGE(pw_dev, Fr, ws, all_pw.data(), all_pw.size() * 32);
+      STAGE(jobs_dev, chain::Job, ws, plan.jobs.data(), plan.jobs.size() * sizeof(chain::Job));
+      const chain::Sum no_sum{};   // no chunked set: nothing is staged, but not from a null pointer
+      STAGE(sums_dev, chain::Sum, ws, plan.sums.empty() ? &no_sum : plan.sums.data(), plan.sums.size() * sizeof(chain::Sum));
+      CK(flush_staged(ctx, ws));
+      const unsigned gx = grid_for(ctx, n), nj = (unsigned)plan.jobs.size(), tail_rows = (grid_for(ctx, ns * n) + gx - 1) / gx;
+      // k_sh_zs rides along while the launch cannot reach the 7 waves per SIMD its registers allow (a workgroup is 4 waves, a CU has 4
+      // SIMDs); a fuller launch keeps the jobs at their own 8 waves and k_sh_zs in a launch of its own
+      if ((size_t)gx * (nj + tail_rows) <= (size_t)7 * ctx->num_cu) {
+        zkp::k_chain_jobs<zkp::TAIL_ZS><<<dim3(gx, nj + tail_rows), 256, 0, ctx->stream>>>(jobs_dev, nj, ptrs_dev, pw_dev, n, F, ws->partials.fr(), sets_dev, (unsigned)ns, dom->fwd, zs);
+        ZK_LAUNCH_CHECK(ctx);
+      } else {
+        zkp::k_chain_jobs<zkp::TAIL_NONE><<<dim3(gx, nj), 256, 0, ctx->stream>>>(jobs_dev, nj, ptrs_dev, pw_dev, n, F, ws->partials.fr(), nullptr, 0, nullptr, nullptr);
+        ZK_LAUNCH_CHECK(ctx);
+        zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
+        ZK_LAUNCH_CHECK(ctx);
+      }
+      if (!plan.sums.empty()) {
+        zkp::k_chain_sums<<<dim3(gx, (unsigned)plan.sums.size()), 256, 0, ctx->stream>>>(sums_dev, ws->partials.fr(), n, F);
+        ZK_LAUNCH_CHECK(ctx);
+      }
+    } else {
+      CK(flush_staged(ctx, ws));
+      // One proof over several GPUs, long rows: every rank sums its share of a set's members (a k_lincomb_ptrs over zero members
+      // writes zeros), the W partial combinations of all sets are all-gathered (ns n values per rank) and added up.
+      const bool shard_sets = W_sh > 1 && k >= 14;
+      if (shard_sets) CK(grow_qgather((size_t)W_sh * ns * n * 32));   // [set][rank][n]: the buffer of the quotient shares, grown if there are more sets than coset rows
+      for (size_t j = 0; j < ns; ++j) {
+        const size_t all = sets[j].members.size();
+        const size_t m_lo = shard_sets ? all * r_sh / W_sh : 0, m_hi = shard_sets ? all * (r_sh + 1) / W_sh : all;
+        CK(lincomb(set_ptrs[j] + m_lo, set_pw[j] + m_lo, (unsigned)(m_hi - m_lo), F + j * n));
+        // set j's share goes onto the communicator's stream as soon as it is formed (16 MB per rank at k = 19) and travels while the
+        // next set is combined; the sums wait for the join below
+        if (shard_sets) CK(zkfhe_comm_all_gather_async(ctx, srs->comm, F + j * n, ws->qgather.fr() + j * (size_t)W_sh * n, n * 32));
+      }
+      if (shard_sets) CK(sum_shares(ns, F));
+      zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
+      ZK_LAUNCH_CHECK(ctx);
+    }
     CK(zkfhe_fr_batch_invert(ctx, (zkfhe_fr *)zs, ns * n));
     zkp::k_sh_h<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, F, zs, dom->fwd, n, hq);
     ZK_LAUNCH_CHECK(ctx);

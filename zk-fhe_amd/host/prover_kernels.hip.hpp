@@ -5,15 +5,19 @@
 #pragma once
 #include "../csrc/ctx.hpp"
 #include "../csrc/fr9.hip.hpp"
+#include "chain_jobs.hpp"
 
 namespace zkp {
 
 using zk::Fr;
 
 // ------------------------------------------------------------------------------------------- small utilities
+// Kernel bodies that more than one launch runs are __device__ functions of (blk, nblk): the index of the workgroup among the nblk
+// workgroups that share the body's rows.  A kernel of its own passes (blockIdx.x, gridDim.x); a launch that runs several bodies side
+// by side gives every body a range of its workgroups (the "side by side" kernels below).  No body waits for another workgroup.
 // out[i] = start * base^i
-static __global__ void __launch_bounds__(256) k_powers(Fr start, Fr base, Fr *__restrict__ out, size_t n) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void powers_body(Fr start, Fr base, Fr *__restrict__ out, size_t n, unsigned blk, unsigned nblk) {
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)nblk * blockDim.x) {
     Fr r = start, b = base;
     for (size_t e = i; e; e >>= 1) {
       if (e & 1) r = r * b;
@@ -22,6 +26,7 @@ static __global__ void __launch_bounds__(256) k_powers(Fr start, Fr base, Fr *__
     out[i] = r;
   }
 }
+static __global__ void __launch_bounds__(256) k_powers(Fr start, Fr base, Fr *__restrict__ out, size_t n) { powers_body(start, base, out, n, blockIdx.x, gridDim.x); }
 
 // SRS: den[i] = n (s - w^i)   (inverted by the caller);  then li[i] = w^i (s^n - 1) * inv[i]
 // ---- the blinding stream on the device ------------------------------------------------------------------------------
@@ -210,17 +215,31 @@ static __global__ void __launch_bounds__(256) k_perm_num_den(PermArgs a, Fr *__r
   }
 }
 // lookup: num = (a + beta)(s + gamma), den = (a' + beta)(s' + gamma)
-static __global__ void __launch_bounds__(256) k_lookup_num_den(const Fr *__restrict__ a_cols, const Fr *__restrict__ table, const Fr *__restrict__ la,
-                                                        const Fr *__restrict__ ls, Fr beta, Fr gamma, unsigned n_lookup, size_t n,
-                                                        Fr *__restrict__ num, Fr *__restrict__ den) {
+__device__ __forceinline__ void lookup_num_den_body(const Fr *__restrict__ a_cols, const Fr *__restrict__ table, const Fr *__restrict__ la, const Fr *__restrict__ ls,
+                                                    const Fr &beta, const Fr &gamma, unsigned n_lookup, size_t n, Fr *__restrict__ num, Fr *__restrict__ den, unsigned blk,
+                                                    unsigned nblk) {
   const size_t total = (size_t)n_lookup * n;
   const zk::Fr9S beta9 = zk::fr9_load(beta);
   const zk::Fr9C gamma9 = zk::fr9_load32(gamma);
-  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+  for (size_t g = blk * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)nblk * blockDim.x) {
     const size_t i = g % n;
     num[g] = zk::fr9_store(zk::fr9_lookup_term(zk::fr9_load(a_cols[g]), beta9, zk::fr9_lookup_sum(zk::fr9_load32(table[i]), gamma9)));
     den[g] = zk::fr9_store(zk::fr9_lookup_term(zk::fr9_load(la[g]), beta9, zk::fr9_lookup_sum(zk::fr9_load32(ls[g]), gamma9)));
   }
+}
+static __global__ void __launch_bounds__(256) k_lookup_num_den(const Fr *__restrict__ a_cols, const Fr *__restrict__ table, const Fr *__restrict__ la,
+                                                        const Fr *__restrict__ ls, Fr beta, Fr gamma, unsigned n_lookup, size_t n,
+                                                        Fr *__restrict__ num, Fr *__restrict__ den) {
+  lookup_num_den_body(a_cols, table, la, ls, beta, gamma, n_lookup, n, num, den, blockIdx.x, gridDim.x);
+}
+// Side by side: the lookup ratios' two factors and, in the last workgroup, pout[i] = pstart * pbase^i (beta * delta^c: the
+// permutation argument's constants).  Neither reads what the other writes; both start from the round's beta and gamma.  Grid: the
+// workgroups of k_lookup_num_den (none when n_lookup == 0) + 1.
+static __global__ void __launch_bounds__(256) k_lookup_num_den_powers(const Fr *__restrict__ a_cols, const Fr *__restrict__ table, const Fr *__restrict__ la,
+                                                               const Fr *__restrict__ ls, Fr beta, Fr gamma, unsigned n_lookup, size_t n, Fr *__restrict__ num,
+                                                               Fr *__restrict__ den, Fr pstart, Fr pbase, Fr *__restrict__ pout, size_t pn) {
+  if (blockIdx.x + 1 == gridDim.x) powers_body(pstart, pbase, pout, pn, 0, 1);
+  else lookup_num_den_body(a_cols, table, la, ls, beta, gamma, n_lookup, n, num, den, blockIdx.x, gridDim.x - 1);
 }
 
 // Exclusive running product per column: z[0] = 1, z[i+1] = z[i] * r[i] for i < u; z has u+1 defined entries.
@@ -331,7 +350,7 @@ static __global__ void __launch_bounds__(1024) k_prefix_seg_apply(const Fr *__re
 // Chunk carries of the permutation argument on the device (was: download the totals, multiply on the host, upload):
 // carry[j] = prod_{i < j} total[i] in place, *closes = (the product of all of them == 1).  With check_ones every total itself
 // has to be one (the lookup products) and the array is left alone.  One workgroup of 1024 threads; count <= 4096.
-static __global__ void __launch_bounds__(1024) k_chunk_carry(Fr *__restrict__ total, unsigned count, int check_ones, int *__restrict__ closes) {
+__device__ __forceinline__ void chunk_carry_body(Fr *__restrict__ total, unsigned count, int check_ones, int *__restrict__ closes) {
   __shared__ Fr sh[1024];
   __shared__ int bad;
   const unsigned t = threadIdx.x;
@@ -370,6 +389,15 @@ static __global__ void __launch_bounds__(1024) k_chunk_carry(Fr *__restrict__ to
     acc = acc * vals[k];
   }
   if (active == 0 ? t == 0 : t == active - 1) *closes = (active == 0 || sh[t] == Fr::one()) ? 1 : 0;   // the threads past it hold ones: sh[active - 1] is the product of all
+}
+static __global__ void __launch_bounds__(1024) k_chunk_carry(Fr *__restrict__ total, unsigned count, int check_ones, int *__restrict__ closes) {
+  chunk_carry_body(total, count, check_ones, closes);
+}
+// Side by side, one workgroup each: the carries of total[0, n_carry) with closes[0], and the all-ones check of
+// total[n_carry, n_carry + n_ones) with closes[1] (grid 2; grid 1 when there are no lookups)
+static __global__ void __launch_bounds__(1024) k_chunk_carry_both(Fr *__restrict__ total, unsigned n_carry, unsigned n_ones, int *__restrict__ closes) {
+  if (blockIdx.x == 0) chunk_carry_body(total, n_carry, 0, closes);
+  else chunk_carry_body(total + n_carry, n_ones, 1, closes + 1);
 }
 // z[col][0..u] *= carry[col]
 static __global__ void __launch_bounds__(256) k_scale_rows(Fr *__restrict__ z, const Fr *__restrict__ carry, size_t n, unsigned rows, unsigned n_cols) {
@@ -526,11 +554,15 @@ static __global__ void __launch_bounds__(256) k_ext3_combine(const Fr *__restric
 
 // ------------------------------------------------------------------------------------------- evaluations
 // barycentric weights: d[r][i] = z_r - w^i (inverted by the caller), then b[r][i] = c * w^i * inv
+__device__ __forceinline__ void bary_den_body(const Fr *__restrict__ wpow, const Fr *__restrict__ pts, unsigned n_pts, size_t n, Fr *__restrict__ out, unsigned blk,
+                                              unsigned nblk) {
+  const size_t total = (size_t)n_pts * n;
+  for (size_t g = blk * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)nblk * blockDim.x)
+    out[g] = pts[g / n] - wpow[g % n];
+}
 static __global__ void __launch_bounds__(256) k_bary_den(const Fr *__restrict__ wpow, const Fr *__restrict__ pts, unsigned n_pts, size_t n,
                                                   Fr *__restrict__ out) {
-  const size_t total = (size_t)n_pts * n;
-  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x)
-    out[g] = pts[g / n] - wpow[g % n];
+  bary_den_body(wpow, pts, n_pts, n, out, blockIdx.x, gridDim.x);
 }
 static __global__ void __launch_bounds__(256) k_bary_weights(const Fr *__restrict__ wpow, Fr c, size_t total, size_t n, Fr *__restrict__ inout) {
   for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x)
@@ -601,24 +633,31 @@ static __device__ __forceinline__ Fr lincomb29(const Fr *const *__restrict__ ptr
   if (k < k1) acc = zk::fr29_weak_reduce(zk::f29_add(acc, zk::fr29_mul(zk::fr29_unpack(ptrs[k][i]), zk::fr29_unpack(s29[k]))));
   return zk::fr29_pack(zk::fr29_canonical(acc));
 }
+// out[i] = the sum over the members [k0, k1) of the lists: the body of the plain kernel, of a chunk of the chunked one and of a job
+__device__ __forceinline__ void lincomb_body(const Fr *const *__restrict__ ptrs, const Fr *__restrict__ s29, unsigned k0, unsigned k1, size_t n, Fr *__restrict__ out,
+                                             unsigned blk, unsigned nblk) {
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)nblk * blockDim.x) out[i] = lincomb29(ptrs, s29, k0, k1, i);
+}
 static __global__ void __launch_bounds__(256) k_lincomb_ptrs(const Fr *const *__restrict__ ptrs, const Fr *__restrict__ s29, unsigned m, size_t n,
                                                       Fr *__restrict__ out) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = lincomb29(ptrs, s29, 0, m, i);
+  lincomb_body(ptrs, s29, 0, m, n, out, blockIdx.x, gridDim.x);
 }
 // the same sum split over blockIdx.y chunks of `per` pointers: partial[chunk][i]; k_sum_rows adds the chunks up.  One thread
 // looping over ~600 columns is a 0.7 ms dependent chain; 13 chunks of 48 run side by side.
 static __global__ void __launch_bounds__(256) k_lincomb_ptrs_chunked(const Fr *const *__restrict__ ptrs, const Fr *__restrict__ s29, unsigned m, unsigned per, size_t n,
                                                               Fr *__restrict__ partial) {
   const unsigned k0 = blockIdx.y * per, k1 = min(k0 + per, m);
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    partial[(size_t)blockIdx.y * n + i] = lincomb29(ptrs, s29, k0, k1, i);
+  lincomb_body(ptrs, s29, k0, k1, n, partial + (size_t)blockIdx.y * n, blockIdx.x, gridDim.x);
 }
-static __global__ void __launch_bounds__(256) k_sum_rows(const Fr *__restrict__ partial, unsigned rows, size_t n, Fr *__restrict__ out) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void sum_rows_body(const Fr *__restrict__ partial, unsigned rows, size_t n, Fr *__restrict__ out, unsigned blk, unsigned nblk) {
+  for (size_t i = blk * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)nblk * blockDim.x) {
     Fr acc = partial[i];
     for (unsigned r = 1; r < rows; ++r) acc = acc + partial[(size_t)r * n + i];
     out[i] = acc;
   }
+}
+static __global__ void __launch_bounds__(256) k_sum_rows(const Fr *__restrict__ partial, unsigned rows, size_t n, Fr *__restrict__ out) {
+  sum_rows_body(partial, rows, n, out, blockIdx.x, gridDim.x);
 }
 struct ShSet {
   Fr rc[4];    // r_j coefficients (ascending), unused ones zero
@@ -629,16 +668,46 @@ struct ShSet {
   int n_pts, pad[3];
 };
 // zs[j][i] = prod_{p in S_j} (w^i - p)
-static __global__ void __launch_bounds__(256) k_sh_zs(const ShSet *__restrict__ sets, unsigned n_sets, const Fr *__restrict__ wpow, size_t n,
-                                               Fr *__restrict__ zs) {
+__device__ __forceinline__ void sh_zs_body(const ShSet *__restrict__ sets, unsigned n_sets, const Fr *__restrict__ wpow, size_t n, Fr *__restrict__ zs, unsigned blk,
+                                           unsigned nblk) {
   const size_t total = (size_t)n_sets * n;
-  for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+  for (size_t g = blk * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)nblk * blockDim.x) {
     const ShSet &s = sets[g / n];
     const Fr w = wpow[g % n];
     Fr acc = Fr::one();
     for (int t = 0; t < s.n_pts; ++t) acc = acc * (w - s.pts[t]);
     zs[g] = acc;
   }
+}
+static __global__ void __launch_bounds__(256) k_sh_zs(const ShSet *__restrict__ sets, unsigned n_sets, const Fr *__restrict__ wpow, size_t n,
+                                               Fr *__restrict__ zs) {
+  sh_zs_body(sets, n_sets, wpow, n, zs, blockIdx.x, gridDim.x);
+}
+// Side by side: every linear combination of a round in one launch.  blockIdx.y < n_jobs picks a job of the list that chain_jobs.hpp
+// cuts (one per chunk of at most 48 members of a set): the k_lincomb_ptrs body over the members [first, first + m) of the round's
+// pointer and scalar lists, into row `set` of `direct` (a set of one chunk) or into slot `slot` of `partial` (k_chain_sums adds a
+// set's slots up).  The rows blockIdx.y >= n_jobs run, TAIL_ZS: the k_sh_zs body, TAIL_BARY: the k_bary_den body -- neither reads
+// what a job writes.  `tab`: the ShSet records / the evaluation points, `count` of them.  TAIL_NONE: jobs only (gridDim.y == n_jobs).
+// The launch takes the larger register count of its bodies: TAIL_ZS has 66 VGPRs, 7 waves per SIMD, where the jobs alone have 60 and
+// 8 -- the prover uses it while the whole launch stays below 7 waves per SIMD, and TAIL_NONE with k_sh_zs behind it otherwise.
+enum { TAIL_ZS = 0, TAIL_BARY = 1, TAIL_NONE = 2 };
+template <int TAIL>
+static __global__ void __launch_bounds__(256) k_chain_jobs(const chain::Job *__restrict__ jobs, unsigned n_jobs, const Fr *const *__restrict__ ptrs, const Fr *__restrict__ s29,
+                                                    size_t n, Fr *__restrict__ direct, Fr *__restrict__ partial, const void *__restrict__ tab, unsigned count,
+                                                    const Fr *__restrict__ wpow, Fr *__restrict__ tail_out) {
+  if (blockIdx.y < n_jobs) {
+    const chain::Job j = jobs[blockIdx.y];
+    lincomb_body(ptrs, s29, j.first, j.first + j.m, n, j.slot < 0 ? direct + (size_t)j.set * n : partial + (size_t)j.slot * n, blockIdx.x, gridDim.x);
+    return;
+  }
+  const unsigned blk = (blockIdx.y - n_jobs) * gridDim.x + blockIdx.x, nblk = (gridDim.y - n_jobs) * gridDim.x;
+  if (TAIL == TAIL_ZS) sh_zs_body((const ShSet *)tab, count, wpow, n, tail_out, blk, nblk);
+  else if (TAIL == TAIL_BARY) bary_den_body(wpow, (const Fr *)tab, count, n, tail_out, blk, nblk);
+}
+// direct[set] = the sum of the `chunks` slots of `partial` from `slot0` on, for the set blockIdx.y picks: k_sum_rows per chunked set
+static __global__ void __launch_bounds__(256) k_chain_sums(const chain::Sum *__restrict__ sums, const Fr *__restrict__ partial, size_t n, Fr *__restrict__ direct) {
+  const chain::Sum s = sums[blockIdx.y];
+  sum_rows_body(partial + (size_t)s.slot0 * n, s.chunks, n, direct + (size_t)s.set * n, blockIdx.x, gridDim.x);
 }
 // hq[i] = sum_j v^j (F_j[i] - r_j(w^i)) * zs_inv[j][i]
 static __global__ void __launch_bounds__(256) k_sh_h(const ShSet *__restrict__ sets, unsigned n_sets, const Fr *__restrict__ F, const Fr *__restrict__ zs_inv,
