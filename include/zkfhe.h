@@ -1103,6 +1103,72 @@ int zkfhe_bfv_cts_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const int32_t *gro
  * count in the slots of their host-array calls. */
 #define ZKFHE_PROF_BFV_RESIDENT 25   /* k_cts_check, k_cts_gather, k_cts_group_sum */
 
+/* ---- Evaluation keys that stay on the device: slot sums and inner products on batches (bfv_evk.hip, bfv_resident.hip) ----
+ * zkfhe_bfv_cts_mul and zkfhe_bfv_cts_apply_galois take their keys as host arrays and check, upload and transform them on every
+ * call.  A key set keeps one relinearization key and any number of Galois keys on the device: it is opaque and holds, for the
+ * relinearization key (if any) and then for each Galois key in the order of g, the [2 l][5][N] uint32_t transform that the key
+ * switch reads (l = zkfhe_bfv_relin_digits), in one device allocation of its own: device_bytes = (has_relin + n_galois) 2 l 5 N 4 =
+ * zkfhe_bfv_evk_bytes.  No new arithmetic is defined, there is no new randomness and no new ChaCha20 domain.
+ * zkfhe_bfv_evk_create: rlk0, rlk1 are [l][N] or both NULL; g holds n_galois elements and gk0, gk1 are [n_galois][l][N] (n_galois
+ * may be 0, but not beside a NULL relinearization key).  It runs the host checks of the host-array calls with their texts under
+ * "bfv_evk_create: ...": a NULL argument; neither key ("... neither a relinearization key nor a Galois key"); bad parameters;
+ * base_bits outside [1, 32]; a g even or >= 2N; a g given twice ("... the Galois element G is repeated"); a key coefficient >= Q.
+ * Then it uploads the keys in chunks through the context's workspace and transforms them straight into the set, so the stored
+ * words are exactly those a host-array call computes from the same key.  On any failure (ZKFHE_ENOMEM included) everything is freed
+ * and *out is NULL.  The set is read-only and complete when the call returns: any context of the same device may use it, a context of
+ * another device is refused ("...: the key set lives on device D and the context on device E").  zkfhe_bfv_evk_info and
+ * zkfhe_bfv_evk_bytes are host only; any output of info may be NULL, g_out takes n_galois elements.  zkfhe_bfv_evk_destroy waits
+ * for the context it is given and then frees.
+ * The calls on batches that take a set follow the conventions of "Resident ciphertext batches": dst is caller-provided, nothing is
+ * allocated on the device, every call waits for its result, a refused call leaves dst as it was.
+ *   call                                                  definition (bit for bit)                              dst may be a source
+ *   zkfhe_bfv_cts_mul_evk(ctx, a, b, evk, dst)            zkfhe_bfv_mul with the set's relinearization key      yes
+ *   zkfhe_bfv_cts_apply_galois_evk(ctx, a, g, evk, dst)   zkfhe_bfv_apply_galois with the set's key for g       yes
+ *   zkfhe_bfv_cts_slot_sum(ctx, a, evk, dst)              zkfhe_bfv_slot_sum with the set's keys for the        yes
+ *                                                         elements of zkfhe_bfv_slot_sum_elements
+ *   zkfhe_bfv_cts_dot(ctx, a, b, n_terms, evk, dst)       zkfhe_bfv_dot: n_groups = dst's count, a holds        no (refused)
+ *                                                         n_groups n_terms ciphertexts in [group][term] order,
+ *                                                         b n_terms (shared) or n_groups n_terms
+ *   zkfhe_bfv_cts_dot_plain(ctx, a, n_terms, m_groups,    zkfhe_bfv_dot_plain: a as for dot; m a host array of  no (refused)
+ *                           m, dst)                       m_groups n_terms plaintexts; takes no key set
+ * Alias rules: where the table says yes, dst may be a or b (or both); a chunk is read completely before it is written.
+ * Refusals: ZKFHE_EINVAL with a message "bfv_cts_<name>: ...", in this order and all before any device work: a NULL argument or a
+ * zero count; a batch on another device; the key set on another device; "the key set and the batch have different parameters";
+ * batches of different parameters; a count that does not fit ("X holds H ciphertexts and the call needs W"); dst among the sources
+ * where the table says no ("dst must not be a source"); g even or >= 2N; "the key set has no relinearization key"; "the key set
+ * has no key for the Galois element G"; m_groups neither 1 nor n_groups; n_terms above zkfhe_bfv_dot_max_terms, with the text of
+ * zkfhe_bfv_dot; a plaintext out of range.
+ * The digit-parallel key switch.  The key switch of the host-array calls (k_key_switch) runs one workgroup per (ciphertext, prime)
+ * that walks the l digits one after the other: 5 workgroups for one ciphertext.  The calls above run, where l >= 2 and a chunk
+ * holds at most zkfhe_bfv_evk_wide_max ciphertexts, k_key_switch_digit (one workgroup per (digit, ciphertext, prime): the digit
+ * transformed and multiplied by its two key rows into partials in the workspace) and k_key_switch_fold (one workgroup per
+ * (component, ciphertext, prime): the l partials summed mod p, one inverse transform).  Every partial is a canonical residue in
+ * [0, p) and addition mod p is exact, so the result is bit for bit that of k_key_switch.  The bound keeps the grid of
+ * k_key_switch_digit, 5 l workgroups per ciphertext, at or below 5/4 of the device's CU count (16 ciphertexts at l = 4 on 256 CUs)
+ * and the partials within the accumulators a full chunk already needs;
+ * profiles/bfv_evk.md holds the measurement behind it (for which alone the environment variable ZKFHE_EVK_WIDE_MAX, read once per
+ * process, replaces the first of the two limits by a count).  The calls of the earlier sections never take this path: their
+ * kernels and launch counts are unchanged. */
+typedef struct zkfhe_bfv_evk zkfhe_bfv_evk;
+int zkfhe_bfv_evk_create(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, int base_bits, const uint64_t *rlk0, const uint64_t *rlk1,
+                         size_t n_galois, const uint64_t *g, const uint64_t *gk0, const uint64_t *gk1, zkfhe_bfv_evk **out);
+int zkfhe_bfv_evk_bytes(const zkfhe_bfv_params *params, int base_bits, int has_relin, size_t n_galois, uint64_t *bytes);
+int zkfhe_bfv_evk_info(const zkfhe_bfv_evk *evk, zkfhe_bfv_params *params, int *base_bits, int *has_relin, size_t *n_galois,
+                       uint64_t *g_out, uint64_t *device_bytes);
+/* waits for ctx (a context of the set's device; may be NULL), then frees the set; a NULL set is not an error */
+int zkfhe_bfv_evk_destroy(zkfhe_ctx *ctx, zkfhe_bfv_evk *evk);
+/* the largest count of ciphertexts in a chunk that takes the digit-parallel key switch on this device (0: never, as for l = 1) */
+int zkfhe_bfv_evk_wide_max(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, int base_bits, size_t *c_max);
+int zkfhe_bfv_cts_mul_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_apply_galois_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t g, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_dot(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, size_t n_terms, const zkfhe_bfv_evk *evk,
+                      zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_terms, size_t m_groups, const uint64_t *m, zkfhe_bfv_cts *dst);
+/* zkfhe_prof_read slot of the digit-parallel key switch: algorithmic bytes = the words read and written.  Everything else a call
+ * with a key set launches counts in the slots of its host-array call; no such call launches a key transform. */
+#define ZKFHE_PROF_BFV_KEY_SWITCH_WIDE 26   /* k_key_switch_digit, k_key_switch_fold */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

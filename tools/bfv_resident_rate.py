@@ -17,7 +17,20 @@ BallotBox.tally + the host chain against BallotBox.tally_cts + the batch chain.
 One JSON line per row (with the launches and the ms of every profiling slot of the last profiled pass), then the markdown table of
 profiles/bfv_resident.md.
 
-    python tools/bfv_resident_rate.py [--reps 7] [--prof-reps 3] [--box]
+    python tools/bfv_resident_rate.py [--reps 7] [--prof-reps 3] [--box] [--cts 1,64,1024]
+
+--evk times the chain a third way, alternating with the other two:
+
+    evk     the batch chain with a resident key set (zkfhe_bfv_evk) and the slot sum as one call: zkfhe_bfv_cts_store,
+            zkfhe_bfv_cts_mul_plain, zkfhe_bfv_cts_plan_apply, zkfhe_bfv_cts_slot_sum, zkfhe_bfv_cts_download
+
+and prints the tables of profiles/bfv_evk.md: the chain three ways, and the launches per profiling slot of each way.
+
+--key-switch measures the digit-parallel key switch (k_key_switch_digit + k_key_switch_fold, slot 26) against k_key_switch instead of
+the chain: zkfhe_bfv_cts_apply_galois (slot 14: the key switch and its epilogue) against zkfhe_bfv_cts_apply_galois_evk (slot 26 plus
+slot 14: the same epilogue), and zkfhe_bfv_cts_mul (slot 9) against zkfhe_bfv_cts_mul_evk (slot 26), the two calls alternating, at
+1 to 64 ciphertexts, N = 1024 and 4096, a 60-bit Q, w = 8 and 16; the median of --reps repeats with the lowest and the highest.  It
+sets ZKFHE_EVK_WIDE_MAX=64 before the library loads, so that the digit-parallel path runs at every count measured.
 """
 import argparse
 import ctypes
@@ -98,14 +111,32 @@ class Chain:
         x.store(c0, c1)
         return self.on_batch(x, rot, out)
 
+    def make_evk(self):
+        self.evk = self.ctx.bfv_evk(self.prm, W, None, self.elements, self.sk0, self.sk1)
+
+    def on_batch_evk(self, x, out):
+        """the chain on what x holds with the resident keys, the slot sum one call, into the host arrays out"""
+        x.mul_plain(self.weight, out=x)
+        self.plan.apply_cts(self.ctx, x, out=x)
+        x.slot_sum(self.evk, out=x)
+        x._call("zkfhe_bfv_cts_download", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, self.u64p, self.u64p], None, x._handle(), 0, x.n,
+                *[a.ctypes.data_as(self.u64p) for a in out])
+        return out
+
+    def batch_evk(self, c0, c1, x, out):
+        x.store(c0, c1)
+        return self.on_batch_evk(x, out)
+
     def close(self):
         self.plan.close()
+        if getattr(self, "evk", None):
+            self.evk.close()
 
 
 def kernel_ms(ctx, zk, fn):
     ctx.prof_enable(True)   # resets the slots
     fn()
-    prof = {s: ctx.prof_read(s) for s in range(zk.PROF_BFV_RESIDENT + 1)}
+    prof = {s: ctx.prof_read(s) for s in range(zk.PROF_BFV_KEY_SWITCH_WIDE + 1)}
     ctx.prof_enable(False)
     return sum(p["total_ms"] for p in prof.values()), {s: [p["launches"], round(p["total_ms"], 4)] for s, p in prof.items() if p["launches"]}
 
@@ -114,7 +145,7 @@ def compare(ctx, zk, np, legs, reps, prof_reps):
     """legs: {"host": fn, "batch": fn}, each returning its two result arrays -> wall and kernel ms per leg (lists), and the slots of
     the last profiled pass"""
     res = {name: [a.copy() for a in fn()] for name, fn in legs.items()}   # warm-up: tables, arena, code objects
-    assert all(np.array_equal(a, b) for a, b in zip(res["host"], res["batch"])), "the two chains differ"
+    assert all(np.array_equal(a, b) for name in res for a, b in zip(res["host"], res[name])), "the chains differ"
     wall, kern, slots = {name: [] for name in legs}, {name: [] for name in legs}, {}
     for _ in range(reps):
         for name, fn in legs.items():   # A/B
@@ -139,6 +170,8 @@ def row_of(what, prm, count, wall, kern, slots):
         row[name] = {"wall_ms": stats(wall[name]), "kernel_ms": stats(kern[name]), "slots": slots[name]}
     row["wall_ratio"] = round(row["host"]["wall_ms"]["median"] / row["batch"]["wall_ms"]["median"], 2)
     row["kernel_ratio"] = round(row["host"]["kernel_ms"]["median"] / row["batch"]["kernel_ms"]["median"], 3)
+    if "evk" in row:
+        row["evk_wall_ratio"] = round(row["host"]["wall_ms"]["median"] / row["evk"]["wall_ms"]["median"], 2)
     print(json.dumps(row), flush=True)
     return row
 
@@ -153,12 +186,17 @@ def measure(a):
     for prm in SHAPES:
         n, q = prm[0], prm[1]
         chain = Chain(ctx, zk, np, prm, rng)
-        for count in CTS:
+        if a.evk:
+            chain.make_evk()
+        for count in a.cts:
             c0 = rng.integers(0, q, size=(count, n), dtype=np.uint64)   # the cost does not depend on the values
             c1 = rng.integers(0, q, size=(count, n), dtype=np.uint64)
             host, x, rot = chain.buffers(count)
             out = [np.zeros((count, n), dtype=np.uint64) for _ in range(2)]
             legs = {"host": lambda: chain.host(c0, c1, host), "batch": lambda: chain.batch(c0, c1, x, rot, out)}
+            if a.evk:
+                out3 = [np.zeros((count, n), dtype=np.uint64) for _ in range(2)]
+                legs["evk"] = lambda: chain.batch_evk(c0, c1, x, out3)
             rows.append(row_of("chain", prm, count, *compare(ctx, zk, np, legs, a.reps, a.prof_reps)))
             x.close(), rot.close()
         chain.close()
@@ -187,6 +225,8 @@ def box_row(ctx, zk, np, rng, a):
     srs.destroy()
     pk0, pk1, _, _ = zk.bfv_instance_words(prm, items[0][0])
     chain = Chain(ctx, zk, np, prm, rng)
+    if a.evk:
+        chain.make_evk()
     box = zk.BallotBox(ctx, vk, prm, pk0, pk1, n_groups=3)
     assert all(s == zk.BALLOT_COUNTED for s, _ in box.add(items, [0, 1, 2, 0, 1, 2]))
     host, x, rot = chain.buffers(3)
@@ -200,9 +240,75 @@ def box_row(ctx, zk, np, rng, a):
         box.tally_cts(out=x)
         return chain.on_batch(x, rot, out)
 
-    row = row_of("box_tally_chain", prm, 3, *compare(ctx, zk, np, {"host": through_host, "batch": on_device}, a.reps, a.prof_reps))
+    legs = {"host": through_host, "batch": on_device}
+    if a.evk:
+        out3 = [np.zeros((3, n), dtype=np.uint64) for _ in range(2)]
+
+        def on_device_evk():
+            box.tally_cts(out=x)
+            return chain.on_batch_evk(x, out3)
+
+        legs["evk"] = on_device_evk
+    row = row_of("box_tally_chain", prm, 3, *compare(ctx, zk, np, legs, a.reps, a.prof_reps))
     x.close(), rot.close(), box.close(), chain.close()
     return row
+
+
+KS_COUNTS = (1, 2, 3, 4, 8, 16, 32, 64)
+
+
+def key_switch_rows(a):
+    """the key-switch kernels of one call, sequential against digit-parallel, from the profiling slots"""
+    os.environ.setdefault("ZKFHE_EVK_WIDE_MAX", str(max(KS_COUNTS)))   # before the library loads: the bound itself is what is measured
+    import numpy as np
+    import torch  # noqa: F401
+    import zk_fhe_amd as zk
+    ctx = zk.Context(0)
+    rng = np.random.default_rng(1)
+    GAL, REL, EPI, WIDE = zk.PROF_BFV_GALOIS, zk.PROF_BFV_RELIN, zk.PROF_BFV_EVAL_EPILOGUE, zk.PROF_BFV_KEY_SWITCH_WIDE
+    rows = []
+
+    def slots_ms(fn, slots):
+        ctx.prof_enable(True)
+        fn()
+        ms = sum(ctx.prof_read(s)["total_ms"] for s in slots)
+        ctx.prof_enable(False)
+        return ms
+
+    for prm in SHAPES:
+        n, q = prm[0], prm[1]
+        for w in (8, 16):
+            sk = ctx.bfv_fhe_keypair(prm, os.urandom(32))[0]
+            gk0, gk1 = ctx.bfv_galois_keygen(prm, sk, 5, base_bits=w)
+            rlk = ctx.bfv_relin_keygen(prm, sk, base_bits=w)
+            evk = ctx.bfv_evk(prm, w, rlk, [5], gk0[None], gk1[None])
+            l = zk.bfv_relin_digits(prm, w)
+            for count in KS_COUNTS:
+                assert count <= ctx.bfv_evk_wide_max(prm, w), "the digit-parallel path is not forced"
+                c = [rng.integers(0, q, size=(count, n), dtype=np.uint64) for _ in range(4)]
+                x, y, out = ctx.bfv_cts(prm, c[0], c[1]), ctx.bfv_cts(prm, c[2], c[3]), ctx.bfv_cts_zeros(prm, count)
+                for kind, old, new, old_slots, new_slots in [
+                        ("galois", lambda: x.apply_galois(5, gk0, gk1, base_bits=w, out=out), lambda: x.apply_galois_evk(5, evk, out=out), (GAL,), (WIDE, GAL)),
+                        ("relin", lambda: x.mul(y, rlk[0], rlk[1], base_bits=w, out=out), lambda: x.mul_evk(y, evk, out=out), (REL,), (WIDE,))]:
+                    old(), new()   # warm-up
+                    ms = {"seq": [], "wide": []}
+                    for _ in range(a.reps):
+                        ms["seq"].append(slots_ms(old, old_slots))
+                        ms["wide"].append(slots_ms(new, new_slots))
+                    row = {"what": "key_switch", "kind": kind, "N": n, "w": w, "l": l, "cts": count, "grid_seq": 5 * count, "grid_wide": 5 * count * l,
+                           "num_cu": ctx.device_info()["num_cu"], "seq_ms": stats(ms["seq"]), "wide_ms": stats(ms["wide"])}
+                    row["wide_below_seq"] = row["wide_ms"]["max"] < row["seq_ms"]["min"]
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+                x.close(), y.close(), out.close()
+            evk.close()
+    ctx.close()
+    rng_of = lambda s: "%.4f (%.4f .. %.4f)" % (s["median"], s["min"], s["max"])  # noqa: E731
+    print("\n| key switch | N | w | l | ciphertexts | grid k_key_switch | grid k_key_switch_digit | ms k_key_switch: median (min .. max) of %d | "
+          "ms digit-parallel | highest digit-parallel < lowest k_key_switch |\n|---|---|---|---|---|---|---|---|---|---|" % a.reps)
+    for r in rows:
+        print("| %s | %d | %d | %d | %d | %d | %d | %s | %s | %s |" % (r["kind"], r["N"], r["w"], r["l"], r["cts"], r["grid_seq"], r["grid_wide"],
+                                                                      rng_of(r["seq_ms"]), rng_of(r["wide_ms"]), "yes" if r["wide_below_seq"] else "no"))
 
 
 def main():
@@ -210,7 +316,12 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--prof-reps", type=int, default=3)
     ap.add_argument("--box", action="store_true", help="also the chain on the tally of a ballot box of 3 groups (makes six k = 13 proofs)")
+    ap.add_argument("--evk", action="store_true", help="also the batch chain with a resident key set and the slot sum as one call")
+    ap.add_argument("--key-switch", action="store_true", help="the digit-parallel key switch against k_key_switch instead of the chain")
+    ap.add_argument("--cts", type=lambda v: tuple(int(x) for x in v.split(",")), default=CTS, help="the ciphertext counts of the chain rows")
     a = ap.parse_args()
+    if a.key_switch:
+        return key_switch_rows(a)
     rows = measure(a)
     rng_of = lambda s: "%.3f (%.3f .. %.3f)" % (s["median"], s["min"], s["max"])  # noqa: E731
     print("\n| chain | N | Q bits | ciphertexts | wall ms host arrays: median (min .. max) of %d | wall ms batch | host / batch | kernel ms host arrays: median (min .. max) of %d | "
@@ -219,6 +330,22 @@ def main():
         print("| %s | %d | %d | %d | %s | %s | %.2f | %s | %s | %.3f |" % (
             r["what"], r["N"], r["Q"].bit_length(), r["cts"], rng_of(r["host"]["wall_ms"]), rng_of(r["batch"]["wall_ms"]), r["wall_ratio"],
             rng_of(r["host"]["kernel_ms"]), rng_of(r["batch"]["kernel_ms"]), r["kernel_ratio"]))
+
+    if a.evk:
+        print("\n| chain | N | ciphertexts | wall ms host arrays | wall ms batch | wall ms batch + key set | host / key set | kernel ms host arrays | "
+              "kernel ms batch | kernel ms batch + key set |\n|---|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            print("| %s | %d | %d | %s | %s | %s | %.2f | %s | %s | %s |" % (
+                r["what"], r["N"], r["cts"], rng_of(r["host"]["wall_ms"]), rng_of(r["batch"]["wall_ms"]), rng_of(r["evk"]["wall_ms"]), r["evk_wall_ratio"],
+                rng_of(r["host"]["kernel_ms"]), rng_of(r["batch"]["kernel_ms"]), rng_of(r["evk"]["kernel_ms"])))
+        print("\n| chain | N | ciphertexts | slot | host arrays: launches, ms | batch: launches, ms | batch + key set: launches, ms |\n|---|---|---|---|---|---|---|")
+        for r in rows:
+            if r["cts"] > 3:
+                continue
+            used = sorted({int(s) for name in ("host", "batch", "evk") for s in r[name]["slots"]})
+            cell = lambda name, s: "%d, %.3f" % tuple(r[name]["slots"][s]) if s in r[name]["slots"] else "none"  # noqa: E731
+            for s in used:
+                print("| %s | %d | %d | %d | %s | %s | %s |" % (r["what"], r["N"], r["cts"], s, cell("host", s), cell("batch", s), cell("evk", s)))
 
 
 if __name__ == "__main__":

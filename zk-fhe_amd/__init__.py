@@ -28,6 +28,7 @@ PROF_BFV_PCKS_COMBINE, PROF_BFV_REFRESH_COMBINE = 21, 22   # ... and of the key-
 PROF_G1_FFT = 23   # ... and of the G1 FFT's butterfly kernels
 PROF_BFV_BALLOT = 24   # ... and of the ballot box's unpack and sum kernels
 PROF_BFV_RESIDENT = 25   # ... and of the resident batches' check, gather and group-sum kernels
+PROF_BFV_KEY_SWITCH_WIDE = 26   # ... and of the digit-parallel key switch of the calls that take a resident key set
 # per-item statuses of Context.bfv_sum_instances and BallotBox.add (ZKFHE_BALLOT_* of zkfhe.h)
 BALLOT_COUNTED, BALLOT_SKIPPED, BALLOT_BAD_GROUP, BALLOT_NOT_A_CIPHERTEXT, BALLOT_WRONG_KEY, BALLOT_REJECTED, BALLOT_REPEATED = range(7)
 BALLOT_STATUSES = 7
@@ -69,6 +70,8 @@ EXPORTS = [
     "zkfhe_bfv_cts_alloc", "zkfhe_bfv_cts_upload", "zkfhe_bfv_cts_store", "zkfhe_bfv_cts_download", "zkfhe_bfv_cts_info", "zkfhe_bfv_cts_destroy",
     "zkfhe_bfv_box_tally_cts", "zkfhe_bfv_cts_add", "zkfhe_bfv_cts_add_plain", "zkfhe_bfv_cts_mul_plain", "zkfhe_bfv_cts_mul",
     "zkfhe_bfv_cts_apply_galois", "zkfhe_bfv_cts_plan_apply", "zkfhe_bfv_cts_select", "zkfhe_bfv_cts_sum",
+    "zkfhe_bfv_evk_create", "zkfhe_bfv_evk_bytes", "zkfhe_bfv_evk_info", "zkfhe_bfv_evk_destroy", "zkfhe_bfv_evk_wide_max",
+    "zkfhe_bfv_cts_mul_evk", "zkfhe_bfv_cts_apply_galois_evk", "zkfhe_bfv_cts_slot_sum", "zkfhe_bfv_cts_dot", "zkfhe_bfv_cts_dot_plain",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -1003,6 +1006,95 @@ class Context:
         self._bfv("zkfhe_bfv_cts_alloc", "nP", params, int(n), ctypes.byref(h))
         return BfvCiphertexts(self, h)
 
+    # ---- resident evaluation keys: checked, uploaded and transformed once (zkfhe.h, bfv_evk.hip)
+
+    def bfv_evk(self, params, base_bits=16, rlk=None, elements=(), gk0=None, gk1=None):
+        """zkfhe_bfv_evk_create: rlk = (rlk0, rlk1) of shape (l, N) or None; elements: Galois elements with their keys stacked as gk0,
+        gk1 of shape (len(elements), l, N) -> a BfvEvalKeys, resident on this context's device until it is closed."""
+        n = int(params[0])
+        r0 = r1 = None
+        if rlk is not None:
+            r0, r1 = self._galois_keys(params, rlk[0], rlk[1], base_bits, ())
+        g = np.ascontiguousarray([int(x) for x in elements], dtype=np.uint64).reshape(-1)
+        k0 = k1 = None
+        if g.shape[0]:
+            if gk0 is None or gk1 is None:
+                raise ValueError("gk0 and gk1 hold one key per element")
+            k0, k1 = self._galois_keys(params, gk0, gk1, base_bits, (g.shape[0],))
+        f = self.lib.zkfhe_bfv_evk_create
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_int, _U64P, _U64P, ctypes.c_size_t, _U64P, _U64P, _U64P,
+                      ctypes.POINTER(ctypes.c_void_p)]
+        ptr = lambda a: a.ctypes.data_as(_U64P) if a is not None else None  # noqa: E731
+        h = ctypes.c_void_p()
+        self._check(f(self.h, ctypes.byref(BfvParamsC(*[int(x) for x in params])), int(base_bits), ptr(r0), ptr(r1), g.shape[0],
+                      ptr(g) if g.shape[0] else None, ptr(k0), ptr(k1), ctypes.byref(h)))
+        return BfvEvalKeys(self, h)
+
+    def bfv_evk_wide_max(self, params, base_bits=16):
+        """zkfhe_bfv_evk_wide_max: the largest count of ciphertexts in a chunk whose key switch takes the digit-parallel kernels on
+        this device in the calls that take a BfvEvalKeys (0: never)"""
+        out = ctypes.c_size_t()
+        f = self.lib.zkfhe_bfv_evk_wide_max
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+        self._check(f(self.h, ctypes.byref(BfvParamsC(*[int(x) for x in params])), int(base_bits), ctypes.byref(out)))
+        return out.value
+
+
+class BfvEvalKeys:
+    """A resident evaluation key set (zkfhe_bfv_evk): one relinearization key and any number of Galois keys, transformed once and
+    read-only on the device.  Any Context of the same device may use it in BfvCiphertexts.mul_evk, apply_galois_evk, slot_sum and dot;
+    close() (or leaving the with block) frees it, and no context may still be using it then."""
+
+    def __init__(self, ctx, handle=None):
+        if not isinstance(ctx, Context):
+            raise ZkfheError("BfvEvalKeys needs a Context: use Context.bfv_evk")
+        if not handle:
+            raise ZkfheError("BfvEvalKeys wraps a key set made by Context.bfv_evk")
+        self.ctx = ctx
+        self.h = handle
+        self.params = self.info()["params"]
+
+    def _handle(self):
+        if not self.h:
+            raise ZkfheError("the key set is closed")
+        return self.h
+
+    def info(self):
+        """zkfhe_bfv_evk_info -> params (N, Q, T, B), base_bits, has_relin, elements (the Galois elements in the order of their keys)
+        and device_bytes ((has_relin + len(elements)) 2 l 5 N 4)"""
+        f = self.ctx.lib.zkfhe_bfv_evk_info
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                      ctypes.POINTER(ctypes.c_size_t), _U64P, ctypes.POINTER(ctypes.c_uint64)]
+        prm, w, relin, ng, nbytes = BfvParamsC(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t(), ctypes.c_uint64()
+        rc = f(self._handle(), ctypes.byref(prm), ctypes.byref(w), ctypes.byref(relin), ctypes.byref(ng), None, ctypes.byref(nbytes))
+        g = np.empty(ng.value, dtype=np.uint64)
+        if rc == 0 and ng.value:
+            rc = f(self._handle(), None, None, None, None, g.ctypes.data_as(_U64P), None)
+        if rc != 0:
+            raise ZkfheError("zkfhe_bfv_evk_info failed (%d): %s" % (rc, self.ctx.lib.zkfhe_last_error(None).decode()))
+        return {"params": tuple(int(getattr(prm, name)) for name, _ in BfvParamsC._fields_), "base_bits": w.value, "has_relin": bool(relin.value),
+                "elements": [int(x) for x in g], "device_bytes": nbytes.value}
+
+    def close(self):
+        if self.h:
+            f = self.ctx.lib.zkfhe_bfv_evk_destroy
+            f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            h, self.h = self.h, None
+            self.ctx._check(f(self.ctx.h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class BfvCiphertexts:
     """A resident batch (zkfhe_bfv_cts): n ciphertexts on the device, every word a residue below Q.  The methods are the evaluation
@@ -1122,6 +1214,43 @@ class BfvCiphertexts:
         ng = int(n_groups)
         return self._into(out, ctx, ng if 1 <= ng <= 4096 else 1, "zkfhe_bfv_cts_sum", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
                           self._handle(), grp.ctypes.data_as(ctypes.c_void_p) if grp is not None else None, ng)
+
+    # ---- the calls that take a resident key set (BfvEvalKeys): no key is checked, uploaded or transformed per call
+
+    def mul_evk(self, other, evk, out=None, ctx=None):
+        """zkfhe_bfv_cts_mul_evk: the relinearized products self * other under the set's relinearization key; bit for bit mul"""
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_mul_evk", [ctypes.c_void_p] * 3, self._handle(), other._handle(), evk._handle())
+
+    def apply_galois_evk(self, g, evk, out=None, ctx=None):
+        """zkfhe_bfv_cts_apply_galois_evk: sigma_g of every ciphertext with the set's key for g; bit for bit apply_galois"""
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_apply_galois_evk", [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p], self._handle(), int(g),
+                          evk._handle())
+
+    def slot_sum(self, evk, out=None, ctx=None):
+        """zkfhe_bfv_cts_slot_sum: every slot of every ciphertext holds its total, with the set's keys for bfv_slot_sum_elements; bit
+        for bit Context.bfv_slot_sum, as one call"""
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_slot_sum", [ctypes.c_void_p, ctypes.c_void_p], self._handle(), evk._handle())
+
+    def _groups(self, n_terms):
+        n_terms = int(n_terms)
+        return n_terms, (self.n // n_terms if n_terms > 0 and self.n % n_terms == 0 else 1)
+
+    def dot(self, other, n_terms, evk, out=None, ctx=None):
+        """zkfhe_bfv_cts_dot: self holds n_groups * n_terms ciphertexts in [group][term] order, other n_terms (shared by every group)
+        or as many as self -> n_groups inner products, one rescale and one relinearization each; out must not be a source"""
+        n_terms, n_groups = self._groups(n_terms)
+        return self._into(out, ctx, n_groups, "zkfhe_bfv_cts_dot", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p],
+                          self._handle(), other._handle(), n_terms, evk._handle())
+
+    def dot_plain(self, m, n_terms, out=None, ctx=None):
+        """zkfhe_bfv_cts_dot_plain: self as for dot; m: plaintexts (n_terms, N), shared by every group, or (n_groups, n_terms, N) ->
+        n_groups weighted sums; out must not be self"""
+        n_terms, n_groups = self._groups(n_terms)
+        m = np.ascontiguousarray(m, dtype=np.uint64)
+        if m.ndim not in (2, 3) or m.shape[-1] != self.params[0] or m.shape[-2] != n_terms or 0 in m.shape:
+            raise ValueError("m must have shape (n_terms, N) or (n_groups, n_terms, N)")
+        return self._into(out, ctx, n_groups, "zkfhe_bfv_cts_dot_plain", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _U64P], self._handle(),
+                          n_terms, 1 if m.ndim == 2 else m.shape[0], m.ctypes.data_as(_U64P))
 
     def close(self):
         if self.h:
@@ -1249,6 +1378,14 @@ def bfv_plan_bytes(params, base_bits, n_elems_total, n_key_slots, n_diagonals):
     out = ctypes.c_uint64()
     _host_bfv("zkfhe_bfv_plan_bytes", [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)], params,
               int(base_bits), int(n_elems_total), int(n_key_slots), int(n_diagonals), ctypes.byref(out))
+    return out.value
+
+
+def bfv_evk_bytes(params, base_bits, has_relin, n_galois):
+    """zkfhe_bfv_evk_bytes (host only): the device bytes of a key set, (has_relin + n_galois) 2 l 5 N 4 with l = bfv_relin_digits."""
+    out = ctypes.c_uint64()
+    _host_bfv("zkfhe_bfv_evk_bytes", [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)], params, int(base_bits),
+              int(bool(has_relin)), int(n_galois), ctypes.byref(out))
     return out.value
 
 

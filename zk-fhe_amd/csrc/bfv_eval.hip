@@ -251,7 +251,11 @@ int zk_bfv_mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l
   ZK_CK(zk_bfv_hat(ctx, w.in_d, LOAD_CENTRED, q, 4 * c, log_n, w.hat, w.flag));
   ZK_CK(launch_tensor(ctx, w.hat, c, log_n, w.res));
   ZK_CK(zk_bfv_eval_epilogue(ctx, w.res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = prm->t}, w.chat));
-  ZK_CK(zk_bfv_key_switch(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, w.rlk_hat, c, log_n, w.res));
+  const uint32_t *key = w.key ? w.key : w.rlk_hat;
+  if (w.part)
+    ZK_CK(zk_bfv_key_switch_wide(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, key, c, log_n, w.part, w.res));
+  else
+    ZK_CK(zk_bfv_key_switch(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, key, c, log_n, w.res));
   return zk_bfv_eval_epilogue(ctx, w.res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = w.chat}, w.o_d);
 }
 

@@ -9,7 +9,8 @@
 //                              component (sum < l N 2^w Q < 2^116)
 //   k_eval_epilogue EV_GALOIS  Garner over the five primes, x mod Q, + sigma_g(c0) on component 0, + x_in when set (slot_sum's
 //                              x <- x + apply_galois(x), fused: the same sums mod Q as zkfhe_bfv_add)
-// The Galois key is transformed once per call; slot_sum transforms all log2(N) keys once and runs every step on device buffers.
+// The Galois key is transformed once per call; slot_sum transforms all log2(N) keys once and runs every step on device buffers
+// (zk_bfv_slot_sum_core, which bfv_resident.hip drives from a resident batch and a resident key set).
 // Galois keys (and their threshold shares) are products a_j s with a ternary s: the three-prime k_rns_ntt against the transform of
 // s, then k_rns_epilogue (bfv_enc.hip) in EPI_GADGET mode: 2^(j w) sigma_g(s) - a_j s - e_j mod Q.
 //
@@ -197,11 +198,24 @@ int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn) {
 }
 
 int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
-                       bool accumulate, uint32_t *acc, uint64_t *out_d) {
+                       bool accumulate, uint32_t *acc, uint64_t *out_d, uint32_t *part) {
   const unsigned ginv = galois_inv(g, (uint64_t)1 << log_n);
-  ZK_CK(zk_bfv_key_switch(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, acc));
+  if (part)
+    ZK_CK(zk_bfv_key_switch_wide(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, part, acc));
+  else
+    ZK_CK(zk_bfv_key_switch(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, acc));
   const EvEpi epi{.mode = EV_GALOIS, .add = accumulate ? x_d : nullptr, .poly = x_d, .ginv = ginv, .c = c};
   return zk_bfv_eval_epilogue(ctx, acc, 2 * c, log_n, q, epi, out_d);
+}
+
+int zk_bfv_slot_sum_core(zkfhe_ctx *ctx, uint64_t *x, uint64_t *y, size_t c, int log_n, uint64_t q, size_t steps, const uint64_t *gs, int l, int w,
+                         const uint32_t *const *key_hat, uint32_t *acc, uint32_t *part, uint64_t **out) {
+  for (size_t k = 0; k < steps; ++k) {   // x <- x + apply_galois(x, g_k), on the device
+    ZK_CK(zk_bfv_galois_core(ctx, x, c, log_n, q, gs[k], l, w, key_hat[k], true, acc, y, part));
+    std::swap(x, y);
+  }
+  *out = x;
+  return ZKFHE_OK;
 }
 
 }  // namespace zkrns
@@ -332,15 +346,14 @@ int zkfhe_bfv_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_
     ZK_CK(zkfhe_upload(ctx, key_d + (2 * k + 1) * kw, gk1 + k * kw, kw * 8));
   }
   ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * steps * l, log_n, nullptr, 0, key_hat, flag));
+  std::vector<const uint32_t *> keys(steps);
+  for (size_t k = 0; k < steps; ++k) keys[k] = key_hat + 2 * k * kw * NP;
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
     const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-    uint64_t *x = x_d, *y = y_d;
-    ZK_CK(zkfhe_upload(ctx, x, c0 + lo * n, bytes));
-    ZK_CK(zkfhe_upload(ctx, x + c * n, c1 + lo * n, bytes));
-    for (size_t k = 0; k < steps; ++k) {   // x <- x + apply_galois(x, g_k), on the device
-      ZK_CK(zk_bfv_galois_core(ctx, x, c, log_n, q, gs[k], l, base_bits, key_hat + 2 * k * kw * NP, true, acc, y));
-      std::swap(x, y);
-    }
+    uint64_t *x = nullptr;
+    ZK_CK(zkfhe_upload(ctx, x_d, c0 + lo * n, bytes));
+    ZK_CK(zkfhe_upload(ctx, x_d + c * n, c1 + lo * n, bytes));
+    ZK_CK(zk_bfv_slot_sum_core(ctx, x_d, y_d, c, log_n, q, steps, gs.data(), l, base_bits, keys.data(), acc, nullptr, &x));
     ZK_CK(zkfhe_download(ctx, out0 + lo * n, x, bytes));
     ZK_CK(zkfhe_download(ctx, out1 + lo * n, x + c * n, bytes));
   }

@@ -13,6 +13,9 @@
 // contiguous copy in the work arena where it wants one), writes its result to the work arena, and the result is copied into dst
 // afterwards on the same stream: a chunk is read completely before it is written, and dst may be a source.  No call allocates or
 // frees device memory apart from alloc, upload and destroy.
+// The calls that take a resident key set (bfv_evk.hip: mul_evk, apply_galois_evk, slot_sum, dot; dot_plain takes none) drive the same
+// cores plus zk_bfv_slot_sum_core and zk_bfv_dot_core with the set's transformed keys: no key is checked, uploaded or transformed,
+// and a chunk of at most zk_bfv_wide_max ciphertexts takes the digit-parallel key switch, whose partials come from the work arena.
 // This file's own kernels are three plain passes over memory, 16 bytes per lane, a capped grid with a grid stride:
 //   k_cts_check      any word >= Q raises one flag word
 //   k_cts_gather     dst[j] = src[idx[j]], both planes (select; idx == null: j itself, the box's [group][2][N] layout to two planes)
@@ -205,6 +208,64 @@ int plain_args(zkfhe_ctx *ctx, const char *fn, const zkfhe_bfv_cts *a, size_t m_
   ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
   if (m_count != 1 && m_count != a->n) return refuse(ctx, fn, "m_count must be 1 or the ciphertext count");
   return check_plain(ctx, m, m_count * a->params.n, a->params.q, a->params.t, fn);
+}
+
+// a call that takes a key set: the set on the context's device, with the batch's parameters
+int evk_args(zkfhe_ctx *ctx, const char *fn, const zkfhe_bfv_evk *evk, const zkfhe_bfv_cts *a, EvkView *view) {
+  zk_bfv_evk_view(evk, view);
+  if (ctx->device != view->device)
+    return refuse(ctx, fn, "the key set lives on device " + std::to_string(view->device) + " and the context on device " + std::to_string(ctx->device));
+  if (!same_params(view->params, a->params)) return refuse(ctx, fn, "the key set and the batch have different parameters");
+  return ZKFHE_OK;
+}
+
+int need_relin(zkfhe_ctx *ctx, const char *fn, const EvkView &view) {
+  if (!view.rlk_hat) return refuse(ctx, fn, "the key set has no relinearization key");
+  return ZKFHE_OK;
+}
+
+int need_galois(zkfhe_ctx *ctx, const char *fn, const zkfhe_bfv_evk *evk, uint64_t g, const uint32_t **key_hat) {
+  *key_hat = zk_bfv_evk_galois(evk, g);
+  if (!*key_hat) return refuse(ctx, fn, "the key set has no key for the Galois element " + std::to_string(g));
+  return ZKFHE_OK;
+}
+
+// the words of the digit-parallel key switch's partials for chunks of `chunk` ciphertexts: 0 where the chunk takes k_key_switch
+size_t wide_words(const zkfhe_ctx *ctx, uint64_t n, int l, size_t chunk) { return chunk <= zk_bfv_wide_max(ctx, n, l) ? wide_part_words(n, l, chunk) : 0; }
+
+// the chunk loop of apply_galois_evk and slot_sum: steps key switches per chunk, each added to its input when accumulate
+int galois_chain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const EvkView &view, size_t steps, const uint64_t *gs, const uint32_t *const *keys,
+                 bool accumulate, zkfhe_bfv_cts *dst) {
+  const uint64_t n = a->params.n, q = a->params.q;
+  const int log_n = bit_log2(n);
+  const size_t chunk = std::min<size_t>(a->n, chunk_polys(n)), cw = chunk * n;
+  uint64_t *x_d, *y_d;
+  uint32_t *acc, *part;
+  const size_t pw = wide_words(ctx, n, view.l, chunk);
+  ZK_CK(Arena().add(x_d, 2 * cw).add(y_d, 2 * cw).add(acc, 2 * cw * NP).add(part, pw).carve(ctx));
+  for (size_t lo = 0; lo < a->n; lo += chunk) {
+    const size_t c = std::min(chunk, a->n - lo), bytes = c * n * 8;
+    ZK_CK(zk_copy_d2d(ctx, x_d, a->plane(0) + lo * n, bytes));   // the core reads [c0 | c1] of the chunk
+    ZK_CK(zk_copy_d2d(ctx, x_d + c * n, a->plane(1) + lo * n, bytes));
+    uint64_t *r = y_d;
+    if (accumulate)
+      ZK_CK(zk_bfv_slot_sum_core(ctx, x_d, y_d, c, log_n, q, steps, gs, view.l, view.base_bits, keys, acc, pw ? part : nullptr, &r));
+    else
+      ZK_CK(zk_bfv_galois_core(ctx, x_d, c, log_n, q, gs[0], view.l, view.base_bits, keys[0], false, acc, y_d, pw ? part : nullptr));
+    ZK_CK(put(ctx, dst, 0, lo, r, c));
+    ZK_CK(put(ctx, dst, 1, lo, r + c * n, c));
+  }
+  ZK_HIP(ctx, zk_wait(ctx));
+  return ZKFHE_OK;
+}
+
+// dot and dot_plain on batches: the shapes, then the core on the planes
+int dot_args(zkfhe_ctx *ctx, const char *fn, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, size_t n_terms, const zkfhe_bfv_cts *dst) {
+  const size_t want = n_terms >> 31 ? ~(size_t)0 : dst->n * n_terms;   // counts are below 2^31: the product fits
+  ZK_CK(same_count(ctx, fn, a->n, want, "a"));
+  if (b && b->n != n_terms) ZK_CK(same_count(ctx, fn, b->n, want, "b"));
+  if (dst == a || dst == b) return refuse(ctx, fn, "dst must not be a source");
+  return ZKFHE_OK;
 }
 
 }  // namespace
@@ -532,6 +593,106 @@ int zkfhe_bfv_cts_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const int32_t *gro
                                                                      (ulonglong2 *)dst->w);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_RESIDENT, (double)(off[n_groups] + n_groups) * 2 * n * 8);
+  ZK_HIP(ctx, zk_wait(ctx));
+  return ZKFHE_OK;
+}
+
+// ---- the calls that take a resident key set (bfv_evk.hip): no key is checked, uploaded or transformed here
+
+int zkfhe_bfv_cts_mul_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
+  CTS_CALL("mul_evk");
+  if (!(ctx && a && b && evk && dst)) return null_arg(ctx, fn);
+  ZK_CK(on_device(ctx, fn, {a, b, dst}));
+  EvkView view;
+  ZK_CK(evk_args(ctx, fn, evk, a, &view));
+  ZK_CK(alike(ctx, fn, a, b));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(same_count(ctx, fn, b->n, a->n, "b"));
+  ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
+  ZK_CK(need_relin(ctx, fn, view));
+  const uint64_t n = a->params.n;
+  MulWork w;
+  Arena arena;
+  add_mul_work(arena, n, 0, a->n, w);   // no rows of a key to stage
+  arena.add(w.part, wide_words(ctx, n, view.l, w.chunk));
+  ZK_CK(arena.carve(ctx));
+  w.key = view.rlk_hat;
+  if (!wide_words(ctx, n, view.l, w.chunk)) w.part = nullptr;
+  const uint64_t *src[4] = {a->plane(0), a->plane(1), b->plane(0), b->plane(1)};
+  for (size_t lo = 0; lo < a->n; lo += w.chunk) {
+    const size_t c = std::min(w.chunk, a->n - lo);
+    for (int i = 0; i < 4; ++i) ZK_CK(zk_copy_d2d(ctx, w.in_d + i * c * n, src[i] + lo * n, c * n * 8));   // the 4 c transforms want them contiguous
+    ZK_CK(zk_bfv_mul_core(ctx, &a->params, c, view.l, view.base_bits, w));
+    ZK_CK(put(ctx, dst, 0, lo, w.o_d, c));
+    ZK_CK(put(ctx, dst, 1, lo, w.o_d + c * n, c));
+  }
+  ZK_HIP(ctx, zk_wait(ctx));
+  return ZKFHE_OK;
+}
+
+int zkfhe_bfv_cts_apply_galois_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t g, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
+  CTS_CALL("apply_galois_evk");
+  if (!(ctx && a && evk && dst)) return null_arg(ctx, fn);
+  ZK_CK(on_device(ctx, fn, {a, dst}));
+  EvkView view;
+  ZK_CK(evk_args(ctx, fn, evk, a, &view));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
+  ZK_CK(check_g(ctx, a->params.n, g, fn));
+  const uint32_t *key;
+  ZK_CK(need_galois(ctx, fn, evk, g, &key));
+  return galois_chain(ctx, a, view, 1, &g, &key, false, dst);
+}
+
+int zkfhe_bfv_cts_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
+  CTS_CALL("slot_sum");
+  if (!(ctx && a && evk && dst)) return null_arg(ctx, fn);
+  ZK_CK(on_device(ctx, fn, {a, dst}));
+  EvkView view;
+  ZK_CK(evk_args(ctx, fn, evk, a, &view));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
+  size_t steps = 0;
+  ZK_CK(zkfhe_bfv_slot_sum_elements(&a->params, nullptr, &steps));
+  std::vector<uint64_t> gs(steps);
+  ZK_CK(zkfhe_bfv_slot_sum_elements(&a->params, gs.data(), &steps));
+  std::vector<const uint32_t *> keys(steps);
+  for (size_t k = 0; k < steps; ++k) ZK_CK(need_galois(ctx, fn, evk, gs[k], &keys[k]));
+  return galois_chain(ctx, a, view, steps, gs.data(), keys.data(), true, dst);
+}
+
+int zkfhe_bfv_cts_dot(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, size_t n_terms, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
+  CTS_CALL("dot");
+  if (!(ctx && a && b && evk && dst && n_terms > 0)) return null_arg(ctx, fn);
+  ZK_CK(on_device(ctx, fn, {a, b, dst}));
+  EvkView view;
+  ZK_CK(evk_args(ctx, fn, evk, a, &view));
+  ZK_CK(alike(ctx, fn, a, b));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(dot_args(ctx, fn, a, b, n_terms, dst));
+  ZK_CK(need_relin(ctx, fn, view));
+  ZK_CK(check_dot_terms(ctx, &a->params, false, n_terms, fn));
+  DotIo io;
+  io.resident = true, io.a0 = a->plane(0), io.a1 = a->plane(1), io.b0 = b->plane(0), io.b1 = b->plane(1);
+  io.out0 = dst->plane(0), io.out1 = dst->plane(1), io.key_hat = view.rlk_hat, io.wide_max = zk_bfv_wide_max(ctx, a->params.n, view.l);
+  ZK_CK(zk_bfv_dot_core(ctx, &a->params, false, dst->n, n_terms, b->n / n_terms, io, view.l, view.base_bits));
+  ZK_HIP(ctx, zk_wait(ctx));
+  return ZKFHE_OK;
+}
+
+int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_terms, size_t m_groups, const uint64_t *m, zkfhe_bfv_cts *dst) {
+  CTS_CALL("dot_plain");
+  if (!(ctx && a && m && dst && n_terms > 0)) return null_arg(ctx, fn);
+  ZK_CK(on_device(ctx, fn, {a, dst}));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(dot_args(ctx, fn, a, nullptr, n_terms, dst));
+  if (m_groups != 1 && m_groups != dst->n) return refuse(ctx, fn, "m_groups must be 1 or n_groups");
+  ZK_CK(check_dot_terms(ctx, &a->params, true, n_terms, fn));
+  const uint64_t n = a->params.n;
+  ZK_CK(check_plain(ctx, m, m_groups * n_terms * n, a->params.q, a->params.t, fn));
+  DotIo io;   // the plaintexts are the call's one host operand
+  io.resident = true, io.b_host = true, io.a0 = a->plane(0), io.a1 = a->plane(1), io.b0 = m, io.out0 = dst->plane(0), io.out1 = dst->plane(1);
+  ZK_CK(zk_bfv_dot_core(ctx, &a->params, true, dst->n, n_terms, m_groups, io, 0, 0));
   ZK_HIP(ctx, zk_wait(ctx));
   return ZKFHE_OK;
 }

@@ -479,6 +479,8 @@ struct MulWork {
   int *flag;
   uint64_t *rlk_d, *in_d, *chat, *o_d;
   uint32_t *rlk_hat, *hat, *res;
+  const uint32_t *key = nullptr;   // the transformed key where it is resident (a key set), else rlk_hat
+  uint32_t *part = nullptr;        // the partials of the digit-parallel key switch ([l][2][c][5][N]), null: k_key_switch
 };
 void add_mul_work(Arena &a, uint64_t n, int l, size_t n_pairs, MulWork &w);
 // steps 1 to 5 of bfv_eval.hip for c pairs: w.in_d = [a0 | a1 | b0 | b1] ([4 c][N]), w.rlk_hat the transformed key; w.o_d = [out0 | out1]
@@ -487,8 +489,47 @@ int zk_bfv_mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l
 // "fn: ..." unless g is odd and below 2N
 int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn);
 // one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
+// part: the partials of the digit-parallel key switch ([l][2][c][5][N]); null: k_key_switch<true>
 int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
-                       bool accumulate, uint32_t *acc, uint64_t *out_d);
+                       bool accumulate, uint32_t *acc, uint64_t *out_d, uint32_t *part = nullptr);
+// the step loop of slot_sum on one chunk of c ciphertexts: x <- x + apply_galois(x, gs[k]) for k < steps with the transformed key
+// key_hat[k], x and y ([2 c][N] each) taking turns; *out is the one of the two that holds the result
+int zk_bfv_slot_sum_core(zkfhe_ctx *ctx, uint64_t *x, uint64_t *y, size_t c, int log_n, uint64_t q, size_t steps, const uint64_t *gs, int l, int w,
+                         const uint32_t *const *key_hat, uint32_t *acc, uint32_t *part, uint64_t **out);
+// ---- defined in bfv_dot.hip
+// The chunk loops of bfv_dot (plain: bfv_dot_plain) behind the host checks.  resident = false: a, b and out are host arrays, moved
+// with zkfhe_upload / zkfhe_download, and (rlk0, rlk1) is uploaded and transformed first.  resident = true: they are planes on the
+// device ([n_groups n_terms][N], [b_groups n_terms][N], [n_groups][N]), moved by device copies, and key_hat is the transformed key of
+// a key set; wide_max > 0 lets a pass of at most so many groups take the digit-parallel key switch.  b_host: b (the plaintexts of
+// bfv_dot_plain) is a host array beside resident ciphertexts.
+struct DotIo {
+  bool resident = false, b_host = false;
+  const uint64_t *a0 = nullptr, *a1 = nullptr, *b0 = nullptr, *b1 = nullptr;
+  uint64_t *out0 = nullptr, *out1 = nullptr;
+  const uint64_t *rlk0 = nullptr, *rlk1 = nullptr;
+  const uint32_t *key_hat = nullptr;
+  size_t wide_max = 0;
+};
+int zk_bfv_dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, bool plain, size_t n_groups, size_t n_terms, size_t b_groups, const DotIo &io,
+                    int l, int base_bits);
+// "fn: n_terms ... is above the limit ..." unless n_terms is at most zkfhe_bfv_dot_max_terms
+int check_dot_terms(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, bool plain, size_t n_terms, const char *fn);
+// ---- defined in bfv_evk.hip
+// The digit-parallel key switch: what zk_bfv_key_switch computes, bit for bit, as k_key_switch_digit over c 5 l workgroups into part
+// ([l][2][c][5][N]) and k_key_switch_fold over 2 c 5 workgroups into acc, both in profiling slot ZKFHE_PROF_BFV_KEY_SWITCH_WIDE
+int zk_bfv_key_switch_wide(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64_t q, int l, int w, const uint32_t *key_hat, size_t c,
+                           int log_n, uint32_t *part, uint32_t *acc);
+// the largest count of ciphertexts whose key switch goes the digit-parallel way on this device (0: never), and the words of `part`
+size_t zk_bfv_wide_max(const zkfhe_ctx *ctx, uint64_t n, int l);
+inline size_t wide_part_words(uint64_t n, int l, size_t c) { return (size_t)l * 2 * c * NP_MAX * n; }
+// a key set as its callers see it: the transformed relinearization key (null: none) and the transformed key of g (null: none)
+struct EvkView {
+  zkfhe_bfv_params params;
+  int device, base_bits, l;
+  const uint32_t *rlk_hat;
+};
+void zk_bfv_evk_view(const zkfhe_bfv_evk *evk, EvkView *view);
+const uint32_t *zk_bfv_evk_galois(const zkfhe_bfv_evk *evk, uint64_t g);
 // ---- defined in bfv_linear.hip
 // the parameters and the device of a plan
 void zk_bfv_plan_view(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int *device);
