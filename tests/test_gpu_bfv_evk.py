@@ -229,6 +229,20 @@ def test_slot_sum_at_the_largest_ring_uses_all_fifteen_keys(ctx):
         k.evk.close()
 
 
+def test_slot_sum_across_a_chunk(ctx, big):
+    """65 ciphertexts in place: the batch call with the key set and the host-array call both cross a chunk, each with all fifteen
+    keys, in one loop; w = 32 gives l = 2, the smallest keys"""
+    a, _ = big
+    w = 32
+    k = Keys(ctx, BIG, w, relin=False)
+    try:
+        want = ctx.bfv_slot_sum(BIG, *a, k.gk0, k.gk1, base_bits=w)
+        with ctx.bfv_cts(BIG, *a) as x:
+            assert x.slot_sum(k.evk, out=x) is x and same(x, want)   # the destination is the source
+    finally:
+        k.evk.close()
+
+
 # ---- 3. which kernels ran --------------------------------------------------------------------------------------------------------
 
 def all_launches(ctx, fn):

@@ -195,6 +195,19 @@ def test_plaintext_calls(ctx, params, count, op):
         check_call(ctx, params, [a], lambda c0, c1: getattr(ctx, "bfv_" + op)(params, c0, c1, m), lambda x, out: getattr(x, op)(m, out=out))
 
 
+@pytest.mark.parametrize("op", ["add_plain", "mul_plain"])
+def test_plaintext_calls_across_a_chunk(ctx, big, op):
+    """one plaintext per ciphertext: the second chunk's plaintexts are uploaded from their own offset, into a fresh destination and
+    in place"""
+    a, _ = big
+    m = plaintexts(np.random.default_rng(34), BIG, (CROSS,))
+    want = getattr(ctx, "bfv_" + op)(BIG, *a, m)
+    with ctx.bfv_cts(BIG, *a) as x:
+        with getattr(x, op)(m) as out:
+            assert same(out, want) and same(x, a)
+        assert getattr(x, op)(m, out=x) is x and same(x, want)
+
+
 def relin_key(ctx, params, w, seed):
     sk = ctx.bfv_fhe_keypair(params, bytes([seed]) * 32)[0]
     return sk, ctx.bfv_relin_keygen(params, sk, bytes([seed + 1]) * 32, base_bits=w)

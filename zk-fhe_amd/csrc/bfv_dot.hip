@@ -13,8 +13,9 @@
 // Sizes: |x1| <= n_terms 2 N floor(Q/2)^2 (PLAIN: n_terms N floor(Q/2) floor(T/2)), which zkfhe_bfv_dot_max_terms keeps at or below
 // half of the primes' product; the call refuses more terms.  Every value is a residue below p < 2^31, every product a mont_mul and
 // every sum an add_p; no step branches on or addresses by a coefficient's value.  No kernel uses scratch.
-// Each entry point is a wrapper (the host checks) around zk_bfv_dot_core, the chunk loops on operands that are host arrays or device
-// planes (DotIo, rns_ntt.hip.hpp); bfv_resident.hip drives the same core from resident batches and a resident key.
+// Each entry point is a wrapper (the host checks) around zk_bfv_dot_core, the chunk loops on operands that are each host arrays or
+// device planes and a key that is host rows or resident (DotIo of Planes and a KeySource, rns_ntt.hip.hpp); bfv_resident.hip calls
+// the same core on resident batches, with a key set or, for dot_plain, host plaintexts beside the device planes.
 #include <string>
 
 #include "rns_ntt.hip.hpp"
@@ -197,14 +198,6 @@ int launch_dot(zkfhe_ctx *ctx, const uint32_t *ah0, const uint32_t *ah1, const u
   return ZKFHE_OK;
 }
 
-// moves between a call's operands and the work arena: host arrays (the host-array calls) or device planes (the calls on batches)
-int fetch(zkfhe_ctx *ctx, const DotIo &io, void *dst_d, const uint64_t *src, size_t bytes, bool is_b = false) {
-  return io.resident && !(is_b && io.b_host) ? zk_copy_d2d(ctx, dst_d, src, bytes) : zkfhe_upload(ctx, dst_d, src, bytes);
-}
-int deliver(zkfhe_ctx *ctx, const DotIo &io, uint64_t *dst, const void *src_d, size_t bytes) {
-  return io.resident ? zk_copy_d2d(ctx, dst, src_d, bytes) : zkfhe_download(ctx, dst, src_d, bytes);
-}
-
 // both calls behind their checks: PLAIN is bfv_dot_plain (a = c, b0 = m, b1 unused)
 template <bool PLAIN>
 int dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, size_t n_terms, size_t b_groups, const DotIo &io, int l, int base_bits) {
@@ -212,44 +205,40 @@ int dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, si
   const uint64_t n = params->n, q = params->q;
   const int log_n = bit_log2(n);
   const size_t plane = (size_t)NP * n;
-  const size_t lw = io.key_hat ? 0 : (size_t)l * n;   // a resident key needs no staging
   const bool shared = b_groups == 1 && n_groups > 1;
   const DotPlan pl = dot_plan(ctx, n, n_groups, n_terms);
   const size_t c_max = pl.c, sub = pl.sub, gc_max = pl.gc;
   const size_t a_polys = 2 * sub * c_max, b_polys = NB * (shared ? 1 : sub) * c_max;
-  const bool wide = !PLAIN && gc_max <= io.wide_max;
+  KeySource key = io.key;
+  const size_t ks_words = PLAIN ? 0 : wide_words(ctx, key, n, l, gc_max);
   int *flag;
-  uint64_t *rlk_d, *in_d, *chat, *o_d;
-  uint32_t *rlk_hat, *hat, *part, *acc, *ks_part;
-  ZK_CK(Arena().add(flag, 1).add(rlk_d, 2 * lw).add(rlk_hat, 2 * lw * NP).add(in_d, (a_polys + b_polys) * n).add(hat, (a_polys + b_polys) * plane)
-            .add(part, pl.slices > 1 ? pl.slices * NC * sub * plane : 0).add(acc, NC * gc_max * plane).add(chat, PLAIN ? 0 : 3 * gc_max * n)
-            .add(o_d, 2 * gc_max * n).add(ks_part, wide ? wide_part_words(n, l, gc_max) : 0).carve(ctx));
-  const uint32_t *key_hat = io.key_hat;
-  if (!PLAIN && !key_hat) {
-    ZK_CK(zkfhe_upload(ctx, rlk_d, io.rlk0, lw * 8));
-    ZK_CK(zkfhe_upload(ctx, rlk_d + lw, io.rlk1, lw * 8));
-    ZK_CK(launch_rns_ntt<NP>(ctx, false, rlk_d, LOAD_RESIDUE, q, 2 * l, log_n, nullptr, 0, rlk_hat, flag));
-    key_hat = rlk_hat;
-  }
+  uint64_t *in_d, *chat, *o_d;
+  uint32_t *hat, *part, *acc, *ks_part;
+  Arena ar;
+  ar.add(flag, 1);
+  if (!PLAIN) key.add(ar, n, l);
+  ZK_CK(ar.add(in_d, (a_polys + b_polys) * n).add(hat, (a_polys + b_polys) * plane).add(part, pl.slices > 1 ? pl.slices * NC * sub * plane : 0)
+            .add(acc, NC * gc_max * plane).add(chat, PLAIN ? 0 : 3 * gc_max * n).add(o_d, 2 * gc_max * n).add(ks_part, ks_words).carve(ctx));
+  if (!PLAIN) ZK_CK(stage_keys<NP>(ctx, key, n, q, l, flag));
   for (size_t g0 = 0; g0 < n_groups; g0 += gc_max) {
     const size_t gc = std::min(gc_max, n_groups - g0);
     for (size_t lo = 0; lo < n_terms; lo += c_max) {
       const size_t c = std::min(c_max, n_terms - lo);
       if (shared) {   // one b for every group: fetched and transformed once per pass, behind the a region
         uint64_t *b_d = in_d + a_polys * n;
-        ZK_CK(fetch(ctx, io, b_d, io.b0 + lo * n, c * n * 8, true));
-        if (!PLAIN) ZK_CK(fetch(ctx, io, b_d + c * n, io.b1 + lo * n, c * n * 8, true));
+        ZK_CK(io.b.in(ctx, 0, lo, c, n, b_d));
+        if (!PLAIN) ZK_CK(io.b.in(ctx, 1, lo, c, n, b_d + c * n));
         ZK_CK(launch_rns_ntt<NP>(ctx, false, b_d, LOAD_CENTRED, q, NB * c, log_n, nullptr, 0, hat + a_polys * plane, flag));
       }
       for (size_t s0 = 0; s0 < gc; s0 += sub) {
         // sg groups of c terms: one block per operand (sg > 1 only where c = n_terms)
-        const size_t sg = std::min(sub, gc - s0), w = sg * c * n, from = ((g0 + s0) * n_terms + lo) * n;
+        const size_t sg = std::min(sub, gc - s0), w = sg * c * n, from = (g0 + s0) * n_terms + lo;   // sg c polynomials from `from` on
         const size_t b_at = shared ? a_polys : 2 * sg * c;   // the b region, in polynomials: [a0 | a1 | b0 | b1] when every group has its b
-        ZK_CK(fetch(ctx, io, in_d, io.a0 + from, w * 8));
-        ZK_CK(fetch(ctx, io, in_d + w, io.a1 + from, w * 8));
+        ZK_CK(io.a.in(ctx, 0, from, sg * c, n, in_d));
+        ZK_CK(io.a.in(ctx, 1, from, sg * c, n, in_d + w));
         if (!shared) {   // b_groups = n_groups
-          ZK_CK(fetch(ctx, io, in_d + 2 * w, io.b0 + from, w * 8, true));
-          if (!PLAIN) ZK_CK(fetch(ctx, io, in_d + 3 * w, io.b1 + from, w * 8, true));
+          ZK_CK(io.b.in(ctx, 0, from, sg * c, n, in_d + 2 * w));
+          if (!PLAIN) ZK_CK(io.b.in(ctx, 1, from, sg * c, n, in_d + 3 * w));
         }
         ZK_CK(launch_rns_ntt<NP>(ctx, false, in_d, LOAD_CENTRED, q, (shared ? 2 : 2 + NB) * sg * c, log_n, nullptr, 0, hat, flag));
         const uint32_t *bh = hat + b_at * plane;
@@ -262,16 +251,16 @@ int dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, si
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 2 * gc, log_n, q, EvEpi{}, o_d));
     } else {
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 3 * gc, log_n, q, EvEpi{.mode = EV_ROUND, .t = params->t}, chat));
-      if (wide)
-        ZK_CK(zk_bfv_key_switch_wide(ctx, chat + 2 * gc * n, 0, q, l, base_bits, key_hat, gc, log_n, ks_part, acc));
+      if (ks_words)
+        ZK_CK(zk_bfv_key_switch_wide(ctx, chat + 2 * gc * n, 0, q, l, base_bits, key.hat(0), gc, log_n, ks_part, acc));
       else
-        ZK_CK(zk_bfv_key_switch(ctx, chat + 2 * gc * n, 0, q, l, base_bits, key_hat, gc, log_n, acc));
+        ZK_CK(zk_bfv_key_switch(ctx, chat + 2 * gc * n, 0, q, l, base_bits, key.hat(0), gc, log_n, acc));
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 2 * gc, log_n, q, EvEpi{.mode = EV_ADD, .add = chat}, o_d));
     }
-    ZK_CK(deliver(ctx, io, io.out0 + g0 * n, o_d, gc * n * 8));
-    ZK_CK(deliver(ctx, io, io.out1 + g0 * n, o_d + gc * n, gc * n * 8));
+    ZK_CK(io.out.out(ctx, 0, g0, gc, n, o_d));
+    ZK_CK(io.out.out(ctx, 1, g0, gc, n, o_d + gc * n));
   }
-  return ZKFHE_OK;
+  return io.out.done(ctx);
 }
 
 // the host checks of both calls, then the core on the host arrays
@@ -293,8 +282,7 @@ int dot_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, si
     ZK_CK(check_below_q(ctx, b0, b_groups * n_terms * n, q, fn, "a ciphertext", b1));
     ZK_CK(check_below_q(ctx, rlk0, (size_t)l * n, q, fn, "a relinearization-key", rlk1));
   }
-  DotIo io;
-  io.a0 = a0, io.a1 = a1, io.b0 = b0, io.b1 = b1, io.out0 = out0, io.out1 = out1, io.rlk0 = rlk0, io.rlk1 = rlk1;
+  const DotIo io{host_planes(a0, a1), host_planes(b0, b1), host_planes(out0, out1), host_keys(rlk0, rlk1)};
   return dot_core<PLAIN>(ctx, params, n_groups, n_terms, b_groups, io, l, base_bits);
 }
 

@@ -13,8 +13,9 @@
 //   5. k_eval_epilogue (EV_ADD): out_j = c^_j + sum mod Q.
 // The relinearization key is transformed once per call.  No step branches on or addresses by a coefficient's value.
 // k_eval_epilogue and k_key_switch also serve the Galois key switch of bfv_galois.hip (EV_GALOIS, k_key_switch<true>).
-// Each entry point is a wrapper (host checks, uploads, downloads) around a device core on device pointers (zk_bfv_add_core,
-// zk_bfv_mul_plain_core, zk_bfv_mul_core: the body of its chunk loop), which bfv_resident.hip drives from resident memory.
+// add / subtract, add_plain / mul_plain and mul each have one runner (zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run: the chunk
+// loop, on operands that are host arrays or device planes and a key that is host rows or resident, rns_ntt.hip.hpp).  An entry point
+// here is its host checks and one call of a runner on host arrays; the batch calls of bfv_resident.hip call the same runners.
 #include <cstring>
 
 #include "rns_ntt.hip.hpp"
@@ -191,15 +192,6 @@ int launch_tensor(zkfhe_ctx *ctx, const uint32_t *hat, size_t c, int log_n, uint
 
 namespace zkrns {
 
-int zk_bfv_add_core(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtract, const uint64_t *m, int m_shared, uint64_t delta,
-                    size_t total, int log_n, uint64_t q, uint64_t *out) {
-  zk_prof_begin(ctx);
-  k_bfv_add<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(a, b, subtract, m, m_shared, delta, total, log_n, q, out);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ZKFHE_PROF_BFV_ELEMENTWISE, (double)total * 24);
-  return ZKFHE_OK;
-}
-
 int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out) {
   const size_t total = n_polys << log_n;
   zk_prof_begin(ctx);
@@ -228,35 +220,143 @@ int zk_bfv_key_switch(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64
   return ZKFHE_OK;
 }
 
-int zk_bfv_hat(zkfhe_ctx *ctx, const uint64_t *src, int mode, uint64_t q, size_t rows, int log_n, uint32_t *hat, int *flag) {
-  return launch_rns_ntt<NP>(ctx, false, src, mode, q, rows, log_n, nullptr, 0, hat, flag);
+namespace {
+
+// k_bfv_add over total words: out = a +/- b (b set) or a + delta m (m set; m_shared: one plaintext of N words for every polynomial)
+int add_core(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtract, const uint64_t *m, int m_shared, uint64_t delta, size_t total,
+             int log_n, uint64_t q, uint64_t *out) {
+  zk_prof_begin(ctx);
+  k_bfv_add<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(a, b, subtract, m, m_shared, delta, total, log_n, q, out);
+  ZK_LAUNCH_CHECK(ctx);
+  zk_prof_end(ctx, ZKFHE_PROF_BFV_ELEMENTWISE, (double)total * 24);
+  return ZKFHE_OK;
 }
 
-int zk_bfv_mul_plain_core(zkfhe_ctx *ctx, const uint64_t *x, size_t c, int log_n, uint64_t q, const uint32_t *m_hat, size_t hat_stride,
-                          uint32_t *res, int *flag, uint64_t *out) {
+// rows centred polynomials of src ([rows][N]) transformed with the five primes into hat ([rows][5][N])
+int centred_hat(zkfhe_ctx *ctx, const uint64_t *src, uint64_t q, size_t rows, int log_n, uint32_t *hat, int *flag) {
+  return launch_rns_ntt<NP>(ctx, false, src, LOAD_CENTRED, q, rows, log_n, nullptr, 0, hat, flag);
+}
+
+// one component of mul_plain: out = x m mod (x^N + 1, Q) for the c polynomials of x against m_hat (hat_stride 0: one plaintext)
+int mul_plain_core(zkfhe_ctx *ctx, const uint64_t *x, size_t c, int log_n, uint64_t q, const uint32_t *m_hat, size_t hat_stride, uint32_t *res,
+                   int *flag, uint64_t *out) {
   ZK_CK(launch_rns_ntt<NP>(ctx, true, x, LOAD_CENTRED, q, c, log_n, m_hat, hat_stride, res, flag));
   return zk_bfv_eval_epilogue(ctx, res, c, log_n, q, EvEpi{}, out);
 }
 
-void add_mul_work(Arena &a, uint64_t n, int l, size_t n_pairs, MulWork &w) {
-  w.chunk = std::min<size_t>(n_pairs, chunk_polys(n));
-  const size_t cw = w.chunk * n, lw = (size_t)l * n;
-  a.add(w.flag, 1).add(w.rlk_d, 2 * lw).add(w.rlk_hat, 2 * lw * NP).add(w.in_d, 4 * cw).add(w.hat, 4 * cw * NP).add(w.res, 3 * cw * NP)
-      .add(w.chat, 3 * cw).add(w.o_d, 2 * cw);
-}
+// the work buffers of mul behind its key
+struct MulWork {
+  int *flag;
+  uint64_t *in_d, *chat, *o_d;
+  uint32_t *hat, *res;
+  const uint32_t *key;        // the transformed key ([2 l][5][N])
+  uint32_t *part = nullptr;   // the partials of the digit-parallel key switch ([l][2][c][5][N]), null: k_key_switch
+};
 
-int zk_bfv_mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l, int base_bits, const MulWork &w) {
+// steps 1 to 5 of the top of the file for c pairs: w.in_d = [a0 | a1 | b0 | b1] ([4 c][N]); w.o_d = [out0 | out1]
+int mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l, int base_bits, const MulWork &w) {
   const uint64_t n = prm->n, q = prm->q;
   const int log_n = bit_log2(n);
-  ZK_CK(zk_bfv_hat(ctx, w.in_d, LOAD_CENTRED, q, 4 * c, log_n, w.hat, w.flag));
+  ZK_CK(centred_hat(ctx, w.in_d, q, 4 * c, log_n, w.hat, w.flag));
   ZK_CK(launch_tensor(ctx, w.hat, c, log_n, w.res));
   ZK_CK(zk_bfv_eval_epilogue(ctx, w.res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = prm->t}, w.chat));
-  const uint32_t *key = w.key ? w.key : w.rlk_hat;
   if (w.part)
-    ZK_CK(zk_bfv_key_switch_wide(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, key, c, log_n, w.part, w.res));
+    ZK_CK(zk_bfv_key_switch_wide(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, w.key, c, log_n, w.part, w.res));
   else
-    ZK_CK(zk_bfv_key_switch(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, key, c, log_n, w.res));
+    ZK_CK(zk_bfv_key_switch(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, w.key, c, log_n, w.res));
   return zk_bfv_eval_epilogue(ctx, w.res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = w.chat}, w.o_d);
+}
+
+}  // namespace
+
+int zk_bfv_add_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, const Planes &b, int subtract, const Planes &out) {
+  const uint64_t n = prm->n, q = prm->q;
+  const int log_n = bit_log2(n);
+  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n;
+  uint64_t *a_d = nullptr, *b_d = nullptr, *o_d;
+  Arena ar;
+  a.stage(ar, a_d, cw), b.stage(ar, b_d, cw);
+  ZK_CK(ar.add(o_d, cw).carve(ctx));
+  for (int comp = 0; comp < 2; ++comp)
+    for (size_t lo = 0; lo < count; lo += chunk) {
+      const size_t c = std::min(chunk, count - lo);
+      const uint64_t *x, *y;
+      ZK_CK(a.at(ctx, comp, lo, c, n, a_d, &x));
+      ZK_CK(b.at(ctx, comp, lo, c, n, b_d, &y));
+      ZK_CK(add_core(ctx, x, y, subtract, nullptr, 0, 0, c * n, log_n, q, o_d));
+      ZK_CK(out.out(ctx, comp, lo, c, n, o_d));
+    }
+  return out.done(ctx);
+}
+
+int zk_bfv_plain_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, bool mul, size_t count, const Planes &a, size_t m_count, const uint64_t *m,
+                     const Planes &out) {
+  const uint64_t n = prm->n, q = prm->q;
+  const int log_n = bit_log2(n);
+  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n;
+  int *flag = nullptr;
+  uint64_t *c_d = nullptr, *m_d, *o_d;
+  uint32_t *hat = nullptr, *res = nullptr;
+  Arena ar;
+  if (mul) ar.add(flag, 1);
+  a.stage(ar, c_d, cw);
+  ar.add(m_d, cw).add(o_d, cw);
+  if (mul) ar.add(hat, cw * NP).add(res, cw * NP);
+  ZK_CK(ar.carve(ctx));
+  const bool shared = m_count == 1;
+  if (shared) {
+    ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
+    if (mul) ZK_CK(centred_hat(ctx, m_d, q, 1, log_n, hat, flag));
+  }
+  for (size_t lo = 0; lo < count; lo += chunk) {
+    const size_t c = std::min(chunk, count - lo);
+    if (!shared) {
+      ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, c * n * 8));
+      if (mul) ZK_CK(centred_hat(ctx, m_d, q, c, log_n, hat, flag));
+    }
+    for (int comp = 0; comp < (mul ? 2 : 1); ++comp) {
+      const uint64_t *x;
+      ZK_CK(a.at(ctx, comp, lo, c, n, c_d, &x));
+      if (mul)
+        ZK_CK(mul_plain_core(ctx, x, c, log_n, q, hat, shared ? 0 : (size_t)NP * n, res, flag, o_d));
+      else
+        ZK_CK(add_core(ctx, x, nullptr, 0, m_d, shared, q / prm->t, c * n, log_n, q, o_d));
+      ZK_CK(out.out(ctx, comp, lo, c, n, o_d));
+    }
+  }
+  if (!mul && out.p[1] != a.p[1]) {   // add_plain leaves c1 as it is: copied where the data lives, not at all in place
+    if (out.dev)
+      ZK_CK(a.in(ctx, 1, 0, count, n, out.p[1]));
+    else if (a.dev)
+      ZK_CK(out.out(ctx, 1, 0, count, n, a.p[1]));
+    else
+      memcpy(out.p[1], a.p[1], count * n * 8);
+  }
+  return out.done(ctx);
+}
+
+int zk_bfv_mul_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, const Planes &b, KeySource key, int l, int base_bits,
+                   const Planes &out) {
+  const uint64_t n = prm->n;
+  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n, pw = wide_words(ctx, key, n, l, chunk);
+  MulWork w;
+  Arena ar;
+  ar.add(w.flag, 1);
+  key.add(ar, n, l);
+  ar.add(w.in_d, 4 * cw).add(w.hat, 4 * cw * NP).add(w.res, 3 * cw * NP).add(w.chat, 3 * cw).add(w.o_d, 2 * cw);
+  if (pw) ar.add(w.part, pw);
+  ZK_CK(ar.carve(ctx));
+  ZK_CK(stage_keys<NP>(ctx, key, n, prm->q, l, w.flag));
+  w.key = key.hat(0);
+  const Planes *src[2] = {&a, &b};
+  for (size_t lo = 0; lo < count; lo += chunk) {
+    const size_t c = std::min(chunk, count - lo);
+    for (int i = 0; i < 4; ++i) ZK_CK(src[i / 2]->in(ctx, i % 2, lo, c, n, w.in_d + i * c * n));   // the 4 c transforms want them contiguous
+    ZK_CK(mul_core(ctx, prm, c, l, base_bits, w));
+    ZK_CK(out.out(ctx, 0, lo, c, n, w.o_d));
+    ZK_CK(out.out(ctx, 1, lo, c, n, w.o_d + c * n));
+  }
+  return out.done(ctx);
 }
 
 }  // namespace zkrns
@@ -271,22 +371,7 @@ int zkfhe_bfv_add(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, 
   const uint64_t n = params->n, q = params->q;
   ZK_CK(check_below_q(ctx, a0, n_cts * n, q, "bfv_add", "a ciphertext", a1));
   ZK_CK(check_below_q(ctx, b0, n_cts * n, q, "bfv_add", "a ciphertext", b1));
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
-  uint64_t *a_d, *b_d, *o_d;
-  ZK_CK(Arena().add(a_d, cw).add(b_d, cw).add(o_d, cw).carve(ctx));
-  for (int comp = 0; comp < 2; ++comp) {
-    const uint64_t *a = comp ? a1 : a0, *b = comp ? b1 : b0;
-    uint64_t *out = comp ? out1 : out0;
-    for (size_t lo = 0; lo < n_cts; lo += chunk) {
-      const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-      ZK_CK(zkfhe_upload(ctx, a_d, a + lo * n, bytes));
-      ZK_CK(zkfhe_upload(ctx, b_d, b + lo * n, bytes));
-      ZK_CK(zk_bfv_add_core(ctx, a_d, b_d, subtract, nullptr, 0, 0, c * n, log_n, q, o_d));
-      ZK_CK(zkfhe_download(ctx, out + lo * n, o_d, bytes));
-    }
-  }
-  return ZKFHE_OK;
+  return zk_bfv_add_run(ctx, params, n_cts, host_planes(a0, a1), host_planes(b0, b1), subtract, host_planes(out0, out1));
 }
 
 int zkfhe_bfv_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0,
@@ -323,21 +408,7 @@ int zkfhe_bfv_add_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
   const uint64_t n = params->n, q = params->q;
   ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_add_plain", "a ciphertext", c1));
   ZK_CK(check_plain(ctx, m, m_count * n, q, params->t, "bfv_add_plain"));
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
-  uint64_t *c_d, *m_d, *o_d;
-  ZK_CK(Arena().add(c_d, cw).add(m_d, cw).add(o_d, cw).carve(ctx));
-  const bool shared = m_count == 1;
-  if (shared) ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
-  for (size_t lo = 0; lo < n_cts; lo += chunk) {
-    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-    ZK_CK(zkfhe_upload(ctx, c_d, c0 + lo * n, bytes));
-    if (!shared) ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, bytes));
-    ZK_CK(zk_bfv_add_core(ctx, c_d, nullptr, 0, m_d, shared, q / params->t, c * n, log_n, q, o_d));
-    ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
-  }
-  if (out1 != c1) memcpy(out1, c1, n_cts * n * 8);
-  return ZKFHE_OK;
+  return zk_bfv_plain_run(ctx, params, false, n_cts, host_planes(c0, c1), m_count, m, host_planes(out0, out1));
 }
 
 int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, size_t m_count,
@@ -349,30 +420,7 @@ int zkfhe_bfv_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
   const uint64_t n = params->n, q = params->q;
   ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_mul_plain", "a ciphertext", c1));
   ZK_CK(check_plain(ctx, m, m_count * n, q, params->t, "bfv_mul_plain"));
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
-  int *flag;
-  uint64_t *c_d, *m_d, *o_d;
-  uint32_t *hat, *res;
-  ZK_CK(Arena().add(flag, 1).add(c_d, cw).add(m_d, cw).add(o_d, cw).add(hat, cw * NP).add(res, cw * NP).carve(ctx));
-  const bool shared = m_count == 1;
-  if (shared) {
-    ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
-    ZK_CK(zk_bfv_hat(ctx, m_d, LOAD_CENTRED, q, 1, log_n, hat, flag));
-  }
-  for (size_t lo = 0; lo < n_cts; lo += chunk) {
-    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-    if (!shared) {
-      ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, bytes));
-      ZK_CK(zk_bfv_hat(ctx, m_d, LOAD_CENTRED, q, c, log_n, hat, flag));
-    }
-    for (int comp = 0; comp < 2; ++comp) {
-      ZK_CK(zkfhe_upload(ctx, c_d, (comp ? c1 : c0) + lo * n, bytes));
-      ZK_CK(zk_bfv_mul_plain_core(ctx, c_d, c, log_n, q, hat, shared ? 0 : (size_t)NP * n, res, flag, o_d));
-      ZK_CK(zkfhe_download(ctx, (comp ? out1 : out0) + lo * n, o_d, bytes));
-    }
-  }
-  return ZKFHE_OK;
+  return zk_bfv_plain_run(ctx, params, true, n_cts, host_planes(c0, c1), m_count, m, host_planes(out0, out1));
 }
 
 int zkfhe_bfv_relin_digits(const zkfhe_bfv_params *params, int base_bits, size_t *l) {
@@ -421,27 +469,10 @@ int zkfhe_bfv_mul(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_pairs
   int l = 0;
   ZK_CK(relin_rows(ctx, params, base_bits, "bfv_mul", &l));
   const uint64_t n = params->n, q = params->q;
-  const int log_n = bit_log2(n);
-  const size_t lw = (size_t)l * n;
   ZK_CK(check_below_q(ctx, a0, n_pairs * n, q, "bfv_mul", "a ciphertext", a1));
   ZK_CK(check_below_q(ctx, b0, n_pairs * n, q, "bfv_mul", "a ciphertext", b1));
-  ZK_CK(check_below_q(ctx, rlk0, lw, q, "bfv_mul", "a relinearization-key", rlk1));
-  MulWork w;
-  Arena a;
-  add_mul_work(a, n, l, n_pairs, w);
-  ZK_CK(a.carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, w.rlk_d, rlk0, lw * 8));
-  ZK_CK(zkfhe_upload(ctx, w.rlk_d + lw, rlk1, lw * 8));
-  ZK_CK(zk_bfv_hat(ctx, w.rlk_d, LOAD_RESIDUE, q, 2 * l, log_n, w.rlk_hat, w.flag));
-  const uint64_t *src[4] = {a0, a1, b0, b1};
-  for (size_t lo = 0; lo < n_pairs; lo += w.chunk) {
-    const size_t c = std::min(w.chunk, n_pairs - lo), bytes = c * n * 8;
-    for (int i = 0; i < 4; ++i) ZK_CK(zkfhe_upload(ctx, w.in_d + i * c * n, src[i] + lo * n, bytes));
-    ZK_CK(zk_bfv_mul_core(ctx, params, c, l, base_bits, w));
-    ZK_CK(zkfhe_download(ctx, out0 + lo * n, w.o_d, bytes));
-    ZK_CK(zkfhe_download(ctx, out1 + lo * n, w.o_d + c * n, bytes));
-  }
-  return ZKFHE_OK;
+  ZK_CK(check_below_q(ctx, rlk0, (size_t)l * n, q, "bfv_mul", "a relinearization-key", rlk1));
+  return zk_bfv_mul_run(ctx, params, n_pairs, host_planes(a0, a1), host_planes(b0, b1), host_keys(rlk0, rlk1), l, base_bits, host_planes(out0, out1));
 }
 
 int zkfhe_bfv_noise(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *sk, size_t n_cts, const uint64_t *c0, const uint64_t *c1,

@@ -4,9 +4,10 @@
 //
 // A key set is one device allocation of its own: for the relinearization key (if any) and then for each Galois key in the order of
 // `g`, the [2 l][5][N] uint32_t transform that k_key_switch reads (the l rows of key0, then the l rows of key1).  Creation stages the
-// keys through the work arena and runs k_rns_ntt (LOAD_RESIDUE, five primes) straight into the set, so the stored words are exactly
-// the key_hat that a host-array call computes per call.  The set is read-only afterwards and complete when creation returns: any
-// context of the device may read it from its own stream.
+// keys through the work arena (upload_key_pair, as stage_keys of rns_ntt.hip.hpp does for a host-array call) and runs k_rns_ntt
+// (LOAD_RESIDUE, five primes) straight into the set, so the stored words are exactly the key_hat that a host-array call computes per
+// call.  The set is read-only afterwards and complete when creation returns: any context of the device may read it from its own
+// stream.  A call that takes the set hands its keys to the operation's runner as a resident KeySource, which stages nothing.
 //
 // The digit-parallel key switch.  k_key_switch (bfv_eval.hip) runs one workgroup per (ciphertext, prime) that walks the l digits
 // one after the other: 5 workgroups for one ciphertext.  Here the l digit transforms run side by side:
@@ -156,8 +157,7 @@ int evk_fill(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, int base_bits, cons
       const size_t at = lo + i;
       const bool relin = e->has_relin && at == 0;
       const size_t gi = at - (e->has_relin ? 1 : 0);
-      ZK_CK(zkfhe_upload(ctx, key_d + 2 * i * lw, relin ? rlk0 : gk0 + gi * lw, lw * 8));
-      ZK_CK(zkfhe_upload(ctx, key_d + (2 * i + 1) * lw, relin ? rlk1 : gk1 + gi * lw, lw * 8));
+      ZK_CK(upload_key_pair(ctx, key_d + 2 * i * lw, relin ? rlk0 : gk0 + gi * lw, relin ? rlk1 : gk1 + gi * lw, lw));
     }
     ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * c * l, log_n, nullptr, 0, e->hat + lo * e->key_words(), flag));
   }

@@ -9,8 +9,9 @@
 //                              component (sum < l N 2^w Q < 2^116)
 //   k_eval_epilogue EV_GALOIS  Garner over the five primes, x mod Q, + sigma_g(c0) on component 0, + x_in when set (slot_sum's
 //                              x <- x + apply_galois(x), fused: the same sums mod Q as zkfhe_bfv_add)
-// The Galois key is transformed once per call; slot_sum transforms all log2(N) keys once and runs every step on device buffers
-// (zk_bfv_slot_sum_core, which bfv_resident.hip drives from a resident batch and a resident key set).
+// apply_galois and slot_sum are one chunk loop, zk_bfv_galois_run: `steps` key switches per chunk on device buffers, each added to
+// its input or not.  Host keys are transformed once per call, all of them in one launch (stage_keys); the batch calls of
+// bfv_resident.hip call the same runner on device planes, with host keys or the keys of a resident key set.
 // Galois keys (and their threshold shares) are products a_j s with a ternary s: the three-prime k_rns_ntt against the transform of
 // s, then k_rns_epilogue (bfv_enc.hip) in EPI_GADGET mode: 2^(j w) sigma_g(s) - a_j s - e_j mod Q.
 //
@@ -188,17 +189,10 @@ int galois_key(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *s
   return ZKFHE_OK;
 }
 
-}  // namespace
-
-namespace zkrns {
-
-int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn) {
-  if (!(g & 1) || g >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": the Galois element g must be odd and below 2N");
-  return ZKFHE_OK;
-}
-
-int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
-                       bool accumulate, uint32_t *acc, uint64_t *out_d, uint32_t *part) {
+// one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
+// part: the partials of the digit-parallel key switch ([l][2][c][5][N]); null: k_key_switch<true>
+int galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
+                bool accumulate, uint32_t *acc, uint64_t *out_d, uint32_t *part) {
   const unsigned ginv = galois_inv(g, (uint64_t)1 << log_n);
   if (part)
     ZK_CK(zk_bfv_key_switch_wide(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, part, acc));
@@ -208,14 +202,43 @@ int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n,
   return zk_bfv_eval_epilogue(ctx, acc, 2 * c, log_n, q, epi, out_d);
 }
 
-int zk_bfv_slot_sum_core(zkfhe_ctx *ctx, uint64_t *x, uint64_t *y, size_t c, int log_n, uint64_t q, size_t steps, const uint64_t *gs, int l, int w,
-                         const uint32_t *const *key_hat, uint32_t *acc, uint32_t *part, uint64_t **out) {
-  for (size_t k = 0; k < steps; ++k) {   // x <- x + apply_galois(x, g_k), on the device
-    ZK_CK(zk_bfv_galois_core(ctx, x, c, log_n, q, gs[k], l, w, key_hat[k], true, acc, y, part));
-    std::swap(x, y);
-  }
-  *out = x;
+}  // namespace
+
+namespace zkrns {
+
+int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn) {
+  if (!(g & 1) || g >= 2 * n) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": the Galois element g must be odd and below 2N");
   return ZKFHE_OK;
+}
+
+int zk_bfv_galois_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, size_t steps, const uint64_t *gs, KeySource key,
+                      int l, int base_bits, bool accumulate, const Planes &out) {
+  const uint64_t n = prm->n, q = prm->q;
+  const int log_n = bit_log2(n);
+  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n, pw = wide_words(ctx, key, n, l, chunk);
+  int *flag = nullptr;
+  uint64_t *x_d, *y_d;
+  uint32_t *acc, *part = nullptr;
+  Arena ar;
+  if (!key.resident()) ar.add(flag, 1);   // of the key transform
+  key.add(ar, n, l);
+  ar.add(x_d, 2 * cw).add(y_d, 2 * cw).add(acc, 2 * cw * NP);
+  if (pw) ar.add(part, pw);
+  ZK_CK(ar.carve(ctx));
+  ZK_CK(stage_keys<NP>(ctx, key, n, q, l, flag));
+  for (size_t lo = 0; lo < count; lo += chunk) {
+    const size_t c = std::min(chunk, count - lo);
+    uint64_t *x = x_d, *y = y_d;
+    ZK_CK(a.in(ctx, 0, lo, c, n, x));   // a key switch reads [c0 | c1] of the chunk
+    ZK_CK(a.in(ctx, 1, lo, c, n, x + c * n));
+    for (size_t k = 0; k < steps; ++k) {   // y = apply_galois(x, g_k) (+ x), then the two change places
+      ZK_CK(galois_core(ctx, x, c, log_n, q, gs[k], l, base_bits, key.hat(k), accumulate, acc, y, part));
+      std::swap(x, y);
+    }
+    ZK_CK(out.out(ctx, 0, lo, c, n, x));
+    ZK_CK(out.out(ctx, 1, lo, c, n, x + c * n));
+  }
+  return out.done(ctx);
 }
 
 }  // namespace zkrns
@@ -296,27 +319,9 @@ int zkfhe_bfv_apply_galois(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_
   int l = 0;
   ZK_CK(relin_rows(ctx, params, base_bits, "bfv_apply_galois", &l));
   const uint64_t n = params->n, q = params->q;
-  const int log_n = bit_log2(n);
-  const size_t lw = (size_t)l * n;
   ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_apply_galois", "a ciphertext", c1));
-  ZK_CK(check_below_q(ctx, gk0, lw, q, "bfv_apply_galois", "a Galois-key", gk1));
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
-  int *flag;
-  uint64_t *key_d, *x_d, *o_d;
-  uint32_t *key_hat, *acc;
-  ZK_CK(Arena().add(flag, 1).add(key_d, 2 * lw).add(key_hat, 2 * lw * NP).add(x_d, 2 * cw).add(o_d, 2 * cw).add(acc, 2 * cw * NP).carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, key_d, gk0, lw * 8));
-  ZK_CK(zkfhe_upload(ctx, key_d + lw, gk1, lw * 8));
-  ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * l, log_n, nullptr, 0, key_hat, flag));
-  for (size_t lo = 0; lo < n_cts; lo += chunk) {
-    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-    ZK_CK(zkfhe_upload(ctx, x_d, c0 + lo * n, bytes));
-    ZK_CK(zkfhe_upload(ctx, x_d + c * n, c1 + lo * n, bytes));
-    ZK_CK(zk_bfv_galois_core(ctx, x_d, c, log_n, q, g, l, base_bits, key_hat, false, acc, o_d));
-    ZK_CK(zkfhe_download(ctx, out0 + lo * n, o_d, bytes));
-    ZK_CK(zkfhe_download(ctx, out1 + lo * n, o_d + c * n, bytes));
-  }
-  return ZKFHE_OK;
+  ZK_CK(check_below_q(ctx, gk0, (size_t)l * n, q, "bfv_apply_galois", "a Galois-key", gk1));
+  return zk_bfv_galois_run(ctx, params, n_cts, host_planes(c0, c1), 1, &g, host_keys(gk0, gk1), l, base_bits, false, host_planes(out0, out1));
 }
 
 int zkfhe_bfv_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, const uint64_t *c0, const uint64_t *c1, const uint64_t *gk0,
@@ -331,33 +336,10 @@ int zkfhe_bfv_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_
   ZK_CK(zkfhe_bfv_slot_sum_elements(params, nullptr, &steps));
   std::vector<uint64_t> gs(steps);
   ZK_CK(zkfhe_bfv_slot_sum_elements(params, gs.data(), &steps));
-  const int log_n = bit_log2(n);
-  const size_t kw = (size_t)l * n;   // words of one key half
   ZK_CK(check_below_q(ctx, c0, n_cts * n, q, "bfv_slot_sum", "a ciphertext", c1));
-  ZK_CK(check_below_q(ctx, gk0, steps * kw, q, "bfv_slot_sum", "a Galois-key", gk1));
-  const size_t chunk = std::min<size_t>(n_cts, chunk_polys(n)), cw = chunk * n;
-  int *flag;
-  uint64_t *key_d, *x_d, *y_d;
-  uint32_t *key_hat, *acc;
-  ZK_CK(Arena().add(flag, 1).add(key_d, 2 * steps * kw).add(key_hat, 2 * steps * kw * NP).add(x_d, 2 * cw).add(y_d, 2 * cw)
-            .add(acc, 2 * cw * NP).carve(ctx));
-  for (size_t k = 0; k < steps; ++k) {   // key k: its gk0 rows, then its gk1 rows
-    ZK_CK(zkfhe_upload(ctx, key_d + 2 * k * kw, gk0 + k * kw, kw * 8));
-    ZK_CK(zkfhe_upload(ctx, key_d + (2 * k + 1) * kw, gk1 + k * kw, kw * 8));
-  }
-  ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * steps * l, log_n, nullptr, 0, key_hat, flag));
-  std::vector<const uint32_t *> keys(steps);
-  for (size_t k = 0; k < steps; ++k) keys[k] = key_hat + 2 * k * kw * NP;
-  for (size_t lo = 0; lo < n_cts; lo += chunk) {
-    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-    uint64_t *x = nullptr;
-    ZK_CK(zkfhe_upload(ctx, x_d, c0 + lo * n, bytes));
-    ZK_CK(zkfhe_upload(ctx, x_d + c * n, c1 + lo * n, bytes));
-    ZK_CK(zk_bfv_slot_sum_core(ctx, x_d, y_d, c, log_n, q, steps, gs.data(), l, base_bits, keys.data(), acc, nullptr, &x));
-    ZK_CK(zkfhe_download(ctx, out0 + lo * n, x, bytes));
-    ZK_CK(zkfhe_download(ctx, out1 + lo * n, x + c * n, bytes));
-  }
-  return ZKFHE_OK;
+  ZK_CK(check_below_q(ctx, gk0, steps * l * n, q, "bfv_slot_sum", "a Galois-key", gk1));
+  return zk_bfv_galois_run(ctx, params, n_cts, host_planes(c0, c1), steps, gs.data(), host_keys(gk0, gk1, steps), l, base_bits, true,
+                           host_planes(out0, out1));
 }
 
 }  // extern "C"

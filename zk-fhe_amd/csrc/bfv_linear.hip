@@ -26,7 +26,7 @@
 // and transformed: struct zkfhe_bfv_plan) and a run half (the ciphertext check and the chunk loop, from that struct alone).  The
 // host-array calls prepare into the context's work arena and run; zkfhe_bfv_plan_create* prepare into allocations of the plan's own,
 // and zkfhe_bfv_plan_apply is the run half.  The run half takes its ciphertexts from host arrays or, for the resident batches of
-// bfv_resident.hip, from device arrays (zk_bfv_plan_run_dev): only the copies around a chunk differ.
+// bfv_resident.hip, from device planes (zk_bfv_plan_run_dev): only the copies around a chunk differ (Planes, rns_ntt.hip.hpp).
 #include <string>
 
 #include "rns_ntt.hip.hpp"
@@ -351,8 +351,7 @@ int prepare_device(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, const KeyLists &ks, 
   ZK_CK(zkfhe_upload(ctx, p.elem_d, p.elem.data(), p.elem.size() * 4));
   for (size_t k = 0; k < ks.count(); ++k) {   // key slot s: its gk0 rows, then its gk1 rows
     if (p.elem[2 * k + 1] == NO_KEY) continue;
-    ZK_CK(zkfhe_upload(ctx, key_d + (size_t)p.elem[2 * k + 1] * 2 * lw, ks.k0(k, lw), lw * 8));
-    ZK_CK(zkfhe_upload(ctx, key_d + ((size_t)p.elem[2 * k + 1] * 2 + 1) * lw, ks.k1(k, lw), lw * 8));
+    ZK_CK(upload_key_pair(ctx, key_d + (size_t)p.elem[2 * k + 1] * 2 * lw, ks.k0(k, lw), ks.k1(k, lw), lw));
   }
   if (p.slots) ZK_CK(launch_rns_ntt<NP>(ctx, false, key_d, LOAD_RESIDUE, q, 2 * p.slots * p.l, p.log_n, nullptr, 0, p.key_hat, flag));
   if (p.n_diag) {
@@ -376,15 +375,6 @@ int check_cts(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint6
   return check_below_q(ctx, c0, n_cts * p.params.n, p.params.q, fn, "a ciphertext", c1);
 }
 
-// A chunk into the work arena and its result out of it: from and to host arrays (the host-array calls, which wait for each copy) or
-// device arrays (dev: zk_bfv_plan_run_dev, stream-ordered copies)
-int chunk_in(zkfhe_ctx *ctx, bool dev, uint64_t *dst_d, const uint64_t *src, size_t bytes) {
-  return dev ? zk_copy_d2d(ctx, dst_d, src, bytes) : zkfhe_upload(ctx, dst_d, src, bytes);
-}
-int chunk_out(zkfhe_ctx *ctx, bool dev, uint64_t *dst, const uint64_t *src_d, size_t bytes) {
-  return dev ? zk_copy_d2d(ctx, dst, src_d, bytes) : zkfhe_download(ctx, dst, src_d, bytes);
-}
-
 // the work buffers of linear_run for n_cts ciphertexts
 struct LinearWork {
   size_t chunk;
@@ -399,10 +389,9 @@ void add_linear_work(Arena &a, const zkfhe_bfv_plan &p, size_t n_cts, LinearWork
   a.add(w.x_d, 2 * cw).add(w.hst, rows * cw * NP).add(w.res, per_ct * cw * NP).add(w.o_d, per_ct * cw);
 }
 
-// The run half of the flat calls: the chunk loop over the ciphertexts, from the prepared buffers of p.  p.n_diag == 0 is
-// apply_galois_many.
-int linear_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0, uint64_t *out1,
-               const LinearWork &w, bool dev = false) {
+// The run half of the flat calls: the chunk loop over the ciphertexts x (host arrays or device planes, as out), from the prepared
+// buffers of p.  p.n_diag == 0 is apply_galois_many.
+int linear_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const Planes &x, const Planes &out, const LinearWork &w) {
   const uint64_t n = p.params.n, q = p.params.q;
   const int l = p.l, log_n = p.log_n, base_bits = p.base_bits;
   const bool diag = p.n_diag != 0;
@@ -418,9 +407,9 @@ int linear_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint
   for (int j = 0; j < NP; ++j) gs.step[j] = (uint32_t)((((uint64_t)1 << base_bits) % PRIMES[j]) * (((uint64_t)1 << 32) % PRIMES[j]) % PRIMES[j]);
   const double words = (double)NP * n;   // one polynomial at every prime
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
-    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8, polys = per_ct * c;
-    ZK_CK(chunk_in(ctx, dev, x_d, c0 + lo * n, bytes));
-    ZK_CK(chunk_in(ctx, dev, x_d + c * n, c1 + lo * n, bytes));
+    const size_t c = std::min(chunk, n_cts - lo), polys = per_ct * c;
+    ZK_CK(x.in(ctx, 0, lo, c, n, x_d));
+    ZK_CK(x.in(ctx, 1, lo, c, n, x_d + c * n));
     zk_prof_begin(ctx);
     k_hoist<<<(unsigned)(c * rows * NP), NTT_THREADS, lds_h, ctx->stream>>>(x_d, c, l, base_bits, q, log_n, tw, rc, hst);
     ZK_LAUNCH_CHECK(ctx);
@@ -437,8 +426,8 @@ int linear_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint
     ZK_CK(zk_rns_intt(ctx, res, polys, log_n, rc_inv));
     ZK_CK(zk_bfv_eval_epilogue(ctx, res, polys, log_n, q, EvEpi{}, o_d));
     for (size_t k = 0; k < (diag ? 1 : n_elems); ++k) {   // o_d: [element][component][c][N]
-      ZK_CK(chunk_out(ctx, dev, out0 + (k * n_cts + lo) * n, o_d + 2 * k * c * n, bytes));
-      ZK_CK(chunk_out(ctx, dev, out1 + (k * n_cts + lo) * n, o_d + (2 * k + 1) * c * n, bytes));
+      ZK_CK(out.out(ctx, 0, k * n_cts + lo, c, n, o_d + 2 * k * c * n));
+      ZK_CK(out.out(ctx, 1, k * n_cts + lo, c, n, o_d + (2 * k + 1) * c * n));
     }
   }
   return ZKFHE_OK;
@@ -461,7 +450,7 @@ int linear_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, co
   add_linear_work(a, p, n_cts, w);
   ZK_CK(a.carve(ctx));
   ZK_CK(prepare_device(ctx, p, ks, diag, key_d, diag_d, flag));
-  return linear_run(ctx, p, n_cts, c0, c1, out0, out1, w);
+  return linear_run(ctx, p, n_cts, host_planes(c0, c1), host_planes(out0, out1), w);
 }
 
 template <int GT, int CTI>
@@ -487,8 +476,7 @@ void add_bsgs_work(Arena &a, const zkfhe_bfv_plan &p, size_t n_cts, BsgsWork &w)
 }
 
 // The run half of linear_transform_bsgs: the chunk loop over the ciphertexts and, inside it, the groups of giant steps.
-int bsgs_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0, uint64_t *out1,
-             const BsgsWork &w, bool dev = false) {
+int bsgs_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const Planes &x, const Planes &out, const BsgsWork &w) {
   const uint64_t n = p.params.n, q = p.params.q;
   const int l = p.l, log_n = p.log_n, base_bits = p.base_bits;
   const size_t n_baby = p.n_baby, n_giant = p.n_giant, rows = (size_t)l + 1, chunk = w.chunk, group = w.group;
@@ -508,9 +496,9 @@ int bsgs_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64
   for (size_t k = 0; k < n_baby; ++k) baby_slots += elem[2 * k + 1] != NO_KEY;
   const double words = (double)NP * n;   // one polynomial at every prime
   for (size_t lo = 0; lo < n_cts; lo += chunk) {
-    const size_t c = std::min(chunk, n_cts - lo), bytes = c * n * 8;
-    ZK_CK(chunk_in(ctx, dev, x_d, c0 + lo * n, bytes));
-    ZK_CK(chunk_in(ctx, dev, x_d + c * n, c1 + lo * n, bytes));
+    const size_t c = std::min(chunk, n_cts - lo);
+    ZK_CK(x.in(ctx, 0, lo, c, n, x_d));
+    ZK_CK(x.in(ctx, 1, lo, c, n, x_d + c * n));
     zk_prof_begin(ctx);
     k_hoist<<<(unsigned)(c * rows * NP), NTT_THREADS, lds_h, ctx->stream>>>(x_d, c, l, base_bits, q, log_n, tw, rc, hst);
     ZK_LAUNCH_CHECK(ctx);
@@ -551,8 +539,8 @@ int bsgs_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &p, size_t n_cts, const uint64
     }
     ZK_CK(zk_rns_intt(ctx, res, 2 * c, log_n, rc_outer));
     ZK_CK(zk_bfv_eval_epilogue(ctx, res, 2 * c, log_n, q, EvEpi{}, o_d));
-    ZK_CK(chunk_out(ctx, dev, out0 + lo * n, o_d, bytes));
-    ZK_CK(chunk_out(ctx, dev, out1 + lo * n, o_d + c * n, bytes));
+    ZK_CK(out.out(ctx, 0, lo, c, n, o_d));
+    ZK_CK(out.out(ctx, 1, lo, c, n, o_d + c * n));
   }
   return ZKFHE_OK;
 }
@@ -574,23 +562,22 @@ int bsgs_call(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_cts, cons
   add_bsgs_work(a, p, n_cts, w);
   ZK_CK(a.carve(ctx));
   ZK_CK(prepare_device(ctx, p, ks, diag, key_d, diag_d, flag));
-  return bsgs_run(ctx, p, n_cts, c0, c1, out0, out1, w);
+  return bsgs_run(ctx, p, n_cts, host_planes(c0, c1), host_planes(out0, out1), w);
 }
 
-// the run half of a plan: its work buffers carved, then the chunk loop on host arrays or (dev) device arrays
-int plan_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &plan, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0, uint64_t *out1,
-             bool dev) {
+// the run half of a plan: its work buffers carved, then the chunk loop on host arrays or device planes
+int plan_run(zkfhe_ctx *ctx, const zkfhe_bfv_plan &plan, size_t n_cts, const Planes &x, const Planes &out) {
   Arena a;
   if (plan.bsgs) {
     BsgsWork w;
     add_bsgs_work(a, plan, n_cts, w);
     ZK_CK(a.carve(ctx));
-    return bsgs_run(ctx, plan, n_cts, c0, c1, out0, out1, w, dev);
+    return bsgs_run(ctx, plan, n_cts, x, out, w);
   }
   LinearWork w;
   add_linear_work(a, plan, n_cts, w);
   ZK_CK(a.carve(ctx));
-  return linear_run(ctx, plan, n_cts, c0, c1, out0, out1, w, dev);
+  return linear_run(ctx, plan, n_cts, x, out, w);
 }
 
 // a plan's own buffers and the plan itself; hipFree waits for the device
@@ -661,7 +648,7 @@ void zk_bfv_plan_view(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int 
 
 int zk_bfv_plan_run_dev(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, size_t n_cts, const uint64_t *c0, const uint64_t *c1, uint64_t *out0,
                         uint64_t *out1) {
-  return plan_run(ctx, *plan, n_cts, c0, c1, out0, out1, true);
+  return plan_run(ctx, *plan, n_cts, device_planes(c0, c1), device_planes(out0, out1));
 }
 
 int zk_rns_intt(zkfhe_ctx *ctx, uint32_t *res, size_t n_polys, int log_n, const RnsConst<NP_MAX> &rc) {
@@ -735,7 +722,7 @@ int zkfhe_bfv_plan_apply(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, size_t n_ct
     return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": the plan lives on device " + std::to_string(plan->device) + " and the context on device " +
                                               std::to_string(ctx->device));
   ZK_CK(check_cts(ctx, *plan, n_cts, c0, c1, fn));
-  return plan_run(ctx, *plan, n_cts, c0, c1, out0, out1, false);
+  return plan_run(ctx, *plan, n_cts, host_planes(c0, c1), host_planes(out0, out1));
 }
 
 int zkfhe_bfv_plan_info(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int *base_bits, size_t counts[3], uint64_t *device_bytes) {

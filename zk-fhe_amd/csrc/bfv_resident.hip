@@ -7,15 +7,15 @@
 // host-array call computed mod Q from residues below Q; select, sum and box_tally copy or add residues mod Q.  So no call on a batch
 // runs a range pass over ciphertexts: only the host arrays of a call (plaintexts, keys, indices, groups) are checked, on the host.
 //
-// The evaluation calls drive the device cores of the host-array calls (rns_ntt.hip.hpp: zk_bfv_add_core, zk_bfv_mul_plain_core,
-// zk_bfv_mul_core, zk_bfv_galois_core, zk_bfv_plan_run_dev) chunk by chunk with the chunk rule of the host-array call, so the
-// kernels, their order and their profiling slots are those of that call.  A core reads its operands from the batch (or from a
-// contiguous copy in the work arena where it wants one), writes its result to the work arena, and the result is copied into dst
-// afterwards on the same stream: a chunk is read completely before it is written, and dst may be a source.  No call allocates or
-// frees device memory apart from alloc, upload and destroy.
-// The calls that take a resident key set (bfv_evk.hip: mul_evk, apply_galois_evk, slot_sum, dot; dot_plain takes none) drive the same
-// cores plus zk_bfv_slot_sum_core and zk_bfv_dot_core with the set's transformed keys: no key is checked, uploaded or transformed,
-// and a chunk of at most zk_bfv_wide_max ciphertexts takes the digit-parallel key switch, whose partials come from the work arena.
+// An evaluation call here is its argument checks and one call of the runner of the host-array call (rns_ntt.hip.hpp:
+// zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run, zk_bfv_galois_run, zk_bfv_dot_core, zk_bfv_plan_run_dev) on the batch's planes:
+// one chunk loop per operation, so the chunk rule, the kernels, their order and their profiling slots are those of that call.  A
+// runner reads a chunk from the batch (or from a contiguous copy in the work arena where a kernel wants one), writes its result to
+// the work arena, and copies it into dst afterwards on the same stream: a chunk is read completely before it is written, and dst may
+// be a source.  No call allocates or frees device memory apart from alloc, upload and destroy.
+// The calls that take a resident key set (bfv_evk.hip: mul_evk, apply_galois_evk, slot_sum, dot; dot_plain takes none) hand the
+// runner the set's transformed keys in place of host rows: no key is checked, uploaded or transformed, and a chunk of at most
+// zk_bfv_wide_max ciphertexts takes the digit-parallel key switch, whose partials come from the work arena.
 // This file's own kernels are three plain passes over memory, 16 bytes per lane, a capped grid with a grid stride:
 //   k_cts_check      any word >= Q raises one flag word
 //   k_cts_gather     dst[j] = src[idx[j]], both planes (select; idx == null: j itself, the box's [group][2][N] layout to two planes)
@@ -90,6 +90,7 @@ struct zkfhe_bfv_cts {
   size_t n = 0;        // ciphertexts
   uint64_t *w = nullptr;   // the allocation: c0[n][N], then c1[n][N]
   uint64_t *plane(int comp) const { return w + comp * n * params.n; }
+  Planes planes() const { return device_planes(plane(0), plane(1)); }   // what the runners of the evaluation calls take
 };
 
 namespace {
@@ -195,11 +196,6 @@ int upload_fill(zkfhe_ctx *ctx, zkfhe_bfv_cts *b, const uint64_t *c0, const uint
 
 int null_arg(zkfhe_ctx *ctx, const char *fn) { return refuse(ctx, fn, "a NULL argument or a zero count"); }
 
-// the result of a chunk, c polynomials at o_d, into a plane of dst
-int put(zkfhe_ctx *ctx, const zkfhe_bfv_cts *dst, int comp, size_t lo, const uint64_t *o_d, size_t c) {
-  return zk_copy_d2d(ctx, dst->plane(comp) + lo * dst->params.n, o_d, c * dst->params.n * 8);
-}
-
 // add_plain and mul_plain: the plaintext rules of the host-array calls
 int plain_args(zkfhe_ctx *ctx, const char *fn, const zkfhe_bfv_cts *a, size_t m_count, const uint64_t *m, const zkfhe_bfv_cts *dst) {
   if (!(ctx && a && m && dst)) return null_arg(ctx, fn);
@@ -227,35 +223,6 @@ int need_relin(zkfhe_ctx *ctx, const char *fn, const EvkView &view) {
 int need_galois(zkfhe_ctx *ctx, const char *fn, const zkfhe_bfv_evk *evk, uint64_t g, const uint32_t **key_hat) {
   *key_hat = zk_bfv_evk_galois(evk, g);
   if (!*key_hat) return refuse(ctx, fn, "the key set has no key for the Galois element " + std::to_string(g));
-  return ZKFHE_OK;
-}
-
-// the words of the digit-parallel key switch's partials for chunks of `chunk` ciphertexts: 0 where the chunk takes k_key_switch
-size_t wide_words(const zkfhe_ctx *ctx, uint64_t n, int l, size_t chunk) { return chunk <= zk_bfv_wide_max(ctx, n, l) ? wide_part_words(n, l, chunk) : 0; }
-
-// the chunk loop of apply_galois_evk and slot_sum: steps key switches per chunk, each added to its input when accumulate
-int galois_chain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const EvkView &view, size_t steps, const uint64_t *gs, const uint32_t *const *keys,
-                 bool accumulate, zkfhe_bfv_cts *dst) {
-  const uint64_t n = a->params.n, q = a->params.q;
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(a->n, chunk_polys(n)), cw = chunk * n;
-  uint64_t *x_d, *y_d;
-  uint32_t *acc, *part;
-  const size_t pw = wide_words(ctx, n, view.l, chunk);
-  ZK_CK(Arena().add(x_d, 2 * cw).add(y_d, 2 * cw).add(acc, 2 * cw * NP).add(part, pw).carve(ctx));
-  for (size_t lo = 0; lo < a->n; lo += chunk) {
-    const size_t c = std::min(chunk, a->n - lo), bytes = c * n * 8;
-    ZK_CK(zk_copy_d2d(ctx, x_d, a->plane(0) + lo * n, bytes));   // the core reads [c0 | c1] of the chunk
-    ZK_CK(zk_copy_d2d(ctx, x_d + c * n, a->plane(1) + lo * n, bytes));
-    uint64_t *r = y_d;
-    if (accumulate)
-      ZK_CK(zk_bfv_slot_sum_core(ctx, x_d, y_d, c, log_n, q, steps, gs, view.l, view.base_bits, keys, acc, pw ? part : nullptr, &r));
-    else
-      ZK_CK(zk_bfv_galois_core(ctx, x_d, c, log_n, q, gs[0], view.l, view.base_bits, keys[0], false, acc, y_d, pw ? part : nullptr));
-    ZK_CK(put(ctx, dst, 0, lo, r, c));
-    ZK_CK(put(ctx, dst, 1, lo, r + c * n, c));
-  }
-  ZK_HIP(ctx, zk_wait(ctx));
   return ZKFHE_OK;
 }
 
@@ -391,70 +358,19 @@ int zkfhe_bfv_cts_add(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_ct
   ZK_CK(alike(ctx, fn, a, dst));
   ZK_CK(same_count(ctx, fn, b->n, a->n, "b"));
   ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
-  const uint64_t n = a->params.n, q = a->params.q;
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(a->n, chunk_polys(n));
-  uint64_t *o_d;
-  ZK_CK(Arena().add(o_d, chunk * n).carve(ctx));
-  for (int comp = 0; comp < 2; ++comp)
-    for (size_t lo = 0; lo < a->n; lo += chunk) {
-      const size_t c = std::min(chunk, a->n - lo);
-      ZK_CK(zk_bfv_add_core(ctx, a->plane(comp) + lo * n, b->plane(comp) + lo * n, subtract, nullptr, 0, 0, c * n, log_n, q, o_d));
-      ZK_CK(put(ctx, dst, comp, lo, o_d, c));
-    }
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  return zk_bfv_add_run(ctx, &a->params, a->n, a->planes(), b->planes(), subtract, dst->planes());
 }
 
 int zkfhe_bfv_cts_add_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t m_count, const uint64_t *m, zkfhe_bfv_cts *dst) {
   CTS_CALL("add_plain");
   ZK_CK(plain_args(ctx, fn, a, m_count, m, dst));
-  const uint64_t n = a->params.n, q = a->params.q;
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(a->n, chunk_polys(n)), cw = chunk * n;
-  uint64_t *m_d, *o_d;
-  ZK_CK(Arena().add(m_d, cw).add(o_d, cw).carve(ctx));
-  const bool shared = m_count == 1;
-  if (shared) ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
-  for (size_t lo = 0; lo < a->n; lo += chunk) {
-    const size_t c = std::min(chunk, a->n - lo);
-    if (!shared) ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, c * n * 8));
-    ZK_CK(zk_bfv_add_core(ctx, a->plane(0) + lo * n, nullptr, 0, m_d, shared, q / a->params.t, c * n, log_n, q, o_d));
-    ZK_CK(put(ctx, dst, 0, lo, o_d, c));
-  }
-  if (dst != a) ZK_CK(zk_copy_d2d(ctx, dst->plane(1), a->plane(1), a->n * n * 8));
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  return zk_bfv_plain_run(ctx, &a->params, false, a->n, a->planes(), m_count, m, dst->planes());
 }
 
 int zkfhe_bfv_cts_mul_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t m_count, const uint64_t *m, zkfhe_bfv_cts *dst) {
   CTS_CALL("mul_plain");
   ZK_CK(plain_args(ctx, fn, a, m_count, m, dst));
-  const uint64_t n = a->params.n, q = a->params.q;
-  const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(a->n, chunk_polys(n)), cw = chunk * n;
-  int *flag;
-  uint64_t *m_d, *o_d;
-  uint32_t *hat, *res;
-  ZK_CK(Arena().add(flag, 1).add(m_d, cw).add(o_d, cw).add(hat, cw * NP).add(res, cw * NP).carve(ctx));
-  const bool shared = m_count == 1;
-  if (shared) {
-    ZK_CK(zkfhe_upload(ctx, m_d, m, n * 8));
-    ZK_CK(zk_bfv_hat(ctx, m_d, LOAD_CENTRED, q, 1, log_n, hat, flag));
-  }
-  for (size_t lo = 0; lo < a->n; lo += chunk) {
-    const size_t c = std::min(chunk, a->n - lo);
-    if (!shared) {
-      ZK_CK(zkfhe_upload(ctx, m_d, m + lo * n, c * n * 8));
-      ZK_CK(zk_bfv_hat(ctx, m_d, LOAD_CENTRED, q, c, log_n, hat, flag));
-    }
-    for (int comp = 0; comp < 2; ++comp) {
-      ZK_CK(zk_bfv_mul_plain_core(ctx, a->plane(comp) + lo * n, c, log_n, q, hat, shared ? 0 : (size_t)NP * n, res, flag, o_d));
-      ZK_CK(put(ctx, dst, comp, lo, o_d, c));
-    }
-  }
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  return zk_bfv_plain_run(ctx, &a->params, true, a->n, a->planes(), m_count, m, dst->planes());
 }
 
 int zkfhe_bfv_cts_mul(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, const uint64_t *rlk0, const uint64_t *rlk1, int base_bits,
@@ -468,26 +384,8 @@ int zkfhe_bfv_cts_mul(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_ct
   ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
   int l = 0;
   ZK_CK(relin_rows(ctx, &a->params, base_bits, fn, &l));
-  const uint64_t n = a->params.n, q = a->params.q;
-  const size_t lw = (size_t)l * n;
-  ZK_CK(check_below_q(ctx, rlk0, lw, q, fn, "a relinearization-key", rlk1));
-  MulWork w;
-  Arena arena;
-  add_mul_work(arena, n, l, a->n, w);
-  ZK_CK(arena.carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, w.rlk_d, rlk0, lw * 8));
-  ZK_CK(zkfhe_upload(ctx, w.rlk_d + lw, rlk1, lw * 8));
-  ZK_CK(zk_bfv_hat(ctx, w.rlk_d, LOAD_RESIDUE, q, 2 * l, bit_log2(n), w.rlk_hat, w.flag));
-  const uint64_t *src[4] = {a->plane(0), a->plane(1), b->plane(0), b->plane(1)};
-  for (size_t lo = 0; lo < a->n; lo += w.chunk) {
-    const size_t c = std::min(w.chunk, a->n - lo);
-    for (int i = 0; i < 4; ++i) ZK_CK(zk_copy_d2d(ctx, w.in_d + i * c * n, src[i] + lo * n, c * n * 8));   // the 4 c transforms want them contiguous
-    ZK_CK(zk_bfv_mul_core(ctx, &a->params, c, l, base_bits, w));
-    ZK_CK(put(ctx, dst, 0, lo, w.o_d, c));
-    ZK_CK(put(ctx, dst, 1, lo, w.o_d + c * n, c));
-  }
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  ZK_CK(check_below_q(ctx, rlk0, (size_t)l * a->params.n, a->params.q, fn, "a relinearization-key", rlk1));
+  return zk_bfv_mul_run(ctx, &a->params, a->n, a->planes(), b->planes(), host_keys(rlk0, rlk1), l, base_bits, dst->planes());
 }
 
 int zkfhe_bfv_cts_apply_galois(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t g, const uint64_t *gk0, const uint64_t *gk1, int base_bits,
@@ -501,27 +399,8 @@ int zkfhe_bfv_cts_apply_galois(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t 
   ZK_CK(check_g(ctx, n, g, fn));
   int l = 0;
   ZK_CK(relin_rows(ctx, &a->params, base_bits, fn, &l));
-  const int log_n = bit_log2(n);
-  const size_t lw = (size_t)l * n;
-  ZK_CK(check_below_q(ctx, gk0, lw, q, fn, "a Galois-key", gk1));
-  const size_t chunk = std::min<size_t>(a->n, chunk_polys(n)), cw = chunk * n;
-  int *flag;
-  uint64_t *key_d, *x_d, *o_d;
-  uint32_t *key_hat, *acc;
-  ZK_CK(Arena().add(flag, 1).add(key_d, 2 * lw).add(key_hat, 2 * lw * NP).add(x_d, 2 * cw).add(o_d, 2 * cw).add(acc, 2 * cw * NP).carve(ctx));
-  ZK_CK(zkfhe_upload(ctx, key_d, gk0, lw * 8));
-  ZK_CK(zkfhe_upload(ctx, key_d + lw, gk1, lw * 8));
-  ZK_CK(zk_bfv_hat(ctx, key_d, LOAD_RESIDUE, q, 2 * l, log_n, key_hat, flag));
-  for (size_t lo = 0; lo < a->n; lo += chunk) {
-    const size_t c = std::min(chunk, a->n - lo), bytes = c * n * 8;
-    ZK_CK(zk_copy_d2d(ctx, x_d, a->plane(0) + lo * n, bytes));   // the core reads [c0 | c1] of the chunk
-    ZK_CK(zk_copy_d2d(ctx, x_d + c * n, a->plane(1) + lo * n, bytes));
-    ZK_CK(zk_bfv_galois_core(ctx, x_d, c, log_n, q, g, l, base_bits, key_hat, false, acc, o_d));
-    ZK_CK(put(ctx, dst, 0, lo, o_d, c));
-    ZK_CK(put(ctx, dst, 1, lo, o_d + c * n, c));
-  }
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  ZK_CK(check_below_q(ctx, gk0, (size_t)l * n, q, fn, "a Galois-key", gk1));
+  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), 1, &g, host_keys(gk0, gk1), l, base_bits, false, dst->planes());
 }
 
 int zkfhe_bfv_cts_plan_apply(zkfhe_ctx *ctx, const zkfhe_bfv_plan *plan, const zkfhe_bfv_cts *a, zkfhe_bfv_cts *dst) {
@@ -610,24 +489,7 @@ int zkfhe_bfv_cts_mul_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bf
   ZK_CK(same_count(ctx, fn, b->n, a->n, "b"));
   ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
   ZK_CK(need_relin(ctx, fn, view));
-  const uint64_t n = a->params.n;
-  MulWork w;
-  Arena arena;
-  add_mul_work(arena, n, 0, a->n, w);   // no rows of a key to stage
-  arena.add(w.part, wide_words(ctx, n, view.l, w.chunk));
-  ZK_CK(arena.carve(ctx));
-  w.key = view.rlk_hat;
-  if (!wide_words(ctx, n, view.l, w.chunk)) w.part = nullptr;
-  const uint64_t *src[4] = {a->plane(0), a->plane(1), b->plane(0), b->plane(1)};
-  for (size_t lo = 0; lo < a->n; lo += w.chunk) {
-    const size_t c = std::min(w.chunk, a->n - lo);
-    for (int i = 0; i < 4; ++i) ZK_CK(zk_copy_d2d(ctx, w.in_d + i * c * n, src[i] + lo * n, c * n * 8));   // the 4 c transforms want them contiguous
-    ZK_CK(zk_bfv_mul_core(ctx, &a->params, c, view.l, view.base_bits, w));
-    ZK_CK(put(ctx, dst, 0, lo, w.o_d, c));
-    ZK_CK(put(ctx, dst, 1, lo, w.o_d + c * n, c));
-  }
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  return zk_bfv_mul_run(ctx, &a->params, a->n, a->planes(), b->planes(), resident_keys(&view.rlk_hat), view.l, view.base_bits, dst->planes());
 }
 
 int zkfhe_bfv_cts_apply_galois_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t g, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
@@ -641,7 +503,7 @@ int zkfhe_bfv_cts_apply_galois_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint6
   ZK_CK(check_g(ctx, a->params.n, g, fn));
   const uint32_t *key;
   ZK_CK(need_galois(ctx, fn, evk, g, &key));
-  return galois_chain(ctx, a, view, 1, &g, &key, false, dst);
+  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), 1, &g, resident_keys(&key), view.l, view.base_bits, false, dst->planes());
 }
 
 int zkfhe_bfv_cts_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
@@ -658,7 +520,8 @@ int zkfhe_bfv_cts_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_b
   ZK_CK(zkfhe_bfv_slot_sum_elements(&a->params, gs.data(), &steps));
   std::vector<const uint32_t *> keys(steps);
   for (size_t k = 0; k < steps; ++k) ZK_CK(need_galois(ctx, fn, evk, gs[k], &keys[k]));
-  return galois_chain(ctx, a, view, steps, gs.data(), keys.data(), true, dst);
+  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), steps, gs.data(), resident_keys(keys.data(), steps), view.l, view.base_bits, true,
+                           dst->planes());
 }
 
 int zkfhe_bfv_cts_dot(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_cts *b, size_t n_terms, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
@@ -672,12 +535,8 @@ int zkfhe_bfv_cts_dot(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_ct
   ZK_CK(dot_args(ctx, fn, a, b, n_terms, dst));
   ZK_CK(need_relin(ctx, fn, view));
   ZK_CK(check_dot_terms(ctx, &a->params, false, n_terms, fn));
-  DotIo io;
-  io.resident = true, io.a0 = a->plane(0), io.a1 = a->plane(1), io.b0 = b->plane(0), io.b1 = b->plane(1);
-  io.out0 = dst->plane(0), io.out1 = dst->plane(1), io.key_hat = view.rlk_hat, io.wide_max = zk_bfv_wide_max(ctx, a->params.n, view.l);
-  ZK_CK(zk_bfv_dot_core(ctx, &a->params, false, dst->n, n_terms, b->n / n_terms, io, view.l, view.base_bits));
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  const DotIo io{a->planes(), b->planes(), dst->planes(), resident_keys(&view.rlk_hat)};
+  return zk_bfv_dot_core(ctx, &a->params, false, dst->n, n_terms, b->n / n_terms, io, view.l, view.base_bits);
 }
 
 int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_terms, size_t m_groups, const uint64_t *m, zkfhe_bfv_cts *dst) {
@@ -690,11 +549,8 @@ int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_ter
   ZK_CK(check_dot_terms(ctx, &a->params, true, n_terms, fn));
   const uint64_t n = a->params.n;
   ZK_CK(check_plain(ctx, m, m_groups * n_terms * n, a->params.q, a->params.t, fn));
-  DotIo io;   // the plaintexts are the call's one host operand
-  io.resident = true, io.b_host = true, io.a0 = a->plane(0), io.a1 = a->plane(1), io.b0 = m, io.out0 = dst->plane(0), io.out1 = dst->plane(1);
-  ZK_CK(zk_bfv_dot_core(ctx, &a->params, true, dst->n, n_terms, m_groups, io, 0, 0));
-  ZK_HIP(ctx, zk_wait(ctx));
-  return ZKFHE_OK;
+  const DotIo io{a->planes(), host_planes(m, nullptr), dst->planes(), KeySource{}};   // the plaintexts are the call's one host operand
+  return zk_bfv_dot_core(ctx, &a->params, true, dst->n, n_terms, m_groups, io, 0, 0);
 }
 
 }  // extern "C"

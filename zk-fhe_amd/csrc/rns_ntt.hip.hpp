@@ -460,55 +460,105 @@ int launch_rns_ntt(zkfhe_ctx *ctx, bool mul, const uint64_t *src, int mode, uint
   return ZKFHE_OK;
 }
 
-// ---- The device cores of the evaluation calls: the body of a call's chunk loop, on device pointers.  The host-array calls drive
-// them between their uploads and downloads; the batch calls of bfv_resident.hip drive the same cores from resident memory, so a
-// batch call runs the kernels of the host-array call, in its order and its profiling slots.  No core checks a range: its caller has.
-// ---- defined in bfv_eval.hip
-// k_bfv_add over total words: out = a +/- b (b set) or a + delta m (m set; m_shared: one plaintext of N words for every polynomial)
-int zk_bfv_add_core(zkfhe_ctx *ctx, const uint64_t *a, const uint64_t *b, int subtract, const uint64_t *m, int m_shared, uint64_t delta,
-                    size_t total, int log_n, uint64_t q, uint64_t *out);
-// rows polynomials of src ([rows][N]) read in `mode` and transformed with the five primes into hat ([rows][5][N]): the keys
-// (LOAD_RESIDUE) and the plaintexts (LOAD_CENTRED) of a call
-int zk_bfv_hat(zkfhe_ctx *ctx, const uint64_t *src, int mode, uint64_t q, size_t rows, int log_n, uint32_t *hat, int *flag);
-// one component of mul_plain: out = x m mod (x^N + 1, Q) for the c polynomials of x against m_hat (hat_stride 0: one plaintext)
-int zk_bfv_mul_plain_core(zkfhe_ctx *ctx, const uint64_t *x, size_t c, int log_n, uint64_t q, const uint32_t *m_hat, size_t hat_stride,
-                          uint32_t *res, int *flag, uint64_t *out);
-// the work buffers of bfv_mul for n_pairs pairs and a key of l rows, in the order the call has always carved them
-struct MulWork {
-  size_t chunk;
-  int *flag;
-  uint64_t *rlk_d, *in_d, *chat, *o_d;
-  uint32_t *rlk_hat, *hat, *res;
-  const uint32_t *key = nullptr;   // the transformed key where it is resident (a key set), else rlk_hat
-  uint32_t *part = nullptr;        // the partials of the digit-parallel key switch ([l][2][c][5][N]), null: k_key_switch
+// ---- The runners of the evaluation calls: one chunk loop per operation, on operands that are host arrays or device planes (a
+// resident batch) and a key that is host rows or a resident key set.  Every extern "C" entry point, host-array (bfv_eval.hip,
+// bfv_galois.hip, bfv_dot.hip) or batch (bfv_resident.hip), is its argument checks and one call of a runner, so a batch call runs
+// the kernels of the host-array call, in its order and its profiling slots.  No runner checks a range: its caller has.
+
+// Where the ciphertexts of a call live: two planes c0, c1 ([count][N] each) of host memory or of device memory.  A chunk comes in
+// with `in` or `at` and leaves with `out`; a runner reads a chunk completely into the work arena before it writes the chunk's
+// result, so a device destination may be a source.  A source is only read.
+struct Planes {
+  uint64_t *p[2] = {nullptr, nullptr};
+  bool dev = false;
+  // c polynomials of plane comp from polynomial lo on into the device buffer dst_d: an upload or a copy on the device
+  int in(zkfhe_ctx *ctx, int comp, size_t lo, size_t c, uint64_t n, uint64_t *dst_d) const {
+    return dev ? zk_copy_d2d(ctx, dst_d, p[comp] + lo * n, c * n * 8) : zkfhe_upload(ctx, dst_d, p[comp] + lo * n, c * n * 8);
+  }
+  // the same polynomials where a kernel may read them: in the plane itself on the device, else uploaded to stage_d
+  int at(zkfhe_ctx *ctx, int comp, size_t lo, size_t c, uint64_t n, uint64_t *stage_d, const uint64_t **x) const {
+    *x = dev ? p[comp] + lo * n : stage_d;
+    return dev ? ZKFHE_OK : zkfhe_upload(ctx, stage_d, p[comp] + lo * n, c * n * 8);
+  }
+  // the stage_d that `at` wants, in the caller's arena only where there is something to upload
+  void stage(Arena &a, uint64_t *&stage_d, size_t words) const {
+    if (!dev) a.add(stage_d, words);
+  }
+  // c polynomials at src_d into plane comp from polynomial lo on: a download (which waits) or a copy on the device
+  int out(zkfhe_ctx *ctx, int comp, size_t lo, size_t c, uint64_t n, const uint64_t *src_d) const {
+    return dev ? zk_copy_d2d(ctx, p[comp] + lo * n, src_d, c * n * 8) : zkfhe_download(ctx, p[comp] + lo * n, src_d, c * n * 8);
+  }
+  // the end of a call that wrote these planes: device planes are complete when the call returns
+  int done(zkfhe_ctx *ctx) const {
+    if (dev) ZK_HIP(ctx, zk_wait(ctx));
+    return ZKFHE_OK;
+  }
 };
-void add_mul_work(Arena &a, uint64_t n, int l, size_t n_pairs, MulWork &w);
-// steps 1 to 5 of bfv_eval.hip for c pairs: w.in_d = [a0 | a1 | b0 | b1] ([4 c][N]), w.rlk_hat the transformed key; w.o_d = [out0 | out1]
-int zk_bfv_mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l, int base_bits, const MulWork &w);
+inline Planes host_planes(const uint64_t *c0, const uint64_t *c1) { return Planes{{(uint64_t *)c0, (uint64_t *)c1}, false}; }
+inline Planes device_planes(const uint64_t *c0, const uint64_t *c1) { return Planes{{(uint64_t *)c0, (uint64_t *)c1}, true}; }
+
+// the key0 rows, then the key1 rows of one key (lw = l N words each) into dst_d ([2 l][N]): what k_rns_ntt transforms into the
+// [2 l][5][N] that the key switch reads
+inline int upload_key_pair(zkfhe_ctx *ctx, uint64_t *dst_d, const uint64_t *k0, const uint64_t *k1, size_t lw) {
+  ZK_CK(zkfhe_upload(ctx, dst_d, k0, lw * 8));
+  return zkfhe_upload(ctx, dst_d + lw, k1, lw * 8);
+}
+
+// Where the `count` key-switch keys of a call come from: host rows still to be staged (key k: k0 + k l N and k1 + k l N, checked by
+// the caller), or keys of a key set, transformed and on the device already (hat_d[k]: [2 l][5][N]).  add() puts the staging
+// buffers into the caller's arena only where there is something to stage; stage_keys fills them; hat(k) is key k either way.
+struct KeySource {
+  const uint64_t *k0 = nullptr, *k1 = nullptr;
+  const uint32_t *const *hat_d = nullptr;
+  size_t count = 1;
+  bool resident() const { return hat_d != nullptr; }
+  void add(Arena &a, uint64_t n, int l) {
+    words_ = (size_t)2 * l * n;
+    if (!resident()) a.add(key_d_, count * words_).add(key_hat_, count * words_ * NP_MAX);
+  }
+  const uint32_t *hat(size_t k) const { return resident() ? hat_d[k] : key_hat_ + k * words_ * NP_MAX; }
+
+  size_t words_ = 0;   // of one key before its transform
+  uint64_t *key_d_ = nullptr;
+  uint32_t *key_hat_ = nullptr;
+};
+inline KeySource host_keys(const uint64_t *k0, const uint64_t *k1, size_t count = 1) { return KeySource{k0, k1, nullptr, count}; }
+inline KeySource resident_keys(const uint32_t *const *hat_d, size_t count = 1) { return KeySource{nullptr, nullptr, hat_d, count}; }
+
+// The staging of host keys, once per call: every key's pair uploaded, one k_rns_ntt (LOAD_RESIDUE, five primes) over all of them.
+// A resident key stages nothing and launches nothing.  A template for the sake of its kernel, which each unit launches as its own.
+template <int NP>
+int stage_keys(zkfhe_ctx *ctx, const KeySource &key, uint64_t n, uint64_t q, int l, int *flag) {
+  if (key.resident()) return ZKFHE_OK;
+  const size_t lw = (size_t)l * n;
+  for (size_t k = 0; k < key.count; ++k) ZK_CK(upload_key_pair(ctx, key.key_d_ + k * 2 * lw, key.k0 + k * lw, key.k1 + k * lw, lw));
+  return launch_rns_ntt<NP>(ctx, false, key.key_d_, LOAD_RESIDUE, q, 2 * key.count * l, bit_log2(n), nullptr, 0, key.key_hat_, flag);
+}
+
+// ---- defined in bfv_eval.hip
+// out = a +/- b, coefficient-wise mod Q
+int zk_bfv_add_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, const Planes &b, int subtract, const Planes &out);
+// out = a + delta m (mul: a m mod (x^N + 1, Q)) with m_count = 1 plaintext for every ciphertext or one per ciphertext (m: a host array)
+int zk_bfv_plain_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, bool mul, size_t count, const Planes &a, size_t m_count, const uint64_t *m,
+                     const Planes &out);
+// out = a b relinearized with the one key of `key` (l rows of digit width base_bits).  A resident key takes the digit-parallel key
+// switch where the chunk is at most zk_bfv_wide_max; host rows never do
+int zk_bfv_mul_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, const Planes &b, KeySource key, int l, int base_bits,
+                   const Planes &out);
 // ---- defined in bfv_galois.hip
 // "fn: ..." unless g is odd and below 2N
 int check_g(zkfhe_ctx *ctx, uint64_t n, uint64_t g, const char *fn);
-// one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
-// part: the partials of the digit-parallel key switch ([l][2][c][5][N]); null: k_key_switch<true>
-int zk_bfv_galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
-                       bool accumulate, uint32_t *acc, uint64_t *out_d, uint32_t *part = nullptr);
-// the step loop of slot_sum on one chunk of c ciphertexts: x <- x + apply_galois(x, gs[k]) for k < steps with the transformed key
-// key_hat[k], x and y ([2 c][N] each) taking turns; *out is the one of the two that holds the result
-int zk_bfv_slot_sum_core(zkfhe_ctx *ctx, uint64_t *x, uint64_t *y, size_t c, int log_n, uint64_t q, size_t steps, const uint64_t *gs, int l, int w,
-                         const uint32_t *const *key_hat, uint32_t *acc, uint32_t *part, uint64_t **out);
+// The Galois chain: `steps` key switches per chunk, step k by gs[k] with key k of `key`.  accumulate: x <- x + apply_galois(x, gs[k])
+// (slot_sum); else steps = 1 and out = apply_galois(a, gs[0]).  The digit-parallel key switch as in zk_bfv_mul_run
+int zk_bfv_galois_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, size_t steps, const uint64_t *gs, KeySource key,
+                      int l, int base_bits, bool accumulate, const Planes &out);
 // ---- defined in bfv_dot.hip
-// The chunk loops of bfv_dot (plain: bfv_dot_plain) behind the host checks.  resident = false: a, b and out are host arrays, moved
-// with zkfhe_upload / zkfhe_download, and (rlk0, rlk1) is uploaded and transformed first.  resident = true: they are planes on the
-// device ([n_groups n_terms][N], [b_groups n_terms][N], [n_groups][N]), moved by device copies, and key_hat is the transformed key of
-// a key set; wide_max > 0 lets a pass of at most so many groups take the digit-parallel key switch.  b_host: b (the plaintexts of
-// bfv_dot_plain) is a host array beside resident ciphertexts.
+// The chunk loops of bfv_dot (plain: bfv_dot_plain, b.p[0] the plaintexts and no key) behind the checks: a ([n_groups n_terms][N]),
+// b ([b_groups n_terms][N]) and out ([n_groups][N]) each host arrays or device planes; with a resident key a pass of at most
+// zk_bfv_wide_max groups takes the digit-parallel key switch
 struct DotIo {
-  bool resident = false, b_host = false;
-  const uint64_t *a0 = nullptr, *a1 = nullptr, *b0 = nullptr, *b1 = nullptr;
-  uint64_t *out0 = nullptr, *out1 = nullptr;
-  const uint64_t *rlk0 = nullptr, *rlk1 = nullptr;
-  const uint32_t *key_hat = nullptr;
-  size_t wide_max = 0;
+  Planes a, b, out;
+  KeySource key;
 };
 int zk_bfv_dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, bool plain, size_t n_groups, size_t n_terms, size_t b_groups, const DotIo &io,
                     int l, int base_bits);
@@ -522,6 +572,11 @@ int zk_bfv_key_switch_wide(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, u
 // the largest count of ciphertexts whose key switch goes the digit-parallel way on this device (0: never), and the words of `part`
 size_t zk_bfv_wide_max(const zkfhe_ctx *ctx, uint64_t n, int l);
 inline size_t wide_part_words(uint64_t n, int l, size_t c) { return (size_t)l * 2 * c * NP_MAX * n; }
+// the words of `part` for the chunks of a call (at most `chunk` ciphertexts each): 0 where they take k_key_switch, as every chunk
+// of a call with host rows does
+inline size_t wide_words(const zkfhe_ctx *ctx, const KeySource &key, uint64_t n, int l, size_t chunk) {
+  return key.resident() && chunk <= zk_bfv_wide_max(ctx, n, l) ? wide_part_words(n, l, chunk) : 0;
+}
 // a key set as its callers see it: the transformed relinearization key (null: none) and the transformed key of g (null: none)
 struct EvkView {
   zkfhe_bfv_params params;
