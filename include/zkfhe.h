@@ -345,7 +345,12 @@ int zkfhe_bfv_tables_copy_break_points(const zkfhe_bfv_tables *t, int which, uin
 /* Process-wide admission gate of the proofs in flight: at most n of them inside the GPU-heavy middle of a proof (grand products,
  * their commitment, coset extension, quotient) at a time, first come first served; 0 = no gate (default, or ZKFHE_GATE), n < 0 =
  * query.  Returns the previous setting.  Spreads proofs that would otherwise move through the Fiat-Shamir rounds in lockstep; pays
- * when the streams are kept full, not for a batch that starts and ends together.  Ignored by sharded proofs. */
+ * when the streams are kept full, not for a batch that starts and ends together.  Ignored by sharded proofs.
+ * A limit above 0 also tells the library that the caller keeps the chip full: a proof reads the gate once, at its entry, and with a
+ * limit above 0 runs the throughput profile to its end -- it leaves out what only shortens the latency of a lone proof (32 elements
+ * per field inversion in the long batch inversions, chunks of 256 points in the table sums of a few columns, no early phase-1
+ * commitment where the Poseidon hash is its only reason).  Same proof bytes under either profile.  ZKFHE_PROFILE=latency|throughput
+ * overrides the gate's choice; ZKFHE_EARLY_P1 and ZKFHE_BI_CHUNK still win over the profile. */
 int zkfhe_prover_gate(int n);
 
 /* `mock` (README.md:18-22, halo2 MockProver::run(..).assert_satisfied()): evaluates every constraint on every row of

@@ -125,6 +125,8 @@ int zkfhe_ctx_create(int device_id, void *hip_stream, zkfhe_ctx **out) {
   ctx->num_cu = prop.multiProcessorCount;
   const char *chain_env = getenv("ZKFHE_CHAIN");
   ctx->chain_serial = chain_env && !strcmp(chain_env, "serial");
+  const char *profile_env = getenv("ZKFHE_PROFILE");
+  ctx->throughput = profile_env && !strcmp(profile_env, "throughput");   // until the first proof on the context decides (prove.hip)
   if (hip_stream) {
     ctx->stream = (hipStream_t)hip_stream;
   } else {
@@ -376,8 +378,20 @@ __global__ void __launch_bounds__(256) k_fr9_op(int op, const Fr *__restrict__ i
 // backward pass (zkfhe_fr_batch_invert_mul) -- no second kernel over both arrays, and no store of the inverses nobody reads.
 #define BI_CHUNK 8
 // from 2^20 elements on (the grand-product denominators of a k = 13 proof: 1.6 M): at least 16 per inversion -- a lone proof is
-// 0.25 ms slower, 96 proofs through 16 streams 1.4 % faster (242.5 / 239.7 against 239.0 / 236.7 proofs/s)
+// 0.25 ms slower, 96 proofs through 16 streams 1.4 % faster (242.5 / 239.7 against 239.0 / 236.7 proofs/s).  Since the two
+// grand-product inversions of a k = 13 proof became one joined call (below) this floor no longer reaches them: under the latency
+// profile they run at 8, and the long groups of a full pipeline are the throughput profile's (BI_WIDE).
 #define BI_LONG ((size_t)1 << 20)
+// Throughput profile (ctx.hpp: other proofs keep the chip full, the waves a longer group takes away are not missed): from 2^17
+// elements on -- the joined grand-product call of a k = 13 proof, 1.11 M ratios, and every long array of k >= 15 -- a thread takes
+// BI_THROUGHPUT elements.  Per element, at 110 product-times per inversion and 4 products in the <true> kernel: 17.75 at 8, 10.9 at
+// 16, 7.4 at 32.  The prefix products live in tmp[], so the registers do not change.  Shorter arrays keep 8.  Measured, 16 streams,
+// gate 4, 768 timed proofs, three runs each, every array forced to one size (ZKFHE_BI_CHUNK): 8 278.2, 16 280.1, 32 280.6, 64 276.0
+// proofs/s; 32 from 2^17 on and 8 below: 281.9 (profiles/throughput_profile.md).  -DBI_THROUGHPUT=n builds another size.
+#define BI_WIDE ((size_t)1 << 17)
+#ifndef BI_THROUGHPUT
+#define BI_THROUGHPUT 32
+#endif
 template <bool NUM>
 __global__ void __launch_bounds__(256) k_fr_batch_invert(Fr *__restrict__ a, Fr *__restrict__ num, Fr *__restrict__ tmp, size_t n, size_t T) {
   size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -471,7 +485,11 @@ static int batch_invert(zkfhe_ctx *ctx, Fr *a, Fr *num, size_t n, bool joined = 
   static const int forced = getenv("ZKFHE_BI_CHUNK") ? atoi(getenv("ZKFHE_BI_CHUNK")) : 0;
   size_t chunk = forced > 0 ? (size_t)forced : n / ((size_t)ctx->num_cu * 1024);
   if (forced <= 0) chunk = chunk < BI_CHUNK ? BI_CHUNK : (chunk > 32 ? 32 : chunk);
-  if (forced <= 0 && n >= BI_LONG && chunk < 16 && !joined) chunk = 16;
+  if (forced <= 0 && ctx->throughput) {
+    if (n >= BI_WIDE && chunk < BI_THROUGHPUT) chunk = BI_THROUGHPUT;   // joined or not: the parts of a joined call add up to one long array
+  } else if (forced <= 0 && n >= BI_LONG && chunk < 16 && !joined) {
+    chunk = 16;
+  }
   size_t T = (n + chunk - 1) / chunk;
   if (num)
     k_fr_batch_invert<true><<<zk_blocks(T, 256), 256, 0, ctx->stream>>>(a, num, (Fr *)tmp, n, T);

@@ -71,6 +71,12 @@ struct zkfhe_ctx {
   // ZKFHE_CHAIN=serial, read when the context is created: a proof's independent thin launches (grand products, SHPLONK sets, H(X) and
   // the barycentric denominators) go out one after the other as they did before they were merged -- the reference of the side-by-side tests
   bool chain_serial = false;
+  // The profile of the work on this context.  A proof sets it at its entry, for itself and its auxiliary context, and keeps it to its
+  // end: throughput when the admission gate is on (zkfhe_prover_gate(n > 0): the caller keeps the chip full with other proofs, so what
+  // only shortens the latency of a lone proof is left out -- more elements per inversion in batch_invert, chunks of 256 points in the
+  // few-column table sums, no early phase-1 commitment), latency otherwise.  ZKFHE_PROFILE=latency|throughput overrides the gate; read
+  // per proof, and when the context is created (the calls made on a context before its first proof).
+  bool throughput = false;
   unsigned *tickets = nullptr;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
   // the BFV calls (rns_ntt.hip.hpp): the RNS twiddle tables (built on first use) and a grow-only work arena
   uint32_t *bfv_tw = nullptr;

@@ -147,9 +147,16 @@ int msm_table(zkfhe_ctx *ctx, const zkfhe_basis *basis, const Fr *scalars, size_
   unsigned long long *adds = (unsigned long long *)(ctx->tickets + 2 * MSM_MAX_COLS);
   const size_t grid_max = (size_t)ctx->num_cu * 3;
   // chunk: 256 points when the call fills the chip that way, else 128 (a lone column of 2^13: 64 workgroups, 11 additions
-  // per thread and a 9-addition butterfly each -- a smaller chunk shortens the chain and multiplies the butterflies)
+  // per thread and a 9-addition butterfly each -- a smaller chunk shortens the chain and multiplies the butterflies).  Under the
+  // throughput profile (ctx.hpp) the chunk stays at 256: the workgroups the call leaves idle belong to other proofs, and every visit
+  // of the <true> kernel that is not made saves its block_sum_256.  -DZK_MSM_THROUGHPUT_P=128 builds the old choice for an A/B run:
+  // 16 streams, gate 4, 768 timed proofs, four runs each, 285.7 against 279.2 proofs/s (+2.3 %; profiles/throughput_profile.md).
+#ifndef ZK_MSM_THROUGHPUT_P
+#define ZK_MSM_THROUGHPUT_P 256
+#endif
   size_t P = 256;
-  while (P > 128 && n_cols * ((n + P - 1) / P) < grid_max) P >>= 1;
+  const size_t P_min = ctx->throughput ? ZK_MSM_THROUGHPUT_P : 128;
+  while (P > P_min && n_cols * ((n + P - 1) / P) < grid_max) P >>= 1;
   const size_t cpc = (n + P - 1) / P, n_items = n_cols * cpc;
   const size_t grid = n_items < grid_max ? n_items : grid_max;
   const size_t max_part = cpc < grid ? cpc : grid;   // visits to one column

@@ -632,6 +632,7 @@ struct Proof {
     CK(zkfhe_sync(ctx));
     CK(alloc_witness_buffers(ctx, pk, ws));
     ws->aux->cmd_owner = ctx;   // the auxiliary stream's commands are this proof's
+    ws->aux->throughput = ctx->throughput;   // ... and run under its profile
     ws->ring_off = ws->ring_flushed = 0;
     ws->inst_pending = false;
     trace.mark("setup (workspace)");
@@ -724,7 +725,12 @@ struct Proof {
     // (k = 19: 6 ms of Horner chains and placement with the GPU idle): 155.8 -> 151.5 ms per proof; at k = 16 it costs 0.7 ms.
     // ZKFHE_EARLY_P1=0 / 1 overrides.
     const char *early_env = getenv("ZKFHE_EARLY_P1");
-    const bool early_want = early_env ? early_env[0] == '1' : (cfg.transcript == TR_POSEIDON || k >= 18);
+    // Under the throughput profile (ctx.hpp) the hash is hidden behind other proofs' GPU work already: off wherever the Poseidon hash
+    // is the only reason (59 launches per proof instead of 64).  The k >= 18 rule hides host RLC work and stays.  Measured with 16
+    // streams, gate 4 and 768 timed proofs, four runs each (profiles/throughput_profile.md): off 285.7 against on 284.5 proofs/s
+    // (+0.4 %) with the profile's chunks of 256 points in the few-column table sums -- but 279.2 against 281.9 (-1.0 %) with chunks of
+    // 128: the two extra commitments are few-column table sums themselves.  The "-1.5 % in steady state" above is from before both.
+    const bool early_want = early_env ? early_env[0] == '1' : ((cfg.transcript == TR_POSEIDON && !ctx->throughput) || k >= 18);
     early_p1 = early_want && !host_witness && cfg.n_lookup > 0 && cfg.lookup_bits == 8;
     if (host_witness) return commit_cols(ctx, srs, small_basis(), ws->adv_l.fr(), cfg.n_gate0, (G1Affine *)ws->points.p, pts);
     // the commitment's points come back through an event; the phase-1 gadget launches queue up behind the MSM
@@ -1493,6 +1499,16 @@ int prove_impl(zkfhe_ctx *ctx, const zkfhe_srs *srs, zkfhe_bfv_pk *pk, const cha
   Workspace *ws;
   CK(get_workspace(ctx, pk, &ws));
   BackendGuard guard(ctx, ws);
+  // One profile per proof (ctx.hpp), chosen here and kept to the end whatever happens to the gate meanwhile: throughput when the
+  // admission gate is on -- the caller says it keeps the chip full --, latency otherwise.  ZKFHE_PROFILE=latency|throughput overrides
+  // (read per proof, like ZKFHE_EARLY_P1: the tests switch it).  The auxiliary context's launches belong to the same proof.
+  {
+    const char *profile_env = getenv("ZKFHE_PROFILE");
+    bool throughput = !srs->sharded() && HeavyGate::get().set(-1) > 0;   // a sharded proof ignores the gate (its ranks must choose alike)
+    if (profile_env && !strcmp(profile_env, "throughput")) throughput = true;
+    else if (profile_env && !strcmp(profile_env, "latency")) throughput = false;
+    ctx->throughput = throughput;   // the auxiliary context exists from setup() on and takes it there
+  }
   Proof P{ctx, srs, pk, pk->cfg, instances, trace, ws, dom};
   memcpy(P.rseed.w, seed, 32);
   CK(P.setup());
