@@ -1174,6 +1174,66 @@ int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_ter
  * with a key set launches counts in the slots of its host-array call; no such call launches a key transform. */
 #define ZKFHE_PROF_BFV_KEY_SWITCH_WIDE 26   /* k_key_switch_digit, k_key_switch_fold */
 
+/* ---- Ring packing: chosen coefficients of many ciphertexts in one (bfv_pack.hip, bfv_resident.hip) ----
+ * Moves one coefficient of each of n ciphertexts into one ciphertext and erases everything else (PackLWEs followed by the field
+ * trace; Chen, Dai, Kim, Song 2021).  It uses Galois key switches, additions and products by a monomial only: no multiplicative
+ * depth, only key-switch noise, any T (no batching modulus is needed: this is coefficient encoding), and the Galois keys of
+ * zkfhe_bfv_galois_keygen or the collective keys of zkfhe_bfv_galois_share, unchanged.  Conventions of "BFV slots and rotations":
+ * N uint64_t per polynomial in CircuitInput order, residues in [0, Q), "coefficient i" is the coefficient of x^i.  No new
+ * randomness and no new ChaCha20 domain.  Two primitives are new:
+ *   Monomial product.  x^k c mod (x^N + 1, Q) for 0 <= k < 2N: coefficient i moves to j = i + k mod 2N; for j >= N it is negated
+ *     mod Q and placed at j - N.  It applies to both components and adds no noise.  For k < N it is bit for bit
+ *     zkfhe_bfv_mul_plain by the plaintext x^k, for k >= N bit for bit zkfhe_bfv_mul_plain by -x^(k - N).
+ *   Scaling.  Every coefficient v becomes v nu mod Q with nu = N^-1 mod Q.  Q must be odd.
+ * Pack elements: g_l = 2^l + 1 for l = 1 ... log2(N), that is 3, 5, 9, ..., N + 1 (zkfhe_bfv_pack_elements; host only, g may be
+ * NULL, *count = log2(N), defined for any T).  Every call uses the keys of all log2(N) of them.
+ * pack of n ciphertexts a_0 ... a_(n-1) with positions pos_i < N, 1 <= n <= N, n' the least power of two >= n, L = log2(n'):
+ *   1. Prepare.  w_i = nu x^((2N - pos_i) mod 2N) a_i for i < n; w_i = (0, 0) for n <= i < n'.
+ *   2. Pack levels l = 1 ... L.  With h = n' / 2^l, s = N / 2^l, g = 2^l + 1, for every i < h: t = x^s w_(i+h);
+ *      w_i <- (w_i + t) + zkfhe_bfv_apply_galois(w_i - t, g).  The sums and differences are those of zkfhe_bfv_add, the key switch
+ *      is exactly the definition of zkfhe_bfv_apply_galois: digits of sigma_g(c1) in [0, Q).
+ *   3. Trace levels l = L + 1 ... log2(N).  w_0 <- w_0 + zkfhe_bfv_apply_galois(w_0, 2^l + 1).
+ *   4. The result is w_0.
+ * Under the key's secret it decrypts to the plaintext whose coefficient i N / n' is coefficient pos_i of the plaintext of a_i, for
+ * i < n; every other coefficient is 0.  The definition is exact, so every implementation is held to it bit for bit.
+ * zkfhe_bfv_mul_monomial: host arrays, n ciphertexts; k_count is 1 (one k for all) or n; every k is below 2N.
+ * zkfhe_bfv_pack: c0, c1 are [n_groups][n][N]; pos is [n_groups][n] or NULL (all 0); gk0, gk1 are [log2 N][l][N], the keys of
+ * the pack elements in order (l = zkfhe_bfv_relin_digits), checked and transformed once per call; out0, out1 are [n_groups][N].
+ * zkfhe_bfv_cts_mul_monomial and zkfhe_bfv_cts_pack are the same calls on resident batches, with the conventions of "Resident
+ * ciphertext batches": dst of mul_monomial holds a's count and may be a; n_groups of pack is dst's count, a holds n_groups n
+ * ciphertexts in [group][input] order, the keys come from the key set, dst must not be a source, nothing is allocated on the
+ * device, and a refused call leaves dst as it was.
+ * Refusals: ZKFHE_EINVAL with a message "bfv_pack: ...", "bfv_mul_monomial: ...", "bfv_cts_pack: ..." or "bfv_cts_mul_monomial:
+ * ...", in this order and before any device work on ciphertexts: a NULL argument, a zero count or bad parameters; "Q must be odd"
+ * (pack only); base_bits outside [1, 32]; "n = ... is above N"; a k_count neither 1 nor n, or a k >= 2N; a position >= N; for
+ * the batch calls the device, parameter and count refusals with the texts of the other bfv_cts_* calls ("a holds H ciphertexts and
+ * the call needs W", "dst must not be a source"); "the key set has no key for the Galois element G", naming the first missing
+ * pack element; the coefficient >= Q checks of the host-array calls, for ciphertexts and keys.
+ * Kernels.  One launch prepares every input (k_pack_prepare).  A level is a key switch that reads the digits of
+ * sigma_g(e1 - x^s o1) straight from the two operands (k_pack_switch: one workgroup per (pair, prime) walking the digits; or, where
+ * the key is resident, l >= 2 and the level has at most zkfhe_bfv_evk_wide_max pairs, k_pack_digit per (digit, pair, prime)
+ * followed by k_key_switch_fold) and k_pack_finish: Garner over the five primes, mod Q, plus (e0 + x^s o0) + sigma_g(e0 - x^s o0)
+ * on component 0 and e1 + x^s o1 on component 1, out of place between two work arrays.  A call of more leaves than a chunk holds
+ * (2^21 / N ciphertexts) reduces the subtrees of leaves with equal index mod n' / C one after another and merges their roots
+ * depth first; everything is exact, so the result does not depend on the chunking.
+ * Noise.  The input noise is not amplified (nu N = 1 mod Q: the N-fold sum of the trace undoes the scaling).  The key switch of
+ * level l is amplified by 2^(log2 N - l).  Sufficient bound, with l_digits rows of width w and B the error bound:
+ *   noise(out) <= max_i noise(a_i) + (N - 1) l_digits N (2^w - 1) B.
+ * The bound is loose: at N = 1024 it certifies nothing at a 29-bit Q (2.4e9 at w = 4).  Measured (zkfhe_bfv_noise of packed fresh
+ * encryptions, profiles/bfv_pack.md) at N = 1024, Q = 536870909, T = 7, where floor(Q/T)/2 = 3.8e7: a full pack of n = 1024 came to
+ * 3.8e6 at w = 4 and to 3.6e7 at w = 8 (n = 1: 1.1e6 and 1.6e7).  Keep w small for packing: at these parameters w = 4 leaves a factor
+ * of ten, w = 8 none.  At N = 4096, a 60-bit Q and T = 65537 (limit 8.8e12) n = 4096 came to 4.6e8 at w = 8 and 9.9e10 at w = 16. */
+int zkfhe_bfv_pack_elements(const zkfhe_bfv_params *params, uint64_t *g, size_t *count);
+int zkfhe_bfv_mul_monomial(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n, const uint64_t *c0, const uint64_t *c1, size_t k_count,
+                           const uint64_t *k, uint64_t *out0, uint64_t *out1);
+int zkfhe_bfv_pack(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, size_t n, const uint64_t *c0, const uint64_t *c1,
+                   const uint64_t *pos, const uint64_t *gk0, const uint64_t *gk1, int base_bits, uint64_t *out0, uint64_t *out1);
+int zkfhe_bfv_cts_mul_monomial(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t k_count, const uint64_t *k, zkfhe_bfv_cts *dst);
+int zkfhe_bfv_cts_pack(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n, const uint64_t *pos, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst);
+/* zkfhe_prof_read slot of the packing kernels: algorithmic bytes = the words read and written.  k_key_switch_fold counts in
+ * ZKFHE_PROF_BFV_KEY_SWITCH_WIDE; the one key transform of the host-array call in ZKFHE_PROF_RNS_NTT */
+#define ZKFHE_PROF_BFV_PACK 27   /* k_pack_prepare, k_pack_switch, k_pack_digit, k_pack_finish, k_pack_monomial */
+
 const char *zkfhe_version(void);
 
 #ifdef __cplusplus

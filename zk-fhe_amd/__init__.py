@@ -29,6 +29,7 @@ PROF_G1_FFT = 23   # ... and of the G1 FFT's butterfly kernels
 PROF_BFV_BALLOT = 24   # ... and of the ballot box's unpack and sum kernels
 PROF_BFV_RESIDENT = 25   # ... and of the resident batches' check, gather and group-sum kernels
 PROF_BFV_KEY_SWITCH_WIDE = 26   # ... and of the digit-parallel key switch of the calls that take a resident key set
+PROF_BFV_PACK = 27   # ... and of the ring-packing kernels
 # per-item statuses of Context.bfv_sum_instances and BallotBox.add (ZKFHE_BALLOT_* of zkfhe.h)
 BALLOT_COUNTED, BALLOT_SKIPPED, BALLOT_BAD_GROUP, BALLOT_NOT_A_CIPHERTEXT, BALLOT_WRONG_KEY, BALLOT_REJECTED, BALLOT_REPEATED = range(7)
 BALLOT_STATUSES = 7
@@ -72,6 +73,7 @@ EXPORTS = [
     "zkfhe_bfv_cts_apply_galois", "zkfhe_bfv_cts_plan_apply", "zkfhe_bfv_cts_select", "zkfhe_bfv_cts_sum",
     "zkfhe_bfv_evk_create", "zkfhe_bfv_evk_bytes", "zkfhe_bfv_evk_info", "zkfhe_bfv_evk_destroy", "zkfhe_bfv_evk_wide_max",
     "zkfhe_bfv_cts_mul_evk", "zkfhe_bfv_cts_apply_galois_evk", "zkfhe_bfv_cts_slot_sum", "zkfhe_bfv_cts_dot", "zkfhe_bfv_cts_dot_plain",
+    "zkfhe_bfv_pack_elements", "zkfhe_bfv_mul_monomial", "zkfhe_bfv_pack", "zkfhe_bfv_cts_mul_monomial", "zkfhe_bfv_cts_pack",
     "zkfhe_transcript_create", "zkfhe_transcript_destroy", "zkfhe_transcript_common_scalar", "zkfhe_transcript_write_scalar",
     "zkfhe_transcript_common_point", "zkfhe_transcript_write_point", "zkfhe_transcript_squeeze", "zkfhe_transcript_bytes",
     "zkfhe_poseidon_permute", "zkfhe_poseidon_constants", "zkfhe_poseidon_hash_many", "zkfhe_host_hash_mode", "zkfhe_prover_gate",
@@ -919,6 +921,49 @@ class Context:
         self._bfv("zkfhe_bfv_slot_sum", "nppppipp", params, c0.shape[0], c0, c1, gk0, gk1, int(base_bits), *out)
         return tuple(out)
 
+    # ------------------------------------------------------------------ ring packing (zkfhe.h, bfv_pack.hip)
+
+    @staticmethod
+    def _exponents(k, what):
+        k = np.ascontiguousarray(k, dtype=np.uint64)
+        if k.ndim > 1:
+            raise ValueError("%s must be one integer or one per ciphertext" % what)
+        return k.reshape(-1)
+
+    def bfv_mul_monomial(self, params, c0, c1, k):
+        """zkfhe_bfv_mul_monomial: n ciphertexts (n, N) -> x^k times each, mod (x^N + 1, Q); k is one exponent below 2N for every
+        ciphertext or one per ciphertext."""
+        c0, c1 = self._eval_arrays(params, c0, c1)
+        k = self._exponents(k, "k")
+        out = [np.empty(c0.shape, dtype=np.uint64) for _ in range(2)]
+        self._bfv("zkfhe_bfv_mul_monomial", "nppnppp", params, c0.shape[0], c0, c1, k.shape[0], k, *out)
+        return tuple(out)
+
+    def bfv_pack(self, params, c0, c1, gk0, gk1, pos=None, base_bits=16):
+        """zkfhe_bfv_pack: c0, c1 of shape (n, N) (one group) or (n_groups, n, N) -> (out0, out1) of shape (n_groups, N): coefficient
+        i N / n' of result g is coefficient pos[g][i] (None: 0) of input i of group g, every other coefficient 0.  gk0, gk1: the keys
+        of bfv_pack_elements stacked as (log2(N), l, N)."""
+        n = int(params[0])
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64)
+        if c0.shape != c1.shape or c0.ndim not in (2, 3) or c0.shape[-1] != n or 0 in c0.shape:
+            raise ValueError("c0 and c1 must have the same shape (n, N) or (n_groups, n, N)")
+        n_groups, n_in = (1, c0.shape[0]) if c0.ndim == 2 else c0.shape[:2]
+        p = None
+        if pos is not None:
+            p = np.ascontiguousarray(pos, dtype=np.uint64)
+            if p.size != n_groups * n_in:
+                raise ValueError("pos must hold one position per input")
+        gk0, gk1 = self._galois_keys(params, gk0, gk1, base_bits, (n.bit_length() - 1,))
+        out = [np.empty((n_groups, n), dtype=np.uint64) for _ in range(2)]
+        f = self.lib.zkfhe_bfv_pack
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(BfvParamsC), ctypes.c_size_t, ctypes.c_size_t, _U64P, _U64P, _U64P, _U64P, _U64P, ctypes.c_int,
+                      _U64P, _U64P]
+        ptr = lambda a: a.ctypes.data_as(_U64P) if a is not None else None  # noqa: E731
+        self._check(f(self.h, ctypes.byref(BfvParamsC(*[int(x) for x in params])), n_groups, n_in, ptr(c0), ptr(c1), ptr(p), ptr(gk0), ptr(gk1),
+                      int(base_bits), ptr(out[0]), ptr(out[1])))
+        return tuple(out)
+
     # ------------------------------------------------------------------ encrypted matrix-vector products (zkfhe.h, bfv_linear.hip)
     # elements: K Galois elements (repeats allowed); their keys stacked as gk0, gk1 of shape (K, l, N) (the rows of g = 1 are not read).
 
@@ -1252,6 +1297,28 @@ class BfvCiphertexts:
         return self._into(out, ctx, n_groups, "zkfhe_bfv_cts_dot_plain", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, _U64P], self._handle(),
                           n_terms, 1 if m.ndim == 2 else m.shape[0], m.ctypes.data_as(_U64P))
 
+    # ---- ring packing (zkfhe.h "Ring packing")
+
+    def mul_monomial(self, k, out=None, ctx=None):
+        """zkfhe_bfv_cts_mul_monomial: x^k times every ciphertext; k one exponent below 2N or one per ciphertext; out may be self"""
+        k = Context._exponents(k, "k")
+        return self._into(out, ctx, None, "zkfhe_bfv_cts_mul_monomial", [ctypes.c_void_p, ctypes.c_size_t, _U64P], self._handle(), k.shape[0],
+                          k.ctypes.data_as(_U64P))
+
+    def pack(self, n, evk, pos=None, out=None, ctx=None):
+        """zkfhe_bfv_cts_pack: self holds n_groups * n ciphertexts in [group][input] order -> n_groups ciphertexts, each the pack of
+        its group's n inputs at pos (n_groups * n positions; None: all 0) with the set's keys for bfv_pack_elements; out must not
+        be self"""
+        n = int(n)
+        n_groups = out.n if out is not None else (self.n // n if n > 0 and self.n % n == 0 else 1)
+        p = None
+        if pos is not None:
+            p = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+            if p.size != n_groups * n:
+                raise ValueError("pos must hold one position per input")
+        return self._into(out, ctx, n_groups, "zkfhe_bfv_cts_pack", [ctypes.c_void_p, ctypes.c_size_t, _U64P, ctypes.c_void_p], self._handle(), n,
+                          p.ctypes.data_as(_U64P) if p is not None else None, evk._handle())
+
     def close(self):
         if self.h:
             f = self.ctx.lib.zkfhe_bfv_cts_destroy
@@ -1416,6 +1483,11 @@ def bfv_galois_element(params, steps=0, swap_rows=False):
 def bfv_slot_sum_elements(params):
     """zkfhe_bfv_slot_sum_elements (host only): the log2(N) Galois elements of bfv_slot_sum in order, a list of ints."""
     return [int(x) for x in _host_bfv_list("zkfhe_bfv_slot_sum_elements", params)]
+
+
+def bfv_pack_elements(params):
+    """zkfhe_bfv_pack_elements (host only): the log2(N) Galois elements 2^l + 1 of bfv_pack in order, a list of ints; any T."""
+    return [int(x) for x in _host_bfv_list("zkfhe_bfv_pack_elements", params)]
 
 
 def bfv_matrix_diagonals(params, matrix):

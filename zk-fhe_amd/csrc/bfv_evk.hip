@@ -185,7 +185,6 @@ int zk_bfv_key_switch_wide(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, u
   ZK_CK(zk_rns_tables(ctx, &tw));
   int lds;
   ZK_CK(ntt_lds(ctx, ginv ? (const void *)k_key_switch_digit<true> : (const void *)k_key_switch_digit<false>, log_n, &lds));
-  ZK_CK(ntt_lds(ctx, (const void *)k_key_switch_fold, log_n, &lds));
   const RnsConst<NP> rc = rns_const<NP>(log_n);
   const double words = (double)c * NP * ((size_t)1 << log_n);
   zk_prof_begin(ctx);
@@ -195,8 +194,17 @@ int zk_bfv_key_switch_wide(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, u
     k_key_switch_digit<false><<<(unsigned)(c * NP * l), NTT_THREADS, lds, ctx->stream>>>(src, l, w, key_hat, c, log_n, tw, rc, part, 0, q);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_KEY_SWITCH_WIDE, words * l * (8.0 + 8.0 + 8.0));   // the digit's source, two key rows, two partials
+  return zk_bfv_key_switch_fold(ctx, part, l, c, log_n, acc);
+}
+
+int zk_bfv_key_switch_fold(zkfhe_ctx *ctx, const uint32_t *part, int l, size_t c, int log_n, uint32_t *acc) {
+  const uint32_t *tw;
+  ZK_CK(zk_rns_tables(ctx, &tw));
+  int lds;
+  ZK_CK(ntt_lds(ctx, (const void *)k_key_switch_fold, log_n, &lds));
+  const double words = (double)c * NP * ((size_t)1 << log_n);
   zk_prof_begin(ctx);
-  k_key_switch_fold<<<(unsigned)(2 * c * NP), NTT_THREADS, lds, ctx->stream>>>(part, l, c, log_n, tw, rc, acc);
+  k_key_switch_fold<<<(unsigned)(2 * c * NP), NTT_THREADS, lds, ctx->stream>>>(part, l, c, log_n, tw, rns_const<NP>(log_n), acc);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_KEY_SWITCH_WIDE, words * 2 * (4.0 * l + 4.0));
   return ZKFHE_OK;

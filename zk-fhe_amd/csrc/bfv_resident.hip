@@ -8,7 +8,8 @@
 // runs a range pass over ciphertexts: only the host arrays of a call (plaintexts, keys, indices, groups) are checked, on the host.
 //
 // An evaluation call here is its argument checks and one call of the runner of the host-array call (rns_ntt.hip.hpp:
-// zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run, zk_bfv_galois_run, zk_bfv_dot_core, zk_bfv_plan_run_dev) on the batch's planes:
+// zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run, zk_bfv_galois_run, zk_bfv_dot_core, zk_bfv_plan_run_dev, zk_bfv_monomial_run,
+// zk_bfv_pack_run) on the batch's planes:
 // one chunk loop per operation, so the chunk rule, the kernels, their order and their profiling slots are those of that call.  A
 // runner reads a chunk from the batch (or from a contiguous copy in the work arena where a kernel wants one), writes its result to
 // the work arena, and copies it into dst afterwards on the same stream: a chunk is read completely before it is written, and dst may
@@ -537,6 +538,35 @@ int zkfhe_bfv_cts_dot(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_ct
   ZK_CK(check_dot_terms(ctx, &a->params, false, n_terms, fn));
   const DotIo io{a->planes(), b->planes(), dst->planes(), resident_keys(&view.rlk_hat)};
   return zk_bfv_dot_core(ctx, &a->params, false, dst->n, n_terms, b->n / n_terms, io, view.l, view.base_bits);
+}
+
+// ---- ring packing (bfv_pack.hip): the runners of zkfhe_bfv_mul_monomial and zkfhe_bfv_pack on the batches' planes
+
+int zkfhe_bfv_cts_mul_monomial(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t k_count, const uint64_t *k, zkfhe_bfv_cts *dst) {
+  CTS_CALL("mul_monomial");
+  if (!(ctx && a && k && dst)) return null_arg(ctx, fn);
+  ZK_CK(check_monomial(ctx, &a->params, a->n, k_count, k, fn));
+  ZK_CK(on_device(ctx, fn, {a, dst}));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
+  return zk_bfv_monomial_run(ctx, &a->params, a->n, a->planes(), k_count, k, dst->planes());
+}
+
+int zkfhe_bfv_cts_pack(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n, const uint64_t *pos, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
+  CTS_CALL("pack");
+  if (!(ctx && a && evk && dst && n > 0)) return null_arg(ctx, fn);
+  ZK_CK(check_pack(ctx, &a->params, nullptr, nullptr, dst->n, n, pos, fn));
+  ZK_CK(on_device(ctx, fn, {a, dst}));
+  EvkView view;
+  ZK_CK(evk_args(ctx, fn, evk, a, &view));
+  ZK_CK(alike(ctx, fn, a, dst));
+  ZK_CK(same_count(ctx, fn, a->n, dst->n * n, "a"));   // n <= N and counts are below 2^31: the product fits
+  if (dst == a) return refuse(ctx, fn, "dst must not be a source");
+  std::vector<uint64_t> gs((size_t)bit_log2(a->params.n));
+  pack_elements(a->params.n, gs.data());
+  std::vector<const uint32_t *> keys(gs.size());
+  for (size_t i = 0; i < gs.size(); ++i) ZK_CK(need_galois(ctx, fn, evk, gs[i], &keys[i]));
+  return zk_bfv_pack_run(ctx, &a->params, dst->n, n, a->planes(), pos, resident_keys(keys.data(), keys.size()), view.l, view.base_bits, dst->planes());
 }
 
 int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_terms, size_t m_groups, const uint64_t *m, zkfhe_bfv_cts *dst) {

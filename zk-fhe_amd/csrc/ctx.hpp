@@ -51,8 +51,9 @@ struct zkfhe_ctx {
   // [16] = k_hoist, [17] = k_linear_acc, [18] = k_bsgs_inner, [19] = k_linear_acc<ACC_GIANT> (bfv_linear.hip),
   // [20] = k_bfv_dot_acc / k_bfv_dot_fold (bfv_dot.hip), [21] = k_bfv_pcks_combine, [22] = k_bfv_refresh_combine (bfv_refresh.hip),
   // [23] = k_g1_fft_shared / k_g1_fft_window (g1_fft.hip), [24] = k_ballot_unpack / k_ballot_sum / k_ballot_totals (bfv_ballot.hip),
-  // [25] = k_cts_check / k_cts_gather / k_cts_group_sum (bfv_resident.hip), [26] = k_key_switch_digit / k_key_switch_fold (bfv_evk.hip)
-  static constexpr int PROF_SLOTS = 27;
+  // [25] = k_cts_check / k_cts_gather / k_cts_group_sum (bfv_resident.hip), [26] = k_key_switch_digit / k_key_switch_fold (bfv_evk.hip),
+  // [27] = k_pack_prepare / k_pack_switch / k_pack_digit / k_pack_finish / k_pack_monomial (bfv_pack.hip)
+  static constexpr int PROF_SLOTS = 28;
   double prof_ms[PROF_SLOTS] = {}, prof_bytes[PROF_SLOTS] = {}, prof_ops[PROF_SLOTS] = {};
   uint64_t prof_launches[PROF_SLOTS] = {};
   // pinned bounce buffer for small host<->device transfers (pageable copies go through the runtime's shared staging path)

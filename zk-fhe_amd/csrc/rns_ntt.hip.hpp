@@ -569,6 +569,9 @@ int check_dot_terms(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, bool plain, siz
 // ([l][2][c][5][N]) and k_key_switch_fold over 2 c 5 workgroups into acc, both in profiling slot ZKFHE_PROF_BFV_KEY_SWITCH_WIDE
 int zk_bfv_key_switch_wide(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64_t q, int l, int w, const uint32_t *key_hat, size_t c,
                            int log_n, uint32_t *part, uint32_t *acc);
+// k_key_switch_fold alone, over 2 c 5 workgroups: the l partials of part ([l][2][c][5][N]) summed into acc (the second half of
+// zk_bfv_key_switch_wide, for a caller that wrote the partials with a kernel of its own), in the same profiling slot
+int zk_bfv_key_switch_fold(zkfhe_ctx *ctx, const uint32_t *part, int l, size_t c, int log_n, uint32_t *acc);
 // the largest count of ciphertexts whose key switch goes the digit-parallel way on this device (0: never), and the words of `part`
 size_t zk_bfv_wide_max(const zkfhe_ctx *ctx, uint64_t n, int l);
 inline size_t wide_part_words(uint64_t n, int l, size_t c) { return (size_t)l * 2 * c * NP_MAX * n; }
@@ -585,6 +588,24 @@ struct EvkView {
 };
 void zk_bfv_evk_view(const zkfhe_bfv_evk *evk, EvkView *view);
 const uint32_t *zk_bfv_evk_galois(const zkfhe_bfv_evk *evk, uint64_t g);
+// ---- defined in bfv_pack.hip
+// out = x^k a mod (x^N + 1, Q) with k_count = 1 exponent for every ciphertext or one per ciphertext (k: a host array, every k < 2N)
+int zk_bfv_monomial_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, size_t k_count, const uint64_t *k,
+                        const Planes &out);
+// Ring packing (zkfhe.h "Ring packing"): a holds n_groups n ciphertexts in [group][input] order, pos (a host array, [n_groups][n],
+// or null: all 0) the coefficient of each that is kept, `key` the log2(N) keys of the pack elements in order; out takes n_groups
+// ciphertexts.  A level's key switch takes the digit-parallel kernels where the key is resident and the level has at most
+// zk_bfv_wide_max pairs
+int zk_bfv_pack_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t n_groups, size_t n, const Planes &a, const uint64_t *pos, KeySource key,
+                    int l, int base_bits, const Planes &out);
+// the log2(N) pack elements 2^l + 1, l = 1 ... log2(N)
+void pack_elements(uint64_t n, uint64_t *g);
+// the refusals of a pack in their order: "fn: Q must be odd", base_bits outside [1, 32] (base_bits set: relin_rows into *l), "fn: n =
+// ... is above N", "fn: a position is not below N" (pos: [n_groups][n] or null)
+int check_pack(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, const int *base_bits, int *l, size_t n_groups, size_t n, const uint64_t *pos,
+               const char *fn);
+// "fn: ..." unless k_count is 1 or count and every k is below 2N
+int check_monomial(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, size_t k_count, const uint64_t *k, const char *fn);
 // ---- defined in bfv_linear.hip
 // the parameters and the device of a plan
 void zk_bfv_plan_view(const zkfhe_bfv_plan *plan, zkfhe_bfv_params *params, int *device);
