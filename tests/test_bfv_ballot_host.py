@@ -188,7 +188,6 @@ def unpack_status(params, inst, outputs=True):
     lib = zk.load_library()
     raw = b"".join(int(v).to_bytes(32, "little") for v in inst)
     u64p = ctypes.POINTER(ctypes.c_uint64)
-    lib.zkfhe_bfv_instances_unpack.argtypes = [ctypes.POINTER(zk.BfvParamsC), ctypes.c_char_p, ctypes.c_size_t] + [u64p] * 4 + [ctypes.POINTER(ctypes.c_int32)]
     out = [np.full(params[0], 77, dtype=np.uint64) for _ in range(4)]
     st = ctypes.c_int32(-1)
     rc = lib.zkfhe_bfv_instances_unpack(ctypes.byref(zk.BfvParamsC(*params)), raw, len(inst),
@@ -278,8 +277,6 @@ def sum_instances_rc(ctx_h, params, n_items=1, n_groups=1, null=None):
     }
     if null:
         args[null] = None
-    vp = ctypes.c_void_p
-    lib.zkfhe_bfv_sum_instances.argtypes = [vp, ctypes.POINTER(zk.BfvParamsC), ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
     prm = ctypes.byref(zk.BfvParamsC(*params)) if params else None
     rc = lib.zkfhe_bfv_sum_instances(ctx_h, prm, n_items, args["instances"], args["n_instances"], None, n_groups, args["out0"], args["out1"],
                                      args["counted"], args["status"])
@@ -307,9 +304,6 @@ def box_create_rc(params, n_groups=1, null=None, seed=b"zkfhe-unsafe-srs", g2=No
     args = {"vk": b"ZKFHEVK2" + bytes(64), "pk0": pk, "pk1": pk, "out": ctypes.pointer(ctypes.c_void_p(1))}
     if null:
         args[null] = None
-    vp = ctypes.c_void_p
-    lib.zkfhe_bfv_box_create.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(zk.BfvParamsC), vp, vp, ctypes.c_size_t, ctypes.c_char_p,
-                                         ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p, vp]
     prm = ctypes.byref(zk.BfvParamsC(*params)) if params else None
     rc = lib.zkfhe_bfv_box_create(None, args["vk"], 72 if args["vk"] else 0, prm, args["pk0"], args["pk1"], n_groups, seed, len(seed) if seed else 0,
                                   g2, s_g2, args["out"])
@@ -331,7 +325,5 @@ def test_box_create_refusals_without_a_device():
     assert box_create_rc(good, g2=bytes(128)) == (-1, "bfv_box: give srs_seed, or both g2 and s_g2")
     assert box_create_rc(good) == (-1, "bfv_box: ctx is NULL")
     lib = zk.load_library()
-    lib.zkfhe_bfv_box_info.argtypes = [ctypes.c_void_p] * 4
-    lib.zkfhe_bfv_box_destroy.argtypes = [ctypes.c_void_p] * 2
     assert lib.zkfhe_bfv_box_info(None, None, None, None) == -1 and lib.zkfhe_last_error(None).decode() == "bfv_box: box is NULL"
     assert lib.zkfhe_bfv_box_destroy(None, None) == 0     # a NULL box is not an error

@@ -229,20 +229,15 @@ def test_python_methods_exist():
 
 def test_calls_without_a_context_are_refused_before_any_device_work():
     lib = zk.load_library()
-    vp, sz = ctypes.c_void_p, ctypes.c_size_t
     prm = zk.BfvParamsC(8, Q29, 7, 19)
-    cases = [("zkfhe_bfv_mul_monomial", "bfv_mul_monomial", [vp, ctypes.POINTER(zk.BfvParamsC), sz, vp, vp, sz, vp, vp, vp],
-              [None, ctypes.byref(prm), 1, None, None, 1, None, None, None]),
-             ("zkfhe_bfv_pack", "bfv_pack", [vp, ctypes.POINTER(zk.BfvParamsC), sz, sz, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp],
-              [None, ctypes.byref(prm), 1, 1, None, None, None, None, None, 8, None, None]),
-             ("zkfhe_bfv_cts_mul_monomial", "bfv_cts_mul_monomial", [vp, vp, sz, vp, vp], [None, None, 1, None, None]),
-             ("zkfhe_bfv_cts_pack", "bfv_cts_pack", [vp, vp, sz, vp, vp, vp], [None, None, 1, None, None, None])]
-    for symbol, name, argtypes, args in cases:
+    cases = [("zkfhe_bfv_mul_monomial", "bfv_mul_monomial", [None, ctypes.byref(prm), 1, None, None, 1, None, None, None]),
+             ("zkfhe_bfv_pack", "bfv_pack", [None, ctypes.byref(prm), 1, 1, None, None, None, None, None, 8, None, None]),
+             ("zkfhe_bfv_cts_mul_monomial", "bfv_cts_mul_monomial", [None, None, 1, None, None]),
+             ("zkfhe_bfv_cts_pack", "bfv_cts_pack", [None, None, 1, None, None, None])]
+    for symbol, name, args in cases:
         f = getattr(lib, symbol)
-        f.argtypes = argtypes
         assert f(*args) != 0, name
         assert lib.zkfhe_last_error(None).decode() == "%s: a NULL argument or a zero count" % name
     g = lib.zkfhe_bfv_pack_elements
-    g.argtypes = [ctypes.POINTER(zk.BfvParamsC), vp, vp]
     assert g(ctypes.byref(prm), None, None) != 0
     assert lib.zkfhe_last_error(None).decode() == "bfv_pack_elements: count is NULL"

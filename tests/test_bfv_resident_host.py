@@ -27,7 +27,6 @@ def test_names_are_exported_and_declared():
 def test_info_of_null_is_refused():
     lib = zk.load_library()
     f = lib.zkfhe_bfv_cts_info
-    f.argtypes = [ctypes.c_void_p] * 4
     assert f(None, None, None, None) != 0
     assert lib.zkfhe_last_error(None).decode() == "bfv_cts_info: cts is NULL"
 
@@ -37,7 +36,6 @@ def test_destroy_of_null_is_not_an_error():
     lib = zk.load_library()
     for name in ("zkfhe_bfv_plan_destroy", "zkfhe_bfv_cts_destroy"):
         f = getattr(lib, name)
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         assert f(None, None) == 0, name
 
 
@@ -46,11 +44,9 @@ def test_calls_without_a_context_are_refused_before_any_device_work():
     prm = zk.BfvParamsC(8, 536870909, 7, 1)
     out = ctypes.c_void_p(1)
     f = lib.zkfhe_bfv_cts_alloc
-    f.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
     assert f(None, ctypes.byref(prm), 1, ctypes.byref(out)) != 0 and not out.value
     assert lib.zkfhe_last_error(None).decode() == "bfv_cts_alloc: a NULL argument or a zero count"
     g = lib.zkfhe_bfv_cts_add
-    g.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     assert g(None, None, None, 0, None) != 0
     assert lib.zkfhe_last_error(None).decode() == "bfv_cts_add: a NULL argument or a zero count"
 

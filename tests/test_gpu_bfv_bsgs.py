@@ -306,10 +306,9 @@ def test_refusals(ctx):
         z1000, k1000 = np.zeros((1, 1000), np.uint64), np.zeros((2, l, 1000), np.uint64)
         call(c0=z1000, c1=z1000, bk0=k1000, bk1=k1000, hk0=k1000, hk1=k1000, d=np.zeros((2, 2, 1000), np.uint64), prm=(1000, q, t, 19))
     # NULL pointers, zero counts and counts of 2^20 at the C boundary
-    u64p, sz = ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     lib, prm = ctx.lib, zk.BfvParamsC(*params)
     fn = lib.zkfhe_bfv_linear_transform_bsgs
-    fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), sz, u64p, u64p, sz, u64p, u64p, u64p, sz, u64p, u64p, u64p, ctypes.c_int, u64p, u64p, u64p]
     p, kp, dp = z.ctypes.data_as(u64p), keys.ctypes.data_as(u64p), diag.ctypes.data_as(u64p)
     out = np.zeros((2, n), dtype=np.uint64)
     op = out.ctypes.data_as(u64p)

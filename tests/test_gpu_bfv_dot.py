@@ -265,12 +265,10 @@ def test_dot_argument_errors(ctx):
     a0, a1, b0, b1 = c0[:2], c1[:2], c0[2:], c1[2:]
     g0, g1 = np.stack([a0] * 3), np.stack([a1] * 3)   # three groups
 
-    def raw(fn, sig, prm, *args):   # the C call itself, past the wrappers' shape checks
-        ctx._bfv(fn, sig, prm, *args)
-
+    raw = ctx._call   # the C call itself, past the wrappers' shape checks
     out = [np.empty(n, dtype=np.uint64) for _ in range(2)]
-    dot = lambda prm, ng, nt, bg, bb: raw("zkfhe_bfv_dot", "nnppnppppipp", prm, ng, nt, a0, a1, bg, b0, b1, rlk0, rlk1, bb, *out)  # noqa: E731
-    plain = lambda prm, ng, nt, mg: raw("zkfhe_bfv_dot_plain", "nnppnppp", prm, ng, nt, a0, a1, mg, m[:2], *out)  # noqa: E731
+    dot = lambda prm, ng, nt, bg, bb: raw("zkfhe_bfv_dot", prm, ng, nt, a0, a1, bg, b0, b1, rlk0, rlk1, bb, *out)  # noqa: E731
+    plain = lambda prm, ng, nt, mg: raw("zkfhe_bfv_dot_plain", prm, ng, nt, a0, a1, mg, m[:2], *out)  # noqa: E731
     # a zero count, a NULL argument, bad parameters
     with pytest.raises(zk.ZkfheError, match="bfv_dot: a NULL argument or a zero count"):
         dot(params, 1, 0, 1, w)
@@ -279,8 +277,9 @@ def test_dot_argument_errors(ctx):
     with pytest.raises(zk.ZkfheError, match="bfv_dot_plain: a NULL argument or a zero count"):
         plain(params, 1, 0, 1)
     f = ctx.lib.zkfhe_bfv_dot_plain
-    f.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC)] + [ctypes.c_size_t] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 3
-    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), 1, 2, a0.ctypes.data, a1.ctypes.data, 1, None, out[0].ctypes.data, out[1].ctypes.data) != 0
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), 1, 2, a0.ctypes.data_as(u64p), a1.ctypes.data_as(u64p), 1, None,
+             out[0].ctypes.data_as(u64p), out[1].ctypes.data_as(u64p)) != 0
     assert b"bfv_dot_plain: a NULL argument or a zero count" in ctx.lib.zkfhe_last_error(ctx.h)
     with pytest.raises(zk.ZkfheError, match="bfv params"):
         dot((1000, q, t, 19), 1, 2, 1, w)

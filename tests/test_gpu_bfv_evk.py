@@ -404,8 +404,7 @@ def test_calls_refuse_and_leave_dst_alone(ctx, keysets):
             refused("bfv_cts_dot: dst must not be a source", lambda: x.dot(src, 1, k.evk, out=src), src, a)
             refused("bfv_cts_dot_plain: dst must not be a source", lambda: src.dot_plain(m[:1], 1, out=src), src, a)
         f = ctx.lib.zkfhe_bfv_cts_dot_plain   # two weight groups for three groups: the Python wrapper passes what it is given
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
-        assert f(ctx.h, x.h, 1, 2, m.ctypes.data, dst.h) != 0 and same(dst, d)
+        assert f(ctx.h, x.h, 1, 2, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dst.h) != 0 and same(dst, d)
         assert ctx.lib.zkfhe_last_error(ctx.h).decode() == "bfv_cts_dot_plain: m_groups must be 1 or n_groups"
         wide = m[:1].copy()
         wide[0, 3] = params[2] // 2 + 1   # the first value past the plaintext range
@@ -465,12 +464,11 @@ def test_create_refuses(ctx, keysets):
         assert ok.info()["elements"] == k.elements
     # the C call: *out is NULL after a refusal
     f = ctx.lib.zkfhe_bfv_evk_create
-    f.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     out = ctypes.c_void_p(1)
     g = np.array([5, 5], dtype=np.uint64)
-    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), w, None, None, 2, g.ctypes.data, two0.ctypes.data, two1.ctypes.data, ctypes.byref(out)) != 0
+    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), w, None, None, 2, *[a.ctypes.data_as(u64p) for a in (g, two0, two1)], ctypes.byref(out)) != 0
     assert out.value is None
     out = ctypes.c_void_p(1)   # one half of the relinearization key alone
-    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), w, k.rlk[0].ctypes.data, None, 0, None, None, None, ctypes.byref(out)) != 0
+    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), w, k.rlk[0].ctypes.data_as(u64p), None, 0, None, None, None, ctypes.byref(out)) != 0
     assert out.value is None and ctx.lib.zkfhe_last_error(ctx.h).decode() == "bfv_evk_create: a NULL argument or a zero count"

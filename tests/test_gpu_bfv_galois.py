@@ -307,20 +307,14 @@ def test_refusals(ctx):
     u64p = ctypes.POINTER(ctypes.c_uint64)
     prm = zk.BfvParamsC(*params)
     lib = ctx.lib
-    lib.zkfhe_bfv_encode_slots.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), ctypes.c_size_t, u64p, u64p]
-    lib.zkfhe_bfv_decode_slots.argtypes = lib.zkfhe_bfv_encode_slots.argtypes
     buf = np.zeros(n, dtype=np.uint64)
     p = buf.ctypes.data_as(u64p)
     for fn in (lib.zkfhe_bfv_encode_slots, lib.zkfhe_bfv_decode_slots):
         assert fn(ctx.h, ctypes.byref(prm), 0, p, p) != 0
         assert fn(ctx.h, ctypes.byref(prm), 1, None, p) != 0
         assert fn(ctx.h, ctypes.byref(prm), 1, p, None) != 0
-    lib.zkfhe_bfv_apply_galois.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), ctypes.c_size_t, u64p, u64p, ctypes.c_uint64,
-                                           u64p, u64p, ctypes.c_int, u64p, u64p]
     gp = gk0.ctypes.data_as(u64p)
     assert lib.zkfhe_bfv_apply_galois(ctx.h, ctypes.byref(prm), 0, p, p, 5, gp, gp, 16, p, p) != 0
     assert lib.zkfhe_bfv_apply_galois(ctx.h, ctypes.byref(prm), 1, p, p, 5, None, gp, 16, p, p) != 0
-    lib.zkfhe_bfv_slot_count.argtypes = [ctypes.POINTER(zk.BfvParamsC), ctypes.c_void_p]
     assert lib.zkfhe_bfv_slot_count(ctypes.byref(prm), None) != 0
-    lib.zkfhe_bfv_galois_element.argtypes = [ctypes.POINTER(zk.BfvParamsC), ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
     assert lib.zkfhe_bfv_galois_element(ctypes.byref(prm), 1, 0, None) != 0

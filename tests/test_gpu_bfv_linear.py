@@ -229,11 +229,8 @@ def test_refusals(ctx):
         with pytest.raises(zk.ZkfheError, match="bfv params"):
             call()
     # n = 0, n_elems = 0 and NULL pointers, at the C boundary
-    u64p, sz = ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t
-    head = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), sz, u64p, u64p, sz, u64p, u64p, u64p, ctypes.c_int]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     lib, prm = ctx.lib, zk.BfvParamsC(*params)
-    lib.zkfhe_bfv_apply_galois_many.argtypes = head + [u64p, u64p]
-    lib.zkfhe_bfv_linear_transform.argtypes = head + [u64p, u64p, u64p]
     p, kp, dp = z.ctypes.data_as(u64p), keys.ctypes.data_as(u64p), diag.ctypes.data_as(u64p)
     out = np.zeros((2, n), dtype=np.uint64)
     op = out.ctypes.data_as(u64p)

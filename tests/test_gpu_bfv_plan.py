@@ -351,15 +351,13 @@ def test_creation_refusals_in_order(ctx):
     refused(bsgs, S, ODD, gb=(5,), bk0=wide_keys, bk1=wide_keys, gg=(2 * WIDE[0],), hk0=wide_keys, hk1=wide_keys, d=wide_d, w=32, prm=WIDE)
 
     # at the C boundary: NULL pointers, zero counts, counts of 2^20, and *out after a failure
-    u64p, sz, vp = ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_void_p
+    u64p, vp = ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p
     lib, prm, bad_prm = ctx.lib, zk.BfvParamsC(*params), zk.BfvParamsC(*p1000)
     g = np.array([5, 3], dtype=np.uint64)
     gp, kp, dp = g.ctypes.data_as(u64p), keys.ctypes.data_as(u64p), d2.ctypes.data_as(u64p)
-    for name, fn, argtypes, good, counts, bits in (
-            (F, lib.zkfhe_bfv_plan_create, [sz, u64p, u64p, u64p, ctypes.c_int, u64p], [2, gp, kp, kp, 16, dp], (0,), 4),
-            (S, lib.zkfhe_bfv_plan_create_bsgs, [sz, u64p, u64p, u64p, sz, u64p, u64p, u64p, ctypes.c_int, u64p],
-             [2, gp, kp, kp, 2, gp, kp, kp, 16, dp], (0, 4), 8)):
-        fn.argtypes = [vp, ctypes.POINTER(zk.BfvParamsC)] + argtypes + [ctypes.POINTER(vp)]
+    for name, fn, good, counts, bits in (
+            (F, lib.zkfhe_bfv_plan_create, [2, gp, kp, kp, 16, dp], (0,), 4),
+            (S, lib.zkfhe_bfv_plan_create_bsgs, [2, gp, kp, kp, 2, gp, kp, kp, 16, dp], (0, 4), 8)):
 
         def create(args, p=prm):
             h = vp(0xdead0)   # whatever the caller left there
@@ -401,9 +399,8 @@ def test_apply_refusals_write_nothing(ctx):
     z = np.zeros((2, n), dtype=np.uint64)
     big = z.copy()
     big[1, 3] = q
-    u64p, vp = ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     fn = ctx.lib.zkfhe_bfv_plan_apply
-    fn.argtypes = [vp, vp, ctypes.c_size_t, u64p, u64p, u64p, u64p]
     plans = [ctx.bfv_plan(params, [5, 3], keys, keys, z, base_bits=w),
              ctx.bfv_plan_bsgs(params, [5, 3], keys, keys, [25, 3], keys, keys, np.zeros((2, 2, n), np.uint64), base_bits=w)]
     try:

@@ -111,9 +111,9 @@ def test_upload_refuses_a_word_equal_to_q(ctx, what, params, count, comp, ct, wo
     with pytest.raises(zk.ZkfheError, match="bfv_cts_upload: a ciphertext coefficient >= Q"):
         ctx.bfv_cts(params, *planes)
     f = ctx.lib.zkfhe_bfv_cts_upload   # the C call: *out is NULL
-    f.argtypes = [ctypes.c_void_p, ctypes.POINTER(zk.BfvParamsC), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     out = ctypes.c_void_p(1)
-    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), count, planes[0].ctypes.data, planes[1].ctypes.data, ctypes.byref(out)) != 0
+    assert f(ctx.h, ctypes.byref(zk.BfvParamsC(*params)), count, planes[0].ctypes.data_as(u64p), planes[1].ctypes.data_as(u64p), ctypes.byref(out)) != 0
     assert out.value is None
     # a refused store leaves the batch's old contents
     with ctx.bfv_cts(params, *src) as cts:
@@ -491,9 +491,8 @@ def test_mismatches_are_refused_and_leave_dst_alone(ctx):
         refused("bfv_cts_mul_plain: a plaintext coefficient is outside", lambda: x.mul_plain(wide, out=dst))
         refused("bfv_cts_add_plain: a plaintext coefficient is outside", lambda: x.add_plain(wide, out=dst))
         f = ctx.lib.zkfhe_bfv_cts_add_plain   # two plaintexts for three ciphertexts: the Python wrapper would refuse the shape itself
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
         mm = np.stack([m, m])
-        assert f(ctx.h, x.h, 2, mm.ctypes.data, dst.h) != 0 and same(dst, d)
+        assert f(ctx.h, x.h, 2, mm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dst.h) != 0 and same(dst, d)
         assert ctx.lib.zkfhe_last_error(ctx.h).decode() == "bfv_cts_add_plain: m_count must be 1 or the ciphertext count"
         big_key = rlk1.copy()
         big_key[-1, n - 1] = q

@@ -71,7 +71,6 @@ def test_field_random_vs_oracle(ctx):
 def test_radix29_product_on_device(ctx):
     """fq29.hip.hpp on the GPU (the field arithmetic inside the MSM kernels): k squarings in the radix-2^29 Montgomery form
     (R' = 2^261) against python integers: x -> x^(2^k) * R'^-(2^k - 1) mod q, for random, tiny and q - 1 inputs."""
-    import ctypes
     rng = np.random.default_rng(29)
     Q, n, iters = pyref.Q, 4096, 7
     xs = [int.from_bytes(rng.bytes(32), "little") % Q for _ in range(n)]
@@ -79,7 +78,6 @@ def test_radix29_product_on_device(ctx):
     mask = (1 << 64) - 1
     raw = np.array([[(v >> (64 * j)) & mask for j in range(4)] for v in xs], dtype=np.uint64)
     d, o = ctx.to_device(raw), ctx.alloc(n * 32)
-    ctx.lib.zkfhe_fq29_sqr_chain.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
     ctx._check(ctx.lib.zkfhe_fq29_sqr_chain(ctx.h, d.at(0), o.at(0), n, iters))
     got = o.download(shape=(n, 4))
     rinv = pow(pow(2, 261, Q), -1, Q)
@@ -445,8 +443,6 @@ def test_lookup_permute_matches_halo2_semantics(ctx, k):
     S = np.stack([orc.ints_to_mont(c + [123456789] * (n - u)) for c in cols])   # rows >= u hold junk: they must be ignored
     d = ctx.to_device(S)
     a, s = ctx.alloc(len(cols) * n * 32), ctx.alloc(len(cols) * n * 32)
-    vp = ctypes.c_void_p
-    ctx.lib.zkfhe_lookup_permute.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, vp, vp, ctypes.POINTER(ctypes.c_int)]
     flag = ctypes.c_int(-1)
     ctx._check(ctx.lib.zkfhe_lookup_permute(ctx.h, d.at(0), len(cols), n, u, a.at(0), s.at(0), ctypes.byref(flag)))
     assert flag.value == 0
@@ -490,8 +486,6 @@ def test_msm_sparse_terms(ctx):
     raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
     d = ctx.to_device(raw)
     out = ctx.alloc(n_slots * 64)
-    vp = ctypes.c_void_p
-    ctx.lib.zkfhe_msm_sparse.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, vp]
     assert ctx.lib.zkfhe_basis_has_multiples(B.h) == 1
     ctx._check(ctx.lib.zkfhe_msm_sparse(ctx.h, B.h, d.at(0), len(cells), n_slots, out.at(0)))
     assert np.array_equal(out.download(shape=(n_slots, 8)), want)

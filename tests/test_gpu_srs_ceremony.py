@@ -161,7 +161,6 @@ def test_check_refuses_an_srs_without_g2(ctx, files):
     with pytest.raises(zk.ZkfheError, match="srs_check: the SRS has no G2 half"):
         srs.check(SEED)
     failed = ctypes.c_uint32()
-    ctx.lib.zkfhe_srs_check.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)]
     assert ctx.lib.zkfhe_srs_check(ctx.h, None, SEED, ctypes.byref(failed)) == -1
     assert ctx.lib.zkfhe_srs_check(ctx.h, srs.h, SEED, None) == -1
     assert ctx.lib.zkfhe_last_error(ctx.h).decode().startswith("srs_check:")

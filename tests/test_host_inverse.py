@@ -81,7 +81,6 @@ def test_xyzz_batch_normalisation_on_the_host():
     import zk_fhe_amd as zk
     from oracle import pyref
     lib = zk.load_library()
-    lib.zkfhe_g1_xyzz_to_affine.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     rnd = random.Random(5)
     Q = pyref.Q
 

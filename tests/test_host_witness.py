@@ -175,7 +175,7 @@ def test_host_poly_mul_u32_is_the_integer_product():
     import numpy as np
     import zk_fhe_amd as zk
     lib = zk.load_library()
-    lib.zkfhe_host_poly_mul_u32.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_size_t] + [ctypes.c_void_p] * 2
+    u64p = ctypes.POINTER(ctypes.c_uint64)
     rng = np.random.default_rng(5)
     Q = 536870909
 
@@ -183,7 +183,7 @@ def test_host_poly_mul_u32_is_the_integer_product():
         n = len(a)
         A, B = np.array(a, dtype=np.uint64), np.array(b, dtype=np.uint64)
         lo, hi = np.zeros(2 * n - 1, dtype=np.uint64), np.zeros(2 * n - 1, dtype=np.uint64)
-        rc = lib.zkfhe_host_poly_mul_u32(A.ctypes.data, B.ctypes.data, n, lo.ctypes.data, hi.ctypes.data)
+        rc = lib.zkfhe_host_poly_mul_u32(*[x.ctypes.data_as(u64p) for x in (A, B)], n, *[x.ctypes.data_as(u64p) for x in (lo, hi)])
         return rc, [int(lo[i]) | (int(hi[i]) << 64) for i in range(2 * n - 1)]
 
     def want(a, b):

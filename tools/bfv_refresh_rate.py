@@ -80,19 +80,19 @@ def main():
         c1 = tile(rng.integers(0, q, size=(base, n), dtype=np.uint64))
         h = np.ascontiguousarray(np.broadcast_to(c1, (p,) + c1.shape))
         seed = os.urandom(32)
-        # (name, the C entry point's signature for Context._bfv, its arguments before the outputs, the number of outputs, slots)
+        # (name, the C entry point's arguments before the outputs, the number of outputs, slots)
         calls = (
-            ("refresh_share", "psnpsuupp", (sk, crs, count, c1, seed, 0, bound), 2, share_slots),
-            ("pcks_share", "pppnpsuupp", (sk, pk0_to, pk1_to, count, c1, seed, 0, bound), 2, share_slots),
-            ("decrypt_share", "pnpsuup", (sk, count, c1, seed, 0, bound), 1, share_slots),
-            ("refresh_combine", "nnsuppppp", (p, count, crs, 0, c0, h, h), 2, (("sample", zk.PROF_BFV_SAMPLE), ("combine", zk.PROF_BFV_REFRESH_COMBINE))),
-            ("pcks_combine", "nnppppp", (p, count, c0, h, h), 2, (("combine", zk.PROF_BFV_PCKS_COMBINE),)),
-            ("decrypt_combine", "nnppp", (p, count, c0, h), 1, (("combine", zk.PROF_BFV_DECRYPT_COMBINE),)),
+            ("refresh_share", (sk, crs, count, c1, seed, 0, bound), 2, share_slots),
+            ("pcks_share", (sk, pk0_to, pk1_to, count, c1, seed, 0, bound), 2, share_slots),
+            ("decrypt_share", (sk, count, c1, seed, 0, bound), 1, share_slots),
+            ("refresh_combine", (p, count, crs, 0, c0, h, h), 2, (("sample", zk.PROF_BFV_SAMPLE), ("combine", zk.PROF_BFV_REFRESH_COMBINE))),
+            ("pcks_combine", (p, count, c0, h, h), 2, (("combine", zk.PROF_BFV_PCKS_COMBINE),)),
+            ("decrypt_combine", (p, count, c0, h), 1, (("combine", zk.PROF_BFV_DECRYPT_COMBINE),)),
         )
-        for what, sig, args, n_out, slots in calls:
+        for what, args, n_out, slots in calls:
             if a.reuse_outputs:   # output arrays allocated and touched once, as a C caller with buffers of its own would
                 outs = [np.zeros((count, n), dtype=np.uint64) for _ in range(n_out)]
-                run = lambda: ctx._bfv("zkfhe_bfv_" + what, sig, prm, *args, *outs)  # noqa: E731
+                run = lambda: ctx._call("zkfhe_bfv_" + what, prm, *args, *outs)  # noqa: E731
             else:                 # the Python methods: every call allocates its outputs
                 method, margs = getattr(ctx, "bfv_" + what), PY_ARGS[what](*args)
                 run = lambda: method(prm, *margs[0], **margs[1])  # noqa: E731

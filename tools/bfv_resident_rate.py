@@ -33,7 +33,6 @@ slot 14: the same epilogue), and zkfhe_bfv_cts_mul (slot 9) against zkfhe_bfv_ct
 sets ZKFHE_EVK_WIDE_MAX=64 before the library loads, so that the digit-parallel path runs at every count measured.
 """
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -79,7 +78,6 @@ class Chain:
         self.elements = [int(g) for g in zk.bfv_slot_sum_elements(prm)]
         self.sum_keys = [key(g) for g in self.elements]
         self.sk0, self.sk1 = stack(self.sum_keys, 0), stack(self.sum_keys, 1)
-        self.u64p = ctypes.POINTER(ctypes.c_uint64)
 
     def buffers(self, count):
         """what a caller keeps between chains: three pairs of host arrays (touched), two batches"""
@@ -89,11 +87,9 @@ class Chain:
 
     def host(self, c0, c1, bufs):
         ctx, prm, count = self.ctx, self.prm, c0.shape[0]
-        ctx._bfv("zkfhe_bfv_mul_plain", "nppnppp", prm, count, c0, c1, 1, self.weight, *bufs[0])
-        f = ctx.lib.zkfhe_bfv_plan_apply
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [self.u64p] * 4
-        ctx._check(f(ctx.h, self.plan._handle(), count, *[a.ctypes.data_as(self.u64p) for a in (*bufs[0], *bufs[1])]))
-        ctx._bfv("zkfhe_bfv_slot_sum", "nppppipp", prm, count, *bufs[1], self.sk0, self.sk1, W, *bufs[2])
+        ctx._call("zkfhe_bfv_mul_plain", prm, count, c0, c1, 1, self.weight, *bufs[0])
+        ctx._call("zkfhe_bfv_plan_apply", self.plan._handle(), count, *bufs[0], *bufs[1])
+        ctx._call("zkfhe_bfv_slot_sum", prm, count, *bufs[1], self.sk0, self.sk1, W, *bufs[2])
         return bufs[2]
 
     def on_batch(self, x, rot, out):
@@ -103,8 +99,7 @@ class Chain:
         for g, (k0, k1) in zip(self.elements, self.sum_keys):
             x.apply_galois(g, k0, k1, base_bits=W, out=rot)
             x.add(rot, out=x)
-        x._call("zkfhe_bfv_cts_download", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, self.u64p, self.u64p], None, x._handle(), 0, x.n,
-                *[a.ctypes.data_as(self.u64p) for a in out])
+        self.ctx._call("zkfhe_bfv_cts_download", x._handle(), 0, x.n, *out)
         return out
 
     def batch(self, c0, c1, x, rot, out):
@@ -119,8 +114,7 @@ class Chain:
         x.mul_plain(self.weight, out=x)
         self.plan.apply_cts(self.ctx, x, out=x)
         x.slot_sum(self.evk, out=x)
-        x._call("zkfhe_bfv_cts_download", [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, self.u64p, self.u64p], None, x._handle(), 0, x.n,
-                *[a.ctypes.data_as(self.u64p) for a in out])
+        self.ctx._call("zkfhe_bfv_cts_download", x._handle(), 0, x.n, *out)
         return out
 
     def batch_evk(self, c0, c1, x, out):

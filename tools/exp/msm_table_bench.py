@@ -1,9 +1,9 @@
 """Timing of one MSM call against a basis with a digit-multiple table (k_msm_table) and against the bucket pipeline.
 usage: python tools/exp/msm_table_bench.py [log_n] [n_cols] [kind]   (kind: full | small | mixed)"""
-import importlib.util, os, sys, time
+import os, sys, time
 import numpy as np
-spec = importlib.util.spec_from_file_location("zk_fhe_amd", os.path.join(os.path.dirname(__file__), "../../zk-fhe_amd/__init__.py"))
-zk = importlib.util.module_from_spec(spec); sys.modules["zk_fhe_amd"] = zk; spec.loader.exec_module(zk)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+import zk_fhe_amd as zk
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 def limbs(v): return [(v >> (64 * i)) & (2**64 - 1) for i in range(4)]
