@@ -651,7 +651,7 @@ int zkfhe_bfv_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n
                         uint64_t *out0, uint64_t *out1);
 /* zkfhe_prof_read slots of the BFV evaluation kernels */
 #define ZKFHE_PROF_BFV_TENSOR 8            /* k_bfv_tensor */
-#define ZKFHE_PROF_BFV_RELIN 9             /* k_key_switch<false> (the relinearization) */
+#define ZKFHE_PROF_BFV_RELIN 9             /* k_key_switch on c^2 itself (the relinearization) */
 #define ZKFHE_PROF_BFV_EVAL_EPILOGUE 10    /* k_eval_epilogue */
 #define ZKFHE_PROF_BFV_ELEMENTWISE 11      /* k_bfv_sum, k_bfv_add */
 #define ZKFHE_PROF_BFV_DOT 20              /* k_bfv_dot_acc, and k_bfv_dot_fold where a pass is split into slices */
@@ -820,7 +820,7 @@ int zkfhe_bfv_galois_share(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const
                            const uint8_t party_seed[32], uint64_t g, int base_bits, uint64_t *r_out, uint64_t *a_out);
 /* zkfhe_prof_read slots of the slot and rotation kernels; the CRT epilogue of the key calls (k_rns_epilogue) counts in
  * ZKFHE_PROF_RNS_EPILOGUE */
-#define ZKFHE_PROF_BFV_GALOIS 14     /* k_key_switch<true>, k_eval_epilogue of the key switch */
+#define ZKFHE_PROF_BFV_GALOIS 14     /* k_key_switch on sigma_g(c1), k_eval_epilogue of the key switch */
 #define ZKFHE_PROF_BFV_SLOT_NTT 15   /* k_slot_ntt */
 
 /* ---- Encrypted matrix-vector products: hoisted rotations and slot-wise linear transforms (bfv_linear.hip) ----
@@ -1108,7 +1108,7 @@ int zkfhe_bfv_cts_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const int32_t *gro
  * count in the slots of their host-array calls. */
 #define ZKFHE_PROF_BFV_RESIDENT 25   /* k_cts_check, k_cts_gather, k_cts_group_sum */
 
-/* ---- Evaluation keys that stay on the device: slot sums and inner products on batches (bfv_evk.hip, bfv_resident.hip) ----
+/* ---- Evaluation keys that stay on the device: slot sums and inner products on batches (bfv_evk.hip, bfv_resident.hip, bfv_key_switch.hip) ----
  * zkfhe_bfv_cts_mul and zkfhe_bfv_cts_apply_galois take their keys as host arrays and check, upload and transform them on every
  * call.  A key set keeps one relinearization key and any number of Galois keys on the device: it is opaque and holds, for the
  * relinearization key (if any) and then for each Galois key in the order of g, the [2 l][5][N] uint32_t transform that the key
@@ -1147,8 +1147,9 @@ int zkfhe_bfv_cts_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const int32_t *gro
  * that walks the l digits one after the other: 5 workgroups for one ciphertext.  The calls above run, where l >= 2 and a chunk
  * holds at most zkfhe_bfv_evk_wide_max ciphertexts, k_key_switch_digit (one workgroup per (digit, ciphertext, prime): the digit
  * transformed and multiplied by its two key rows into partials in the workspace) and k_key_switch_fold (one workgroup per
- * (component, ciphertext, prime): the l partials summed mod p, one inverse transform).  Every partial is a canonical residue in
- * [0, p) and addition mod p is exact, so the result is bit for bit that of k_key_switch.  The bound keeps the grid of
+ * (component, ciphertext, prime): the l partials summed mod p, one inverse transform).  Both ways share the digit load and the
+ * product with the key rows, and a sum of canonical residues mod p does not depend on its order, so the result is bit for bit that
+ * of k_key_switch.  The bound keeps the grid of
  * k_key_switch_digit, 5 l workgroups per ciphertext, at or below 5/4 of the device's CU count (16 ciphertexts at l = 4 on 256 CUs)
  * and the partials within the accumulators a full chunk already needs;
  * profiles/bfv_evk.md holds the measurement behind it (for which alone the environment variable ZKFHE_EVK_WIDE_MAX, read once per
@@ -1210,8 +1211,8 @@ int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_ter
  * the call needs W", "dst must not be a source"); "the key set has no key for the Galois element G", naming the first missing
  * pack element; the coefficient >= Q checks of the host-array calls, for ciphertexts and keys.
  * Kernels.  One launch prepares every input (k_pack_prepare).  A level is a key switch that reads the digits of
- * sigma_g(e1 - x^s o1) straight from the two operands (k_pack_switch: one workgroup per (pair, prime) walking the digits; or, where
- * the key is resident, l >= 2 and the level has at most zkfhe_bfv_evk_wide_max pairs, k_pack_digit per (digit, pair, prime)
+ * sigma_g(e1 - x^s o1) straight from the two operands (k_key_switch: one workgroup per (pair, prime) walking the digits; or, where
+ * the key is resident, l >= 2 and the level has at most zkfhe_bfv_evk_wide_max pairs, k_key_switch_digit per (digit, pair, prime)
  * followed by k_key_switch_fold) and k_pack_finish: Garner over the five primes, mod Q, plus (e0 + x^s o0) + sigma_g(e0 - x^s o0)
  * on component 0 and e1 + x^s o1 on component 1, out of place between two work arrays.  A call of more leaves than a chunk holds
  * (2^21 / N ciphertexts) reduces the subtrees of leaves with equal index mod n' / C one after another and merges their roots
@@ -1232,7 +1233,7 @@ int zkfhe_bfv_cts_mul_monomial(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t k_
 int zkfhe_bfv_cts_pack(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n, const uint64_t *pos, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst);
 /* zkfhe_prof_read slot of the packing kernels: algorithmic bytes = the words read and written.  k_key_switch_fold counts in
  * ZKFHE_PROF_BFV_KEY_SWITCH_WIDE; the one key transform of the host-array call in ZKFHE_PROF_RNS_NTT */
-#define ZKFHE_PROF_BFV_PACK 27   /* k_pack_prepare, k_pack_switch, k_pack_digit, k_pack_finish, k_pack_monomial */
+#define ZKFHE_PROF_BFV_PACK 27   /* k_pack_prepare, k_key_switch and k_key_switch_digit of a level, k_pack_finish, k_pack_monomial */
 
 const char *zkfhe_version(void);
 

@@ -163,7 +163,7 @@ def test_three_parties_pack_and_open_with_one_round_of_shares(ctx):
                          ids=["K13-1x64", "K13-3x64", "K13-3x37", "P4096-1x64", "P4096-3x40", "P4096-1x600-split", "BIG-1x65-split"])
 def test_batch_pack_is_the_host_array_call(ctx, keysets, params, w, n_groups, n):
     """the levels of every case have sizes on both sides of bfv_evk_wide_max, so the key set's call takes both key-switch kernels and
-    the host-array call k_pack_switch alone; 600 inputs at N = 4096 and 65 at N = 32768 do not fit a chunk"""
+    the host-array call k_key_switch alone; 600 inputs at N = 4096 and 65 at N = 32768 do not fit a chunk"""
     n_ring = params[0]
     k = keysets(params, w)
     bound = ctx.bfv_evk_wide_max(params, w)
@@ -260,10 +260,14 @@ def test_a_level_is_at_most_three_launches_and_no_key_is_transformed(ctx, keyset
         got = all_launches(ctx, lambda: a.pack(n, k.evk, out=out))
     for slot in (zk.PROF_BFV_ELEMENTWISE, zk.PROF_BFV_GALOIS, RNS_NTT):
         assert got[slot] == 0, slot
-    assert got[PACK] + got[WIDE] <= 1 + 3 * log_n and got[WIDE] > 0
+    # k_pack_prepare, then per level one key-switch kernel and k_pack_finish; a fold for every level that goes the digit-parallel way
+    pairs = [32, 16, 8, 4, 2, 1] + [1] * (log_n - 6)   # six pack levels of the 64 leaves, then the trace on the root
+    bound = ctx.bfv_evk_wide_max(params, w)
+    assert got[PACK] == 1 + 2 * log_n
+    assert got[WIDE] == sum(1 for c in pairs if c <= bound)
     assert all(got[s] == 0 for s in range(len(got)) if s not in (PACK, WIDE))
     host = all_launches(ctx, lambda: ctx.bfv_pack(params, c0, c1, k.gk0, k.gk1, base_bits=w))
-    assert host[RNS_NTT] == 1 and host[WIDE] == 0 and host[PACK] == 1 + 2 * log_n   # the one key transform; k_pack_switch at every level
+    assert host[RNS_NTT] == 1 and host[WIDE] == 0 and host[PACK] == 1 + 2 * log_n   # the one key transform; k_key_switch at every level
     assert all(host[s] == 0 for s in range(len(host)) if s not in (PACK, RNS_NTT))
 
 

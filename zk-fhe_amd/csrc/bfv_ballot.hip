@@ -18,7 +18,7 @@
 #include <string>
 
 #include "../host/transcript.hpp"
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 

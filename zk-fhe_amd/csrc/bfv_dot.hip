@@ -14,11 +14,11 @@
 // half of the primes' product; the call refuses more terms.  Every value is a residue below p < 2^31, every product a mont_mul and
 // every sum an add_p; no step branches on or addresses by a coefficient's value.  No kernel uses scratch.
 // Each entry point is a wrapper (the host checks) around zk_bfv_dot_core, the chunk loops on operands that are each host arrays or
-// device planes and a key that is host rows or resident (DotIo of Planes and a KeySource, rns_ntt.hip.hpp); bfv_resident.hip calls
+// device planes and a key that is host rows or resident (DotIo of Planes and a KeySource, bfv_host.hpp); bfv_resident.hip calls
 // the same core on resident batches, with a key set or, for dot_plain, host plaintexts beside the device planes.
 #include <string>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 
@@ -210,15 +210,17 @@ int dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, si
   const size_t c_max = pl.c, sub = pl.sub, gc_max = pl.gc;
   const size_t a_polys = 2 * sub * c_max, b_polys = NB * (shared ? 1 : sub) * c_max;
   KeySource key = io.key;
-  const size_t ks_words = PLAIN ? 0 : wide_words(ctx, key, n, l, gc_max);
+  KeySwitch ks{log_n, l, base_bits, q};
   int *flag;
   uint64_t *in_d, *chat, *o_d;
-  uint32_t *hat, *part, *acc, *ks_part;
+  uint32_t *hat, *part, *acc;
   Arena ar;
   ar.add(flag, 1);
   if (!PLAIN) key.add(ar, n, l);
-  ZK_CK(ar.add(in_d, (a_polys + b_polys) * n).add(hat, (a_polys + b_polys) * plane).add(part, pl.slices > 1 ? pl.slices * NC * sub * plane : 0)
-            .add(acc, NC * gc_max * plane).add(chat, PLAIN ? 0 : 3 * gc_max * n).add(o_d, 2 * gc_max * n).add(ks_part, ks_words).carve(ctx));
+  ar.add(in_d, (a_polys + b_polys) * n).add(hat, (a_polys + b_polys) * plane).add(part, pl.slices > 1 ? pl.slices * NC * sub * plane : 0)
+      .add(acc, NC * gc_max * plane).add(chat, PLAIN ? 0 : 3 * gc_max * n).add(o_d, 2 * gc_max * n);
+  if (!PLAIN) ks.add(ar, ctx, key, gc_max);
+  ZK_CK(ar.carve(ctx));
   if (!PLAIN) ZK_CK(stage_keys<NP>(ctx, key, n, q, l, flag));
   for (size_t g0 = 0; g0 < n_groups; g0 += gc_max) {
     const size_t gc = std::min(gc_max, n_groups - g0);
@@ -251,10 +253,7 @@ int dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, si
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 2 * gc, log_n, q, EvEpi{}, o_d));
     } else {
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 3 * gc, log_n, q, EvEpi{.mode = EV_ROUND, .t = params->t}, chat));
-      if (ks_words)
-        ZK_CK(zk_bfv_key_switch_wide(ctx, chat + 2 * gc * n, 0, q, l, base_bits, key.hat(0), gc, log_n, ks_part, acc));
-      else
-        ZK_CK(zk_bfv_key_switch(ctx, chat + 2 * gc * n, 0, q, l, base_bits, key.hat(0), gc, log_n, acc));
+      ZK_CK(zk_bfv_key_switch(ctx, ks, SrcPlain{chat + 2 * gc * n}, key.hat(0), gc, acc));
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 2 * gc, log_n, q, EvEpi{.mode = EV_ADD, .add = chat}, o_d));
     }
     ZK_CK(io.out.out(ctx, 0, g0, gc, n, o_d));

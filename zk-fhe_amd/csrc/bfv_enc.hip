@@ -13,12 +13,12 @@
 // word w of a stream = the w-th little-endian u64 of its keystream, array position p reads word p (uniform: words 2p, 2p + 1).
 // The samplers are branch-free and address nothing by a secret value (k_bfv_sample).
 //
-// Also the host helpers that rns_ntt.hip.hpp declares for every BFV file: the parameter and range checks, the error table and the
+// Also the host helpers that bfv_host.hpp declares for every BFV file: the parameter and range checks, the error table and the
 // work arena.
 #include <cmath>
 #include <mutex>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 

@@ -7,18 +7,18 @@
 //   1. k_rns_ntt: forward transforms of a0, a1, b0, b1 (centred), one workgroup per (polynomial, prime);
 //   2. k_bfv_tensor: x0 = a0 b0, x1 = a0 b1 + a1 b0, x2 = a1 b1 pointwise, one inverse transform each;
 //   3. k_eval_epilogue (EV_ROUND): Garner into three u64 limbs, centre, c^_j = floor((2 T x_j + Q) / 2Q) mod Q;
-//   4. k_key_switch<false> (the relinearization): per (pair, prime), every digit d_i = (c^2 >> i w) & (2^w - 1) is loaded,
-//      transformed, multiplied by the transformed rlk0_i and rlk1_i and accumulated pointwise; one inverse transform per component
+//   4. the key switch of bfv_key_switch.hip on c^2 itself (SrcPlain: the relinearization): every digit d_i = (c^2 >> i w) & (2^w - 1)
+//      is transformed, multiplied by the transformed rlk0_i and rlk1_i and summed; one inverse transform per component
 //      (sum < l N 2^w Q < 2^114);
 //   5. k_eval_epilogue (EV_ADD): out_j = c^_j + sum mod Q.
 // The relinearization key is transformed once per call.  No step branches on or addresses by a coefficient's value.
-// k_eval_epilogue and k_key_switch also serve the Galois key switch of bfv_galois.hip (EV_GALOIS, k_key_switch<true>).
+// k_eval_epilogue also serves the Galois key switch of bfv_galois.hip (EV_GALOIS).
 // add / subtract, add_plain / mul_plain and mul each have one runner (zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run: the chunk
-// loop, on operands that are host arrays or device planes and a key that is host rows or resident, rns_ntt.hip.hpp).  An entry point
+// loop, on operands that are host arrays or device planes and a key that is host rows or resident, bfv_host.hpp).  An entry point
 // here is its host checks and one call of a runner on host arrays; the batch calls of bfv_resident.hip call the same runners.
 #include <cstring>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 
@@ -102,50 +102,6 @@ __global__ __launch_bounds__(NTT_THREADS) void k_bfv_tensor(const uint32_t *__re
   for (unsigned d = tid; d < n; d += NTT_THREADS) o[d] = mont_mul(lds[d], rc.scale[j], p, pinv);
 }
 
-// One workgroup per (polynomial, prime), blockIdx.x = k * NP + prime: the key switch of polynomial k of src ([c][N], CircuitInput
-// order).  For every digit i < l, d_i = (v >> i w) & (2^w - 1) of v = src (GALOIS = false: the relinearization of c^2) or
-// v = sigma_g(src) (GALOIS = true, ginv = g^-1 mod 2N) is loaded, transformed and multiplied by the transforms of key0_i and key1_i
-// (key_hat: [2 l][NP][N], the key0_i then the key1_i); the products are summed in acc[0][k][prime] and acc[1][k][prime] (each
-// thread owns its positions), which are then transformed back in place.
-template <bool GALOIS>
-__global__ __launch_bounds__(NTT_THREADS) void k_key_switch(const uint64_t *__restrict__ src, int l, int w, const uint32_t *__restrict__ key_hat,
-                                                            size_t c, int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc,
-                                                            uint32_t *__restrict__ acc, unsigned ginv, uint64_t q) {
-  extern __shared__ uint32_t lds[];
-  const unsigned j = blockIdx.x % NP;
-  const size_t k = blockIdx.x / NP;
-  const unsigned n = 1u << log_n, tid = threadIdx.x;
-  const uint32_t p = rc.p[j], pinv = rc.pinv[j];
-  const size_t plane = (size_t)NP * n;
-  const uint32_t *fw = tw + (size_t)j * 2 * NMAX, *iv = fw + NMAX;
-  uint32_t *acc0 = acc + k * plane + (size_t)j * n, *acc1 = acc0 + c * plane;
-  const uint64_t *s = src + k * n, mask = ((uint64_t)1 << w) - 1;
-  for (int i = 0; i < l; ++i) {
-    const int shift = i * w;   // < bitlen(Q - 1) <= 63
-    for (unsigned d = tid; d < n; d += NTT_THREADS) {
-      const uint64_t v = GALOIS ? auto_coeff(s, d, ginv, n, q) : s[n - 1 - d];
-      lds[d] = (uint32_t)(((v >> shift) & mask) % p);
-    }
-    __syncthreads();
-    rns_forward(lds, fw, log_n, p, pinv);
-    const uint32_t *r0 = key_hat + (size_t)i * plane + (size_t)j * n, *r1 = key_hat + (size_t)(l + i) * plane + (size_t)j * n;
-    for (unsigned d = tid; d < n; d += NTT_THREADS) {
-      const uint32_t x = lds[d], u0 = mont_mul(x, r0[d], p, pinv), u1 = mont_mul(x, r1[d], p, pinv);
-      acc0[d] = i ? add_p(acc0[d], u0, p) : u0;
-      acc1[d] = i ? add_p(acc1[d], u1, p) : u1;
-    }
-    __syncthreads();
-  }
-  for (int comp = 0; comp < 2; ++comp) {
-    uint32_t *a = comp ? acc1 : acc0;
-    for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = a[d];
-    __syncthreads();
-    rns_inverse(lds, iv, log_n, p, pinv);
-    for (unsigned d = tid; d < n; d += NTT_THREADS) a[d] = mont_mul(lds[d], rc.scale[j], p, pinv);
-    __syncthreads();
-  }
-}
-
 // One thread per coefficient of [c0 | c1] (2 N threads): acc[comp][i] (+)= sum over the count ciphertexts of src[comp][k][i] mod Q.
 // src: [2][count][N]; consecutive threads read consecutive words of each ciphertext.
 __global__ __launch_bounds__(256) void k_bfv_sum(const uint64_t *__restrict__ src, size_t count, int log_n, uint64_t q, int first,
@@ -203,23 +159,6 @@ int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, in
   return ZKFHE_OK;
 }
 
-int zk_bfv_key_switch(zkfhe_ctx *ctx, const uint64_t *src, unsigned ginv, uint64_t q, int l, int w, const uint32_t *key_hat, size_t c,
-                      int log_n, uint32_t *acc) {
-  const uint32_t *tw;
-  ZK_CK(zk_rns_tables(ctx, &tw));
-  int lds;
-  ZK_CK(ntt_lds(ctx, ginv ? (const void *)k_key_switch<true> : (const void *)k_key_switch<false>, log_n, &lds));
-  const RnsConst<NP> rc = rns_const<NP>(log_n);
-  zk_prof_begin(ctx);
-  if (ginv)
-    k_key_switch<true><<<(unsigned)(c * NP), NTT_THREADS, lds, ctx->stream>>>(src, l, w, key_hat, c, log_n, tw, rc, acc, ginv, q);
-  else
-    k_key_switch<false><<<(unsigned)(c * NP), NTT_THREADS, lds, ctx->stream>>>(src, l, w, key_hat, c, log_n, tw, rc, acc, 0, q);
-  ZK_LAUNCH_CHECK(ctx);
-  zk_prof_end(ctx, ginv ? ZKFHE_PROF_BFV_GALOIS : ZKFHE_PROF_BFV_RELIN, (double)c * NP * (l * (8.0 + 8.0 + 16.0) + 16.0) * ((size_t)1 << log_n));
-  return ZKFHE_OK;
-}
-
 namespace {
 
 // k_bfv_add over total words: out = a +/- b (b set) or a + delta m (m set; m_shared: one plaintext of N words for every polynomial)
@@ -249,21 +188,17 @@ struct MulWork {
   int *flag;
   uint64_t *in_d, *chat, *o_d;
   uint32_t *hat, *res;
-  const uint32_t *key;        // the transformed key ([2 l][5][N])
-  uint32_t *part = nullptr;   // the partials of the digit-parallel key switch ([l][2][c][5][N]), null: k_key_switch
+  const uint32_t *key;   // the transformed key ([2 l][5][N])
 };
 
 // steps 1 to 5 of the top of the file for c pairs: w.in_d = [a0 | a1 | b0 | b1] ([4 c][N]); w.o_d = [out0 | out1]
-int mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, int l, int base_bits, const MulWork &w) {
+int mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, const KeySwitch &ks, const MulWork &w) {
   const uint64_t n = prm->n, q = prm->q;
   const int log_n = bit_log2(n);
   ZK_CK(centred_hat(ctx, w.in_d, q, 4 * c, log_n, w.hat, w.flag));
   ZK_CK(launch_tensor(ctx, w.hat, c, log_n, w.res));
   ZK_CK(zk_bfv_eval_epilogue(ctx, w.res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = prm->t}, w.chat));
-  if (w.part)
-    ZK_CK(zk_bfv_key_switch_wide(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, w.key, c, log_n, w.part, w.res));
-  else
-    ZK_CK(zk_bfv_key_switch(ctx, w.chat + 2 * c * n, 0, q, l, base_bits, w.key, c, log_n, w.res));
+  ZK_CK(zk_bfv_key_switch(ctx, ks, SrcPlain{w.chat + 2 * c * n}, w.key, c, w.res));
   return zk_bfv_eval_epilogue(ctx, w.res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = w.chat}, w.o_d);
 }
 
@@ -338,13 +273,14 @@ int zk_bfv_plain_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, bool mul, size
 int zk_bfv_mul_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, const Planes &b, KeySource key, int l, int base_bits,
                    const Planes &out) {
   const uint64_t n = prm->n;
-  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n, pw = wide_words(ctx, key, n, l, chunk);
+  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n;
+  KeySwitch ks{bit_log2(n), l, base_bits, prm->q};
   MulWork w;
   Arena ar;
   ar.add(w.flag, 1);
   key.add(ar, n, l);
   ar.add(w.in_d, 4 * cw).add(w.hat, 4 * cw * NP).add(w.res, 3 * cw * NP).add(w.chat, 3 * cw).add(w.o_d, 2 * cw);
-  if (pw) ar.add(w.part, pw);
+  ks.add(ar, ctx, key, chunk);
   ZK_CK(ar.carve(ctx));
   ZK_CK(stage_keys<NP>(ctx, key, n, prm->q, l, w.flag));
   w.key = key.hat(0);
@@ -352,7 +288,7 @@ int zk_bfv_mul_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, co
   for (size_t lo = 0; lo < count; lo += chunk) {
     const size_t c = std::min(chunk, count - lo);
     for (int i = 0; i < 4; ++i) ZK_CK(src[i / 2]->in(ctx, i % 2, lo, c, n, w.in_d + i * c * n));   // the 4 c transforms want them contiguous
-    ZK_CK(mul_core(ctx, prm, c, l, base_bits, w));
+    ZK_CK(mul_core(ctx, prm, c, ks, w));
     ZK_CK(out.out(ctx, 0, lo, c, n, w.o_d));
     ZK_CK(out.out(ctx, 1, lo, c, n, w.o_d + c * n));
   }

@@ -3,10 +3,10 @@
 //
 // sigma_g(m)(x) = m(x^g) mod (x^N + 1) for odd g < 2N moves degree i to i g mod 2N, negated and placed at i g - N past N.  Read
 // backwards, degree d of sigma_g(v) is degree j = d g^-1 mod 2N of v if j < N, else minus degree j - N (auto_coeff): a gather whose
-// addresses depend on g (public) and never on a coefficient's value.  The key switch is the relinearization's (bfv_eval.hip):
-//   k_key_switch<true>         per (ciphertext, prime), every digit d_i = (sigma_g(c1) >> i w) & (2^w - 1) is transformed with the
-//                              five primes, multiplied by the transformed gk0_i and gk1_i and accumulated; one inverse transform per
-//                              component (sum < l N 2^w Q < 2^116)
+// addresses depend on g (public) and never on a coefficient's value.  The key switch is the relinearization's (bfv_key_switch.hip):
+//   k_key_switch (SrcGalois)   every digit d_i = (sigma_g(c1) >> i w) & (2^w - 1) is transformed with the five primes, multiplied
+//                              by the transformed gk0_i and gk1_i and summed; one inverse transform per component
+//                              (sum < l N 2^w Q < 2^116)
 //   k_eval_epilogue EV_GALOIS  Garner over the five primes, x mod Q, + sigma_g(c0) on component 0, + x_in when set (slot_sum's
 //                              x <- x + apply_galois(x), fused: the same sums mod Q as zkfhe_bfv_add)
 // apply_galois and slot_sum are one chunk loop, zk_bfv_galois_run: `steps` key switches per chunk on device buffers, each added to
@@ -21,7 +21,7 @@
 // exponent (slot p = row N/2 + j is the evaluation at zeta^((-1)^row 5^j)).  No kernel uses scratch.
 #include <string>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 
@@ -190,16 +190,12 @@ int galois_key(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *s
 }
 
 // one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
-// part: the partials of the digit-parallel key switch ([l][2][c][5][N]); null: k_key_switch<true>
-int galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, int log_n, uint64_t q, uint64_t g, int l, int w, const uint32_t *key_hat,
-                bool accumulate, uint32_t *acc, uint64_t *out_d, uint32_t *part) {
-  const unsigned ginv = galois_inv(g, (uint64_t)1 << log_n);
-  if (part)
-    ZK_CK(zk_bfv_key_switch_wide(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, part, acc));
-  else
-    ZK_CK(zk_bfv_key_switch(ctx, x_d + (c << log_n), ginv, q, l, w, key_hat, c, log_n, acc));
+int galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, const KeySwitch &ks, uint64_t g, const uint32_t *key_hat, bool accumulate,
+                uint32_t *acc, uint64_t *out_d) {
+  const unsigned ginv = galois_inv(g, (uint64_t)1 << ks.log_n);
+  ZK_CK(zk_bfv_key_switch(ctx, ks, SrcGalois{x_d + (c << ks.log_n), ginv}, key_hat, c, acc));
   const EvEpi epi{.mode = EV_GALOIS, .add = accumulate ? x_d : nullptr, .poly = x_d, .ginv = ginv, .c = c};
-  return zk_bfv_eval_epilogue(ctx, acc, 2 * c, log_n, q, epi, out_d);
+  return zk_bfv_eval_epilogue(ctx, acc, 2 * c, ks.log_n, ks.q, epi, out_d);
 }
 
 }  // namespace
@@ -215,15 +211,16 @@ int zk_bfv_galois_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count,
                       int l, int base_bits, bool accumulate, const Planes &out) {
   const uint64_t n = prm->n, q = prm->q;
   const int log_n = bit_log2(n);
-  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n, pw = wide_words(ctx, key, n, l, chunk);
+  const size_t chunk = std::min<size_t>(count, chunk_polys(n)), cw = chunk * n;
+  KeySwitch ks{log_n, l, base_bits, q};
   int *flag = nullptr;
   uint64_t *x_d, *y_d;
-  uint32_t *acc, *part = nullptr;
+  uint32_t *acc;
   Arena ar;
   if (!key.resident()) ar.add(flag, 1);   // of the key transform
   key.add(ar, n, l);
   ar.add(x_d, 2 * cw).add(y_d, 2 * cw).add(acc, 2 * cw * NP);
-  if (pw) ar.add(part, pw);
+  ks.add(ar, ctx, key, chunk);
   ZK_CK(ar.carve(ctx));
   ZK_CK(stage_keys<NP>(ctx, key, n, q, l, flag));
   for (size_t lo = 0; lo < count; lo += chunk) {
@@ -232,7 +229,7 @@ int zk_bfv_galois_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count,
     ZK_CK(a.in(ctx, 0, lo, c, n, x));   // a key switch reads [c0 | c1] of the chunk
     ZK_CK(a.in(ctx, 1, lo, c, n, x + c * n));
     for (size_t k = 0; k < steps; ++k) {   // y = apply_galois(x, g_k) (+ x), then the two change places
-      ZK_CK(galois_core(ctx, x, c, log_n, q, gs[k], l, base_bits, key.hat(k), accumulate, acc, y, part));
+      ZK_CK(galois_core(ctx, x, c, ks, gs[k], key.hat(k), accumulate, acc, y));
       std::swap(x, y);
     }
     ZK_CK(out.out(ctx, 0, lo, c, n, x));

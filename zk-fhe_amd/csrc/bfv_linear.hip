@@ -26,10 +26,10 @@
 // and transformed: struct zkfhe_bfv_plan) and a run half (the ciphertext check and the chunk loop, from that struct alone).  The
 // host-array calls prepare into the context's work arena and run; zkfhe_bfv_plan_create* prepare into allocations of the plan's own,
 // and zkfhe_bfv_plan_apply is the run half.  The run half takes its ciphertexts from host arrays or, for the resident batches of
-// bfv_resident.hip, from device planes (zk_bfv_plan_run_dev): only the copies around a chunk differ (Planes, rns_ntt.hip.hpp).
+// bfv_resident.hip, from device planes (zk_bfv_plan_run_dev): only the copies around a chunk differ (Planes, bfv_host.hpp).
 #include <string>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(ACC_THREADS) void k_bsgs_inner(const uint32_t *__re
 }
 
 // One workgroup per (polynomial, prime) of res ([polys][NP][N]): the inverse transform in place, times scale[prime].  Launched through
-// zk_rns_intt (rns_ntt.hip.hpp), which bfv_dot.hip calls too.
+// zk_rns_intt (bfv_host.hpp), which bfv_dot.hip calls too.
 __global__ __launch_bounds__(NTT_THREADS) void k_rns_intt(uint32_t *__restrict__ res, int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc) {
   extern __shared__ uint32_t lds[];
   const unsigned j = blockIdx.x % NP, n = 1u << log_n, tid = threadIdx.x;

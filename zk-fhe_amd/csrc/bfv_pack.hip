@@ -7,11 +7,9 @@
 // k (public) only.  v nu with nu = N^-1 mod Q is log2(N) exact halvings mod the odd Q (v even: v / 2, else (v + Q) / 2), each the
 // canonical residue of v 2^-1, so the result is the canonical residue of v nu.
 //   k_pack_prepare   one launch: w_(group, i) = nu x^(2N - pos) a_(group, i) for the leaves of the launch, zeros for the padding
-//   k_pack_switch    the shape of k_key_switch<true> (bfv_eval.hip): one workgroup per (pair, prime) walks the digits of
-//                    sigma_g(e1 - x^s o1), read straight from the two operands (pack_src; no odd operand: sigma_g(e1), a trace level)
-//   k_pack_digit     the shape of k_key_switch_digit (bfv_evk.hip): one workgroup per (digit, pair, prime) writing partials, summed by
-//                    k_key_switch_fold (zk_bfv_key_switch_fold); where the key is resident and the level has at most zk_bfv_wide_max
-//                    pairs
+//   k_key_switch     the key switch of bfv_key_switch.hip on the digits of sigma_g(e1 - x^s o1), read straight from the two operands
+//                    (SrcPack; no odd operand: sigma_g(e1), a trace level); digit-parallel (k_key_switch_digit, k_key_switch_fold)
+//                    where the key is resident and the level has at most zk_bfv_wide_max pairs
 //   k_pack_finish    Garner over the five primes, x mod Q, as k_eval_epilogue EV_GALOIS; the same thread adds (e0 + x^s o0) +
 //                    sigma_g(e0 - x^s o0) on component 0 and e1 + x^s o1 on component 1.  Out of place: a level reads sigma-permuted
 //                    positions of its operands, so levels go back and forth between two work arrays.
@@ -25,37 +23,13 @@
 // coefficient's value.
 #include <string>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 
 namespace {
 
 constexpr int NP = NP_MAX;
-
-// degree d of x^k v for k < 2N, v one polynomial in CircuitInput order
-__device__ __forceinline__ uint64_t mono_coeff(const uint64_t *__restrict__ v, unsigned d, unsigned k, unsigned n, uint64_t q) {
-  const unsigned j = (d + 2 * n - k) & (2 * n - 1);
-  const uint64_t x = v[n - 1 - (j & (n - 1))];
-  return j >= n && x ? q - x : x;
-}
-
-// degree d of sigma_g(e - x^s o), or of sigma_g(e) where o is null (auto_coeff of the difference; ginv = g^-1 mod 2N, s < N)
-__device__ __forceinline__ uint64_t pack_src(const uint64_t *__restrict__ e, const uint64_t *__restrict__ o, unsigned d, unsigned ginv, unsigned s,
-                                             unsigned n, uint64_t q) {
-  const unsigned j = (d * ginv) & (2 * n - 1), jj = j & (n - 1);   // d ginv < 2^15 2^16
-  uint64_t x = e[n - 1 - jj];
-  if (o) x = sub_q(x, mono_coeff(o, jj, s, n, q), q);
-  return j >= n && x ? q - x : x;
-}
-
-// The operands of a level: pair p = (group p / h, i = p % h) reads polynomial (p / h) gstride + i of e[comp] and of o[comp]
-// (o[comp] null: a trace level, no odd operand)
-struct PackOps {
-  const uint64_t *e[2], *o[2];
-  size_t h, gstride;
-  __device__ __forceinline__ size_t at(size_t p) const { return (p / h) * gstride + p % h; }
-};
 
 // One thread per coefficient of out ([2][groups m][N]): leaf j < m of group grp is input leaf0 + j leaf_stride of that group, read
 // at polynomial grp src_gstride + src_off + j src_jstride of src[comp]; an input past n is padding.  pos: [groups][n] or null.
@@ -75,67 +49,6 @@ __global__ __launch_bounds__(256) void k_pack_prepare(const uint64_t *__restrict
     for (int i = 0; i < log_n; ++i) v = (v >> 1) + ((v & 1) ? (q >> 1) + 1 : 0);   // v / 2 mod the odd q: (v + q) / 2 for an odd v
   }
   (comp ? out1 : out0)[poly * n + (n - 1 - d)] = v;
-}
-
-// blockIdx.x = pair * NP + prime; acc: [2][c][NP][N] as k_key_switch leaves it
-__global__ __launch_bounds__(NTT_THREADS) void k_pack_switch(PackOps op, unsigned s, int l, int w, const uint32_t *__restrict__ key_hat, size_t c,
-                                                             int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc,
-                                                             uint32_t *__restrict__ acc, unsigned ginv, uint64_t q) {
-  extern __shared__ uint32_t lds[];
-  const unsigned j = blockIdx.x % NP;
-  const size_t k = blockIdx.x / NP;
-  const unsigned n = 1u << log_n, tid = threadIdx.x;
-  const uint32_t p = rc.p[j], pinv = rc.pinv[j];
-  const size_t plane = (size_t)NP * n;
-  const uint32_t *fw = tw + (size_t)j * 2 * NMAX, *iv = fw + NMAX;
-  uint32_t *acc0 = acc + k * plane + (size_t)j * n, *acc1 = acc0 + c * plane;
-  const size_t at = op.at(k);
-  const uint64_t *e = op.e[1] + at * n, *o = op.o[1] ? op.o[1] + at * n : nullptr, mask = ((uint64_t)1 << w) - 1;
-  for (int i = 0; i < l; ++i) {
-    const int shift = i * w;   // < bitlen(Q - 1) <= 63
-    for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = (uint32_t)(((pack_src(e, o, d, ginv, s, n, q) >> shift) & mask) % p);
-    __syncthreads();
-    rns_forward(lds, fw, log_n, p, pinv);
-    const uint32_t *r0 = key_hat + (size_t)i * plane + (size_t)j * n, *r1 = key_hat + (size_t)(l + i) * plane + (size_t)j * n;
-    for (unsigned d = tid; d < n; d += NTT_THREADS) {
-      const uint32_t x = lds[d], u0 = mont_mul(x, r0[d], p, pinv), u1 = mont_mul(x, r1[d], p, pinv);
-      acc0[d] = i ? add_p(acc0[d], u0, p) : u0;
-      acc1[d] = i ? add_p(acc1[d], u1, p) : u1;
-    }
-    __syncthreads();
-  }
-  for (int comp = 0; comp < 2; ++comp) {
-    uint32_t *a = comp ? acc1 : acc0;
-    for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = a[d];
-    __syncthreads();
-    rns_inverse(lds, iv, log_n, p, pinv);
-    for (unsigned d = tid; d < n; d += NTT_THREADS) a[d] = mont_mul(lds[d], rc.scale[j], p, pinv);
-    __syncthreads();
-  }
-}
-
-// blockIdx.x = (digit * c + pair) * NP + prime; part: [l][2][c][NP][N], what k_key_switch_fold reads
-__global__ __launch_bounds__(NTT_THREADS) void k_pack_digit(PackOps op, unsigned s, int l, int w, const uint32_t *__restrict__ key_hat, size_t c,
-                                                            int log_n, const uint32_t *__restrict__ tw, RnsConst<NP> rc,
-                                                            uint32_t *__restrict__ part, unsigned ginv, uint64_t q) {
-  extern __shared__ uint32_t lds[];
-  const unsigned j = blockIdx.x % NP;
-  const size_t ik = blockIdx.x / NP, i = ik / c, k = ik % c;
-  const unsigned n = 1u << log_n, tid = threadIdx.x;
-  const uint32_t p = rc.p[j], pinv = rc.pinv[j];
-  const size_t plane = (size_t)NP * n, at = op.at(k);
-  const uint64_t *e = op.e[1] + at * n, *o = op.o[1] ? op.o[1] + at * n : nullptr, mask = ((uint64_t)1 << w) - 1;
-  const int shift = (int)i * w;   // < bitlen(Q - 1) <= 63
-  for (unsigned d = tid; d < n; d += NTT_THREADS) lds[d] = (uint32_t)(((pack_src(e, o, d, ginv, s, n, q) >> shift) & mask) % p);
-  __syncthreads();
-  rns_forward(lds, tw + (size_t)j * 2 * NMAX, log_n, p, pinv);
-  const uint32_t *r0 = key_hat + i * plane + (size_t)j * n, *r1 = key_hat + ((size_t)l + i) * plane + (size_t)j * n;
-  uint32_t *o0 = part + ((i * 2) * c + k) * plane + (size_t)j * n, *o1 = o0 + c * plane;
-  for (unsigned d = tid; d < n; d += NTT_THREADS) {
-    const uint32_t x = lds[d];
-    o0[d] = mont_mul(x, r0[d], p, pinv);
-    o1[d] = mont_mul(x, r1[d], p, pinv);
-  }
 }
 
 // One thread per coefficient of res ([2][c][NP][N], total = 2 c N): pair k of component comp goes to polynomial k of out[comp]
@@ -170,8 +83,6 @@ __global__ __launch_bounds__(256) void k_pack_monomial(const uint64_t *__restric
 
 // ------------------------------------------------------------------------------------------------------------------ host side
 
-int refuse(zkfhe_ctx *ctx, const char *fn, const std::string &what) { return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": " + what); }
-
 unsigned bitrev(unsigned k, int bits) {
   unsigned r = 0;
   for (int i = 0; i < bits; ++i) r |= ((k >> i) & 1) << (bits - 1 - i);
@@ -180,40 +91,22 @@ unsigned bitrev(unsigned k, int bits) {
 
 // what a level needs beside its operands
 struct PackCtx {
-  int log_n, l, w;
-  uint64_t q;
+  KeySwitch ks;
   const KeySource *key;
-  uint32_t *acc, *part;   // part null: every level takes k_pack_switch
-  size_t wide_max;
+  uint32_t *acc;
 };
 
 // level lv (pack: op.o set; trace: null) over c pairs into out0, out1 ([c][N] each)
 int pack_level(zkfhe_ctx *ctx, const PackCtx &pc, int lv, const PackOps &op, size_t c, uint64_t *out0, uint64_t *out1) {
-  const int log_n = pc.log_n, l = pc.l;
+  const int log_n = pc.ks.log_n;
   const uint64_t n = (uint64_t)1 << log_n;
   const unsigned s = (unsigned)(n >> lv), ginv = (unsigned)pow_mod(((uint64_t)1 << lv) + 1, n - 1, 2 * n);   // the units mod 2N have order N
-  const uint32_t *key_hat = pc.key->hat(lv - 1), *tw;
-  ZK_CK(zk_rns_tables(ctx, &tw));
-  const RnsConst<NP> rc = rns_const<NP>(log_n);
-  const double words = (double)c * NP * n, src = op.o[1] ? 16.0 : 8.0;
-  int lds;
-  if (pc.part && c <= pc.wide_max) {
-    ZK_CK(ntt_lds(ctx, (const void *)k_pack_digit, log_n, &lds));
-    zk_prof_begin(ctx);
-    k_pack_digit<<<(unsigned)(c * NP * l), NTT_THREADS, lds, ctx->stream>>>(op, s, l, pc.w, key_hat, c, log_n, tw, rc, pc.part, ginv, pc.q);
-    ZK_LAUNCH_CHECK(ctx);
-    zk_prof_end(ctx, ZKFHE_PROF_BFV_PACK, words * l * (src + 8.0 + 8.0));
-    ZK_CK(zk_bfv_key_switch_fold(ctx, pc.part, l, c, log_n, pc.acc));
-  } else {
-    ZK_CK(ntt_lds(ctx, (const void *)k_pack_switch, log_n, &lds));
-    zk_prof_begin(ctx);
-    k_pack_switch<<<(unsigned)(c * NP), NTT_THREADS, lds, ctx->stream>>>(op, s, l, pc.w, key_hat, c, log_n, tw, rc, pc.acc, ginv, pc.q);
-    ZK_LAUNCH_CHECK(ctx);
-    zk_prof_end(ctx, ZKFHE_PROF_BFV_PACK, words * (l * (src + 8.0 + 16.0) + 16.0));
-  }
+  const SrcPack sp{op, s, ginv};
+  const double src = sp.bytes();
+  ZK_CK(zk_bfv_key_switch(ctx, pc.ks, sp, pc.key->hat(lv - 1), c, pc.acc));
   const size_t total = 2 * c * n;
   zk_prof_begin(ctx);
-  k_pack_finish<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(pc.acc, op, s, c, total, log_n, pc.q, crt5_const(), ginv, out0, out1);
+  k_pack_finish<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(pc.acc, op, s, c, total, log_n, pc.ks.q, crt5_const(), ginv, out0, out1);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_PACK, (double)total * (NP * 4 + 8 + src) + (double)c * n * src);
   return ZKFHE_OK;
@@ -272,7 +165,7 @@ int zk_bfv_pack_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t n_groups
   const int log_c = bit_log2(C), depth = L - log_c;   // R = 2^depth subtrees per group
   const size_t held = gb * C, pairs = std::max(held / 2, gb), plane = held * N;
   const size_t stage_polys = split ? C : gb * n;
-  PackCtx pc{log_n, l, base_bits, q, &key, nullptr, nullptr, key.resident() ? zk_bfv_wide_max(ctx, N, l) : 0};
+  PackCtx pc{{log_n, l, base_bits, q}, &key, nullptr};
   int *flag = nullptr;
   uint64_t *stage = nullptr, *pos_d = nullptr, *stack = nullptr;
   PingPong w;
@@ -283,7 +176,7 @@ int zk_bfv_pack_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t n_groups
   if (!a.dev) ar.add(stage, 2 * stage_polys * N);
   if (pos) ar.add(pos_d, gb * n);
   ar.add(w.buf[0], 2 * plane).add(w.buf[1], 2 * plane).add(pc.acc, 2 * pairs * NP * N);
-  if (pc.wide_max) ar.add(pc.part, wide_part_words(N, l, std::min(pc.wide_max, pairs)));
+  pc.ks.add(ar, ctx, key, pairs, true);   // the levels halve: each decides for itself
   if (split) ar.add(stack, (size_t)(depth + 2) * 2 * N);
   ZK_CK(ar.carve(ctx));
   ZK_CK(stage_keys<NP>(ctx, key, N, q, l, flag));

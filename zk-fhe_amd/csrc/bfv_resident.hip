@@ -7,7 +7,7 @@
 // host-array call computed mod Q from residues below Q; select, sum and box_tally copy or add residues mod Q.  So no call on a batch
 // runs a range pass over ciphertexts: only the host arrays of a call (plaintexts, keys, indices, groups) are checked, on the host.
 //
-// An evaluation call here is its argument checks and one call of the runner of the host-array call (rns_ntt.hip.hpp:
+// An evaluation call here is its argument checks and one call of the runner of the host-array call (bfv_host.hpp:
 // zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run, zk_bfv_galois_run, zk_bfv_dot_core, zk_bfv_plan_run_dev, zk_bfv_monomial_run,
 // zk_bfv_pack_run) on the batch's planes:
 // one chunk loop per operation, so the chunk rule, the kernels, their order and their profiling slots are those of that call.  A
@@ -24,7 +24,7 @@
 #include <cstring>
 #include <string>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 
@@ -95,8 +95,6 @@ struct zkfhe_bfv_cts {
 };
 
 namespace {
-
-int refuse(zkfhe_ctx *ctx, const char *fn, const std::string &what) { return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(fn) + ": " + what); }
 
 bool same_params(const zkfhe_bfv_params &a, const zkfhe_bfv_params &b) { return a.n == b.n && a.q == b.q && a.t == b.t && a.b == b.b; }
 

@@ -17,7 +17,7 @@
 // Randomness: the ChaCha20 streams and samplers of bfv_enc.hip, with the domains of zkfhe.h (Domain of rns_ntt.hip.hpp).
 #include <string>
 
-#include "rns_ntt.hip.hpp"
+#include "bfv_host.hpp"
 
 using namespace zkrns;
 

@@ -45,14 +45,14 @@ struct zkfhe_ctx {
   hipEvent_t pe0 = nullptr, pe1 = nullptr;
   hipEvent_t wait_ev = nullptr;  // hipEventBlockingSync: host waits sleep instead of spinning (zk_wait)
   // [2] = k_msm_table of a call of a few columns, [3] = k_g1_decompress, [4] = k_msm_segmented (verify.hip),
-  // [5] = k_bfv_sample, [6] = k_rns_ntt, [7] = k_rns_epilogue (bfv_enc.hip), [8] = k_bfv_tensor, [9] = k_key_switch<false>,
+  // [5] = k_bfv_sample, [6] = k_rns_ntt, [7] = k_rns_epilogue (bfv_enc.hip), [8] = k_bfv_tensor, [9] = k_key_switch of the relinearization (bfv_key_switch.hip),
   // [10] = k_eval_epilogue, [11] = k_bfv_sum / k_bfv_add (bfv_eval.hip), [12] = k_bfv_share_sum, [13] = k_bfv_decrypt_combine
-  // (bfv_threshold.hip), [14] = k_key_switch<true> / k_eval_epilogue of the Galois calls, [15] = k_slot_ntt (bfv_galois.hip),
+  // (bfv_threshold.hip), [14] = k_key_switch / k_eval_epilogue of the Galois calls, [15] = k_slot_ntt (bfv_galois.hip),
   // [16] = k_hoist, [17] = k_linear_acc, [18] = k_bsgs_inner, [19] = k_linear_acc<ACC_GIANT> (bfv_linear.hip),
   // [20] = k_bfv_dot_acc / k_bfv_dot_fold (bfv_dot.hip), [21] = k_bfv_pcks_combine, [22] = k_bfv_refresh_combine (bfv_refresh.hip),
   // [23] = k_g1_fft_shared / k_g1_fft_window (g1_fft.hip), [24] = k_ballot_unpack / k_ballot_sum / k_ballot_totals (bfv_ballot.hip),
-  // [25] = k_cts_check / k_cts_gather / k_cts_group_sum (bfv_resident.hip), [26] = k_key_switch_digit / k_key_switch_fold (bfv_evk.hip),
-  // [27] = k_pack_prepare / k_pack_switch / k_pack_digit / k_pack_finish / k_pack_monomial (bfv_pack.hip)
+  // [25] = k_cts_check / k_cts_gather / k_cts_group_sum (bfv_resident.hip), [26] = k_key_switch_digit of the relinearization and the Galois calls / every k_key_switch_fold (bfv_key_switch.hip),
+  // [27] = k_pack_prepare / k_pack_finish / k_pack_monomial (bfv_pack.hip) and the k_key_switch / k_key_switch_digit of a pack level
   static constexpr int PROF_SLOTS = 28;
   double prof_ms[PROF_SLOTS] = {}, prof_bytes[PROF_SLOTS] = {}, prof_ops[PROF_SLOTS] = {};
   uint64_t prof_launches[PROF_SLOTS] = {};
@@ -79,7 +79,7 @@ struct zkfhe_ctx {
   // per proof, and when the context is created (the calls made on a context before its first proof).
   bool throughput = false;
   unsigned *tickets = nullptr;   // zeroed counters: "last workgroup done" tickets of the table-path MSM, one per column (self-resetting)
-  // the BFV calls (rns_ntt.hip.hpp): the RNS twiddle tables (built on first use) and a grow-only work arena
+  // the BFV calls (rns_ntt.hip.hpp, bfv_host.hpp): the RNS twiddle tables (built on first use) and a grow-only work arena
   uint32_t *bfv_tw = nullptr;
   void *bfv_work = nullptr;
   size_t bfv_work_sz = 0;
