@@ -1175,6 +1175,68 @@ int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_ter
  * with a key set launches counts in the slots of its host-array call; no such call launches a key transform. */
 #define ZKFHE_PROF_BFV_KEY_SWITCH_WIDE 26   /* k_key_switch_digit, k_key_switch_fold */
 
+/* ---- Evaluation keys modulo Q P: hybrid key switching (bfv_hybrid.hip, bfv_evk.hip) ----
+ * The key switch of the sections above adds the key errors times the digits, about l N 2^w B of noise.  A hybrid key set
+ * (Gentry-Halevi-Smart) keeps its keys modulo Q P for a special modulus P that no ciphertext ever sees, scales the gadget by P and
+ * divides the sum over the digits by P, with rounding, before it is added: the added noise is at most
+ * ceil(l N (2^w - 1) B / P) + (N + 1) / 2 for a ternary key.  Hybrid keys are a property of a resident key set: a set made by
+ * zkfhe_bfv_evk_create_hybrid is taken by zkfhe_bfv_cts_mul_evk, zkfhe_bfv_cts_apply_galois_evk, zkfhe_bfv_cts_slot_sum,
+ * zkfhe_bfv_cts_dot and zkfhe_bfv_cts_pack with their signatures, refusals and alias rules unchanged.
+ * Special modulus: 2 <= P < 2^63, gcd(P, Q) = 1 and l N (2^w - 1) (Q P - 1) <= floor(P5 / 2), with l = zkfhe_bfv_relin_digits(w) and
+ * P5 the product of the five RNS primes (2^151.2); P need not be prime.  zkfhe_bfv_hybrid_max_p (host only) returns the largest P
+ * below 2^63 that meets the bound; it ignores the gcd condition and is never below 2^34 for admissible parameters.
+ * A hybrid key has rows K0_i, K1_i, i < l, each a polynomial of integers in [0, Q P).  It is passed as two planes of [l][N] words
+ * each, in the conventions of the ordinary keys: the q-plane K mod Q (coefficients below Q) and the p-plane K mod P (coefficients
+ * below P); K is the unique integer below Q P with those two residues.
+ * Hybrid key switch of a source polynomial v (residues in [0, Q), exactly what the ordinary key switch decomposes):
+ *   d_i = (v >> i w) & (2^w - 1);  X_j = sum_i d_i Kj_i exactly over Z in Z[x]/(x^N + 1), j = 0, 1;
+ *   r_j = floor((2 X_j + P) / 2P) mod Q coefficient-wise: to nearest, ties upward, a true floor for negative X_j.
+ * Wherever the definition of a call says sum_i d_i key0_i and sum_i d_i key1_i mod Q, a hybrid set puts r_0 and r_1; every other
+ * word of the definitions of mul, dot, apply_galois, slot_sum and pack stands.
+ * Keys (w = base_bits; s ternary, lifted to {-1, 0, 1}; e_i the centred error integer of the error sampler, the same integer in
+ * both planes, which needs 2 B < Q: "...: B must be below Q / 2" otherwise):
+ *   relinearization key   q-plane  K0_i = -(aQ_i s + e_i) + (P mod Q) 2^(i w) s^2 mod Q,  K1_i = aQ_i
+ *                         p-plane  K0_i = -(aP_i s + e_i) mod P,                          K1_i = aP_i
+ *     aQ_i, e_i: the a_i, e_i of zkfhe_bfv_relin_keygen (domains 7 and 8, index i); aP_i: ChaCha20 domain 23, index i, the uniform
+ *     sampler with P in place of Q
+ *   Galois key for g      the same with sigma_g(s) in place of s^2; aQ_i, e_i from domains 14 and 15, index g 64 + i; aP_i from
+ *     domain 24 with the same index.  As in zkfhe_bfv_galois_share, the a come from crs_seed and the e from party_seed;
+ *     zkfhe_bfv_galois_keygen_hybrid is the share with crs_seed = party_seed = seed, bit for bit.
+ * Domains 1 to 22 keep their meaning; the new ones are 23 (aP_i of the relinearization key) and 24 (aP_i of a Galois key).
+ * A committee's hybrid Galois key is formed from the planes separately: gk0_q = zkfhe_bfv_share_aggregate of the r_q shares as
+ * today, gk0_p = the same call on the r_p shares under parameters whose q is P (the parameter check then asks 2 <= T < P and
+ * 1 <= B < min(P, 1024) of them, which T = 2, B = 1 meet for every P >= 3; the sum does not read T or B); gk1_q = a_q, gk1_p = a_p.
+ * zkfhe_bfv_evk_create_hybrid: the arguments of zkfhe_bfv_evk_create with P and a p-plane beside every q-plane.  The words of a
+ * hybrid set have the layout of an ordinary one ([keys][2 l][5][N]: the transform of K mod p_j, formed from the planes by Garner,
+ * t = (kp - kq) Q^-1 mod P, K = kq + Q t), so zkfhe_bfv_evk_bytes holds for both and zkfhe_bfv_evk_info is unchanged.
+ * zkfhe_bfv_evk_special_modulus gives P, and 1 for an ordinary set.  Refusals: ZKFHE_EINVAL with a message "bfv_evk_create_hybrid:
+ * ..." (the key generators: "bfv_relin_keygen_hybrid: ...", "bfv_galois_keygen_hybrid: ...", "bfv_galois_share_hybrid: ..."), in
+ * this order and before any device work: a NULL argument or nothing to hold, as zkfhe_bfv_evk_create; bad parameters or base_bits;
+ * "... P must satisfy 2 <= P < 2^63"; "... P and Q must be coprime"; "... P is above the limit L of zkfhe_bfv_hybrid_max_p"; the
+ * checks on g of the ordinary call; a q-plane word >= Q (the texts of zkfhe_bfv_evk_create); a p-plane word >= P ("... a
+ * relinearization-key p-plane coefficient is not below P", "... a Galois-key p-plane coefficient is not below P").
+ * On the device the key switch kernels are those of an ordinary set: the sum X_j is at most l N (2^w - 1) (Q P - 1) <= P5 / 2 in
+ * size, so the five-prime CRT recovers it, and the epilogues of the five calls (k_eval_epilogue<true>, k_pack_finish<true>) divide
+ * its magnitude by 2P limb by limb where the ordinary ones reduce it mod Q.
+ * Security: the keys are RLWE samples modulo Q P, so the lattice security of a hybrid key set is that of log2(Q P) at degree N, not
+ * of log2 Q.
+ * Out of scope: hybrid keys for the calls that take key rows as host arrays (they always switch the ordinary way), for the hoisted
+ * rotations, linear transforms, BSGS and plans (there the division by P belongs after the diagonal sum), the two-round collective
+ * relinearization key modulo Q P, and a P of more than one word. */
+int zkfhe_bfv_hybrid_max_p(const zkfhe_bfv_params *params, int base_bits, uint64_t *p_max);
+int zkfhe_bfv_relin_keygen_hybrid(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, uint64_t p, const uint64_t *sk, const uint8_t seed[32],
+                                  int base_bits, uint64_t *rlk0_q, uint64_t *rlk1_q, uint64_t *rlk0_p, uint64_t *rlk1_p);
+int zkfhe_bfv_galois_share_hybrid(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, uint64_t p, const uint64_t *sk_i,
+                                  const uint8_t crs_seed[32], const uint8_t party_seed[32], uint64_t g, int base_bits, uint64_t *r_q,
+                                  uint64_t *a_q, uint64_t *r_p, uint64_t *a_p);
+int zkfhe_bfv_galois_keygen_hybrid(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, uint64_t p, const uint64_t *sk, const uint8_t seed[32],
+                                   uint64_t g, int base_bits, uint64_t *gk0_q, uint64_t *gk1_q, uint64_t *gk0_p, uint64_t *gk1_p);
+int zkfhe_bfv_evk_create_hybrid(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, uint64_t p, int base_bits, const uint64_t *rlk0_q,
+                                const uint64_t *rlk1_q, const uint64_t *rlk0_p, const uint64_t *rlk1_p, size_t n_galois, const uint64_t *g,
+                                const uint64_t *gk0_q, const uint64_t *gk1_q, const uint64_t *gk0_p, const uint64_t *gk1_p,
+                                zkfhe_bfv_evk **out);
+int zkfhe_bfv_evk_special_modulus(const zkfhe_bfv_evk *evk, uint64_t *p);
+
 /* ---- Ring packing: chosen coefficients of many ciphertexts in one (bfv_pack.hip, bfv_resident.hip) ----
  * Moves one coefficient of each of n ciphertexts into one ciphertext and erases everything else (PackLWEs followed by the field
  * trace; Chen, Dai, Kim, Song 2021).  It uses Galois key switches, additions and products by a monomial only: no multiplicative

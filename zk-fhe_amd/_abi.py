@@ -129,7 +129,10 @@ _ABI = {
     "zkfhe_bfv_cts_plan_apply": "i:vvvv", "zkfhe_bfv_cts_select": "i:vvnpv", "zkfhe_bfv_cts_sum": "i:vvjnv", "zkfhe_bfv_evk_create": "i:vBippnpppV",
     "zkfhe_bfv_evk_bytes": "i:Biinp", "zkfhe_bfv_evk_info": "i:vBIINpp", "zkfhe_bfv_evk_destroy": "i:vv", "zkfhe_bfv_evk_wide_max": "i:vBiN",
     "zkfhe_bfv_cts_mul_evk": "i:vvvvv", "zkfhe_bfv_cts_apply_galois_evk": "i:vvuvv", "zkfhe_bfv_cts_slot_sum": "i:vvvv",
-    "zkfhe_bfv_cts_dot": "i:vvvnvv", "zkfhe_bfv_cts_dot_plain": "i:vvnnpv", "zkfhe_bfv_pack_elements": "i:BpN",
+    "zkfhe_bfv_cts_dot": "i:vvvnvv", "zkfhe_bfv_cts_dot_plain": "i:vvnnpv", "zkfhe_bfv_hybrid_max_p": "i:Bip",
+    "zkfhe_bfv_relin_keygen_hybrid": "i:vBupsipppp", "zkfhe_bfv_galois_share_hybrid": "i:vBupssuipppp",
+    "zkfhe_bfv_galois_keygen_hybrid": "i:vBupsuipppp", "zkfhe_bfv_evk_create_hybrid": "i:vBuippppnpppppV",
+    "zkfhe_bfv_evk_special_modulus": "i:vp", "zkfhe_bfv_pack_elements": "i:BpN",
     "zkfhe_bfv_mul_monomial": "i:vBnppnppp", "zkfhe_bfv_pack": "i:vBnnpppppipp", "zkfhe_bfv_cts_mul_monomial": "i:vvnpv",
     "zkfhe_bfv_cts_pack": "i:vvnpvv", "zkfhe_version": "s:",
 }

@@ -348,6 +348,31 @@ class _BfvCalls:
         crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
         return self._galois_key("zkfhe_bfv_galois_share", params, sk, [crs_seed, party_seed], g, base_bits)
 
+    # ------------------------------------------------------------------ hybrid keys modulo Q P (zkfhe.h, bfv_hybrid.hip)
+
+    def _hybrid_key(self, fn, params, p, sk, tail, base_bits):
+        n, sk = int(params[0]), self._sk(params, sk)
+        out = [np.empty((self._relin_rows(params, base_bits), n), dtype=np.uint64) for _ in range(4)]
+        self._call(fn, params, int(p), sk, *tail, int(base_bits), *out)
+        return tuple(out)
+
+    def bfv_relin_keygen_hybrid(self, params, p, sk, seed=None, base_bits=16):
+        """zkfhe_bfv_relin_keygen_hybrid -> (rlk0_q, rlk1_q, rlk0_p, rlk1_p) of shape (l, N): the relinearization key modulo Q P
+        for the special modulus p as its q-planes and p-planes.  seed: 32 SECRET bytes (None: os.urandom)."""
+        seed = self._seed(seed, "relinearization-key seed", fresh=True)
+        return self._hybrid_key("zkfhe_bfv_relin_keygen_hybrid", params, p, sk, [seed], base_bits)
+
+    def bfv_galois_keygen_hybrid(self, params, p, sk, g, seed=None, base_bits=16):
+        """zkfhe_bfv_galois_keygen_hybrid -> (gk0_q, gk1_q, gk0_p, gk1_p) of shape (l, N): the Galois key of sk for g modulo Q P."""
+        seed = self._seed(seed, "Galois-key seed", fresh=True)
+        return self._hybrid_key("zkfhe_bfv_galois_keygen_hybrid", params, p, sk, [seed, int(g)], base_bits)
+
+    def bfv_galois_share_hybrid(self, params, p, sk, crs_seed, party_seed, g, base_bits=8):
+        """zkfhe_bfv_galois_share_hybrid -> (r_q, a_q, r_p, a_p) of shape (l, N): party i's share of the collective hybrid Galois key
+        for g; gk0_q = bfv_share_aggregate of the r_q, gk0_p = bfv_share_aggregate of the r_p under parameters whose q is p."""
+        crs_seed, party_seed = self._seed(crs_seed, "CRS seed"), self._seed(party_seed, "party seed")
+        return self._hybrid_key("zkfhe_bfv_galois_share_hybrid", params, p, sk, [crs_seed, party_seed, int(g)], base_bits)
+
     def _galois_keys(self, params, gk0, gk1, base_bits, lead):
         n = int(params[0])
         gk0 = np.ascontiguousarray(gk0, dtype=np.uint64)
@@ -489,6 +514,14 @@ def bfv_evk_bytes(params, base_bits, has_relin, n_galois):
     """zkfhe_bfv_evk_bytes (host only): the device bytes of a key set, (has_relin + n_galois) 2 l 5 N 4 with l = bfv_relin_digits."""
     out = ctypes.c_uint64()
     call("zkfhe_bfv_evk_bytes", params, int(base_bits), int(bool(has_relin)), int(n_galois), ctypes.byref(out))
+    return out.value
+
+
+def bfv_hybrid_max_p(params, base_bits):
+    """zkfhe_bfv_hybrid_max_p (host only): the largest special modulus P below 2^63 with l N (2^w - 1) (Q P - 1) <= floor(P5 / 2),
+    P5 the product of the five RNS primes; the gcd with Q is not looked at."""
+    out = ctypes.c_uint64()
+    call("zkfhe_bfv_hybrid_max_p", params, int(base_bits), ctypes.byref(out))
     return out.value
 
 

@@ -254,7 +254,7 @@ int dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, size_t n_groups, si
     } else {
       ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 3 * gc, log_n, q, EvEpi{.mode = EV_ROUND, .t = params->t}, chat));
       ZK_CK(zk_bfv_key_switch(ctx, ks, SrcPlain{chat + 2 * gc * n}, key.hat(0), gc, acc));
-      ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 2 * gc, log_n, q, EvEpi{.mode = EV_ADD, .add = chat}, o_d));
+      ZK_CK(zk_bfv_eval_epilogue(ctx, acc, 2 * gc, log_n, q, EvEpi{.mode = EV_ADD, .add = chat, .p = key.special}, o_d));
     }
     ZK_CK(io.out.out(ctx, 0, g0, gc, n, o_d));
     ZK_CK(io.out.out(ctx, 1, g0, gc, n, o_d + gc * n));

@@ -9,8 +9,8 @@
 //   3. k_eval_epilogue (EV_ROUND): Garner into three u64 limbs, centre, c^_j = floor((2 T x_j + Q) / 2Q) mod Q;
 //   4. the key switch of bfv_key_switch.hip on c^2 itself (SrcPlain: the relinearization): every digit d_i = (c^2 >> i w) & (2^w - 1)
 //      is transformed, multiplied by the transformed rlk0_i and rlk1_i and summed; one inverse transform per component
-//      (sum < l N 2^w Q < 2^114);
-//   5. k_eval_epilogue (EV_ADD): out_j = c^_j + sum mod Q.
+//      (sum < l N 2^w Q < 2^114; with the keys of a hybrid set, integers below Q P, sum <= l N (2^w - 1) (Q P - 1) <= P5 / 2);
+//   5. k_eval_epilogue (EV_ADD): out_j = c^_j + sum mod Q (a hybrid set: the sum divided by P with rounding, k_eval_epilogue<true>).
 // The relinearization key is transformed once per call.  No step branches on or addresses by a coefficient's value.
 // k_eval_epilogue also serves the Galois key switch of bfv_galois.hip (EV_GALOIS).
 // add / subtract, add_plain / mul_plain and mul each have one runner (zk_bfv_add_run, zk_bfv_plain_run, zk_bfv_mul_run: the chunk
@@ -28,7 +28,9 @@ constexpr int NP = NP_MAX;
 typedef unsigned __int128 u128;
 
 // One thread per output coefficient of res ([poly][prime][degree], total = n_polys N): the centred integer x of its residues, then
-// the mode's result (EvMode).  out: CircuitInput order.
+// the mode's result (EvMode).  out: CircuitInput order.  HYB: the epilogue of a hybrid key switch (EV_ADD, EV_GALOIS), which puts
+// floor((2 x + P) / 2P) mod Q where the ordinary one puts x mod Q; the ordinary instance keeps its code.
+template <bool HYB>
 __global__ __launch_bounds__(256) void k_eval_epilogue(const uint32_t *__restrict__ res, size_t total, int log_n, uint64_t q, Crt5 cc,
                                                        EvEpi epi, uint64_t *__restrict__ out) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(256) void k_eval_epilogue(const uint32_t *__restric
   uint64_t m[3];
   bool neg;
   crt5(res + poly * NP * n + d, n, cc, m, neg);
-  if (epi.mode == EV_ROUND) {
+  if (!HYB && epi.mode == EV_ROUND) {
     // num = |x| 2T + (x < 0 ? Q - 1 : Q) in four limbs: floor((2 T x + Q) / 2Q) = -floor((2 T |x| + Q - 1) / 2Q) for x < 0
     const uint64_t t2 = 2 * epi.t, dq = 2 * q;   // both < 2^64
     u128 a = (u128)m[0] * t2 + (neg ? q - 1 : q);
@@ -55,13 +57,13 @@ __global__ __launch_bounds__(256) void k_eval_epilogue(const uint32_t *__restric
     out[pos] = neg && r ? q - r : r;
     return;
   }
-  uint64_t v = crt5_mod_q(m, neg, q);   // x mod Q
+  uint64_t v = HYB ? crt5_div_p_mod_q(m, neg, epi.p, q) : crt5_mod_q(m, neg, q);   // x mod Q
   if (epi.mode == EV_ADD) {
     v = add_q(v, epi.add[pos], q);
-  } else if (epi.mode == EV_RLK) {
+  } else if (!HYB && epi.mode == EV_RLK) {
     const u128 k = (u128)epi.poly[n - 1 - d] << (poly * epi.w);   // i w <= 62, s^2 < 2^63
     v = sub_q(mod128((uint64_t)(k >> 64), (uint64_t)k, q), add_q(v, epi.add[pos], q), q);
-  } else if (epi.mode == EV_NOISE) {
+  } else if (!HYB && epi.mode == EV_NOISE) {
     v = add_q(v, epi.add[pos], q);   // [c0 + c1 s]_Q
     const u128 prod = (u128)epi.delta * decrypt_round(v, q, epi.t);   // delta m, m as a residue
     const uint64_t x = sub_q(v, mod128((uint64_t)(prod >> 64), (uint64_t)prod, q), q);
@@ -151,7 +153,10 @@ namespace zkrns {
 int zk_bfv_eval_epilogue(zkfhe_ctx *ctx, const uint32_t *res, size_t n_polys, int log_n, uint64_t q, const EvEpi &epi, uint64_t *out) {
   const size_t total = n_polys << log_n;
   zk_prof_begin(ctx);
-  k_eval_epilogue<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt5_const(), epi, out);
+  if (epi.p != 1)
+    k_eval_epilogue<true><<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt5_const(), epi, out);
+  else
+    k_eval_epilogue<false><<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(res, total, log_n, q, crt5_const(), epi, out);
   ZK_LAUNCH_CHECK(ctx);
   double bytes = (double)total * (NP * 4 + 8 + (epi.add ? 8 : 0));
   if (epi.mode == EV_GALOIS) bytes += (double)(epi.c << log_n) * 8;   // sigma_g(c0)
@@ -189,6 +194,7 @@ struct MulWork {
   uint64_t *in_d, *chat, *o_d;
   uint32_t *hat, *res;
   const uint32_t *key;   // the transformed key ([2 l][5][N])
+  uint64_t special;      // its special modulus (1: none)
 };
 
 // steps 1 to 5 of the top of the file for c pairs: w.in_d = [a0 | a1 | b0 | b1] ([4 c][N]); w.o_d = [out0 | out1]
@@ -199,7 +205,7 @@ int mul_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t c, const KeySwi
   ZK_CK(launch_tensor(ctx, w.hat, c, log_n, w.res));
   ZK_CK(zk_bfv_eval_epilogue(ctx, w.res, 3 * c, log_n, q, EvEpi{.mode = EV_ROUND, .t = prm->t}, w.chat));
   ZK_CK(zk_bfv_key_switch(ctx, ks, SrcPlain{w.chat + 2 * c * n}, w.key, c, w.res));
-  return zk_bfv_eval_epilogue(ctx, w.res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = w.chat}, w.o_d);
+  return zk_bfv_eval_epilogue(ctx, w.res, 2 * c, log_n, q, EvEpi{.mode = EV_ADD, .add = w.chat, .p = w.special}, w.o_d);
 }
 
 }  // namespace
@@ -283,7 +289,7 @@ int zk_bfv_mul_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, co
   ks.add(ar, ctx, key, chunk);
   ZK_CK(ar.carve(ctx));
   ZK_CK(stage_keys<NP>(ctx, key, n, prm->q, l, w.flag));
-  w.key = key.hat(0);
+  w.key = key.hat(0), w.special = key.special;
   const Planes *src[2] = {&a, &b};
   for (size_t lo = 0; lo < count; lo += chunk) {
     const size_t c = std::min(chunk, count - lo);

@@ -6,9 +6,10 @@
 // addresses depend on g (public) and never on a coefficient's value.  The key switch is the relinearization's (bfv_key_switch.hip):
 //   k_key_switch (SrcGalois)   every digit d_i = (sigma_g(c1) >> i w) & (2^w - 1) is transformed with the five primes, multiplied
 //                              by the transformed gk0_i and gk1_i and summed; one inverse transform per component
-//                              (sum < l N 2^w Q < 2^116)
+//                              (sum < l N 2^w Q < 2^116; a hybrid key set: sum <= l N (2^w - 1) (Q P - 1) <= P5 / 2)
 //   k_eval_epilogue EV_GALOIS  Garner over the five primes, x mod Q, + sigma_g(c0) on component 0, + x_in when set (slot_sum's
-//                              x <- x + apply_galois(x), fused: the same sums mod Q as zkfhe_bfv_add)
+//                              x <- x + apply_galois(x), fused: the same sums mod Q as zkfhe_bfv_add); with the keys of a hybrid
+//                              set floor((2 x + P) / 2P) mod Q stands for x mod Q (k_eval_epilogue<true>)
 // apply_galois and slot_sum are one chunk loop, zk_bfv_galois_run: `steps` key switches per chunk on device buffers, each added to
 // its input or not.  Host keys are transformed once per call, all of them in one launch (stage_keys); the batch calls of
 // bfv_resident.hip call the same runner on device planes, with host keys or the keys of a resident key set.
@@ -189,12 +190,12 @@ int galois_key(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, const uint64_t *s
   return ZKFHE_OK;
 }
 
-// one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N]; out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
-int galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, const KeySwitch &ks, uint64_t g, const uint32_t *key_hat, bool accumulate,
-                uint32_t *acc, uint64_t *out_d) {
+// one key switch of c ciphertexts: x_d = [c0 | c1] ([2 c][N]), key_hat: [2 l][5][N] (special: its special modulus, 1: none); out_d = [sigma_g(c0) + ks0 | ks1] (+ x_d)
+int galois_core(zkfhe_ctx *ctx, const uint64_t *x_d, size_t c, const KeySwitch &ks, uint64_t g, const uint32_t *key_hat, uint64_t special,
+                bool accumulate, uint32_t *acc, uint64_t *out_d) {
   const unsigned ginv = galois_inv(g, (uint64_t)1 << ks.log_n);
   ZK_CK(zk_bfv_key_switch(ctx, ks, SrcGalois{x_d + (c << ks.log_n), ginv}, key_hat, c, acc));
-  const EvEpi epi{.mode = EV_GALOIS, .add = accumulate ? x_d : nullptr, .poly = x_d, .ginv = ginv, .c = c};
+  const EvEpi epi{.mode = EV_GALOIS, .add = accumulate ? x_d : nullptr, .poly = x_d, .ginv = ginv, .c = c, .p = special};
   return zk_bfv_eval_epilogue(ctx, acc, 2 * c, ks.log_n, ks.q, epi, out_d);
 }
 
@@ -229,7 +230,7 @@ int zk_bfv_galois_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count,
     ZK_CK(a.in(ctx, 0, lo, c, n, x));   // a key switch reads [c0 | c1] of the chunk
     ZK_CK(a.in(ctx, 1, lo, c, n, x + c * n));
     for (size_t k = 0; k < steps; ++k) {   // y = apply_galois(x, g_k) (+ x), then the two change places
-      ZK_CK(galois_core(ctx, x, c, ks, gs[k], key.hat(k), accumulate, acc, y));
+      ZK_CK(galois_core(ctx, x, c, ks, gs[k], key.hat(k), key.special, accumulate, acc, y));
       std::swap(x, y);
     }
     ZK_CK(out.out(ctx, 0, lo, c, n, x));

@@ -117,10 +117,13 @@ inline int upload_key_pair(zkfhe_ctx *ctx, uint64_t *dst_d, const uint64_t *k0, 
 // Where the `count` key-switch keys of a call come from: host rows still to be staged (key k: k0 + k l N and k1 + k l N, checked by
 // the caller), or keys of a key set, transformed and on the device already (hat_d[k]: [2 l][5][N]).  add() puts the staging
 // buffers into the caller's arena only where there is something to stage; stage_keys fills them; hat(k) is key k either way.
+// special: the special modulus P of a hybrid key set (zkfhe.h), whose key switch the runner's epilogue divides by P; 1: ordinary
+// keys, which host rows always are.
 struct KeySource {
   const uint64_t *k0 = nullptr, *k1 = nullptr;
   const uint32_t *const *hat_d = nullptr;
   size_t count = 1;
+  uint64_t special = 1;
   bool resident() const { return hat_d != nullptr; }
   void add(Arena &a, uint64_t n, int l) {
     words_ = (size_t)2 * l * n;
@@ -133,7 +136,9 @@ struct KeySource {
   uint32_t *key_hat_ = nullptr;
 };
 inline KeySource host_keys(const uint64_t *k0, const uint64_t *k1, size_t count = 1) { return KeySource{k0, k1, nullptr, count}; }
-inline KeySource resident_keys(const uint32_t *const *hat_d, size_t count = 1) { return KeySource{nullptr, nullptr, hat_d, count}; }
+inline KeySource resident_keys(const uint32_t *const *hat_d, size_t count = 1, uint64_t special = 1) {
+  return KeySource{nullptr, nullptr, hat_d, count, special};
+}
 
 // The staging of host keys, once per call: every key's pair uploaded, one k_rns_ntt (LOAD_RESIDUE, five primes) over all of them.
 // A resident key stages nothing and launches nothing.  A template for the sake of its kernel, which each unit launches as its own.
@@ -197,14 +202,21 @@ int zk_bfv_dot_core(zkfhe_ctx *ctx, const zkfhe_bfv_params *params, bool plain, 
 // "fn: n_terms ... is above the limit ..." unless n_terms is at most zkfhe_bfv_dot_max_terms
 int check_dot_terms(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, bool plain, size_t n_terms, const char *fn);
 // ---- defined in bfv_evk.hip
-// a key set as its callers see it: the transformed relinearization key (null: none) and the transformed key of g (null: none)
+// a key set as its callers see it: the transformed relinearization key (null: none) and the transformed key of g (null: none);
+// special: the special modulus of a hybrid set, 1 for an ordinary one
 struct EvkView {
   zkfhe_bfv_params params;
   int device, base_bits, l;
   const uint32_t *rlk_hat;
+  uint64_t special;
 };
 void zk_bfv_evk_view(const zkfhe_bfv_evk *evk, EvkView *view);
 const uint32_t *zk_bfv_evk_galois(const zkfhe_bfv_evk *evk, uint64_t g);
+// the largest P below 2^63 with l N (2^w - 1) (Q P - 1) <= floor(P5 / 2) (zkfhe_bfv_hybrid_max_p)
+uint64_t hybrid_max_p(const zkfhe_bfv_params *prm, int l, int base_bits);
+// the refusals of a special modulus in their order: "fn: P must satisfy 2 <= P < 2^63", "fn: P and Q must be coprime", "fn: P is
+// above the limit ..." (hybrid_max_p)
+int check_special(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, int l, int base_bits, uint64_t p, const char *fn);
 // ---- defined in bfv_pack.hip
 // out = x^k a mod (x^N + 1, Q) with k_count = 1 exponent for every ciphertext or one per ciphertext (k: a host array, every k < 2N)
 int zk_bfv_monomial_run(zkfhe_ctx *ctx, const zkfhe_bfv_params *prm, size_t count, const Planes &a, size_t k_count, const uint64_t *k,

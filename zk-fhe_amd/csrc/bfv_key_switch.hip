@@ -3,6 +3,8 @@
 // yields) is decomposed into l digits d_i = (v >> i w) & (2^w - 1); each is transformed with the five primes, multiplied by the
 // transforms of key0_i and key1_i (key_hat: [2 l][5][N], the key0_i then the key1_i), the products are summed over the digits and
 // transformed back, one polynomial per component (sum < l N 2^w Q < 2^116), into acc ([2][c][5][N], what the CRT epilogues read).
+// The rows of a hybrid key set are the residues of integers below Q P (bfv_evk.hip): the same kernels, and a sum of at most
+// l N (2^w - 1) (Q P - 1) <= P5 / 2 (zkfhe_bfv_hybrid_max_p), which the hybrid epilogues divide by P.
 //   k_key_switch<Src>        the digit-serial body: one workgroup per (polynomial, prime) walks the l digits and accumulates in acc
 //   k_key_switch_digit<Src>  the digit-parallel body: one workgroup per (digit, polynomial, prime) writes the two products to
 //                            part[digit][comp][k][prime][N]

@@ -12,7 +12,8 @@
 //                    where the key is resident and the level has at most zk_bfv_wide_max pairs
 //   k_pack_finish    Garner over the five primes, x mod Q, as k_eval_epilogue EV_GALOIS; the same thread adds (e0 + x^s o0) +
 //                    sigma_g(e0 - x^s o0) on component 0 and e1 + x^s o1 on component 1.  Out of place: a level reads sigma-permuted
-//                    positions of its operands, so levels go back and forth between two work arrays.
+//                    positions of its operands, so levels go back and forth between two work arrays.  With the keys of a hybrid
+//                    set k_pack_finish<true> puts floor((2 x + P) / 2P) mod Q where x mod Q stands.
 // Every sum is a sum mod Q of canonical residues, so the order of the additions of a level does not matter: a level is bit for bit
 // (w_i + t) + zkfhe_bfv_apply_galois(w_i - t, g) with t = x^s w_(i+h).
 // zk_bfv_pack_run serves the host-array call and the batch call.  Work arrays hold at most chunk_polys(N) ciphertexts.  Groups whose
@@ -51,9 +52,12 @@ __global__ __launch_bounds__(256) void k_pack_prepare(const uint64_t *__restrict
   (comp ? out1 : out0)[poly * n + (n - 1 - d)] = v;
 }
 
-// One thread per coefficient of res ([2][c][NP][N], total = 2 c N): pair k of component comp goes to polynomial k of out[comp]
+// One thread per coefficient of res ([2][c][NP][N], total = 2 c N): pair k of component comp goes to polynomial k of out[comp].
+// HYB: the key switch of a hybrid key set, divided by its special modulus sp
+template <bool HYB>
 __global__ __launch_bounds__(256) void k_pack_finish(const uint32_t *__restrict__ res, PackOps op, unsigned s, size_t c, size_t total, int log_n,
-                                                     uint64_t q, Crt5 cc, unsigned ginv, uint64_t *__restrict__ out0, uint64_t *__restrict__ out1) {
+                                                     uint64_t q, Crt5 cc, unsigned ginv, uint64_t *__restrict__ out0, uint64_t *__restrict__ out1,
+                                                     uint64_t sp) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total) return;
   const unsigned n = 1u << log_n, d = (unsigned)(g & (n - 1));
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256) void k_pack_finish(const uint32_t *__restrict_
   uint64_t m[3];
   bool neg;
   crt5(res + poly * NP * n + d, n, cc, m, neg);
-  uint64_t v = crt5_mod_q(m, neg, q);   // the key switch mod Q
+  uint64_t v = HYB ? crt5_div_p_mod_q(m, neg, sp, q) : crt5_mod_q(m, neg, q);   // the key switch mod Q
   const uint64_t *e = op.e[comp] + at * n, *o = op.o[comp] ? op.o[comp] + at * n : nullptr;
   uint64_t sum = e[n - 1 - d];
   if (o) sum = add_q(sum, mono_coeff(o, d, s, n, q), q);
@@ -106,7 +110,11 @@ int pack_level(zkfhe_ctx *ctx, const PackCtx &pc, int lv, const PackOps &op, siz
   ZK_CK(zk_bfv_key_switch(ctx, pc.ks, sp, pc.key->hat(lv - 1), c, pc.acc));
   const size_t total = 2 * c * n;
   zk_prof_begin(ctx);
-  k_pack_finish<<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(pc.acc, op, s, c, total, log_n, pc.ks.q, crt5_const(), ginv, out0, out1);
+  const uint64_t special = pc.key->special;
+  if (special != 1)
+    k_pack_finish<true><<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(pc.acc, op, s, c, total, log_n, pc.ks.q, crt5_const(), ginv, out0, out1, special);
+  else
+    k_pack_finish<false><<<zk_blocks(total, 256), 256, 0, ctx->stream>>>(pc.acc, op, s, c, total, log_n, pc.ks.q, crt5_const(), ginv, out0, out1, special);
   ZK_LAUNCH_CHECK(ctx);
   zk_prof_end(ctx, ZKFHE_PROF_BFV_PACK, (double)total * (NP * 4 + 8 + src) + (double)c * n * src);
   return ZKFHE_OK;

@@ -488,7 +488,7 @@ int zkfhe_bfv_cts_mul_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bf
   ZK_CK(same_count(ctx, fn, b->n, a->n, "b"));
   ZK_CK(same_count(ctx, fn, dst->n, a->n, "dst"));
   ZK_CK(need_relin(ctx, fn, view));
-  return zk_bfv_mul_run(ctx, &a->params, a->n, a->planes(), b->planes(), resident_keys(&view.rlk_hat), view.l, view.base_bits, dst->planes());
+  return zk_bfv_mul_run(ctx, &a->params, a->n, a->planes(), b->planes(), resident_keys(&view.rlk_hat, 1, view.special), view.l, view.base_bits, dst->planes());
 }
 
 int zkfhe_bfv_cts_apply_galois_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint64_t g, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
@@ -502,7 +502,7 @@ int zkfhe_bfv_cts_apply_galois_evk(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, uint6
   ZK_CK(check_g(ctx, a->params.n, g, fn));
   const uint32_t *key;
   ZK_CK(need_galois(ctx, fn, evk, g, &key));
-  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), 1, &g, resident_keys(&key), view.l, view.base_bits, false, dst->planes());
+  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), 1, &g, resident_keys(&key, 1, view.special), view.l, view.base_bits, false, dst->planes());
 }
 
 int zkfhe_bfv_cts_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_evk *evk, zkfhe_bfv_cts *dst) {
@@ -519,7 +519,7 @@ int zkfhe_bfv_cts_slot_sum(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_b
   ZK_CK(zkfhe_bfv_slot_sum_elements(&a->params, gs.data(), &steps));
   std::vector<const uint32_t *> keys(steps);
   for (size_t k = 0; k < steps; ++k) ZK_CK(need_galois(ctx, fn, evk, gs[k], &keys[k]));
-  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), steps, gs.data(), resident_keys(keys.data(), steps), view.l, view.base_bits, true,
+  return zk_bfv_galois_run(ctx, &a->params, a->n, a->planes(), steps, gs.data(), resident_keys(keys.data(), steps, view.special), view.l, view.base_bits, true,
                            dst->planes());
 }
 
@@ -534,7 +534,7 @@ int zkfhe_bfv_cts_dot(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, const zkfhe_bfv_ct
   ZK_CK(dot_args(ctx, fn, a, b, n_terms, dst));
   ZK_CK(need_relin(ctx, fn, view));
   ZK_CK(check_dot_terms(ctx, &a->params, false, n_terms, fn));
-  const DotIo io{a->planes(), b->planes(), dst->planes(), resident_keys(&view.rlk_hat)};
+  const DotIo io{a->planes(), b->planes(), dst->planes(), resident_keys(&view.rlk_hat, 1, view.special)};
   return zk_bfv_dot_core(ctx, &a->params, false, dst->n, n_terms, b->n / n_terms, io, view.l, view.base_bits);
 }
 
@@ -564,7 +564,7 @@ int zkfhe_bfv_cts_pack(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n, const u
   pack_elements(a->params.n, gs.data());
   std::vector<const uint32_t *> keys(gs.size());
   for (size_t i = 0; i < gs.size(); ++i) ZK_CK(need_galois(ctx, fn, evk, gs[i], &keys[i]));
-  return zk_bfv_pack_run(ctx, &a->params, dst->n, n, a->planes(), pos, resident_keys(keys.data(), keys.size()), view.l, view.base_bits, dst->planes());
+  return zk_bfv_pack_run(ctx, &a->params, dst->n, n, a->planes(), pos, resident_keys(keys.data(), keys.size(), view.special), view.l, view.base_bits, dst->planes());
 }
 
 int zkfhe_bfv_cts_dot_plain(zkfhe_ctx *ctx, const zkfhe_bfv_cts *a, size_t n_terms, size_t m_groups, const uint64_t *m, zkfhe_bfv_cts *dst) {

@@ -47,6 +47,7 @@ enum Domain : uint32_t {
   DOM_PCKS_U = 16, DOM_PCKS_E0 = 17, DOM_PCKS_E1 = 18,   // public collective key switch, index first_index + ciphertext
   DOM_RFR_A = 19,                                        // refresh: CRS a_j, index first_index + ciphertext
   DOM_RFR_M = 20, DOM_RFR_E0 = 21, DOM_RFR_E1 = 22,      // refresh: mask M_ij (uniform mod T), e0_ij (smudging), e1_ij
+  DOM_HYB_RLK_A = 23, DOM_HYB_GK_A = 24,                 // hybrid keys: the p-plane's a_i (uniform mod P), indices as domains 7 and 14
 };
 
 __device__ __forceinline__ uint32_t mont_mul(uint32_t a, uint32_t b, uint32_t p, uint32_t pinv) {
@@ -167,6 +168,22 @@ __device__ __forceinline__ void crt5(const uint32_t *__restrict__ r, size_t n, c
 __device__ __forceinline__ uint64_t crt5_mod_q(const uint64_t m[3], bool neg, uint64_t q) {
   const uint64_t rm = mod128(mod128(m[2], m[1], q), m[0], q);
   return neg && rm ? q - rm : rm;
+}
+// floor((2 x + P) / 2P) mod q for the integer x of crt5 (|x| < 2^151) and 2 <= P < 2^63: x / P rounded to nearest, ties upward
+// (the hybrid key switch, zkfhe.h).  For x < 0 that is -floor((2 |x| + P - 1) / 2P).  Long division by 2P, one limb at a time
+// (the remainder carried in is below 2P, so div128's hi < d holds), as EV_ROUND divides by 2Q
+__device__ __forceinline__ uint64_t crt5_div_p_mod_q(const uint64_t m[3], bool neg, uint64_t sp, uint64_t q) {
+  typedef unsigned __int128 u128;
+  const uint64_t dp = 2 * sp;
+  u128 a = ((u128)m[0] << 1) + (neg ? sp - 1 : sp);
+  const uint64_t n0 = (uint64_t)a;
+  a = ((u128)m[1] << 1) + (uint64_t)(a >> 64);
+  const uint64_t n1 = (uint64_t)a, n2 = (m[2] << 1) + (uint64_t)(a >> 64);   // m[2] < 2^23
+  const uint64_t q2 = div128(0, n2, dp), r2 = n2 - q2 * dp;
+  const uint64_t q1 = div128(r2, n1, dp), r1 = n1 - q1 * dp;
+  const uint64_t q0 = div128(r1, n0, dp);
+  const uint64_t r = mod128(mod128(q2, q1, q), q0, q);
+  return neg && r ? q - r : r;
 }
 
 // the decryption of the residue v = [c0 + c1 s]_Q: round(T x / Q) mod T with x = v centred, as a residue mod Q.  For the residue v
@@ -360,6 +377,7 @@ struct Epi {
 //   EV_RLK     2^(i w) s^2 - x - e mod Q for polynomial i
 //   EV_NOISE   |[c0 + x - delta m]_Q| with m = the decryption of [c0 + x]_Q, maximised per polynomial
 //   EV_GALOIS  x mod Q, + sigma_g(c0) on the first c polynomials, + add when set
+// With a special modulus p != 1 (a hybrid key set: EV_ADD and EV_GALOIS only) floor((2 x + p) / 2p) mod Q stands where x mod Q does.
 enum EvMode { EV_MODQ = 0, EV_ROUND = 1, EV_ADD = 2, EV_RLK = 3, EV_NOISE = 4, EV_GALOIS = 5 };
 struct EvEpi {
   int mode = EV_MODQ;
@@ -370,6 +388,7 @@ struct EvEpi {
   unsigned long long *noise = nullptr;   // EV_NOISE: the maximum per polynomial (zeroed before the launch)
   unsigned ginv = 1;                     // EV_GALOIS: g^-1 mod 2N
   size_t c = 0;                          // EV_GALOIS
+  uint64_t p = 1;                        // EV_ADD, EV_GALOIS: the special modulus of a hybrid key set (1: none)
 };
 
 // ---- defined in bfv_enc.hip

@@ -68,6 +68,24 @@ class _ResidentCalls:
         self._call("zkfhe_bfv_evk_create", params, int(base_bits), r0, r1, g.shape[0], g if g.shape[0] else None, k0, k1, ctypes.byref(h))
         return BfvEvalKeys(self, h)
 
+    def bfv_evk_hybrid(self, params, p, base_bits=16, rlk=None, elements=(), gk=None):
+        """zkfhe_bfv_evk_create_hybrid: a key set modulo Q P for the special modulus p.  rlk = (rlk0_q, rlk1_q, rlk0_p, rlk1_p) of
+        shape (l, N) or None; gk = (gk0_q, gk1_q, gk0_p, gk1_p), the keys of `elements` stacked as (len(elements), l, N) -> a
+        BfvEvalKeys whose key switches divide by p (special_modulus)."""
+        r = [None] * 4
+        if rlk is not None:
+            r = list(self._galois_keys(params, rlk[0], rlk[1], base_bits, ()) + self._galois_keys(params, rlk[2], rlk[3], base_bits, ()))
+        g = np.ascontiguousarray([int(x) for x in elements], dtype=np.uint64).reshape(-1)
+        k = [None] * 4
+        if g.shape[0]:
+            if gk is None or len(gk) != 4:
+                raise ValueError("gk holds the q-planes and the p-planes of one key per element")
+            lead = (g.shape[0],)
+            k = list(self._galois_keys(params, gk[0], gk[1], base_bits, lead) + self._galois_keys(params, gk[2], gk[3], base_bits, lead))
+        h = ctypes.c_void_p()
+        self._call("zkfhe_bfv_evk_create_hybrid", params, int(p), int(base_bits), *r, g.shape[0], g if g.shape[0] else None, *k, ctypes.byref(h))
+        return BfvEvalKeys(self, h)
+
     def bfv_evk_wide_max(self, params, base_bits=16):
         """zkfhe_bfv_evk_wide_max: the largest count of ciphertexts in a chunk whose key switch takes the digit-parallel kernels on
         this device in the calls that take a BfvEvalKeys (0: never)"""
@@ -90,6 +108,13 @@ class BfvEvalKeys(_Handle):
         self.ctx = ctx
         self.h = handle
         self.params = self.info()["params"]
+
+    @property
+    def special_modulus(self):
+        """zkfhe_bfv_evk_special_modulus: the special modulus P of a hybrid set (Context.bfv_evk_hybrid), 1 for an ordinary one"""
+        p = ctypes.c_uint64()
+        call("zkfhe_bfv_evk_special_modulus", self._handle(), ctypes.byref(p))
+        return p.value
 
     def info(self):
         """zkfhe_bfv_evk_info -> params (N, Q, T, B), base_bits, has_relin, elements (the Galois elements in the order of their keys)
