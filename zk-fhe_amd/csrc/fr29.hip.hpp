@@ -79,4 +79,45 @@ ZK_HD Fr fr29_to_mont(const Fr &x) {
   return fr29_mul_const(x, w);
 }
 
+// standard form (s 2^256, any representative below 2^256) -> the integer s, packed, in [0, r] (r itself only for a non-zero multiple of
+// r, which no canonical input is): ONE nine-limb Montgomery reduction of 32 x and nothing else.  The reduction divides by 2^261, so the
+// nine limbs are cut from x five bits early (32 x < 2^261 fills them exactly); with the product operand the literal 1 a column is one
+// limb of x plus the terms m_j r_(k-j): 81 multiply-adds against the 128 with carry pairs of the 8 x 32-bit fp_from_mont, and
+// (32 x + m r) / 2^261 < 1 + r needs no subtraction.  The table MSM's digits take a scalar through this (msm_table.hip.hpp), whose
+// sign split sends r to a magnitude of zero like 0.
+ZK_HD Fr fr29_from_mont_weak(const Fr &x) {
+  using M = fr29_mod;
+  F29 t;
+  t.l[0] = (x.l[0] << 5) & q29::MASK;
+#pragma unroll
+  for (int i = 1; i < 9; ++i) {
+    const int bit = 29 * i - 5, k = bit >> 5, sh = bit & 31;
+    u32 v = x.l[k] >> sh;
+    if (sh > 3 && k + 1 < 8) v |= x.l[k + 1] << (32 - sh);
+    t.l[i] = v & q29::MASK;
+  }
+#ifdef ZK_MONT29_TIED
+  return fr29_pack(mont29u_redc<M, F29>(t));
+#else
+  u32 m[9];
+  F29 r;
+  u64 acc = 0;
+#pragma unroll
+  for (int k = 0; k < 17; ++k) {
+    if (k < 9) acc += t.l[k];
+#pragma unroll
+    for (int j = (k < 9 ? 0 : k - 8); j <= (k < 9 ? k - 1 : 8); ++j) acc += (u64)m[j] * M::P[k - j];
+    if (k < 9) {
+      m[k] = ((u32)acc * M::INV) & q29::MASK;
+      acc += (u64)m[k] * M::P[0];
+    } else {
+      r.l[k - 9] = (u32)acc & q29::MASK;
+    }
+    acc >>= 29;
+  }
+  r.l[8] = (u32)acc;
+  return fr29_pack(r);
+#endif
+}
+
 }  // namespace zk

@@ -134,6 +134,22 @@ BiasArg table_bias(int c, int W) {
   return B;
 }
 
+// k_msm_table with the digit width as a literal for the widths a 2^13 basis gets -- 15 and 13 under the service profile (Lagrange
+// and monomial half), 13 and 11 under the library's default budget, 9 under the 4 GB of the test suite -- and with the width as an
+// argument for the rest.  ZKFHE_TABLE_GENERIC=1 (read per call: a test runs one basis through both) takes the latter for every width.
+using TableKernel = decltype(&k_msm_table<false, 0>);
+template <bool TREE>
+TableKernel table_kernel(int c) {
+  const char *g = getenv("ZKFHE_TABLE_GENERIC");
+  if (!g || g[0] != '1') switch (c) {
+      case 9: return k_msm_table<TREE, 9>;
+      case 11: return k_msm_table<TREE, 11>;
+      case 13: return k_msm_table<TREE, 13>;
+      case 15: return k_msm_table<TREE, 15>;
+    }
+  return k_msm_table<TREE, 0>;
+}
+
 int msm_table(zkfhe_ctx *ctx, const zkfhe_basis *basis, const Fr *scalars, size_t col_stride, size_t n_cols, void *out, bool xyzz) {
   const size_t n = basis->n;
   const int c = basis->mc, W = basis->mw;
@@ -168,7 +184,7 @@ int msm_table(zkfhe_ctx *ctx, const zkfhe_basis *basis, const Fr *scalars, size_
   const int slot = n_cols * n > ((size_t)1 << 16) ? 0 : 2;   // profiling slot: a wide call or one of a few columns
   if (ctx->prof_on) ZK_HIP(ctx, zk_memset_async(ctx, adds, 0, 8, ctx->stream));
   zk_prof_begin(ctx);
-  (tree ? k_msm_table<true> : k_msm_table<false>)<<<(unsigned)grid, 256, 0, ctx->stream>>>(scalars, col_stride, n, basis->mult, c, W, table_bias(c, W), (unsigned)P, (unsigned)cpc,
+  (tree ? table_kernel<true>(c) : table_kernel<false>(c))<<<(unsigned)grid, 256, 0, ctx->stream>>>(scalars, col_stride, n, basis->mult, c, W, table_bias(c, W), (unsigned)P, (unsigned)cpc,
                                                                                            (unsigned)n_cols, (unsigned)max_part, (G1X *)p0, n_part, col_next, (unsigned *)p1,
                                                                                            ctx->prof_on ? adds : nullptr);
   ZK_LAUNCH_CHECK(ctx);
@@ -179,6 +195,7 @@ int msm_table(zkfhe_ctx *ctx, const zkfhe_basis *basis, const Fr *scalars, size_
     unsigned long long h = 0;
     ZK_HIP(ctx, hipMemcpy(&h, adds, 8, hipMemcpyDeviceToHost));
     ctx->prof_ops[slot] += (double)h;
+    if (getenv("ZKFHE_VERBOSE")) fprintf(stderr, "[zkfhe] msm_table: %zu columns of %zu, %d-bit digits: %llu additions\n", n_cols, n, c, h);
   }
   return ZKFHE_OK;
 }

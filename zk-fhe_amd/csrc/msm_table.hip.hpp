@@ -2,6 +2,7 @@
 // digits, the basis tables, k_msm_table and its fold, and the sparse sum.
 #pragma once
 #include "ctx.hpp"
+#include "fr29.hip.hpp"
 #include "g1x29_wave.hip.hpp"
 
 namespace {
@@ -26,16 +27,47 @@ __device__ __forceinline__ u32 bits_at(const u32 (&l)[9], int bit, int c) {
   return (u32)((((u64)hi << 32) | lo) >> sh) & ((1u << c) - 1);
 }
 
-// |s| (sign-magnitude, < 2^253) + bias; returns the sign, and in `bits` the bit length of |s|: windows above
-// bits / c + 1 hold zero digits (a negative digit carries one into the next window, not further)
-__device__ __forceinline__ bool biased_scalar(const Fr &mont, const BiasArg &B, u32 (&out)[9], int &bits) {
-  Fr s = fp_from_mont<FrP>(mont);
-  const bool neg = fr_gt_half(s);
-  if (neg) s = fp_neg<FrP>(s);
+// W of a literal width (0: the width is an argument); windows a magnitude below 2^32 reaches, bias carry included
+constexpr int table_windows(int c) { return c ? (255 + c - 1) / c : 0; }
+constexpr int table_short_windows(int c) { return c ? (32 / c + 2 < table_windows(c) ? 32 / c + 2 : table_windows(c)) : 0; }
+
+// the digit of window w when the width is a literal: after unrolling, limb index and shift are literals too -- a shift pair or a bit
+// field extract and a mask, where bits_at selects among the nine limbs
+template <int C>
+__device__ __forceinline__ u32 digit_at(const u32 (&l)[9], int w) {
+  const int bit = w * C, k = bit >> 5, sh = bit & 31;
+  u32 v = l[k] >> sh;
+  if (sh + C > 32) v |= l[k + 1] << (32 - sh);
+  return v & ((1u << C) - 1);
+}
+
+// the scalar out of its Montgomery form, split into sign and magnitude (|s| < 2^253); returns the sign.  The nine-limb reduction gives
+// s in [0, r] without a final subtraction (fr29.hip.hpp); (r - 1) / 2 - s borrows exactly when s is above the half, and r - r = 0.
+__device__ __forceinline__ bool scalar_magnitude(const Fr &mont, Fr &s) {
+  const u32 H[8] = {0xf8000000u, 0xa1f0fac9u, 0x3cdcb848u, 0x9419f424u, 0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};   // fr_gt_half's
+  s = fr29_from_mont_weak(mont);
+  u32 br = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) (void)zk_subc(H[k], s.l[k], br, &br);
+  const bool neg = br != 0;
+  if (neg) {
+    br = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s.l[k] = zk_subc(FrP::MOD[k], s.l[k], br, &br);
+  }
+  return neg;
+}
+
+// |s| + bias; returns the sign, and in `bits` the bit length of |s|: windows above bits / c + 1 hold zero digits (a negative digit
+// carries one into the next window, not further), that is the bias alone.  `high`: whether |s| has more than 32 bits.
+__device__ __forceinline__ bool biased_scalar(const Fr &mont, const BiasArg &B, u32 (&out)[9], int &bits, bool &high) {
+  Fr s;
+  const bool neg = scalar_magnitude(mont, s);
   bits = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k)
     if (s.l[k]) bits = 32 * k + 32 - __clz(s.l[k]);
+  high = (s.l[1] | s.l[2] | s.l[3] | s.l[4] | s.l[5] | s.l[6] | s.l[7]) != 0;
   u32 carry = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -82,16 +114,19 @@ __global__ void __launch_bounds__(64) k_basis_multiples(const G1Affine *__restri
 // Leaving a column, the workgroup appends to that column's partial list: with TREE one butterfly and one partial (calls of a
 // few columns: thousands of short visits per column, the fold must stay short); without, every thread stores its accumulator
 // as it is -- 256 partials per visit and no butterfly (eight dependent point additions with most lanes idle cost as much as
-// eleven useful ones), and no point-addition code besides the loop's in the kernel: 167 VGPRs (three waves per SIMD; rocprof
-// shows the arch / accumulation halves of the unified file), 12 bytes of scratch -- two values of the digit extraction that
-// live across the addition loop.  k_msm_table_fold sums the lists.
-template <bool TREE>
-__global__ void __launch_bounds__(256, TREE ? 1 : 3) k_msm_table(const Fr *__restrict__ scalars, size_t col_stride, size_t n, const G1Affine *__restrict__ T, int c, int W, BiasArg B,
+// eleven useful ones), and no point-addition code besides the loop's in the kernel: 168 VGPRs (three waves per SIMD; rocprof
+// shows the arch / accumulation halves of the unified file), no scratch.  k_msm_table_fold sums the lists.
+// C: the digit width as a literal for the widths msm.hip's table_kernel() names -- the window loop unrolled, every digit at a
+// literal limb and shift, one extraction pass; the same entries in the same order as the run-time width C = 0 writes
+// (profiles/msm_scalar_prep.md: the 136-column call of a k = 13 proof issues 4.2 % fewer VALU instructions, the 266-column call 12 %).
+template <bool TREE, int C /* the table's digit width as a literal, 0: whatever c_arg says */>
+__global__ void __launch_bounds__(256, TREE ? 1 : 3) k_msm_table(const Fr *__restrict__ scalars, size_t col_stride, size_t n, const G1Affine *__restrict__ T, int c_arg, int W_arg, BiasArg B,
                                                    unsigned P, unsigned cpc /* chunks per column */, unsigned n_cols, unsigned max_part,
                                                    G1X *__restrict__ partials /* [n_cols][max_part][TREE ? 1 : 256] */,
                                                    unsigned *__restrict__ n_part /* [n_cols] visits recorded, zero on entry */,
                                                    unsigned *__restrict__ col_next /* [n_cols] next chunk, zero on entry */,
                                                    unsigned *__restrict__ lists /* [gridDim.x][P * W] */, unsigned long long *__restrict__ adds) {
+  const int c = C ? C : c_arg, W = C ? table_windows(C) : W_arg;
   // the entry list of the chunk in flight: in global memory (written and read by this workgroup only: it stays in this CU's
   // L1 / this XCD's L2), not in LDS -- with no LDS to its name the kernel shares a CU with the NTT tile kernel (147 KB of the
   // 160), whose waves wait on LDS while these issue multiply-adds
@@ -156,16 +191,36 @@ __global__ void __launch_bounds__(256, TREE ? 1 : 3) k_msm_table(const Fr *__res
       const size_t i = (size_t)chunk * P + threadIdx.x;
       const bool valid = threadIdx.x < P && i < n;
       u32 sb[9];
-      bool neg = false;
-      unsigned long long mask = 0;
-      if (valid) {
-        int bits;
-        neg = biased_scalar(scalars[(size_t)col * col_stride + i], B, sb, bits);
+      bool neg = false, high = false;
+      int bits = 0;
+      if (valid) neg = biased_scalar(scalars[(size_t)col * col_stride + i], B, sb, bits, high);
+      // the windows with a non-zero digit, one bit each (W <= 32: c >= 8).  C != 0: one unrolled pass, every digit at a literal
+      // position, and the same unrolled loop writes the entries after the prefix sum, predicated on the mask bit -- the digit is
+      // derived again from its literal position (two instructions; holding seventeen of them would cost registers).  A window above
+      // a short scalar holds the bias alone and tests as zero, so the bound of the run-time loop is not needed per lane; the wave
+      // as a whole skips the windows that no magnitude below 2^32 reaches when none of its lanes has a longer one (two thirds of
+      // a proof's scalars are 0/1 and range cells).
+      constexpr int WS = table_short_windows(C), WC = table_windows(C);
+      u32 mask = 0;
+      bool wide = false;
+      if constexpr (C != 0) {
+        wide = __any(high) != 0;
+        if (valid) {
+#pragma unroll
+          for (int w = 0; w < WS; ++w)
+            if ((int)digit_at<C>(sb, w) != half) mask |= 1u << w;
+          if (wide) {
+#pragma unroll
+            for (int w = WS; w < WC; ++w)
+              if ((int)digit_at<C>(sb, w) != half) mask |= 1u << w;
+          }
+        }
+      } else if (valid) {
         const int wtop = min(W, bits / c + 2);
         for (int w = 0; w < wtop; ++w)
-          if ((int)bits_at(sb, w * c, c) != half) mask |= 1ull << w;
+          if ((int)bits_at(sb, w * c, c) != half) mask |= 1u << w;
       }
-      const unsigned mine = (unsigned)__popcll(mask);
+      const unsigned mine = (unsigned)__popc(mask);
       unsigned incl = mine;
 #pragma unroll
       for (int d = 1; d < 64; d <<= 1) {
@@ -177,13 +232,33 @@ __global__ void __launch_bounds__(256, TREE ? 1 : 3) k_msm_table(const Fr *__res
       unsigned off = incl - mine;
       for (unsigned v = 0; v < wv; ++v) off += wave_cnt[v];
       // table offsets relative to the chunk's first point (31 bits + sign: P * W * 2^(c-1) <= 256 * 32 * 2^14; the whole table of a
-      // 15-bit Lagrange half has more than 2^31 entries)
+      // 15-bit Lagrange half has more than 2^31 entries), in ascending order of the window within a thread
       const unsigned row0 = threadIdx.x * (unsigned)W;
-      while (mask) {
-        const int w = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const int d = (int)bits_at(sb, w * c, c) - half;
-        lst[off++] = (((row0 + (unsigned)w) << (c - 1)) + (unsigned)(d < 0 ? -d : d) - 1u) | ((neg != (d < 0)) ? 0x80000000u : 0u);
+      if constexpr (C != 0) {
+        unsigned base = (row0 << (C - 1)) - 1u;   // |d| >= 1 comes on top
+        // opaque, or base + (w << (C - 1)) is hoisted out of the chunk loop for every w: seventeen registers held across the
+        // addition loop, 40 bytes of them in scratch
+        asm volatile("" : "+v"(base));
+        const u32 flip = neg ? 0x80000000u : 0u;
+        auto entry = [&](int w) {
+          if ((mask >> w) & 1u) {
+            const int d = (int)digit_at<C>(sb, w) - half;
+            lst[off++] = (base + ((unsigned)w << (C - 1)) + (unsigned)(d < 0 ? -d : d)) | (((u32)d ^ flip) & 0x80000000u);
+          }
+        };
+#pragma unroll
+        for (int w = 0; w < WS; ++w) entry(w);
+        if (wide) {
+#pragma unroll
+          for (int w = WS; w < WC; ++w) entry(w);
+        }
+      } else {
+        while (mask) {
+          const int w = __builtin_ctz(mask);
+          mask &= mask - 1;
+          const int d = (int)bits_at(sb, w * c, c) - half;
+          lst[off++] = (((row0 + (unsigned)w) << (c - 1)) + (unsigned)(d < 0 ? -d : d) - 1u) | ((neg != (d < 0)) ? 0x80000000u : 0u);
+        }
       }
     }
     __syncthreads();
@@ -303,7 +378,8 @@ __global__ void __launch_bounds__(64) k_msm_sparse(const zkfhe_sparse_term *__re
     }
     u32 sb[9];
     int bits;
-    const bool neg = biased_scalar(s, B, sb, bits);
+    bool high;
+    const bool neg = biased_scalar(s, B, sb, bits, high);
     const int d = (int)lane < W ? (int)bits_at(sb, (int)lane * c, c) - half : 0;   // window = lane (W <= 64)
     if (d) {
       const G1Affine p = T[(((size_t)terms[t].row * W + lane) << (c - 1)) + (size_t)(d < 0 ? -d : d) - 1];
