@@ -3,6 +3,12 @@
 // table below -- written out from the loop of the dispatcher this header replaced, by number of stages above the 2^13 tile -- and
 // the buffer routing keeps the properties the kernels rely on.  Built and run by tests/test_ntt_plan_host.py (with the address and
 // undefined-behaviour sanitizers).
+//
+//   ntt_plan_check --passes    prints no verdict but the plans themselves, one line per pass, for log_n 14 .. 26 x {no coset, a table
+//                              (eight rows), shifts (four rows)} x LDS passes {on, off} x {out of place, in place}, forward:
+//                                log_n=19 coset=table lds=1 in_place=0 pass=0 kind=lds S=6 first=1 carries_coset=1 in=src out=work
+//                              A refused combination prints nothing.  tests/test_ntt_schedules_host.py holds these lines against the
+//                              shapes that the GPU tests run (tests/ntt_schedules.py).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -99,7 +105,25 @@ static void check(int log_n, bool inverse, bool in_place, NttCoset coset, unsign
   }
 }
 
-int main() {
+static int print_passes() {
+  static const char *const COSET[] = {"none", "table", "shifts"}, *const KIND[] = {"four_step", "lds", "fused", "stage"}, *const BUF[] = {"src", "dst", "work"};
+  for (int log_n = 14; log_n <= 26; ++log_n)
+    for (int coset = 0; coset < 3; ++coset)
+      for (int lds = 1; lds >= 0; --lds)
+        for (int in_place = 0; in_place < 2; ++in_place) {
+          const NttPlan p = ntt_plan(log_n, false, in_place, (NttCoset)coset, coset == NTT_COSET_PRE ? 8 : coset == NTT_COSET_SHIFTS ? 4 : 1, lds);
+          if (p.refused) continue;
+          for (int i = 0; i < p.n_passes; ++i) {
+            const NttPass &ps = p.pass[i];
+            printf("log_n=%d coset=%s lds=%d in_place=%d pass=%d kind=%s S=%d first=%d carries_coset=%d in=%s out=%s\n", log_n, COSET[coset], lds, in_place, i,
+                   KIND[ps.kind], ps.S, i == 0, (int)ps.coset, BUF[ps.in], BUF[ps.out]);
+          }
+        }
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc == 2 && !strcmp(argv[1], "--passes")) return print_passes();
   for (int log_n = 14; log_n <= 26; ++log_n)
     for (int inverse = 0; inverse < 2; ++inverse)
       for (int in_place = 0; in_place < 2; ++in_place)
