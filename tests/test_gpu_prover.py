@@ -30,18 +30,29 @@ def first_diff(a, b):
     return None if len(a) == len(b) else min(len(a), len(b)) // 32
 
 
+_ORACLE_TOY = {}
+
+
+def oracle_toy(transcript):
+    """The toy circuit (k = 9, N = 8) through the CPU oracle, seed b"seed-1": made once per transcript and shared."""
+    if transcript not in _ORACLE_TOY:
+        prm = C.BfvParams(N=8)
+        inp = synth_input(8, prm.Q, prm.T, prm.B, 1)
+        circ = H.BfvCircuit(inp, prm)
+        hcfg = H.auto_config(9, 9, circ, transcript=transcript)
+        srs_o = H.make_srs(9)
+        pk_o, _ = H.keygen_circuit(hcfg, circ, srs_o)
+        proof_o, inst_o = H.prove(hcfg, pk_o, srs_o, circ, b"seed-1")
+        assert H.verify(H.VerifyingKey(pk_o), srs_o, inst_o, proof_o)
+        _ORACLE_TOY[transcript] = (prm, inp, hcfg, srs_o, pk_o, proof_o, inst_o)
+    return _ORACLE_TOY[transcript]
+
+
 @pytest.mark.parametrize("transcript", ["poseidon", "blake2b"])
 def test_toy_proof_bytes_match_oracle(ctx, transcript):
     """Both transcripts: snark-verifier's Poseidon (what the reference proves with, examples/bfv.rs:311) and halo2's Blake2b."""
     import zk_fhe_amd as zk
-    prm = C.BfvParams(N=8)
-    inp = synth_input(8, prm.Q, prm.T, prm.B, 1)
-    circ = H.BfvCircuit(inp, prm)
-    hcfg = H.auto_config(9, 9, circ, transcript=transcript)
-    srs_o = H.make_srs(9)
-    pk_o, _ = H.keygen_circuit(hcfg, circ, srs_o)
-    proof_o, inst_o = H.prove(hcfg, pk_o, srs_o, circ, b"seed-1")
-    assert H.verify(H.VerifyingKey(pk_o), srs_o, inst_o, proof_o)
+    prm, inp, hcfg, srs_o, pk_o, proof_o, inst_o = oracle_toy(transcript)
     srs = zk.Srs(ctx, 9)
     zcfg = zk.BfvConfig(9, hcfg.n_gate0, hcfg.n_gate1, hcfg.n_lookup, hcfg.n_rlc, 9, transcript=transcript)
     pk = zk.BfvProvingKey(ctx, srs, json.dumps(inp), (8, prm.Q, prm.T, prm.B), zcfg)
@@ -66,6 +77,35 @@ def test_toy_proof_bytes_match_oracle(ctx, transcript):
     with pytest.raises(zk.ZkfheError):
         pk.prove(json.dumps(bad), b"seed-1")
     pk.destroy()
+    srs.destroy()
+
+
+def test_toy_proof_four_coset_key(ctx, monkeypatch):
+    """A key built with ZKFHE_CHECK_QUOTIENT=1 evaluates the quotient on all four cosets (partials of groups x 4 rows, the fourth column
+    of h_c for the degree check): the same bytes as the oracle and as the three-coset key, and a wrong witness is still refused."""
+    import zk_fhe_amd as zk
+    prm, inp, hcfg, srs_o, pk_o, proof_o, inst_o = oracle_toy("blake2b")
+    srs = zk.Srs(ctx, 9)
+    zcfg = zk.BfvConfig(9, hcfg.n_gate0, hcfg.n_gate1, hcfg.n_lookup, hcfg.n_rlc, 9, transcript="blake2b")
+    monkeypatch.delenv("ZKFHE_CHECK_QUOTIENT", raising=False)
+    pk3 = zk.BfvProvingKey(ctx, srs, json.dumps(inp), (8, prm.Q, prm.T, prm.B), zcfg)
+    monkeypatch.setenv("ZKFHE_CHECK_QUOTIENT", "1")   # read when a key is built
+    pk4 = zk.BfvProvingKey(ctx, srs, json.dumps(inp), (8, prm.Q, prm.T, prm.B), zcfg)
+    monkeypatch.delenv("ZKFHE_CHECK_QUOTIENT")
+    assert pk4.info()["vk_digest"] == pk_o.vk_digest
+    proof3, inst3, _ = pk3.prove(json.dumps(inp), b"seed-1")
+    proof4, inst4, _ = pk4.prove(json.dumps(inp), b"seed-1")
+    assert inst4 == inst_o and inst3 == inst_o
+    assert first_diff(proof4, proof_o) is None, "first differing 32-byte item: %s" % first_diff(proof4, proof_o)
+    assert proof4 == proof3
+    bad = dict(inp)
+    c0 = list(bad["c0"])
+    c0[1] = str((int(c0[1]) + 1) % prm.Q)
+    bad["c0"] = c0
+    with pytest.raises(zk.ZkfheError):
+        pk4.prove(json.dumps(bad), b"seed-1")
+    pk4.destroy()
+    pk3.destroy()
     srs.destroy()
 
 

@@ -1,5 +1,5 @@
 // keygen (README.md:28-38; halo2 keygen_vk / keygen_pk as driven by halo2-scaffold `run_eth`, reached from reference
-// examples/bfv.rs:311), the per-context prover workspace, and the proving / verifying key files.
+// examples/bfv.rs:311) and the proving / verifying key files.
 #include "prover_internal.hpp"
 
 std::vector<BigInt> GpuPolyMul::mul_u64(const std::vector<uint64_t> &a, const std::vector<uint64_t> &b) {
@@ -33,110 +33,11 @@ const U256 *GpuPolyMul::mul_u64_raw(const std::vector<uint64_t> &a, const std::v
   return host;
 }
 
-int up(zkfhe_ctx *ctx, Workspace *ws, void *dst, const void *src, size_t bytes) {
-  if (!bytes) return ZKFHE_OK;
-  const size_t need = (bytes + 63) & ~(size_t)63;
-  if (!ws->ring || ws->ring_off + need > Workspace::RING_BYTES) return zkfhe_upload(ctx, dst, src, bytes);
-  uint8_t *slot = ws->ring + ws->ring_off;
-  ws->ring_off += need;
-  memcpy(slot, src, bytes);
-  ZK_HIP(ctx, zk_memcpy_async(ctx, dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return ZKFHE_OK;
-}
-
-int alloc_workspace(zkfhe_ctx *ctx, const CircuitConfig &c, Workspace *ws, int ext_rows) {
-  const size_t n = c.n(), ne = (size_t)ext_rows * n, col = n * 32, ecol = ne * 32;
-  const size_t n_all = (size_t)c.n_advice() + 3 * c.n_lookup + c.n_chunks() + 1;
-  ws->n_all = n_all;
-  CK(ws->all_l.alloc(ctx, n_all * col));
-  CK(ws->all_ext.alloc(ctx, n_all * ecol));
-  {
-    size_t o = 0;
-    auto take = [&](View &l, View &e, size_t cols) {
-      l.p = (char *)ws->all_l.p + o * col;
-      e.p = (char *)ws->all_ext.p + o * ecol;
-      o += cols;
-    };
-    take(ws->adv_l, ws->adv_ext, c.n_advice());
-    take(ws->la_l, ws->la_ext, c.n_lookup);
-    take(ws->ls_l, ws->ls_ext, c.n_lookup);
-    take(ws->pz_l, ws->pz_ext, c.n_chunks());
-    take(ws->lz_l, ws->lz_ext, c.n_lookup);
-    take(ws->inst_l, ws->inst_ext, 1);
-  }
-  ZK_HIP(ctx, zk_memset_async(ctx, ws->inst_l.p, 0, col, ctx->stream));   // the prover only ever writes the public-input rows
-  ws->inst_count = 0;
-  CK(ws->tmp_c.alloc(ctx, std::max<size_t>(n_all, c.n_perm()) * col));
-  {
-    // quotient partials: one row set (ext_rows * n values) per expression group -- the groups prove.hip cuts (8 gates, all RLC
-    // gates, 32 chaining terms, 4 permutation chunks, 3 lookups per group; a rank of a sharded proof evaluates a contiguous share:
-    // at most one more group per kind), not a flat 96 x 4 columns (6 GB at k = 19).  The buffer doubles as the receive side of the
-    // sharded SHPLONK gather (ranks x rotation sets columns) and as scratch of the evaluation round: at least 96 columns.
-    const size_t groups = ((size_t)c.n_gate() + 7) / 8 + 1 + 2 + ((size_t)c.n_chunks() + 31) / 32 + ((size_t)c.n_chunks() + 3) / 4 + ((size_t)c.n_lookup + 2) / 3 + 8;
-    CK(ws->partials.alloc(ctx, std::max<size_t>(groups * (size_t)ext_rows, 96) * col));
-  }
-  CK(ws->h_ext.alloc(ctx, 4 * col));
-  CK(ws->h_c.alloc(ctx, 4 * col));
-  CK(ws->misc.alloc(ctx, 32 * col));
-  CK(ws->points.alloc(ctx, std::max<size_t>(n_all, c.n_perm()) * 64 + 64));
-  // the factors of the permutation products' ratios and, behind them, the lookup products': inverted and multiplied up together
-  CK(ws->num.alloc(ctx, ((size_t)c.n_chunks() + c.n_lookup) * col));
-  CK(ws->den.alloc(ctx, ((size_t)c.n_chunks() + c.n_lookup) * col));
-  // ws->small is carved up at fixed offsets (prove.hip): [0, 128 K) beta * delta^i per permutation column, [128 K, 256 K) chunk /
-  // lookup totals, 128 KB each for the quotient groups, y powers and inverses, then pointer / scalar / point lists, the SHPLONK
-  // sets (700 K), gadget arguments (768 K) and the early-commitment patch lists (900 K, 920 K): the widest lists must fit
-  if ((size_t)c.n_perm() > 4096 || (size_t)c.n_chunks() + c.n_lookup > 4096)
-    return zk_fail_msg(ctx, ZKFHE_EINVAL, "configuration too wide for the prover workspace (more than 4096 permutation columns)");
-  CK(ws->small.alloc(ctx, 1 << 20));
-  const size_t max_items = (size_t)c.n_advice() + c.n_fixed() + 2 + c.n_perm() + c.n_chunks() + 3 * c.n_lookup;
-  CK(ws->jobs.alloc(ctx, max_items * sizeof(zkp::EvalJob) + max_items * (sizeof(void *) + 32) + 256));
-  CK(ws->evout.alloc(ctx, (max_items + 64) * 4 * 32));   // + the padding of the sharded evaluations' all-gather (equal slices per rank)
-  CK(ws->polyio.alloc(ctx, 4 * c.n() * 32));
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_adv, (size_t)c.n_advice() * col, hipHostMallocDefault));
-  memset(ws->host_adv, 0, (size_t)c.n_advice() * col);
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_blind, std::max<size_t>(2 * c.n_lookup, 2) * col, hipHostMallocDefault));
-  return ZKFHE_OK;
-}
-
-void free_workspace(Workspace *ws) {
-  (void)hipSetDevice(ws->all_l.device);
-  for (DevBuf *b : ws->all()) b->release();
-  for (void *h : {(void *)ws->host_adv, (void *)ws->host_blind, (void *)ws->host_pool, (void *)ws->host_poly, (void *)ws->host_pts, (void *)ws->ring, (void *)ws->host_rand_pt,
-                  (void *)ws->host_early, (void *)ws->host_early_err, (void *)ws->host_out})
-    if (h) (void)hipHostFree(h);
-  if (ws->ev_pts) (void)hipEventDestroy(ws->ev_pts);
-  if (ws->ev_rand) (void)hipEventDestroy(ws->ev_rand);
-  if (ws->ev_early) (void)hipEventDestroy(ws->ev_early);
-  if (ws->aux) (void)zkfhe_ctx_destroy(ws->aux);
-  delete ws;
-}
-
-int get_workspace(zkfhe_ctx *ctx, zkfhe_bfv_pk *pk, Workspace **out) {
-  std::lock_guard<std::mutex> lock(pk->mu);
-  auto it = pk->workspaces.find(ctx->uid);
-  if (it == pk->workspaces.end()) {
-    Workspace *ws = new Workspace();
-    int rc = alloc_workspace(ctx, pk->cfg, ws, pk->ext_rows);
-    if (rc) {
-      for (DevBuf *b : ws->all()) b->release();
-      delete ws;
-      return rc;
-    }
-    it = pk->workspaces.emplace(ctx->uid, ws).first;
-  }
-  if (it->second->all_l.device != ctx->device) return zk_fail_msg(ctx, ZKFHE_EINVAL, "prover workspace belongs to another device");
-  *out = it->second;
-  return ZKFHE_OK;
-}
-
 // coefficient form of `count` Lagrange columns (copy into tmp, iNTT), then coset-extend into ext
 int extend_cols(zkfhe_ctx *ctx, zkfhe_bfv_pk *pk, Workspace *ws, const Fr *lagr, size_t count, Fr *ext) {
   if (!count) return ZKFHE_OK;
-  const int rows = pk->ext_rows;
-  const size_t n = pk->cfg.n();
   const Fr g = mont_u64(COSET_G);
-  (void)n;
-  return zk_extend_lagrange(ctx, lagr, ws->tmp_c.fr(), ext, count, (int)pk->cfg.k, 2, g, rows);
+  return zk_extend_lagrange(ctx, lagr, ws->extend_scratch(), ext, count, (int)pk->cfg.k, 2, g, pk->ext_rows);
 }
 
 // extended-coset evaluations of the fixed / sigma columns, l_0 / l_last / l_active and X on the coset: derived from the
@@ -159,8 +60,8 @@ static int build_resident_tables(zkfhe_ctx *ctx, zkfhe_bfv_pk *pk, Workspace *ws
     l[0] = fe::one();
     l[n + u] = fe::one();
     for (size_t i = 0; i < u; ++i) l[2 * n + i] = fe::one();
-    CK(upload_canon(ctx, ws->misc.fr(), l.data(), 3 * n));
-    CK(extend_cols(ctx, pk, ws, ws->misc.fr(), 3, pk->l_ext.fr()));
+    CK(upload_canon(ctx, ws->key_l_rows(), l.data(), 3 * n));
+    CK(extend_cols(ctx, pk, ws, ws->key_l_rows(), 3, pk->l_ext.fr()));
   }
   {
     const Fr wext = zk_fr_root_of_unity((int)cfg.k + 2);

@@ -6,40 +6,6 @@
 // evaluations at x, SHPLONK polynomials.
 #include "prover_internal.hpp"
 
-// buffers of the GPU witness generator (sizes known only after keygen)
-int alloc_witness_buffers(zkfhe_ctx *ctx, const zkfhe_bfv_pk *pk, Workspace *ws) {
-  if (ws->stream.p) return ZKFHE_OK;
-  const size_t N = pk->prm.N;
-  CK(ws->stream.alloc(ctx, (pk->gate1_cells + 8) * 32));
-  CK(ws->pool.alloc(ctx, 40 * (2 * N + 8) * 32));
-  CK(ws->invtmp.alloc(ctx, (pk->n_inv_slots + 8) * 32));
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_pool, 24 * (2 * N + 8) * 32, hipHostMallocDefault));
-  ws->host_poly_len = 2 * N + 8;
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_poly, ws->host_poly_len * 32, hipHostMallocDefault));
-  CK(ws->wblind.alloc(ctx, 256));   // the lookup-permutation error flag
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->ring, Workspace::RING_BYTES, hipHostMallocDefault));
-  CK(ws->dev_ring.alloc(ctx, Workspace::RING_BYTES));
-  {
-    const CircuitConfig &c = pk->cfg;
-    const size_t max_items = (size_t)c.n_advice() + c.n_fixed() + 2 + c.n_perm() + c.n_chunks() + 3 * c.n_lookup;
-    ws->out_pts_cap = std::max<size_t>(ws->n_all, c.n_perm()) + 16;
-    ws->out_ev_off = ws->out_pts_cap * PT_SLOT;
-    ws->out_ev_cap = max_items * 4;
-    ws->out_flag_off = ws->out_ev_off + ws->out_ev_cap * 32;
-    ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_out, ws->out_flag_off + 256, hipHostMallocDefault));
-    memset(ws->host_out, 0, ws->out_flag_off + 256);
-  }
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_pts, ((size_t)pk->cfg.n_gate0 + 1) * PT_SLOT, hipHostMallocDefault));
-  ZK_HIP(ctx, hipEventCreateWithFlags(&ws->ev_pts, hipEventDisableTiming | hipEventBlockingSync));
-  ZK_HIP(ctx, hipEventCreateWithFlags(&ws->ev_rand, hipEventDisableTiming | hipEventBlockingSync));
-  ZK_HIP(ctx, hipEventCreateWithFlags(&ws->ev_early, hipEventDisableTiming | hipEventBlockingSync));
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_early, ((size_t)pk->cfg.n_advice() + 2 * pk->cfg.n_lookup + 16) * PT_SLOT, hipHostMallocDefault));
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_early_err, 64, hipHostMallocDefault));
-  ZK_HIP(ctx, hipHostMalloc((void **)&ws->host_rand_pt, PT_SLOT, hipHostMallocDefault));
-  if (zkfhe_ctx_create(ctx->device, nullptr, &ws->aux)) return zk_fail_msg(ctx, ZKFHE_EHIP, std::string("auxiliary context: ") + zkfhe_last_error(nullptr));
-  return ZKFHE_OK;
-}
-
 namespace {
 
 // counting-sort restatement of halo2's permute_expression_pair for 8-bit tables
@@ -612,6 +578,8 @@ struct Proof {
   std::vector<OpenItem> items;    // the opened polynomials, in evaluation-write order (shplonk.hpp OpenLayout)
   size_t idx_H = 0;               // H(X) among them
   double t_wit = 0;               // when the phase-1 witness was queued: the end of the first of prove_impl's timings
+  // the random polynomial, coefficients and Lagrange form: written on the auxiliary stream by setup() (one GPU), read from random_poly() on
+  Fr *const rand_c = ws->rand_c(), *const rand_l = ws->rand_l();
 
   int rng_fill(hipStream_t stream, uint64_t ctr0, uint64_t ctr_col_stride, Fr *dst, size_t per_col, size_t col_stride, size_t n_cols) {
     if (!per_col || !n_cols) return ZKFHE_OK;
@@ -643,7 +611,6 @@ struct Proof {
     early_rand = !srs->sharded();
     if (!early_rand) return ZKFHE_OK;
     zkfhe_ctx *aux = ws->aux;
-    Fr *rand_c = ws->misc.fr() + 8 * n, *rand_l = ws->misc.fr() + 9 * n;
     CK(rng_fill(aux->stream, ctr_rand, 0, rand_c, n, n, 1));
     // the commitment is stored by the MSM's last kernel into pinned memory: no copy command
     if (int rc = zkfhe_msm_batch_xyzz(aux, srs->g, (const zkfhe_fr *)rand_c, 1, (zkfhe_g1_xyzz *)ws->host_rand_pt))
@@ -826,13 +793,12 @@ struct Proof {
   int phase1_early_finish(const U256 evals[12], size_t n_adv1, std::vector<AffinePoint> &pts) {
     const GpuPhase1::PatchPlan plan = g1.patch_plan();
     const size_t np = plan.columns.size();
-    Fr *patch_cols = ws->tmp_c.fr();
+    Fr *patch_cols = ws->patch_cols();
     std::vector<zkfhe_sparse_term> terms;
     const bool sparse = !srs->sharded() && zkfhe_basis_has_multiples(srs->g_lagrange);
     CK(g1.patch(evals, plan, patch_cols, sparse ? &terms : nullptr));
     CK(blind_and_upload(cfg.adv_rlc0(), cfg.n_advice()));
-    // the corrections sit behind the early commitments in ws->points; the last slot of that buffer belongs to the random
-    // polynomial's commitment (auxiliary stream)
+    // the correction points go into the pinned result block: [patched gate columns | RLC columns]
     if (np + cfg.n_rlc > ws->out_pts_cap)
       return zk_fail_msg(ctx, ZKFHE_EINVAL, "early phase-1 commitment: correction points do not fit the workspace (set ZKFHE_EARLY_P1=0)");
     uint8_t *fix_dev = ws->out_pts();   // pinned: the correction points are read by the host right below
@@ -913,7 +879,7 @@ struct Proof {
     pa.n = n;
     return pa;
   }
-  // running products per column; long columns in segments (prover_kernels.hip.hpp), the segment products in the dead `den` buffer
+  // running products per column; long columns in segments (prover_kernels.hip.hpp), the segment products in `den`, whose factors the inversion consumed
   // blind: the blinding rows u + 1 .. n - 1 of the product columns (drawn per column, in order)
   int prefix_products(const Fr *ratio, Fr *z, size_t n_cols, const zkp::RngRows &blind, Fr *totals_dev) {
     const size_t nb_z = nbl - 1;
@@ -924,8 +890,8 @@ struct Proof {
     }
     CK(rng_fill(ctx->stream, blind.ctr0, blind.ctr_col_stride, z + (u + 1), nb_z, n, n_cols));   // long columns: the blinding rows keep their own launch
     const unsigned seg_len = 32768, segs = (unsigned)(n / seg_len);   // u < n: the output row z[u] lies inside the last segment
-    Fr *seg = ws->den.fr();
-    if ((size_t)n_cols * segs * 32 > ws->den.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "prefix products: segment buffer too small");
+    Fr *seg = ws->prefix_segments();
+    if ((size_t)n_cols * segs * 32 > ws->cap(wsl::PREFIX_SEGMENTS)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "prefix products: segment buffer too small");
     zkp::k_prefix_seg_totals<<<dim3(segs, (unsigned)n_cols), 1024, 0, ctx->stream>>>(ratio, seg, n, (unsigned)u, seg_len);
     ZK_LAUNCH_CHECK(ctx);
     zkp::k_prefix_seg_scan<<<(unsigned)((n_cols + 63) / 64), 64, 0, ctx->stream>>>(seg, segs, (unsigned)n_cols, totals_dev);
@@ -945,7 +911,7 @@ struct Proof {
     }
     U256 dcan;
     memcpy(dcan.l, DELTA_CANON, 32);
-    beta_delta_dev = (Fr *)ws->small.p;
+    beta_delta_dev = ws->beta_delta();
     const size_t nch = cfg.n_chunks(), nb_z = nbl - 1;
     if (n <= 65536 && !ctx->chain_serial) return grand_products_side_by_side(mont(dcan));
     zkp::k_powers<<<1, 256, 0, ctx->stream>>>(beta, mont(dcan), beta_delta_dev, cfg.n_perm());
@@ -953,7 +919,7 @@ struct Proof {
     zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(perm_args(), ws->num.fr(), ws->den.fr());
     ZK_LAUNCH_CHECK(ctx);
     CK(zkfhe_fr_batch_invert_mul(ctx, (const zkfhe_fr *)ws->den.p, (zkfhe_fr *)ws->num.p, nch * n));   // num <- num / den: the ratios, in one kernel
-    Fr *totals_dev = (Fr *)ws->small.p + 4096;
+    Fr *totals_dev = ws->chunk_totals();
     CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch, blind_rows(ctr_pz, nb_z), totals_dev));
     int *const closes = ws->out_flags();   // pinned: [0] permutation, [1] lookups -- read after the commitment of the products below
     closes[0] = closes[1] = 1;
@@ -991,7 +957,7 @@ struct Proof {
     zkp::k_perm_num_den<<<grid_for(ctx, nch * n), 256, 0, ctx->stream>>>(perm_args(), ws->num.fr(), ws->den.fr());
     ZK_LAUNCH_CHECK(ctx);
     CK(zk_fr_batch_invert_mul_joined(ctx, ws->den.fr(), ws->num.fr(), (nch + nl) * n));   // every ratio of both arguments
-    Fr *totals_dev = (Fr *)ws->small.p + 4096;   // [n_chunks | n_lookup]
+    Fr *totals_dev = ws->chunk_totals();   // [n_chunks | n_lookup]
     CK(prefix_products(ws->num.fr(), ws->pz_l.fr(), nch + nl, blind_rows(ctr_pz, nb_z), totals_dev));   // pz | lz contiguous
     int *const closes = ws->out_flags();
     closes[0] = closes[1] = 1;
@@ -1014,7 +980,6 @@ struct Proof {
   // ------------------------------------------------------------ vanishing: random polynomial (coefficient form)
   int random_poly() {
     // committed at the start of the proof on the auxiliary stream ("random polynomial, early"): the last n draws of the stream
-    Fr *rand_c = ws->misc.fr() + 8 * n;
     if (early_rand) {
       ZK_HIP(ctx, hipEventSynchronize(ws->ev_rand));
       ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ws->ev_rand, 0));   // later reads of rand_c on the main stream
@@ -1030,13 +995,6 @@ struct Proof {
     return ZKFHE_OK;
   }
   // ------------------------------------------------------------ quotient
-  // the buffer of the gathered shares of a sharded proof (quotient rows, SHPLONK sets), grown to `bytes`
-  int grow_qgather(size_t bytes) {
-    if (ws->qgather.bytes >= bytes) return ZKFHE_OK;
-    CK(zkfhe_sync(ctx));
-    ws->qgather.release();
-    return ws->qgather.alloc(ctx, bytes);
-  }
   // once the gathers are queued: dst[j] = the sum of the W_sh shares of slot j of ws->qgather ([slot][rank][n]), j < slots
   int sum_shares(size_t slots, Fr *dst) {
     CK(zkfhe_comm_join(ctx, srs->comm, 0));
@@ -1060,7 +1018,7 @@ struct Proof {
     qa.xs = pk->xs_ext.fr();
     qa.beta_delta = beta_delta_dev;
     qa.groups = groups_dev;
-    qa.partials = ws->partials.fr();
+    qa.partials = ws->quotient_partials();
     qa.y = y;
     qa.beta = beta;
     qa.gamma = gamma;
@@ -1091,7 +1049,7 @@ struct Proof {
       zkp::k_quotient_partials<<<dim3(blocks, (unsigned)G), 256, 0, ctx->stream>>>(qa);
       ZK_LAUNCH_CHECK(ctx);
     }
-    zkp::k_quotient_combine<<<blocks, 256, 0, ctx->stream>>>(ws->partials.fr(), ypow_dev, (unsigned)G, zinv_dev, k, qa.rows, pt0, count, ws->h_ext.fr());
+    zkp::k_quotient_combine<<<blocks, 256, 0, ctx->stream>>>(ws->quotient_partials(), ypow_dev, (unsigned)G, zinv_dev, k, qa.rows, pt0, count, ws->h_ext.fr());
     ZK_LAUNCH_CHECK(ctx);
     return ZKFHE_OK;
   }
@@ -1161,7 +1119,7 @@ struct Proof {
     // (The same expressions cut by COLUMN BLOCK instead of by kind -- k_quotient_blocks, round 5 -- read a quarter less and were 29 %
     // slower: tools/exp/patches/quotient_blocks.patch, profiles/r5_probes.md section 2.)
     const size_t E = e, G = groups.size();
-    if (G > 96 || G * n * (size_t)q_rows * 32 > ws->partials.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many quotient groups for the workspace");
+    if (G > 96 || G * n * (size_t)q_rows * 32 > ws->cap(wsl::QUOTIENT_PARTIALS)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many quotient groups for the workspace");
     std::vector<Fr> ypow(G);
     for (size_t g = 0; g < G; ++g) ypow[g] = zk::zk_fr_to_29(fr_pow(y, E - 1 - last_e[g]));   // 2^261 form: constant operands of k_quotient_combine
     if (groups.empty()) groups.push_back(zkp::QGroup{});     // a rank that owns nothing still stages a (unread) entry
@@ -1185,7 +1143,7 @@ struct Proof {
       // -- field addition is not an RCCL reduction either.  One coset row at a time: the share of row k1 (n values: 16 MB at k = 19)
       // goes onto the communicator's stream as soon as it is formed and travels over xGMI while the groups of row k1 + 1 are
       // evaluated; only the last row's gather is exposed.  (The callback transport of the tests completes each gather in place.)
-      CK(grow_qgather((size_t)W_sh * npts * 32));
+      CK(grow_qgather(ctx, ws, (size_t)W_sh * npts * 32));
       for (int k1 = 0; k1 < q_rows; ++k1) {
         CK(launch_quotient(qa, (size_t)k1 * n, n, G, ypow_dev, zinv_dev));
         CK(zkfhe_comm_all_gather_async(ctx, srs->comm, ws->h_ext.fr() + (size_t)k1 * n, ws->qgather.fr() + (size_t)k1 * W_sh * n, n * 32));
@@ -1197,7 +1155,7 @@ struct Proof {
       CK(zkfhe_coset_ntt_batch(ctx, (const zkfhe_fr *)ws->h_ext.p, (zkfhe_fr *)ws->h_c.p, 1, (int)k, 2, (const zkfhe_fr *)&g, 1));
     } else {
       // three size-n inverse transforms, then the 3x3 Vandermonde solve per coefficient (prover_kernels.hip.hpp: k_ext3_combine)
-      Fr *rows3 = ws->partials.fr();            // the partials are dead after the combine; 3n values
+      Fr *rows3 = ws->ext3_rows();              // in the partials, dead after the combine; 3n values
       const Fr *pw = pk->ext3_pw.fr();           // (g w_ext^t)^-i, resident in the key
       CK(zkfhe_ntt_batch_to(ctx, (const zkfhe_fr *)ws->h_ext.p, (zkfhe_fr *)rows3, 3, (int)k, 1));
       const Fr c[3] = {fr_pow(g, n), fr_pow(g * wext, n), fr_pow(g * wext * wext, n)};   // (g w_ext^t)^n
@@ -1208,7 +1166,7 @@ struct Proof {
     if (q_rows == 4) {
       // the quotient must have degree < 3n: a non-zero top quarter means a violated constraint
       std::vector<U256> top(8);
-      CK(zkfhe_download(ctx, top.data(), ws->h_c.fr() + 3 * n, 8 * 32));
+      CK(zkfhe_download(ctx, top.data(), ws->quotient_top(), 8 * 32));
       for (const auto &v : top)
         if (!v.is_zero()) return zk_fail_msg(ctx, ZKFHE_EINVAL, "quotient degree too high: a constraint is violated");
     }
@@ -1221,14 +1179,14 @@ struct Proof {
     items.push_back(it);
   }
   // dst = sum over m < msz of pw[m] * (column pp[m]), n rows; pw in the 2^261 form.  Long lists in chunks of 48 members (partial
-  // sums in the dead quotient buffer), then one small reduction
+  // sums in the quotient's partials buffer, dead by then), then one small reduction
   int lincomb(const Fr *const *pp, const Fr *pw, unsigned msz, Fr *dst) {
     const unsigned per = 48, chunks = (msz + per - 1) / per;
-    if (chunks > 1 && (size_t)chunks * n * 32 <= ws->partials.bytes) {
+    if (chunks > 1 && (size_t)chunks * n * 32 <= ws->cap(wsl::LINCOMB_SUMS)) {
       dim3 lg(grid_for(ctx, n), chunks);
-      zkp::k_lincomb_ptrs_chunked<<<lg, 256, 0, ctx->stream>>>(pp, pw, msz, per, n, ws->partials.fr());
+      zkp::k_lincomb_ptrs_chunked<<<lg, 256, 0, ctx->stream>>>(pp, pw, msz, per, n, ws->lincomb_sums());
       ZK_LAUNCH_CHECK(ctx);
-      zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->partials.fr(), chunks, n, dst);
+      zkp::k_sum_rows<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(ws->lincomb_sums(), chunks, n, dst);
     } else {
       zkp::k_lincomb_ptrs<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(pp, pw, msz, n, dst);
     }
@@ -1236,7 +1194,7 @@ struct Proof {
     return ZKFHE_OK;
   }
   int evaluations() {
-    Fr *rand_c = ws->misc.fr() + 8 * n, *rand_l = ws->misc.fr() + 9 * n, *H_c = ws->misc.fr() + 10 * n, *H_l = ws->misc.fr() + 11 * n;
+    Fr *H_c = ws->H_c(), *H_l = ws->H_l();
     const Fr xn = fr_pow(x, n);
     const Fr w = dom->omega;
     pts_rot[0] = x;
@@ -1276,7 +1234,7 @@ struct Proof {
     STAGE(sc_dev, Fr, ws, sc, sizeof(sc));
     STAGE(pts_dev, Fr, ws, pts_rot, sizeof(pts_rot));   // the six evaluation points go up with the same flush
     STAGE(jobs_dev, zkp::EvalJob, ws, jobs.data(), jobs.size() * sizeof(zkp::EvalJob));   // ... and so does the evaluation job list
-    Fr *bw = ws->misc.fr();  // [6][n] barycentric weights
+    Fr *bw = ws->bary_weights();  // [6][n]
     const bool side_by_side = n <= 65536 && !ctx->chain_serial;   // short rows: H(X) and the weights' denominators (which depend on x alone) in one launch
     if (side_by_side) {
       const chain::Job hjob{0, 3, 0, -1};
@@ -1306,20 +1264,20 @@ struct Proof {
     const bool shard_open = W_sh > 1 && k >= 14;
     const size_t per_rank = shard_open ? (jobs.size() + W_sh - 1) / W_sh : jobs.size();
     const size_t j_lo = shard_open ? std::min(jobs.size(), per_rank * r_sh) : 0, j_hi = shard_open ? std::min(jobs.size(), j_lo + per_rank) : jobs.size();
-    if (shard_open && (per_rank * W_sh * 4 * 32 > od.bytes || per_rank * (W_sh + 1) * 4 * 32 > ws->h_ext.bytes))
+    if (shard_open && (per_rank * W_sh * 4 * 32 > od.bytes || per_rank * (W_sh + 1) * 4 * 32 > ws->cap(wsl::EVAL_SLICE)))
       return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many ranks for the evaluation gather buffers");
-    Fr *ev_dst = shard_open ? ws->h_ext.fr() : od.fr();   // my slice first (the quotient's extended values are dead by now)
+    Fr *ev_dst = shard_open ? ws->eval_slice() : od.fr();   // my slice first (the quotient's extended values are dead by now)
     // long columns: 16 row slices per job (partial sums in the dead quotient buffer), then one small reduction
-    const unsigned slices = (n > 32768 && (size_t)16 * jobs.size() * 4 * 32 <= ws->partials.bytes) ? 16u : 1u;
+    const unsigned slices = (n > 32768 && (size_t)16 * jobs.size() * 4 * 32 <= ws->cap(wsl::EVAL_SLICES)) ? 16u : 1u;
     if (j_hi > j_lo) {
       const zkp::EvalJob *jp = jobs_dev + j_lo;
       const unsigned nj = (unsigned)(j_hi - j_lo);
       if (slices == 1) {
         zkp::k_eval_jobs<<<nj, 256, 0, ctx->stream>>>(jp, bw, n, ev_dst + (shard_open ? 0 : j_lo * 4));
       } else {
-        zkp::k_eval_jobs<<<dim3(nj, slices), 256, 0, ctx->stream>>>(jp, bw, n, ws->partials.fr());
+        zkp::k_eval_jobs<<<dim3(nj, slices), 256, 0, ctx->stream>>>(jp, bw, n, ws->eval_slices());
         ZK_LAUNCH_CHECK(ctx);
-        zkp::k_sum_rows<<<grid_for(ctx, (size_t)nj * 4), 256, 0, ctx->stream>>>(ws->partials.fr(), slices, (size_t)nj * 4, ev_dst + (shard_open ? 0 : j_lo * 4));
+        zkp::k_sum_rows<<<grid_for(ctx, (size_t)nj * 4), 256, 0, ctx->stream>>>(ws->eval_slices(), slices, (size_t)nj * 4, ev_dst + (shard_open ? 0 : j_lo * 4));
       }
       ZK_LAUNCH_CHECK(ctx);
     }
@@ -1350,8 +1308,8 @@ struct Proof {
     std::vector<int> all_rots;
     const std::vector<OpenSet> sets = intermediate_sets(layout, open_queries(cfg, layout), all_rots);
     const size_t ns = sets.size();
-    Fr *F = ws->misc.fr() + 12 * n;  // [ns][n]
-    if (ns > 8) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many rotation sets");
+    Fr *F = ws->sh_F();  // [ns][n]
+    if (ns > wsl::MAX_SETS) return zk_fail_msg(ctx, ZKFHE_EINVAL, "too many rotation sets");
     std::vector<zkp::ShSet> shsets(ns);
     // pointer and scalar tables of every set are staged first and go up with one flush; then the launches
     std::vector<const Fr *const *> set_ptrs(ns);
@@ -1404,12 +1362,10 @@ struct Proof {
       vj = vj * v;
     }
     STAGE(sets_dev, zkp::ShSet, ws, shsets.data(), ns * sizeof(zkp::ShSet));
-    Fr *zs = ws->misc.fr() + 20 * n;   // [ns][n]
-    Fr *hq = ws->misc.fr() + 28 * n;   // [n]
-    Fr *Wq = ws->misc.fr() + 29 * n;   // [n]
-    Fr *dinv = ws->misc.fr() + 30 * n; // [n]
+    Fr *zs = ws->sh_zs();   // [ns][n]
+    Fr *hq = ws->sh_hq(), *Wq = ws->sh_Wq(), *dinv = ws->sh_dinv();   // [n] each
     if (side_by_side) {
-      if ((size_t)plan.slots * n * 32 > ws->partials.bytes) return zk_fail_msg(ctx, ZKFHE_EINVAL, "SHPLONK: partial sums do not fit the quotient buffer");
+      if ((size_t)plan.slots * n * 32 > ws->cap(wsl::LINCOMB_SUMS)) return zk_fail_msg(ctx, ZKFHE_EINVAL, "SHPLONK: partial sums do not fit the quotient buffer");
       STAGE(ptrs_dev, const Fr *, ws, all_ptrs.data(), all_ptrs.size() * sizeof(void *));
       STAGE(pw_dev, Fr, ws, all_pw.data(), all_pw.size() * 32);
       STAGE(jobs_dev, chain::Job, ws, plan.jobs.data(), plan.jobs.size() * sizeof(chain::Job));
@@ -1420,16 +1376,16 @@ struct Proof {
       // k_sh_zs rides along while the launch cannot reach the 7 waves per SIMD its registers allow (a workgroup is 4 waves, a CU has 4
       // SIMDs); a fuller launch keeps the jobs at their own 8 waves and k_sh_zs in a launch of its own
       if ((size_t)gx * (nj + tail_rows) <= (size_t)7 * ctx->num_cu) {
-        zkp::k_chain_jobs<zkp::TAIL_ZS><<<dim3(gx, nj + tail_rows), 256, 0, ctx->stream>>>(jobs_dev, nj, ptrs_dev, pw_dev, n, F, ws->partials.fr(), sets_dev, (unsigned)ns, dom->fwd, zs);
+        zkp::k_chain_jobs<zkp::TAIL_ZS><<<dim3(gx, nj + tail_rows), 256, 0, ctx->stream>>>(jobs_dev, nj, ptrs_dev, pw_dev, n, F, ws->lincomb_sums(), sets_dev, (unsigned)ns, dom->fwd, zs);
         ZK_LAUNCH_CHECK(ctx);
       } else {
-        zkp::k_chain_jobs<zkp::TAIL_NONE><<<dim3(gx, nj), 256, 0, ctx->stream>>>(jobs_dev, nj, ptrs_dev, pw_dev, n, F, ws->partials.fr(), nullptr, 0, nullptr, nullptr);
+        zkp::k_chain_jobs<zkp::TAIL_NONE><<<dim3(gx, nj), 256, 0, ctx->stream>>>(jobs_dev, nj, ptrs_dev, pw_dev, n, F, ws->lincomb_sums(), nullptr, 0, nullptr, nullptr);
         ZK_LAUNCH_CHECK(ctx);
         zkp::k_sh_zs<<<grid_for(ctx, ns * n), 256, 0, ctx->stream>>>(sets_dev, (unsigned)ns, dom->fwd, n, zs);
         ZK_LAUNCH_CHECK(ctx);
       }
       if (!plan.sums.empty()) {
-        zkp::k_chain_sums<<<dim3(gx, (unsigned)plan.sums.size()), 256, 0, ctx->stream>>>(sums_dev, ws->partials.fr(), n, F);
+        zkp::k_chain_sums<<<dim3(gx, (unsigned)plan.sums.size()), 256, 0, ctx->stream>>>(sums_dev, ws->lincomb_sums(), n, F);
         ZK_LAUNCH_CHECK(ctx);
       }
     } else {
@@ -1437,7 +1393,7 @@ struct Proof {
       // One proof over several GPUs, long rows: every rank sums its share of a set's members (a k_lincomb_ptrs over zero members
       // writes zeros), the W partial combinations of all sets are all-gathered (ns n values per rank) and added up.
       const bool shard_sets = W_sh > 1 && k >= 14;
-      if (shard_sets) CK(grow_qgather((size_t)W_sh * ns * n * 32));   // [set][rank][n]: the buffer of the quotient shares, grown if there are more sets than coset rows
+      if (shard_sets) CK(grow_qgather(ctx, ws, (size_t)W_sh * ns * n * 32));   // [set][rank][n]: the buffer of the quotient shares, grown if there are more sets than coset rows
       for (size_t j = 0; j < ns; ++j) {
         const size_t all = sets[j].members.size();
         const size_t m_lo = shard_sets ? all * r_sh / W_sh : 0, m_hi = shard_sets ? all * (r_sh + 1) / W_sh : all;
