@@ -205,9 +205,10 @@ def test_tamper_matrix(ctx, k13):
     assert sum(1 for _, why in got if why) >= 6     # decoding / transcript rejections carry their reason
 
 
-def test_randomisers_defeat_cancellation(ctx):
-    """Two valid toy proofs A, B with h2 moved by D, D' so that the UNWEIGHTED sum of their pairing equations still holds: the
-    randomised batch must reject exactly A and B."""
+@pytest.fixture(scope="module")
+def toy3():
+    """Three oracle-made toy proofs (k = 9, 278 words) under one proving key: A and B of one public key, C of a second one
+    (the proving key does not depend on the public key: the oracle prover takes either circuit)."""
     import zk_fhe_amd as zk
     prm = C.BfvParams(N=8)
     from tests.test_proof_oracle import synth_input
@@ -218,7 +219,17 @@ def test_randomisers_defeat_cancellation(ctx):
     pk, _ = H.keygen_circuit(cfg, circ, srs)
     vkb = zk.make_vk_bytes(cfg.k, cfg.n_gate0, cfg.n_gate1, cfg.n_lookup, cfg.n_rlc, cfg.unusable_rows, cfg.lookup_bits,
                            pk.vk_digest, pk.fixed_commit, pk.sigma_commit, "poseidon")
-    proofs = [H.prove(cfg, pk, srs, circ, seed) for seed in (b"A", b"B", b"C")]
+    circ2 = H.BfvCircuit(synth_input(8, prm.Q, prm.T, prm.B, 2), prm)
+    proofs = [H.prove(cfg, pk, srs, c, seed) for c, seed in ((circ, b"A"), (circ, b"B"), (circ2, b"C"))]
+    assert proofs[0][1][:16] == proofs[1][1][:16] != proofs[2][1][:16]      # pk0 | pk1: two prefix groups
+    return pk, srs, vkb, proofs
+
+
+def test_randomisers_defeat_cancellation(ctx, toy3):
+    """Two valid toy proofs A, B with h2 moved by D, D' so that the UNWEIGHTED sum of their pairing equations still holds: the
+    randomised batch must reject exactly A and B."""
+    import zk_fhe_amd as zk
+    pk, srs, vkb, proofs = toy3
     # uu of each proof: the last challenge of the oracle verifier's replay
     T = H.TRANSCRIPTS["poseidon"]
     orig = T.squeeze
@@ -249,6 +260,81 @@ def test_randomisers_defeat_cancellation(ctx):
     items = [(proofs[2][1], proofs[2][0]), (proofs[0][1], A), (proofs[1][1], B), (proofs[0][1], proofs[0][0])]
     got = zk.bfv_verify_batch(ctx, vkb, items)
     assert got == single(vkb, items) == [(True, ""), (False, ""), (False, ""), (True, "")]
+
+
+# ---- across the chunk boundary: 260 toy proofs, 256 per device pass -----------------------------------------------------------
+
+N_CHUNKED = 260
+
+
+@pytest.fixture(scope="module")
+def single_memo():
+    """the single verifier's (verdict, reason), computed once per distinct (instances, proof)"""
+    import zk_fhe_amd as zk
+    memo = {}
+
+    def want(vkb, items):
+        out = []
+        for inst, proof in items:
+            key = (tuple(inst), proof)
+            if key not in memo:
+                memo[key] = zk.bfv_verify(vkb, inst, proof)
+            out.append(memo[key])
+        return out
+    return want
+
+
+def cycled(proofs):
+    """260 good items: the three toy proofs in turn, so both public-key groups have members on either side of item 256"""
+    return [(list(proofs[j % 3][1]), proofs[j % 3][0]) for j in range(N_CHUNKED)]
+
+
+def test_two_chunks_all_good(ctx, toy3, single_memo):
+    import zk_fhe_amd as zk
+    _, _, vkb, proofs = toy3
+    items = cycled(proofs)
+    got = zk.bfv_verify_batch(ctx, vkb, items)
+    assert got == single_memo(vkb, items) == [(True, "")] * N_CHUNKED
+
+
+def test_two_chunks_bad_items_around_the_boundary(ctx, toy3, single_memo):
+    """Bad items at 254, 255 (end of the first pass) and 256, 257, 259 (start of the second): the batch pairing fails, so every
+    other item is accepted by its own pairing; every verdict and reason is the single verifier's."""
+    import zk_fhe_amd as zk
+    _, _, vkb, proofs = toy3
+    items = cycled(proofs)
+    x = 5
+    while pow((x ** 3 + 3) % Q, (Q - 1) // 2, Q) == 1:   # an x with no square root of x^3 + 3
+        x += 1
+
+    def tamper(j, f_inst=lambda i: i, f_proof=lambda p: p):
+        inst, proof = items[j]
+        items[j] = (f_inst(list(inst)), f_proof(proof))
+
+    def flip(p):
+        b = bytearray(p)
+        b[len(p) - 100] ^= 1                                         # an evaluation (scalar) byte
+        return bytes(b)
+    tamper(254, f_proof=flip)
+    tamper(255, f_proof=lambda p: p[:-32])                           # one word short
+    tamper(256, f_proof=lambda p: p[:64] + x.to_bytes(32, "little") + p[96:])   # an x off the curve in commitment 2
+    tamper(257, f_proof=lambda p: recompress(p, 2, None))            # the identity in commitment 2: Poseidon refuses it
+    tamper(259, f_inst=lambda i: i[:-1] + [(i[-1] + 1) % R])         # a public input off by one
+    bad = {254, 255, 256, 257, 259}
+    got = zk.bfv_verify_batch(ctx, vkb, items)
+    assert got == single_memo(vkb, items)
+    assert [j for j, (ok, _) in enumerate(got) if not ok] == sorted(bad)
+    assert got[254] == (False, "") and got[259] == (False, "") and got[255] == (False, "proof truncated")
+    assert got[256] == (False, "point not on curve") and got[257][1] != ""
+
+
+def test_first_chunk_all_rejected_before_the_pairing(ctx, toy3, single_memo):
+    """The whole first device pass leaves no segment (every proof is one word short), the second pass is live."""
+    import zk_fhe_amd as zk
+    _, _, vkb, proofs = toy3
+    items = [(inst, proof[:-32] if j < 256 else proof) for j, (inst, proof) in enumerate(cycled(proofs))]
+    got = zk.bfv_verify_batch(ctx, vkb, items)
+    assert got == single_memo(vkb, items) == [(False, "proof truncated")] * 256 + [(True, "")] * 4
 
 
 def test_arguments(ctx, k13):

@@ -25,7 +25,7 @@ def test_layout_constants():
     assert "return Layout{0x%02x, 0x%02x, 0x%02x};" % (PE.SIGN_BIT, PE.IDENTITY_BIT, PE.X_MASK) in src     # the product's default
     assert "ZKFHE_POINT_ENCODING" in src and "ZKFHE_POINT_ENCODING" in open(PE.__file__).read()           # one switch for both sides
     # nobody keeps a private copy of the layout
-    for f in ("transcript.hpp", "verifier.cpp"):
+    for f in ("transcript.hpp", "proof_reader.hpp"):   # the writer; the verifier's reader and its host point decoding
         body = open(os.path.join(HERE, "..", "zk-fhe_amd", "host", f)).read()
         assert "ptenc::" in body and "b[31] |= 0x" not in body and "b[31] &= 0x" not in body
     assert H.point_compress is PE.point_compress and PR.point_compress is PE.point_compress

@@ -27,7 +27,7 @@ __device__ __forceinline__ Fq fq_times32(const Fq &m) {
 }
 
 // One lane per point.  status: ZKFHE_PT_OK, _X_NOT_REDUCED, _NOT_ON_CURVE, _BAD_IDENTITY; anything but OK leaves (0, 0).
-// The checks and their order are those of the host reader (verifier.cpp Reader::read_point); any 32 bytes are accepted.
+// The checks and their order are those of the host decoder (host/proof_reader.hpp decode_point); any 32 bytes are accepted.
 __global__ void __launch_bounds__(256) k_g1_decompress(const uint8_t *__restrict__ in, size_t n, u32 sign_bit, u32 id_bit, u32 x_mask,
                                                        G1Affine *__restrict__ out, int32_t *__restrict__ status) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;

@@ -32,6 +32,8 @@ namespace fe {
 
 static const U256 MOD = {{0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
 static const unsigned MOD_BITS = 254;
+// the base field's modulus q (coordinates of G1 and G2 points): the one host definition
+static const U256 Q_MOD = {{0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
 
 inline U256 zero() { return U256{{0, 0, 0, 0}}; }
 inline U256 from_u64(uint64_t v) { return U256{{v, 0, 0, 0}}; }

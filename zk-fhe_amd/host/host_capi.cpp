@@ -249,10 +249,9 @@ bool load_fr(const uint8_t b[32], U256 &v) {
   return v < fe::MOD;
 }
 bool load_point(const uint8_t b[64], AffinePoint &p) {
-  static const U256 QMOD = {{0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
   memcpy(p.x.l, b, 32);
   memcpy(p.y.l, b + 32, 32);
-  return p.x < QMOD && p.y < QMOD;
+  return p.x < fe::Q_MOD && p.y < fe::Q_MOD;
 }
 }  // namespace
 

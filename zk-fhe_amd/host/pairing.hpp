@@ -313,7 +313,7 @@ inline Fq12 miller_loop(const Pt<Fq12> &Q, const Pt<Fq12> &P) {
 // (q^12 - 1) / r as little-endian 32-bit limbs, computed once with BigInt arithmetic
 inline const std::vector<uint32_t> &final_exponent() {
   static const std::vector<uint32_t> e = [] {
-    BigInt q = fe::to_bigint(U256{{0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}});
+    BigInt q = fe::to_bigint(fe::Q_MOD);
     BigInt q12(1);
     for (int i = 0; i < 12; ++i) q12 = q12 * q;
     BigInt num = q12 - BigInt(1);

@@ -1,5 +1,5 @@
 // The 32-byte compressed form of a BN254 G1 point in the proof byte stream -- ONE definition, used by the prover's transcript
-// (transcript.hpp), the verifier's reader (verifier.cpp) and mirrored by oracle/point_encoding.py (which both oracle
+// (transcript.hpp), the verifier's reader (proof_reader.hpp) and mirrored by oracle/point_encoding.py (which both oracle
 // transcripts import).  tests/test_point_encoding.py pins the three against tests/golden/point_encoding.json.
 //
 // Layout = halo2curves `new_curve_impl!` `GroupEncoding for G1Affine` as of the 0.3.2 .. 0.5 line that halo2-axiom

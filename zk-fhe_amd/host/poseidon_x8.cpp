@@ -417,7 +417,7 @@ class HashService {
   }
 
  private:
-  static const int MAX_WORKERS = 16;
+  static constexpr int MAX_WORKERS = 16;   // constexpr: std::min takes its address, so it needs a definition
   std::mutex mu;
   std::condition_variable cv;
   std::deque<AbsorbJob *> queue;

@@ -15,6 +15,8 @@
 #include "bfv_circuit.hpp"
 #include "bfv_phase0_fast.hpp"
 #include "gpu_witness.hip.hpp"
+#include "host_g2.hpp"    // the host G2 codec and the powers check that srs.hip borrows
+#include "host_util.hpp"  // mont, mont_u64, canon, fr_pow, fr_inv, point_canon
 #include "prover_kernels.hip.hpp"
 #include "shplonk.hpp"
 #include "transcript.hpp"
@@ -30,7 +32,6 @@ CircuitConfig config_from_c(const zkfhe_bfv_config *c);
 BfvParams params_from_c(const zkfhe_bfv_params *p);
 }  // namespace zkhost
 
-static const uint64_t DELTA_CANON[4] = {0x870e56bbe533e9a2ULL, 0x5b5f898e5e963f25ULL, 0x64ec26aad4c86e71ULL, 0x09226b6e22c6f0caULL};
 static const uint64_t COSET_G = 7;
 
 #define CK(x)                 \
@@ -77,37 +78,8 @@ static inline int srs_msm_pts(zkfhe_ctx *ctx, const zkfhe_srs *srs, const zkfhe_
   return zkfhe_msm_batch_sharded_async(ctx, srs->comm, basis, (const zkfhe_fr *)(cols + srs->lo), (size_t)1 << srs->k, n_cols, (zkfhe_g1_affine *)pinned_out);
 }
 
-// verifier.cpp (host pairing arithmetic): G2 and s G2 as raw Montgomery coordinates; raw <-> canonical; on-curve check of raw coordinates
-void zk_srs_g2_from_secret(const U256 &s, uint8_t g2_raw[128], uint8_t sg2_raw[128]);
-bool zk_g2_raw_to_canon(const uint8_t raw[128], uint8_t canon[128]);   // false: a coordinate is not reduced or the point is off the twist
-bool zk_g2_canon_to_raw(const uint8_t canon[128], uint8_t raw[128]);
-// e(A, s_g2) e(-B, g2) = 1 on the host (affine Montgomery G1 points, raw G2 coordinates): the powers check of zkfhe_srs_check
-bool zk_srs_pairing_powers(const zk::G1Affine &A, const zk::G1Affine &B, const uint8_t g2_raw[128], const uint8_t sg2_raw[128]);
-
 static inline double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-static inline Fr mont(const U256 &v) { return fe::to_mont(v); }
-static inline Fr mont_u64(uint64_t v) { return fe::to_mont(fe::from_u64(v)); }
-static inline U256 canon(const Fr &f) { return fe::from_mont(f); }
-static inline Fr fr_pow(Fr b, uint64_t e) {
-  Fr r = Fr::one();
-  while (e) {
-    if (e & 1) r = r * b;
-    b = b * b;
-    e >>= 1;
-  }
-  return r;
-}
-static inline Fr fr_inv(const Fr &a) { return zk::fp_inv<zk::FrP>(a); }
-
-static inline AffinePoint point_canon(const G1Affine &p) {
-  AffinePoint a;
-  zk::Fq x = zk::fp_from_mont<zk::FqP>(p.x), y = zk::fp_from_mont<zk::FqP>(p.y);
-  memcpy(a.x.l, x.l, 32);
-  memcpy(a.y.l, y.l, 32);
-  return a;
 }
 
 static inline unsigned grid_for(zkfhe_ctx *ctx, size_t work) {

@@ -1,4 +1,4 @@
-// Opening bookkeeping shared by the prover (prove.hip) and the verifier (verifier.cpp): which polynomial is opened at
+// Opening bookkeeping shared by the prover (prove.hip) and the verifier (opening.cpp): which polynomial is opened at
 // which rotation, in which order the evaluations are written, and how halo2's SHPLONK groups them.
 //
 // Restates (third-party halo2_proofs, reached from reference examples/bfv.rs:311; mirrored by oracle/halo2_ref.py
@@ -53,7 +53,19 @@ struct OpenLayout {
       if (rots[item][t] == rot) return (int)t;
     return -1;
   }
+  // 32-byte words of the evaluations as written: every item's rotations but H's
+  size_t eval_words() const {
+    size_t w = 0;
+    for (size_t i = 0; i < count; ++i) w += i == H ? 0 : rots[i].size();
+    return w;
+  }
 };
+
+// Commitments a proof carries before its evaluations, in read order (verifier: opening.cpp replay_commitments): advice, a permuted
+// input and table per lookup, permutation products, lookup products, the random polynomial, three quotient pieces.
+inline size_t commit_words(const CircuitConfig &cfg) { return cfg.n_advice() + 2 * (size_t)cfg.n_lookup + cfg.n_chunks() + cfg.n_lookup + 1 + 3; }
+// 32-byte words of a well-formed proof: commitments, evaluations, then h1 and h2 (what the batch verifier decompresses per proof)
+inline size_t proof_words(const CircuitConfig &cfg) { return commit_words(cfg) + OpenLayout(cfg).eval_words() + 2; }
 
 struct OpenSet {
   std::vector<int> rots;        // the point set (rotation ids, ascending id)

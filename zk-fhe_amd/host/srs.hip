@@ -182,7 +182,7 @@ int zkfhe_srs_load(zkfhe_ctx *ctx, const char *path, zkfhe_srs **out) {
   if (!ok) return zk_fail_msg(ctx, ZKFHE_EINVAL, std::string(path) + ": not a params file (u32 k | 2^k g | 2^k g_lagrange | g2 | s_g2, RawBytes), or k outside 3..20");
   // what halo2's RawBytes read checks: reduced coordinates, y^2 = x^3 + 3 (the identity (0, 0) cannot occur in an SRS)
   const zk::Fq three = zk::fp_to_mont<zk::FqP>([] { zk::Fq t = zk::Fq::zero(); t.l[0] = 3; return t; }());
-  static const U256 QM = {{0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
+  const U256 &QM = fe::Q_MOD;
   for (const auto *v : {&g, &gl})
     for (const G1Affine &p : *v) {
       U256 x, y;
@@ -204,7 +204,7 @@ int zkfhe_srs_load(zkfhe_ctx *ctx, const char *path, zkfhe_srs **out) {
 
 // what zkfhe_srs_load asks of a G1 point: reduced coordinates, y^2 = x^3 + 3
 static bool srs_g1_on_curve(const G1Affine &p) {
-  static const U256 QM = {{0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}};
+  const U256 &QM = fe::Q_MOD;
   static const zk::Fq three = zk::fp_to_mont<zk::FqP>([] { zk::Fq t = zk::Fq::zero(); t.l[0] = 3; return t; }());
   U256 x, y;
   memcpy(x.l, p.x.l, 32);

@@ -25,4 +25,11 @@ inline U256 vk_digest(const CircuitConfig &cfg, const std::vector<AffinePoint> &
   return from_bytes_wide(d);
 }
 
+// a parsed verifying-key file (verifier.cpp parse_vk): what the opening reads of it
+struct Vk {
+  CircuitConfig cfg;
+  std::vector<AffinePoint> fixed_commit, sigma_commit;
+  U256 digest;
+};
+
 }  // namespace zkhost
